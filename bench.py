@@ -34,6 +34,7 @@ PEAK_TFLOPS_F16 = 2500.0           # MI355X dense fp16/bf16 MFMA peak (MI355X_MI
 # out each; + one 4.19 MB fp16 copy; the sampling grid costs 0 bytes: it is consumed inside the kernel that computes it) and, in the same
 # kernel, the softmax over the 22 mask logits that yields the deformation (dense_motion.py:88-94: 22 x 65536 x 4 B = 5.77 MB of logits per call)
 WARP_BYTES_PER_FRAME = 2 * (16.78e6 + 5.77e6) + 4.19e6
+DUMP_BYTES = 64 * 10**6            # --dump-outputs: at most this many bytes of float32 frames
 
 
 def _free_port():
@@ -78,12 +79,18 @@ def parse_args():
                     help="this many source identities resident at once, frame g of the job using identity g mod n")
     ap.add_argument("--dump-crc", default="", help="the leader of stream s writes the CRC32 of every gathered frame of the last step "
                                                    "to this path (stream 0) / path.s<s> (tests)")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="write what the timed path returned in its last step (the uint8 frames rank 0 holds) to DIR/<name>.npy as float32: "
+                         "all frames if they fit in 64 MB, else a fixed, seeded sample of them (DIR/out_frame_index.npy names the frames)")
     ap.add_argument("--force-dist", action="store_true",
                     help="N = 1 through the multi-GPU code: RCCL communicator on a world of one, identity broadcast, chunked asynchronous "
                          "device gather of the uint8 frames inside the timed region, sub-communicators for --streams (VERDICT r4 item 1)")
     ap.add_argument("--backend", default="nccl", choices=["nccl", "gloo"],
                     help="gloo: dry run of the multi-rank flow with all ranks sharing GPU 0 and host-side collectives (test only)")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1 (the timed region runs exactly that many steps)")
+    return args
 
 
 def main():
@@ -277,6 +284,15 @@ def main():
         step(plan, i)
     dt, per_rank, gathered = timed(plan, K)
     _flush_c_stdio()
+    if a.dump_outputs and rank == 0 and gathered is not None:      # before the legs below reuse out_u8
+        n_out = gathered.shape[0]
+        m = min(n_out, DUMP_BYTES // (gathered[0].numel() * 4))
+        sel = np.sort(np.random.default_rng(0).choice(n_out, m, replace=False)) if m < n_out else np.arange(n_out)
+        frames = gathered[torch.from_numpy(sel).to(gathered.device)].cpu().numpy().astype(np.float32)
+        os.makedirs(a.dump_outputs, exist_ok=True)
+        np.save(os.path.join(a.dump_outputs, "out_frames.npy"), frames)             # [m, 512, 512, 3], values 0 .. 255
+        np.save(os.path.join(a.dump_outputs, "out_frame_index.npy"), sel.astype(np.float64))
+        del frames
     if a.dump_crc:                                            # tests: CRC32 of every frame of the last step, per stream, on its leader
         import zlib
         for h, (s, q, _) in enumerate(mine):

@@ -113,3 +113,26 @@ def test_configs3_job_shape_through_rccl_equals_the_plain_run(tmp_path):
     assert len(a) == 1200 and a == b
     print(f"configs[3] shape on 1 GPU: {one['value']:.1f} frames/s plain, {two['value']:.1f} frames/s with the chunked RCCL gather into the "
           f"device receive buffer ({two['value'] / one['value']:.4f})")
+
+
+def test_dump_outputs_are_the_last_timed_step(tmp_path):
+    """--dump-outputs writes the uint8 frames of the last timed step as float32 (the --dump-crc frames, byte for byte): 24 frames of
+    3 MB each exceed the 64 MB cap, so a fixed, seeded sample of 20 is written, the same one in a second run with the same arguments."""
+    import zlib
+
+    import numpy as np
+    common = ["--gpus", "1", "--batch", "24", "--steps", "2", "--warmup", "0", "--no-cpu-baseline", "--no-fixed-job", "--no-single-frame",
+              "--no-chain"]
+    crc, d1, d2 = str(tmp_path / "crc.json"), tmp_path / "d1", tmp_path / "d2"
+    line = _run([sys.executable, "bench.py", *common, "--dump-crc", crc, "--dump-outputs", str(d1)])
+    _run([sys.executable, "bench.py", *common, "--dump-outputs", str(d2)])
+    assert line["steps"] == 2
+    frames, idx = np.load(d1 / "out_frames.npy"), np.load(d1 / "out_frame_index.npy")
+    assert frames.dtype == np.float32 and frames.shape == (20, 512, 512, 3) and frames.nbytes <= 64 * 10**6
+    assert idx.dtype == np.float64 and len(set(idx.tolist())) == 20 and list(idx) == sorted(idx) and idx.max() < 24
+    crcs = json.load(open(crc))
+    assert len(crcs) == 24
+    for j, f in zip(idx.astype(int), frames):
+        assert np.array_equal(f, np.round(f)) and f.min() >= 0 and f.max() <= 255
+        assert zlib.crc32(f.astype(np.uint8).tobytes()) == crcs[j]
+    assert np.array_equal(idx, np.load(d2 / "out_frame_index.npy")) and np.array_equal(frames, np.load(d2 / "out_frames.npy"))
