@@ -33,7 +33,7 @@ class FrameChain:
             raise RuntimeError("FrameChain: the loaded weights hold no 'motion_extractor' state-dict")
         self.se = tail.SoftErosion(self.e, kernel_size, threshold, iterations)      # SoftErosion(21, 0.9, 3): can_swap_pipeline_e2e.py:42
         self._buf = {}
-        self._side, self._free, self._pending, self._nslot = None, None, [], 0        # prefetch(): side stream, double buffer
+        self._side, self._free, self._pending = None, None, []        # prefetch(): side stream, double buffer
 
     def _get(self, key, shape, dtype):
         t = self._buf.get(key)
@@ -65,14 +65,19 @@ class FrameChain:
     def prefetch(self, crops_u8, masks):
         """Stage A of the NEXT batch on a side stream, so that it runs beside the generator of the current one (M and the staging are
         bandwidth / latency bound, the generator is matrix-pipe bound): call it before __call__ of the current batch; the next __call__ with
-        the same crops tensor picks the result up (the soft masks of that batch included: they depend on the parser's labels only).  M's workspace is its own, the batch's inputs land in the other half of a double buffer."""
+        the same crops tensor picks the result up (the soft masks of that batch included: they depend on the parser's labels only).  M's workspace is its own, the batch's inputs land in the other half of a double buffer.
+        Staged batches may be run in any order.  Not on a latency-mode engine: there every small plain conv (M's and the generator's
+        alike) runs split-K on the engine's one partial-sum buffer, which M on the side stream and the generator would share."""
         e = self.e
+        if e.latency_mode:
+            raise RuntimeError("FrameChain.prefetch: the engine is in latency mode (split-K scratch shared by M and the generator); "
+                               "run the chain in-line")
+        if len(self._pending) >= 2:
+            raise RuntimeError("FrameChain.prefetch: two batches are already staged (double buffer); run one of them first")
         if self._side is None:
             self._side = torch.cuda.Stream(device=e.device)      # (a high-priority side stream measured the same: 0.933 either way)
             self._free = [torch.cuda.Event(), torch.cuda.Event()]
-        if len(self._pending) >= 2:
-            raise RuntimeError("FrameChain.prefetch: two batches are already staged (double buffer); run one of them first")
-        slot = self._nslot = 1 - self._nslot
+        slot = 1 - self._pending[0][1] if self._pending else 0      # the half no staged batch holds (they may be run out of order)
         main = torch.cuda.current_stream(e.device)
         self._side.wait_stream(main)                      # the crops were produced on the caller's stream
         self._side.wait_event(self._free[slot])           # the generator that read this half of the double buffer is done
@@ -83,8 +88,11 @@ class FrameChain:
         self._pending.append((crops_u8, slot, res, ready))
 
     def drop_prefetches(self):
-        """Forget staged batches that will not be run (their buffers are reused by the next prefetch)."""
+        """Forget staged batches that will not be run (their buffers are reused by the next prefetch).  Their stage A may still be running
+        on the side stream: the caller's stream waits for it, as an in-line stage A must (both use the engine's M and SoftErosion scratch)."""
         self._pending = []
+        if self._side is not None:
+            torch.cuda.current_stream(self.e.device).wait_stream(self._side)
 
     def __call__(self, crops_u8, masks, M_c2o, frames_ori, source_id=None, slots=None, out=None, keep=False):
         """crops_u8 (B,512,512,3) or (B,256,256,3) u8; masks (B,512,512) u8 0/1 or fp32 (the parser's `torch.isin(labels, valid)`);
@@ -98,6 +106,8 @@ class FrameChain:
             _, slot, (I, x_t, x_can, soft), ready = self._pending.pop(hit[0])
             main.wait_event(ready)
         else:
+            if self._side is not None:
+                main.wait_stream(self._side)      # a prefetch in flight uses the same M and SoftErosion scratch in the engine
             I, x_t, x_can, soft = self._stage_a(crops_u8, masks, "inline")
         B = I.shape[0]
         gen = e.swap_frames(I, x_t, x_can, source_id, want_f32=False, want_u8=True, slots=slots,

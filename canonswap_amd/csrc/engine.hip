@@ -100,7 +100,7 @@ struct cs_engine {
     half_t *m_y = nullptr, *m_h = nullptr;   // split-precision GEMM operands [hi | lo]
     float* m_h32 = nullptr;
     // soft-erosion scratch (allocated on first use for the largest B*H*W seen)
-    float *se_a = nullptr, *se_b = nullptr, *se_part = nullptr; size_t se_cap = 0;
+    float *se_a = nullptr, *se_b = nullptr, *se_part = nullptr; size_t se_cap = 0, se_part_cap = 0;      // se_part: 64 maxima per sample
 
     // ---- workspace
     half_t *f_t0, *f_p0, *f_p1;
@@ -1586,13 +1586,17 @@ static int soft_erosion_impl(cs_engine* e, int B, int H, int W, const void* mask
                              float* soft_out, uint8_t* hard_out, int per_sample, void* stream, const char* who)
 {
     if (!e || !mask || !w || !soft_out || B < 1 || H < 1 || W < 1) { cs_set_error("%s: bad arguments", who); return -1; }
-    if (B > 64) { cs_set_error("%s: batch %d exceeds 64", who, B); return -1; }
+    if (B > 65535 || H > 65535 * 32) { cs_set_error("%s: %d x %d x %d exceeds the launch grid", who, B, H, W); return -1; }      // grid (W/64, H/32, B)
     DevGuard guard(e->dev);
-    const size_t need = (size_t)B * H * W;
-    if (need > e->se_cap) {      // grow-only scratch; buffers of earlier sizes stay owned by the engine until cs_destroy
+    const size_t need = (size_t)B * H * W, need_part = (size_t)64 * B;      // launch_soft_erosion: 64 partial maxima per sample
+    // grow-only scratch; buffers of earlier sizes stay owned by the engine until cs_destroy
+    if (need > e->se_cap) {
         if (e->alloc(&e->se_a, need) || e->alloc(&e->se_b, need)) return -1;
-        if (!e->se_part && e->alloc(&e->se_part, (size_t)64 * 64)) return -1;
         e->se_cap = need;
+    }
+    if (need_part > e->se_part_cap) {
+        if (e->alloc(&e->se_part, need_part)) return -1;
+        e->se_part_cap = need_part;
     }
     hipStream_t st = (hipStream_t)stream;
     return e->run(1, st, [&] { return launch_soft_erosion(mask, mask_u8, e->se_a, e->se_b, w, e->se_part, soft_out, hard_out, B, H, W, ksize, thr, iters,

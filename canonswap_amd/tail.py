@@ -69,11 +69,16 @@ def soft_erosion_frames(e: Engine, masks, weight, kernel_size=21, threshold=0.9,
         m = m.to(torch.uint8) if not m.dtype.is_floating_point else m.float()
     m = m.to(e.device).contiguous()
     B, H, W = m.shape
-    soft = torch.empty((B, H, W), dtype=torch.float32, device=e.device) if out is None else out
+    if out is None:
+        out = torch.empty((B, H, W), dtype=torch.float32, device=e.device)
+    elif out.dtype != torch.float32 or tuple(out.shape) != (B, H, W) or not out.is_contiguous() or out.device != e.device:
+        raise ValueError("out must be a contiguous (B, H, W) fp32 tensor of the masks' shape on the engine's device")
+    if weight.dtype != torch.float32 or weight.numel() != kernel_size * kernel_size or not weight.is_contiguous() or weight.device != e.device:
+        raise ValueError("weight must be the contiguous kernel_size x kernel_size fp32 kernel on the engine's device")
     with torch.cuda.device(e.device):
         _lib.check(e.lib.cs_soft_erosion_frames(e.h, B, H, W, _ptr(m), int(m.dtype == torch.uint8), _ptr(weight), kernel_size, float(threshold),
-                                                iterations, _ptr(soft), None, e._stream()), "cs_soft_erosion_frames")
-    return soft
+                                                iterations, _ptr(out), None, e._stream()), "cs_soft_erosion_frames")
+    return out
 
 
 def paste_back_batch(e: Engine, crops, masks_crop, M_c2o, imgs_ori, out=None):

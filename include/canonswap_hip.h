@@ -96,7 +96,9 @@ int cs_animate_frames(cs_engine* e, int B, const float* f, int nf, const float* 
 /* ---- image-space steps on either side of the generator; all buffers on the device ---- */
 /* SoftErosion.forward (src/utils/crop.py:21-47; the pipeline builds it with kernel_size 21, threshold 0.9, iterations 3 / 2,
  * can_swap_pipeline_e2e.py:42, _v2i.py:43): mask BxHxW fp32 (0/1) -> soft_out BxHxW fp32, hard_out BxHxW u8 (may be NULL).
- * w: the ksize x ksize fp32 kernel (crop.py:29-35), built by the caller exactly as the reference builds it. */
+ * w: the ksize x ksize fp32 kernel (crop.py:29-35), built by the caller exactly as the reference builds it.  ksize 21 or 15, iters >= 1,
+ * any H, W >= 1; B from 1 to 65535 (the maximum is taken over the whole BxHxW tensor, as the module does); the engine's scratch grows to
+ * the largest B x H x W seen, independently of cs_create's max_batch. */
 int cs_soft_erosion(cs_engine* e, int B, int H, int W, const float* mask, const float* w, int ksize, float thr, int iters,
                     float* soft_out, uint8_t* hard_out, void* stream);
 /* Input staging (src/utils/cropper.py:209 + can_swap_e2e.py:126-163): uint8 crops BxHcxWcx3, 512x512 (cv2.resize to 256x256 with
@@ -116,7 +118,7 @@ int cs_paste_back(cs_engine* e, const uint8_t* crop, const float* mask_crop, con
 /* The same steps for the B frames of one launch of the per-frame loop (can_swap_pipeline_e2e.py:273-283 runs them frame by frame):
  * cs_soft_erosion_frames = B independent SoftErosion calls on (1,1,H,W) masks - the maximum of crop.py:45 is taken per frame, as in the
  * pipeline's loop, not over the batch; masks: BxHxW, fp32 or (masks_u8 != 0) uint8 0/1 labels (`torch.isin(labels, valid).to(int)`,
- * can_swap_pipeline_e2e.py:192).  cs_paste_back_batch = prepare_paste_back + paste_back of B frames in one launch: crops BxHcxWcx3 u8
+ * can_swap_pipeline_e2e.py:192); the limits of cs_soft_erosion (B up to 65535, not bound to max_batch).  cs_paste_back_batch = prepare_paste_back + paste_back of B frames in one launch: crops BxHcxWcx3 u8
  * (the generator's frames), masks_crop BxHcxWc fp32 (the soft masks, in the crop frame), M_c2o: HOST, B x 6 doubles (2x3 row major, crop ->
  * original, target_M_c2o_lst[i]), imgs_ori / out BxHoxWox3 u8. */
 int cs_soft_erosion_frames(cs_engine* e, int B, int H, int W, const void* masks, int masks_u8, const float* w, int ksize, float thr, int iters,

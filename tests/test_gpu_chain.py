@@ -210,3 +210,249 @@ def test_prefetched_stage_a_gives_the_same_frames(swapper_m):
     with pytest.raises(RuntimeError):
         chain.prefetch(batches[0][0], batches[0][1]); chain.prefetch(batches[1][0], batches[1][1]); chain.prefetch(batches[2][0], batches[2][1])
     chain.drop_prefetches()
+
+
+# ---- FrameChain call patterns beyond prefetch-then-hit: every result is compared byte for byte with the plain in-line chain
+# on the same inputs (itself held to the oracle by test_chain_vs_oracle_loop)
+def _batch(B, seed, Ho=360, Wo=640):
+    from canonswap_amd import synth
+    r = np.random.Generator(np.random.PCG64(seed))
+    smooth = synth.make_smooth_images(B, seed=2300 + seed, size=512)
+    crops = torch.from_numpy(np.ascontiguousarray((smooth.transpose(0, 2, 3, 1) * 255).astype(np.uint8))).cuda()
+    masks = torch.from_numpy(_masks(B, seed=seed)).cuda()
+    ori = torch.from_numpy(r.integers(0, 256, size=(B, Ho, Wo, 3), dtype=np.uint8)).cuda()
+    Ms = np.stack([_affine(j % 4, Ho, Wo) * np.array([[0.4], [0.4], [1]]) + np.array([[0, 0, 60.], [0, 0, 10.], [0, 0, 0]]) for j in range(B)])
+    return crops, masks, Ms, ori
+
+
+def _timed():
+    return torch.cuda.Event(enable_timing=True)
+
+
+def _occupy(stream, ms):
+    """Keep `stream` busy for about `ms` milliseconds with one bounded spin kernel (torch.cuda._sleep counts GPU clock cycles: calibrated
+    here first), so that work queued behind it on that stream is certainly still pending while the caller's stream runs."""
+    a, b = _timed(), _timed()
+    with torch.cuda.stream(stream):
+        a.record()
+        torch.cuda._sleep(1_000_000)
+        b.record()
+    b.synchronize()
+    per_ms = 1e6 / max(a.elapsed_time(b), 1e-3)
+    with torch.cuda.stream(stream):
+        torch.cuda._sleep(int(min(min(ms, 200.0) * per_ms, 1e9)))
+
+
+def _inline_ms(chain, b, idv):
+    a, z = _timed(), _timed()
+    a.record()
+    chain(*b, idv)
+    z.record()
+    z.synchronize()
+    return a.elapsed_time(z)
+
+
+@pytest.mark.parametrize("dropped", [False, True], ids=["pending", "dropped"])
+def test_inline_stage_a_waits_for_a_prefetch_in_flight(swapper_m, dropped):
+    """prefetch(b1), then chain(b0) with b0 never prefetched (or after drop_prefetches()): the in-line stage A uses the engine's one M and
+    SoftErosion scratch, so it must run after the side stream's stage A.  The side stream is held busy (a spin of several times the
+    in-line call's duration) before the prefetch is queued, so without that ordering the in-line call would end first: the end of the
+    in-line call on the caller's stream must come after the prefetch's completion, and both batches must come out as in the in-line chain."""
+    from canonswap_amd import synth
+    from canonswap_amd.chain import FrameChain
+    idv = torch.from_numpy(synth.make_identity(7)).cuda()
+    b0, b1 = _batch(2, 41), _batch(2, 42)
+    chain = FrameChain(swapper_m)
+    want = [chain(*b, idv)["frames"].clone() for b in (b0, b1)]
+    assert not torch.equal(want[0], want[1])
+    chain.prefetch(b1[0], b1[1])                          # a first prefetch / hit pair creates the side stream
+    assert torch.equal(chain(*b1, idv)["frames"], want[1])
+    dt = _inline_ms(chain, b0, idv)
+    _occupy(chain._side, max(40.0, 8 * dt))
+    chain.prefetch(b1[0], b1[1])
+    staged = _timed()
+    staged.record(chain._side)                            # right behind the prefetch's `ready` event on the side stream
+    if dropped:
+        chain.drop_prefetches()
+    got0 = chain(*b0, idv)["frames"]
+    end0 = _timed()
+    end0.record()
+    got1 = chain(*b1, idv)["frames"]
+    torch.cuda.synchronize()
+    print(f"in-line call {dt:.2f} ms; its end {staged.elapsed_time(end0):.2f} ms after the prefetch's")
+    assert staged.elapsed_time(end0) > 0
+    assert torch.equal(got0, want[0]) and torch.equal(got1, want[1])
+    assert not chain._pending
+
+
+def test_prefetches_consumed_out_of_order(swapper_m):
+    """prefetch(A), prefetch(B), chain(B), prefetch(C), chain(A), chain(C): C must not land in the half of the double buffer A still holds."""
+    from canonswap_amd import synth
+    from canonswap_amd.chain import FrameChain
+    idv = torch.from_numpy(synth.make_identity(7)).cuda()
+    A, Bt, Cc = _batch(2, 51), _batch(2, 52), _batch(2, 53)
+    chain = FrameChain(swapper_m)
+    want = [chain(*b, idv)["frames"].clone() for b in (A, Bt, Cc)]
+    for i in range(3):
+        for j in range(i + 1, 3):
+            assert not torch.equal(want[i], want[j]), (i, j)
+    chain.prefetch(A[0], A[1])
+    chain.prefetch(Bt[0], Bt[1])
+    got_b = chain(*Bt, idv)["frames"]
+    chain.prefetch(Cc[0], Cc[1])
+    got_a = chain(*A, idv)["frames"]
+    got_c = chain(*Cc, idv)["frames"]
+    torch.cuda.synchronize()
+    assert torch.equal(got_b, want[1])
+    assert torch.equal(got_a, want[0])
+    assert torch.equal(got_c, want[2])
+    assert not chain._pending
+
+
+def _oracle_frame(sds, crops, mask, M, ori, idv):
+    """The reference's per-frame loop for one frame (can_swap_pipeline_e2e.py:223-283) composed from the oracle, as in
+    test_chain_vs_oracle_loop: -> (frame, pasted region)."""
+    from oracle import canonswap_ref as O
+    from oracle import cv_ref as R
+    Ho, Wo = ori.shape[:2]
+    with torch.no_grad():
+        Ik = O.prepare_source(R.resize_area_2x_u8(crops))
+        info = O.get_kp_info(sds["motion_extractor"], Ik)
+        x_t = O.transform_keypoint(info)
+        x_can = info["scale"][..., None] * info["kp"]
+        out = O.swap_frame(sds, Ik, x_t, x_can, idv)["out"]
+    soft, _ = R.soft_erosion(torch.from_numpy(mask[None, None].astype(np.float32)), 21, 0.9, 3)
+    mo = R.prepare_paste_back(np.stack([soft.numpy()[0, 0]] * 3, -1), M, (Wo, Ho))
+    return R.paste_back(O.parse_output(out)[0], M, ori, mo), mo[..., 0] > 0
+
+
+def test_latency_mode_chain_refuses_prefetch_and_runs_in_line(sds_m):
+    """On a latency-mode engine every small plain conv goes through split-K on the engine's one partial-sum buffer, so M on a side stream
+    beside the generator would share it: prefetch refuses before it queues anything.  The in-line chain still works there: two batches
+    against the oracle's loop (the gate of test_chain_vs_oracle_loop) and equal to a fresh latency-mode chain byte for byte."""
+    from canonswap_amd import synth
+    from canonswap_amd.can_swap_e2e import can_swapper
+    from canonswap_amd.chain import FrameChain
+    sw = can_swapper(None, state_dicts=sds_m, max_batch=1, latency_mode=True)
+    idv = torch.from_numpy(synth.make_identity(7))
+    b = [_batch(1, 61, 540, 960), _batch(1, 62, 540, 960)]
+    chain = FrameChain(sw)
+    with pytest.raises(RuntimeError, match="latency"):
+        chain.prefetch(b[1][0], b[1][1])
+    assert chain._side is None and not chain._pending
+    got = [chain(*x, idv.cuda())["frames"].clone() for x in b]
+    again = FrameChain(sw)
+    for k in (1, 0):
+        assert torch.equal(again(*b[k], idv.cuda())["frames"], got[k]), k
+    for k, (crops, masks, Ms, ori) in enumerate(b):
+        want, region = _oracle_frame(sds_m, crops[0].cpu().numpy(), masks[0].cpu().numpy(), Ms[0], ori[0].cpu().numpy(), idv)
+        g = got[k][0].cpu().numpy()
+        assert np.array_equal(g[~region], want[~region])
+        d = g[region].astype(np.float64) - want[region].astype(np.float64)
+        p = 10 * np.log10(255.0 ** 2 / max((d ** 2).mean(), 1e-12))
+        print(f"latency-mode batch {k}: PSNR {p:.2f} dB, mean |diff| {np.abs(d).mean():.3f} LSB")
+        assert np.abs(d).mean() < 0.6 and p >= 48.0
+
+
+def test_soft_erosion_frames_beyond_64(swapper_m):
+    """cs_create, cs_swap_frames and cs_paste_back_batch take up to 84 frames; so does SoftErosion (its per-(sample, block) maxima are
+    sized by the batch).  84 frames in one call == 84 single-sample calls, bit for bit, and a few of them against the oracle."""
+    from canonswap_amd import tail
+    from oracle import cv_ref as R
+    from test_gpu_tail import _compare
+    e = swapper_m.engine
+    m = _masks(84, seed=71)
+    m[5] = 0; m[5, 250:262, 250:262] = 1                    # a tiny mask: its own maximum is far below the others'
+    se = swapper_m.soft_mask(21, 0.9, 3)
+    md = torch.from_numpy(m).cuda()
+    got = tail.soft_erosion_frames(e, md, se.weight, 21, 0.9, 3)
+    for k in range(84):
+        one = tail.soft_erosion_frames(e, md[k:k + 1], se.weight, 21, 0.9, 3)
+        assert torch.equal(got[k], one[0]), k
+    got = got.cpu().numpy()
+    for k in (0, 5, 64, 83):
+        want, hard = R.soft_erosion(torch.from_numpy(m[k:k + 1, None].astype(np.float32)), 21, 0.9, 3)
+        want, hard = want.numpy()[0, 0], hard.numpy()[0, 0]
+        hard_got = np.where(hard, got[k] >= 1.0, (got[k] >= 1.0) & (np.abs(want - 1.0) > 1e-5))     # 1.0: above the threshold or the maximum
+        _compare(got[k], want, hard_got, hard, m[k:k + 1], k)
+
+
+def test_soft_erosion_module_beyond_64(swapper_m):
+    """The module path (one maximum over the whole (N,1,H,W) tensor, crop.py:45) at N = 70 against the oracle's whole-batch result."""
+    from oracle import cv_ref as R
+    from test_gpu_tail import _compare
+    m = torch.from_numpy(_masks(70, seed=73).astype(np.float32))[:, None]
+    se = swapper_m.soft_mask(21, 0.9, 3)
+    soft, hard = se(m)
+    want, wmask = R.soft_erosion(m, 21, 0.9, 3)
+    _compare(soft.cpu().numpy()[:, 0], want.numpy()[:, 0], hard.cpu().numpy()[:, 0], wmask.numpy()[:, 0], m.numpy()[:, 0], "N = 70")
+
+
+def test_chain_of_84_frames_is_64_plus_20(sds_m):
+    """A FrameChain call of 84 frames (the engine's largest batch) == a 64-frame call followed by a 20-frame call, byte for byte."""
+    from canonswap_amd import synth
+    from canonswap_amd.can_swap_e2e import can_swapper
+    from canonswap_amd.chain import FrameChain
+    sw = can_swapper(None, state_dicts=sds_m, max_batch=84)
+    idv = torch.from_numpy(synth.make_identity(7)).cuda()
+    crops, masks, Ms, ori = _batch(84, 81)
+    chain = FrameChain(sw)
+    got = chain(crops, masks, Ms, ori, idv)["frames"].clone()
+    lo = chain(crops[:64], masks[:64], Ms[:64], ori[:64], idv)["frames"].clone()
+    hi = chain(crops[64:], masks[64:], Ms[64:], ori[64:], idv)["frames"]
+    torch.cuda.synchronize()
+    assert torch.equal(got, torch.cat([lo, hi]))
+    assert not torch.equal(got[0], got[64])
+    del sw, chain
+    torch.cuda.empty_cache()
+
+
+class _NoLaunch:
+    """Stands in for the engine's library: any call of cs_soft_erosion_frames is a test failure (nothing reaches the device)."""
+
+    def __init__(self, lib):
+        self._lib, self.calls = lib, []
+
+    def __getattr__(self, name):
+        if name == "cs_soft_erosion_frames":
+            def refuse(*a):
+                self.calls.append(a)
+                raise AssertionError("cs_soft_erosion_frames launched on a buffer that should have been refused")
+            return refuse
+        return getattr(self._lib, name)
+
+
+def test_soft_erosion_frames_validates_its_buffers(swapper_m, monkeypatch):
+    """A caller's `out` of the wrong dtype, shape, layout or device, a kernel of another size or on the host, and masks that are not (B,H,W)
+    raise ValueError before any launch: the library is replaced by a stub that fails the test if it is called."""
+    from canonswap_amd import tail
+    e = swapper_m.engine
+    se = swapper_m.soft_mask(21, 0.9, 3)
+    m = torch.from_numpy(_masks(2, seed=91)[:, :300, :200]).cuda().contiguous()
+    want = tail.soft_erosion_frames(e, m, se.weight, 21, 0.9, 3)
+    good = torch.empty((2, 300, 200), dtype=torch.float32, device=e.device)
+    assert tail.soft_erosion_frames(e, m, se.weight, 21, 0.9, 3, out=good) is good and torch.equal(good, want)
+    bad_out = {
+        "fp16": torch.empty((2, 300, 200), dtype=torch.float16, device=e.device),
+        "fp64": torch.empty((2, 300, 200), dtype=torch.float64, device=e.device),
+        "fewer frames": torch.empty((1, 300, 200), dtype=torch.float32, device=e.device),
+        "transposed shape": torch.empty((2, 200, 300), dtype=torch.float32, device=e.device),
+        "flat": torch.empty((2 * 300 * 200,), dtype=torch.float32, device=e.device),
+        "non-contiguous": torch.empty((2, 300, 400), dtype=torch.float32, device=e.device)[..., ::2],
+        "host": torch.empty((2, 300, 200), dtype=torch.float32),
+    }
+    bad_masks = {"2-d": m[0], "(B,2,H,W)": torch.stack([m, m], 1), "5-d": m[None, :, None]}
+    stub = _NoLaunch(e.lib)
+    monkeypatch.setattr(e, "lib", stub)
+    for name, out in bad_out.items():
+        with pytest.raises(ValueError):
+            tail.soft_erosion_frames(e, m, se.weight, 21, 0.9, 3, out=out)
+        assert not stub.calls, name
+    for name, w in {"15 x 15 kernel": swapper_m.soft_mask(15, 0.9, 3).weight, "host kernel": se.weight.cpu()}.items():
+        with pytest.raises(ValueError):
+            tail.soft_erosion_frames(e, m, w, 21, 0.9, 3)
+        assert not stub.calls, name
+    for name, x in bad_masks.items():
+        with pytest.raises(ValueError):
+            tail.soft_erosion_frames(e, x, se.weight, 21, 0.9, 3)
+        assert not stub.calls, name

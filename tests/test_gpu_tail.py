@@ -103,3 +103,75 @@ def test_frame_streamer_equals_whole_video_upload(swapper):
     got = np.concatenate([x for _, _, x in seen])
     want = np.concatenate([O.prepare_source(R.resize_area_2x_u8(f)).numpy() for f in frames])
     assert np.array_equal(got, want)
+
+
+# ---- SoftErosion at its edges: se_conv_kernel's two instantiations (KS = 21 for the pipeline, 15 for the module's defaults, crop.py:21),
+# the scalar tail store (W % 4 != 0, a partial 8-wide group), partial 64 x 32 tiles, images smaller than a tile or than the kernel, one row
+def _edge_masks(H, W, seed):
+    """Four masks with real edges: two ellipses scaled to the image with random blobs toggled in, an all-ones mask (only the zero padding
+    pulls pixels below the threshold: the maximum comes from the border) and a tiny one (its maximum is far below the others')."""
+    r = np.random.Generator(np.random.PCG64(seed))
+    yy, xx = np.mgrid[0:H, 0:W].astype(np.float32)
+    out = []
+    for _ in range(2):
+        cx, cy, a, b = r.uniform(0.4, 0.6) * W, r.uniform(0.4, 0.6) * H, r.uniform(0.25, 0.4) * W, r.uniform(0.3, 0.45) * H
+        m = ((xx - cx) / max(a, 0.5)) ** 2 + ((yy - cy) / max(b, 0.5)) ** 2 <= 1
+        for _ in range(6):
+            bx, by, rad = r.uniform(0, W), r.uniform(0, H), r.uniform(1, max(2, min(H, W) / 6))
+            m ^= np.hypot(xx - bx, yy - by) <= rad
+        m[H // 2, W // 2] = True                              # never empty (an all-zero mask divides 0 by 0)
+        out.append(m)
+    out.append(np.ones((H, W), bool))
+    tiny = np.zeros((H, W), bool)
+    tiny[H // 2:H // 2 + 2, W // 3:W // 3 + 2] = True
+    out.append(tiny)
+    return np.stack(out).astype(np.uint8)
+
+
+def _edge_pixels(masks):
+    """Value changes between neighbouring pixels of the zero-padded masks: the pixels near which a conv value can sit at the threshold."""
+    p = np.pad(np.asarray(masks, dtype=np.int8), ((0, 0), (1, 1), (1, 1)))
+    return int((p[:, 1:] != p[:, :-1]).sum() + (p[:, :, 1:] != p[:, :, :-1]).sum())
+
+
+def _compare(got, want, hard_got, hard_want, masks, what):
+    """Hard-mask flips (conv values within fp32 rounding of the threshold) at most 4 + one per 1000 edge pixels; elsewhere |soft - oracle|
+    < 2e-6.  That bound holds for a tiny mask too, whose normalising maximum is far below 1: the soft value is a ratio of two sums of
+    non-negative fp32 terms, whose rounding is relative, so dividing by a small maximum does not scale the error up (a float64 run of
+    the same operation against the oracle: at most 1.4e-6 at every shape and setting here, 1.2e-7 for the tiny masks)."""
+    flips = hard_got != hard_want
+    limit = 4 + _edge_pixels(masks) // 1000
+    d = np.abs(got - want)[~flips]
+    print(what, "flips", int(flips.sum()), "of at most", limit, "max |soft diff| elsewhere", float(d.max()) if d.size else 0.0)
+    assert flips.sum() <= limit, (what, int(flips.sum()), limit)
+    assert d.size == 0 or d.max() < 2e-6, (what, float(d.max()))
+
+
+@pytest.mark.parametrize("ks", [21, 15])
+@pytest.mark.parametrize("size", [(512, 512), (301, 403), (256, 256), (33, 68), (17, 45), (1, 130)], ids=lambda s: f"{s[0]}x{s[1]}")
+def test_soft_erosion_edges_vs_oracle(swapper, size, ks):
+    """tail.soft_erosion_frames (per-sample maximum; uint8 labels and their fp32 copy give the same bits) and the module path (one maximum
+    for the whole tensor) against oracle/cv_ref.py, for iterations 1 / 2 / 3 and thresholds 0.9 / 0.6."""
+    from canonswap_amd import tail
+    from oracle import cv_ref as R
+    H, W = size
+    e = swapper.engine
+    m = _edge_masks(H, W, seed=H * 1000 + W)
+    mf = torch.from_numpy(m.astype(np.float32))
+    md = torch.from_numpy(m).cuda()
+    for iters in (1, 2, 3):
+        for thr in (0.9, 0.6):
+            se = swapper.soft_mask(ks, thr, iters)
+            what = (H, W, ks, iters, thr)
+            got = tail.soft_erosion_frames(e, md, se.weight, ks, thr, iters)
+            assert torch.equal(got, tail.soft_erosion_frames(e, md.float(), se.weight, ks, thr, iters)), what
+            got = got.cpu().numpy()
+            for k in range(len(m)):
+                want, hard = R.soft_erosion(mf[k:k + 1, None], ks, thr, iters)
+                want, hard = want.numpy()[0, 0], hard.numpy()[0, 0]
+                # the frames entry point returns no hard mask: a pixel at 1.0 is above the threshold or the maximum itself
+                hard_got = np.where(hard, got[k] >= 1.0, (got[k] >= 1.0) & (np.abs(want - 1.0) > 1e-5))
+                _compare(got[k], want, hard_got, hard, m[k:k + 1], what + (k,))
+            soft, hard_got = se(mf[:, None])
+            want, hard = R.soft_erosion(mf[:, None], ks, thr, iters)
+            _compare(soft.cpu().numpy()[:, 0], want.numpy()[:, 0], hard_got.cpu().numpy()[:, 0], hard.numpy()[:, 0], m, what + ("module",))
