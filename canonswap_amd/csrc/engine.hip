@@ -1061,6 +1061,21 @@ static void msplit_in(ConvCall& c, int creal)
     c.cg_ck64 = true;
 }
 
+// M's three split-precision 1x1 conv forms on the stage with C channels and an H x H grid (the conv's own: the downsample's output grid);
+// run_M and cs_op_m_pointwise both build their launches here, so the operator test runs the engine's routing
+enum { M_PW1 = 0, M_PW2 = 1, M_DS = 2 };
+int m_pw2_cout_pad(int C) { return C % 64 ? (C + 127) / 128 * 128 : C; }
+static ConvCall m_pointwise(const ConvL& L, int form, const half_t* in, float* out, int B, int H, int C)
+{
+    const int creal = form == M_PW1 ? C : 4 * C;       // real channels of the split input
+    ConvCall c = mk(L, in, nhwc(nullptr, H, H, 2 * creal), B, 1, H, H);
+    msplit_in(c, creal);
+    c.p.out0 = nhwc(out, H, H, form == M_PW1 ? 4 * C : form == M_PW2 ? C : 2 * C); c.p.out0_f32 = 1;
+    if (form == M_PW1) c.p.act0 = ACT_GELU;                                           // convnextv2.py:39-40
+    if (form == M_PW2) { c.p.res = c.p.out0; c.p.res_f32 = 1; }                       // :42 + residual :45
+    return c;
+}
+
 int run_M(cs_engine* e, int B, const float* img, float* out, hipStream_t st)
 {
     if (!e->has_m) { cs_set_error("the motion extractor weights (M.*) were not uploaded"); return -1; }
@@ -1077,23 +1092,16 @@ int run_M(cs_engine* e, int B, const float* img, float* out, hipStream_t st)
         for (int j = 0; j < S.n; ++j) {
             const cs_engine::MBlk& K = S.blk[j];
             TRY(e->run(1, st, [&] { return launch_m_dwln(e->m_x, K.dw_w, K.dw_b, K.ln_g, K.ln_b, e->m_y, B, H, H, C, st); }, "m_dwln"));
-            ConvCall a = mk(K.pw1, e->m_y, nhwc(nullptr, H, H, 2 * C), B, 1, H, H);              // convnextv2.py:39-40
-            msplit_in(a, C);
-            a.p.act0 = ACT_GELU; a.p.out0 = nhwc(e->m_h32, H, H, 4 * C); a.p.out0_f32 = 1;
+            ConvCall a = m_pointwise(K.pw1, M_PW1, e->m_y, e->m_h32, B, H, C);
             TRY(go(e, a, st));
             TRY(e->run(1, st, [&] { return launch_m_grn(e->m_h32, K.grn_g, K.grn_b, e->m_sumsq, e->m_scale, e->m_h, B, H * H, 4 * C, st); }, "m_grn"));
-            ConvCall b = mk(K.pw2, e->m_h, nhwc(nullptr, H, H, 8 * C), B, 1, H, H);              // :42 + residual :45
-            msplit_in(b, 4 * C);
-            b.p.res = nhwc(e->m_x, H, H, C); b.p.res_f32 = 1;
-            b.p.out0 = nhwc(e->m_x, H, H, C); b.p.out0_f32 = 1;
+            ConvCall b = m_pointwise(K.pw2, M_PW2, e->m_h, e->m_x, B, H, C);
             TRY(go(e, b, st));
         }
         if (i < 3) {   // downsample_layers[i+1]: LayerNorm + Conv2d(k=2, s=2) as space-to-depth + 1x1 conv
             TRY(e->run(1, st, [&] { return launch_m_ln_s2d(e->m_x, S.ds_g, S.ds_b, e->m_y, B, H, H, C, st); }, "m_ln_s2d"));
             H /= 2;
-            ConvCall d = mk(S.ds, e->m_y, nhwc(nullptr, H, H, 8 * C), B, 1, H, H);
-            msplit_in(d, 4 * C);
-            d.p.out0 = nhwc(e->m_x, H, H, 2 * C); d.p.out0_f32 = 1;
+            ConvCall d = m_pointwise(S.ds, M_DS, e->m_y, e->m_x, B, H, C);
             TRY(go(e, d, st));
         }
     }
@@ -1220,7 +1228,7 @@ extern "C" int cs_finalize_weights(cs_engine* e)
                 TRY(get_conv(e, q + ".pw1", 3 * C, 4 * C, 4 * C, 1, 1, 1, 4 * C, (double)C * 4 * C, &K.pw1));   // split-precision: 3 x Cin
                 // (stage 0: 96 output channels in one 128-channel block - 128x128 tiles stage a position's 1152 input channels once; as three
                 // 32-channel blocks on 128x32 tiles every block staged them again: 0.25 -> 0.17 ms per 64 frames; stage 1's 192 channels as two blocks instead of three 64-channel ones: 0.15 -> 0.16, not taken)
-                TRY(get_conv(e, q + ".pw2", 12 * C, C % 64 ? (C + 127) / 128 * 128 : C, C, 1, 1, 1, C, (double)C * 4 * C, &K.pw2));
+                TRY(get_conv(e, q + ".pw2", 12 * C, m_pw2_cout_pad(C), C, 1, 1, 1, C, (double)C * 4 * C, &K.pw2));
             }
             if (i < 3) {
                 snprintf(n, sizeof n, "M.ds%d", i);
@@ -1799,4 +1807,53 @@ extern "C" long cs_op_chan_stats_partial_floats(int N, long P, int C) { return c
 extern "C" int cs_op_chan_stats(const void* x, int is_f32, int N, long P, int C, float eps, float* partials, float* stats, void* stream)
 {
     return launch_chan_stats(x, is_f32, N, P, C, eps, partials, stats, (hipStream_t)stream);
+}
+
+// ---- operator level: the motion extractor's kernels (csrc/motion.hip) without an engine, and its 1x1 convs through the engine's routing
+extern "C" int cs_op_m_stem(const float* img, const float* w, const float* b, const float* g, const float* be, float* x, int N, int HI, int WI,
+                            void* stream)
+{
+    return launch_m_stem(img, w, b, g, be, x, N, HI, WI, (hipStream_t)stream);
+}
+
+extern "C" int cs_op_m_dwln(const float* x, const float* wt, const float* b, const float* g, const float* be, void* y, int N, int H, int W, int C,
+                            void* stream)
+{
+    return launch_m_dwln(x, wt, b, g, be, (half_t*)y, N, H, W, C, (hipStream_t)stream);
+}
+
+extern "C" int cs_op_m_ln_s2d(const float* x, const float* g, const float* be, void* y, int N, int H, int W, int C, void* stream)
+{
+    return launch_m_ln_s2d(x, g, be, (half_t*)y, N, H, W, C, (hipStream_t)stream);
+}
+
+extern "C" int cs_op_m_grn(const float* h, const float* gamma, const float* beta, float* sumsq, float* scale, void* out, int N, int P, int C,
+                           void* stream)
+{
+    return launch_m_grn(h, gamma, beta, sumsq, scale, (half_t*)out, N, P, C, (hipStream_t)stream);
+}
+
+extern "C" int cs_op_m_head(const float* x, const float* g, const float* be, const float* hw, const float* hb, float* out, int N, int P, void* stream)
+{
+    return launch_m_head(x, g, be, hw, hb, out, N, P, (hipStream_t)stream);
+}
+
+extern "C" int cs_op_m_pointwise(cs_engine* e, int form, const void* in, const void* wpacked, const float* bias, float* out, int N, int H, int C,
+                                 void* stream)
+{
+    if (!e) { cs_set_error("null engine"); return -1; }
+    if ((C != 96 && C != 192 && C != 384 && C != 768) || form < M_PW1 || form > M_DS || (form == M_DS && C == 768) || N < 1 || H < 1) {
+        cs_set_error("cs_op_m_pointwise: no such layer (form %d, C %d, N %d, H %d)", form, C, N, H);
+        return -1;
+    }
+    DevGuard guard(e->dev);
+    ConvL L;      // the geometry cs_finalize_weights gives M's layers
+    L.w = (const half_t*)wpacked; L.b = bias;
+    L.Cin = form == M_PW1 ? 3 * C : 12 * C;
+    L.Cout = form == M_PW1 ? 4 * C : form == M_PW2 ? C : 2 * C;
+    L.Cout_pad = form == M_PW2 ? m_pw2_cout_pad(C) : L.Cout;
+    L.macs_per_pos = (double)L.Cout * (L.Cin / 3);
+    L.name = form == M_PW1 ? "m_pw1" : form == M_PW2 ? "m_pw2" : "m_ds";
+    ConvCall c = m_pointwise(L, form, (const half_t*)in, out, N, H, C);
+    return go(e, c, (hipStream_t)stream);
 }

@@ -196,6 +196,24 @@ int cs_op_grid_sample3d(const float* in_hwdc, const float* grid, float* out32, v
 long cs_op_chan_stats_partial_floats(int N, long P, int C);
 int cs_op_chan_stats(const void* x, int is_f32, int N, long P, int C, float eps, float* partials, float* stats, void* stream);
 
+/* The motion extractor's kernels one at a time (csrc/motion.hip; weights as pack._pack_M lays them out).  A split output is the fp16 pair
+ * [hi | lo] per position (hi = fp16(v), lo = fp16(v - hi)), 2 C values.
+ * stem: img fp32 [N][3][HI][256] -> x fp32 [N][HI/4][64][96], Conv2d(3, 96, 4, s 4) + LayerNorm (w: [48][96]) */
+int cs_op_m_stem(const float* img, const float* w, const float* b, const float* g, const float* be, float* x, int N, int HI, int WI, void* stream);
+/* depth-wise 7x7 + LayerNorm: x fp32 [N][H][W][C] -> y split [N][H][W][2C] (wt: [49][C], C = 96, 192, 384 or 768) */
+int cs_op_m_dwln(const float* x, const float* wt, const float* b, const float* g, const float* be, void* y, int N, int H, int W, int C, void* stream);
+/* LayerNorm + space-to-depth: x fp32 [N][H][W][C] -> y split [N][H/2][W/2][2 x 4C], inner channel (dy*2+dx)*C + c */
+int cs_op_m_ln_s2d(const float* x, const float* g, const float* be, void* y, int N, int H, int W, int C, void* stream);
+/* GRN: h fp32 [N][P][C] -> out split [N][P][2C]; scratch sumsq (N x 16 x C floats) and scale (N x C floats) */
+int cs_op_m_grn(const float* h, const float* gamma, const float* beta, float* sumsq, float* scale, void* out, int N, int P, int C, void* stream);
+/* average pool + LayerNorm + the 7 heads: x fp32 [N][P][768] -> out fp32 [N][328] (hw: [328][768]) */
+int cs_op_m_head(const float* x, const float* g, const float* be, const float* hw, const float* hb, float* out, int N, int P, void* stream);
+/* One of M's split-precision 1x1 convs, routed as run_M routes it on this engine (latency mode included).  C: the stage's channels (96, 192, 384,
+ * 768); wpacked / bias: the layer's pack._pack_M blobs.  form 0 (pwconv1): in split [N][H][H][2C] -> out fp32 [N][H][H][4C] = GELU(conv);
+ * form 1 (pwconv2): in split [N][H][H][8C], out fp32 [N][H][H][C] holds the residual and receives out + conv; form 2 (downsample, C < 768):
+ * in split [N][H][H][8C] from cs_op_m_ln_s2d (H: the output grid) -> out fp32 [N][H][H][2C]. */
+int cs_op_m_pointwise(cs_engine* e, int form, const void* in, const void* wpacked, const float* bias, float* out, int N, int H, int C, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -123,3 +123,80 @@ def chan_stats(x, eps=1e-5, with_partials=False):
 def rel_err(a, b):
     a, b = a.double().cpu(), b.double().cpu()
     return float((a - b).norm() / (b.norm() + 1e-30))
+
+
+# ---- the motion extractor's kernels (cs_op_m_*; csrc/motion.hip).  Split outputs are fp16 [hi | lo] pairs per position.
+M_PW1, M_PW2, M_DS = 0, 1, 2
+
+
+def _st():
+    return C.c_void_p(torch.cuda.current_stream().cuda_stream)
+
+
+def m_stem(img, w, b, g, be):
+    """img fp32 [N, 3, HI, WI] -> x fp32 [N, HI/4, WI/4, 96]"""
+    assert img.is_contiguous()
+    N, _, HI, WI = img.shape
+    x = torch.empty(N, HI // 4, WI // 4, 96, dtype=torch.float32, device=img.device)
+    _lib.check(_lib.load().cs_op_m_stem(_p(img), _p(w), _p(b), _p(g), _p(be), _p(x), N, HI, WI, _st()), "cs_op_m_stem")
+    return x
+
+
+def m_dwln(x, wt, b, g, be, y):
+    """x fp32 [N, H, W, C] -> y (caller's fp16 buffer of N H W 2C values): split(LayerNorm(dwconv7x7(x)))"""
+    assert x.is_contiguous() and y.is_contiguous()
+    N, H, W, Cc = x.shape
+    _lib.check(_lib.load().cs_op_m_dwln(_p(x), _p(wt), _p(b), _p(g), _p(be), _p(y), N, H, W, Cc, _st()), "cs_op_m_dwln")
+    return y
+
+
+def m_ln_s2d(x, g, be):
+    """x fp32 [N, H, W, C] -> split fp16 [N, H/2, W/2, 8C], inner channel (dy*2+dx)*C + c of each half"""
+    assert x.is_contiguous()
+    N, H, W, Cc = x.shape
+    y = torch.empty(N, H // 2, W // 2, 8 * Cc, dtype=torch.float16, device=x.device)
+    _lib.check(_lib.load().cs_op_m_ln_s2d(_p(x), _p(g), _p(be), _p(y), N, H, W, Cc, _st()), "cs_op_m_ln_s2d")
+    return y
+
+
+def m_grn(h, gamma, beta):
+    """h fp32 [N, P, C] -> split fp16 [N, P, 2C]"""
+    assert h.is_contiguous()
+    N, P, Cc = h.shape
+    sumsq = torch.empty(N * 16 * Cc, dtype=torch.float32, device=h.device)
+    scale = torch.empty(N * Cc, dtype=torch.float32, device=h.device)
+    out = torch.empty(N, P, 2 * Cc, dtype=torch.float16, device=h.device)
+    _lib.check(_lib.load().cs_op_m_grn(_p(h), _p(gamma), _p(beta), _p(sumsq), _p(scale), _p(out), N, P, Cc, _st()), "cs_op_m_grn")
+    return out
+
+
+def m_head(x, g, be, hw, hb):
+    """x fp32 [N, P, 768] -> fp32 [N, 328]"""
+    assert x.is_contiguous()
+    N, P, _ = x.shape
+    out = torch.empty(N, 328, dtype=torch.float32, device=x.device)
+    _lib.check(_lib.load().cs_op_m_head(_p(x), _p(g), _p(be), _p(hw), _p(hb), _p(out), N, P, _st()), "cs_op_m_head")
+    return out
+
+
+def m_pointwise(engine, form, x, wpacked, bias, out, C_stage):
+    """One of M's split-precision 1x1 convs through the engine's routing (cs_op_m_pointwise): x split fp16 [N, H, H, 2 Cin'],
+    out fp32 [N, H, H, Cout] (form M_PW2: holds the residual and is updated in place)."""
+    assert x.is_contiguous() and out.is_contiguous()
+    N, H = x.shape[0], x.shape[1]
+    _lib.check(engine.lib.cs_op_m_pointwise(engine.h, form, _p(x), _p(wpacked), _p(bias), _p(out), N, H, C_stage, _st()),
+               "cs_op_m_pointwise")
+    return out
+
+
+def split16(v):
+    """fp32 [..., C] -> the split pair [..., 2C] = [hi | lo] as csrc/motion.hip stores it"""
+    hi = v.half()
+    return torch.cat([hi, (v - hi.float()).half()], -1)
+
+
+def unsplit(y):
+    """[..., 2C] fp16 pair -> (hi + lo) in float64, hi, lo"""
+    c = y.shape[-1] // 2
+    hi, lo = y[..., :c], y[..., c:]
+    return hi.double() + lo.double(), hi, lo
