@@ -6,8 +6,13 @@ already resident in HBM.  Frames shard across ranks (weak scaling: B frames per 
 identity is broadcast once over RCCL before the timed region and the uint8 output frames are gathered to
 rank 0 inside it.  Prints ONE JSON line on rank 0.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N --steps K --warmup W
+
+A plain run does only what the headline figure needs: set up, warm up, time the K steps, write --dump-outputs, print the line.
+--full adds everything else the line can carry, each measured after the headline: the fixed-size job, the one-frame latency engine,
+the device-side chain and v2i body, the per-kernel roofline pass, parity against the fp32 CPU oracle (with its 50 dB gate) and the
+CPU baseline; the --no-* options skip single legs of it.
 
 `python bench.py --gpus N` with N > 1 and no WORLD_SIZE in the environment re-executes itself under
 torch.distributed.run (one rank per GPU, rendezvous on 127.0.0.1), so the command has the same shape at every N.
@@ -58,7 +63,7 @@ def parse_args():
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--batch", type=int, default=int(os.environ.get("CANONSWAP_BENCH_BATCH", "64")),
-                    help="frames per launch and GPU (default 64, the engine's maximum: +1.5 % frames/s over 32 - fewer, longer launches leave fewer "
+                    help="frames per launch and GPU (default 64, the engine's maximum: +1.5 %% frames/s over 32 - fewer, longer launches leave fewer "
                          "idle workgroup slots at the head and tail of each kernel; profiles/r03_v_batch_sweep.txt)")
     ap.add_argument("--frames", type=int, default=0,
                     help="fixed-size job (BASELINE configs[3]: --frames 1200): one step = one pass over a video of this many frames, "
@@ -67,10 +72,14 @@ def parse_args():
     ap.add_argument("--streams", type=int, default=0,
                     help="BASELINE configs[4]: this many concurrent videos, each with its own identity, placed by "
                          "parallel.stream_groups (4 streams on 8 GPUs: stream s on GPU pair {2s, 2s+1})")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-fixed-job", action="store_true", help="skip the fixed-size job reported next to the weak-scaling figure")
-    ap.add_argument("--no-single-frame", action="store_true", help="skip the one-frame-per-call measurement (BASELINE configs[1], latency mode) reported next to the headline")
-    ap.add_argument("--no-chain", action="store_true", help="skip the whole-device-side-frame measurement (crops -> M -> generator -> SoftErosion -> paste-back) "
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also run the fixed-size job, the one-frame latency engine, the device-side chain and v2i body, "
+                         "the roofline pass (HIP events around every launch; writes CANONSWAP_PROFILE_CSV if set), parity against the fp32 CPU "
+                         "oracle and the CPU baseline. Off by default: a plain run measures the headline only")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the parity check against the CPU oracle and the CPU baseline")
+    ap.add_argument("--no-fixed-job", action="store_true", help="with --full: skip the fixed-size job reported next to the weak-scaling figure")
+    ap.add_argument("--no-single-frame", action="store_true", help="with --full: skip the one-frame-per-call measurement (BASELINE configs[1], latency mode) reported next to the headline")
+    ap.add_argument("--no-chain", action="store_true", help="with --full: skip the whole-device-side-frame measurement (crops -> M -> generator -> SoftErosion -> paste-back) "
                                                              "and the v2i body reported next to the headline")
     ap.add_argument("--chain-size", default="1080x1920", help="HxW of the original frames the chain pastes back into")
     ap.add_argument("--latency-mode", action="store_true",
@@ -158,10 +167,16 @@ def main():
     shm = os.path.join("/dev/shm" if os.path.isdir("/dev/shm") else "/tmp",
                        f"canonswap_blobs_{socket.gethostname()}_{os.environ.get('MASTER_PORT', os.getpid())}.npz")
     packer = (rank == 0) if share_gpu else (local_rank == 0)
+    # --full only: BASELINE configs[1] in the same line, a second engine of one frame in latency mode (N = 1 default run only; 0.5 GB of
+    # workspace), and the chain leg
+    single_on = (a.full and rank == 0 and world == 1 and not a.no_single_frame and not a.latency_mode and B > 1 and not a.streams
+                 and a.frames <= 0 and max(1, min(a.identities, 8)) == 1)
+    chain_on = (a.full and rank == 0 and world == 1 and not a.no_chain and not a.latency_mode and not a.streams and a.frames <= 0
+                and max(1, min(a.identities, 8)) == 1)
     if packer:
-        # + the motion extractor M: the chain leg below drives the generator from M's key-points; the other modules' weights
-        # do not depend on its presence (one RNG stream per tensor name)
-        sds = synth.to_torch(synth.make_state_dicts(0, modules=synth.MODULES + ("motion_extractor",)))
+        # + the motion extractor M when the chain leg runs: it drives the generator from M's key-points.  The other
+        # modules' weights do not depend on its presence (one RNG stream per tensor name), and packing M is several seconds of host work
+        sds = synth.to_torch(synth.make_state_dicts(0, modules=synth.MODULES + (("motion_extractor",) if chain_on else ())))
         blobs = pack.build_blobs(sds)
         if world > 1:
             np.savez(shm, **blobs)
@@ -175,11 +190,6 @@ def main():
             os.remove(shm)
     sw = can_swapper(type("Cfg", (), {"device_id": local_rank, "flag_force_cpu": False})(), packed_blobs=blobs, max_batch=B,
                      latency_mode=a.latency_mode)
-    # BASELINE configs[1] in the same line: a second engine of one frame in latency mode (N = 1 default run only; 0.5 GB of workspace)
-    single_on = (rank == 0 and world == 1 and not a.no_single_frame and not a.latency_mode and B > 1 and not a.streams and a.frames <= 0
-                 and max(1, min(a.identities, 8)) == 1)
-    chain_on = (rank == 0 and world == 1 and not a.no_chain and not a.latency_mode and not a.streams and a.frames <= 0
-                and max(1, min(a.identities, 8)) == 1)
     if not single_on:
         del blobs                                            # the one-frame engine is built AFTER the headline timing
     eng = sw.engine
@@ -231,7 +241,7 @@ def main():
 
     weak = a.frames <= 0
     plan = Plan((B // k) * len(groups[0]) if weak else a.frames)
-    fixed_T = 0 if (a.frames > 0 or a.streams or a.no_fixed_job) else (1200 if world > 1 else 300)      # configs[3] / configs[2]
+    fixed_T = 0 if (not a.full or a.frames > 0 or a.streams or a.no_fixed_job) else (1200 if world > 1 else 300)      # configs[3] / configs[2]
     fplan = Plan(fixed_T) if fixed_T else None
     out_u8 = torch.empty(max(plan.n_local, fplan.n_local if fplan else 0, 1), 512, 512, 3, dtype=torch.uint8, device=dev)
     gather_on = distd and k == 1 and (len(groups[mine[0][0]]) > 1 or force)
@@ -485,7 +495,7 @@ def main():
 
     # ---- roofline of the dominant kernel family (conv_halo_kernel): HIP events around every launch, same workload
     prof, sparse_ms, sparse_n = None, 0.0, 0
-    if rank == 0:
+    if a.full and rank == 0:
         import csv as _csv2
         import tempfile as _tf
         ptmp = _tf.NamedTemporaryFile(suffix=".csv", delete=False); ptmp.close()
@@ -503,11 +513,11 @@ def main():
                 if row["label"] == "dm_sparse":
                     sparse_ms += float(row["ms"]); sparse_n += 1
         os.remove(ptmp.name)
-    if distd:
+    if a.full and distd:
         dist.barrier()
 
     cpu, parity = None, None
-    if rank == 0 and world == 1 and not a.no_cpu_baseline:
+    if a.full and rank == 0 and world == 1 and not a.no_cpu_baseline:
         from oracle import canonswap_ref as O          # cpu_baseline leg: the oracle timed on this node's host cores
         cores = min(os.cpu_count() or 1, 16)           # threads used ("cores"): the fastest count on the GPU box's host (profiles/r05_r_cpu_threads.txt: 0.59 frames/s at 16, 0.45 at 32, 0.14 at 128 of 256 cores)
         torch.set_num_threads(cores)
@@ -564,7 +574,7 @@ def main():
 
     traffic, traffic_src, warp_traffic = None, None, None
     tpath = os.path.join(ROOT, "profiles", "hbm_traffic.json")
-    if rank == 0 and os.path.exists(tpath):      # PMC counters cannot be read from inside this process: committed rocprofv3 passes
+    if a.full and rank == 0 and os.path.exists(tpath):      # PMC counters cannot be read from inside this process: committed rocprofv3 passes
         t = json.load(open(tpath))
         if int(t.get("batch", -1)) == B:
             traffic = t["fetch_bytes_per_conv_launch_x2"] + t["write_bytes_per_conv_launch_raw"]
@@ -575,8 +585,6 @@ def main():
     if rank == 0:
         frames = K * plan.per_stream * S
         fps = frames / dt
-        conv_s = prof["conv_ms"] / 1e3
-        achieved = prof["conv_flops"] / conv_s / 1e12
         if a.streams:
             wl = (f"BASELINE configs[4]: {S} concurrent 512x512 video streams, stream s on ranks {groups[0] if S == 1 else '/'.join(str(g) for g in groups)}, "
                   "one identity per stream")
@@ -597,39 +605,44 @@ def main():
                        "frames_per_step": plan.per_stream * S, "frames_per_launch_per_gpu": B, "frames_total": frames,
                        "parallelism": f"frame-shard x{world}" + (f", {S} streams" if a.streams else ""), "identities_resident": nid,
                        "latency_mode": bool(a.latency_mode), "accumulate": "fp32", "debug_decodes": False},
-            "roofline": {"bound": "mfma", "achieved": round(achieved, 2), "peak": PEAK_TFLOPS_F16, "unit": "TFLOP/s",
-                         "frac": round(achieved / PEAK_TFLOPS_F16, 4), "traffic": traffic, "traffic_unit": "HBM bytes per conv launch",
-                         "traffic_source": traffic_src,
-                         "kernel": "conv_wide_kernel / conv_halo_kernel / vol32_kernel (every convolution launch of the step)", "launches_per_step": prof["conv_launches"] // K,
-                         "avg_launch_us": round(prof["conv_ms"] * 1e3 / prof["conv_launches"], 2),
-                         "algorithmic_gflop_per_frame": round(prof["conv_flops"] / (K * plan.n_local) / 1e9, 1),
-                         # MFMA work actually issued (padded channel counts, phase-decomposed up-sampling convs): the utilisation of the
-                         # matrix pipe, as opposed to the algorithmic rate above
-                         "executed_tflops": round(prof["exec_flops"] / conv_s / 1e12, 2),
-                         "executed_frac": round(prof["exec_flops"] / conv_s / 1e12 / PEAK_TFLOPS_F16, 4),
-                         "other_kernels_ms_per_step": round((prof["other_ms"] + prof["warp_ms"]) / K, 3),
-                         "conv_ms_per_step": round(prof["conv_ms"] / K, 3),
-                         "end_to_end_frac": round(ALGO_GFLOP_PER_FRAME * 1e9 * fps / world / (PEAK_TFLOPS_F16 * 1e12), 4)},
-            # the HBM-bound row of the path: softmax -> deformation -> trilinear feature warp in one kernel (dm_softmax_warp_kernel)
-            "warp_roofline": {"bound": "hbm", "kernel": "dm_softmax_warp_kernel (mask softmax + deformation + feature warp; the logits arrive as 10 x 22 "
-                                                        "fp32 partial sums per four voxels from the mask conv's in-tile kw sum: 2.5x the algorithmic 5.77 MB)",
-                              "algorithmic_mb_per_frame": round(WARP_BYTES_PER_FRAME / 1e6, 2),
-                              "achieved": round(WARP_BYTES_PER_FRAME * plan.n_local * K / (prof["warp_ms"] / 1e3) / 1e9, 1),
-                              "peak": 8000.0, "unit": "GB/s",
-                              "frac": round(WARP_BYTES_PER_FRAME * plan.n_local * K / (prof["warp_ms"] / 1e3) / 8e12, 4),
-                              "avg_launch_us": round(prof["warp_ms"] * 1e3 / max(prof["warp_launches"], 1), 2), "traffic": warp_traffic,
-                              "traffic_unit": "HBM bytes per warp launch (FETCH_SIZE x2 + WRITE_SIZE, profiles/hbm_traffic.json)"},
-            # the other HBM row SURVEY 8d names: the sparse-motion sampler (dense_motion.py:29-65: 22 deformed copies of the 4-channel compressed
-            # volume + 22 heat maps, concatenated) - per call 4 x 65536 x 2 B read + 22 x 4 x 65536 x 2 B written (the 17 MB grid is generated from
-            # the 21 key-points, never read) = 12.06 MB at 2-byte storage; two calls per frame
-            "sparse_roofline": {"bound": "hbm", "kernel": "dm_sparse_kernel (sparse motions + deformed features + heat maps + concat into the hourglass input)",
-                                "algorithmic_mb_per_call": 12.06, "calls_per_frame": 2,
-                                "achieved": round(12.06e6 * 2 * K * plan.n_local / max(sparse_ms, 1e-9) / 1e6, 1) if sparse_n else None,
-                                "peak": 8000.0, "unit": "GB/s",
-                                "frac": round(12.06e6 * 2 * K * plan.n_local / max(sparse_ms, 1e-9) / 1e6 / 8000.0, 4) if sparse_n else None,
-                                "avg_launch_us": round(sparse_ms * 1e3 / sparse_n, 2) if sparse_n else None},
-            "cpu_baseline": cpu,
         }
+        if a.full:
+            conv_s = prof["conv_ms"] / 1e3
+            achieved = prof["conv_flops"] / conv_s / 1e12
+            line.update({
+                "roofline": {"bound": "mfma", "achieved": round(achieved, 2), "peak": PEAK_TFLOPS_F16, "unit": "TFLOP/s",
+                             "frac": round(achieved / PEAK_TFLOPS_F16, 4), "traffic": traffic, "traffic_unit": "HBM bytes per conv launch",
+                             "traffic_source": traffic_src,
+                             "kernel": "conv_wide_kernel / conv_halo_kernel / vol32_kernel (every convolution launch of the step)", "launches_per_step": prof["conv_launches"] // K,
+                             "avg_launch_us": round(prof["conv_ms"] * 1e3 / prof["conv_launches"], 2),
+                             "algorithmic_gflop_per_frame": round(prof["conv_flops"] / (K * plan.n_local) / 1e9, 1),
+                             # MFMA work actually issued (padded channel counts, phase-decomposed up-sampling convs): the utilisation of the
+                             # matrix pipe, as opposed to the algorithmic rate above
+                             "executed_tflops": round(prof["exec_flops"] / conv_s / 1e12, 2),
+                             "executed_frac": round(prof["exec_flops"] / conv_s / 1e12 / PEAK_TFLOPS_F16, 4),
+                             "other_kernels_ms_per_step": round((prof["other_ms"] + prof["warp_ms"]) / K, 3),
+                             "conv_ms_per_step": round(prof["conv_ms"] / K, 3),
+                             "end_to_end_frac": round(ALGO_GFLOP_PER_FRAME * 1e9 * fps / world / (PEAK_TFLOPS_F16 * 1e12), 4)},
+                # the HBM-bound row of the path: softmax -> deformation -> trilinear feature warp in one kernel (dm_softmax_warp_kernel)
+                "warp_roofline": {"bound": "hbm", "kernel": "dm_softmax_warp_kernel (mask softmax + deformation + feature warp; the logits arrive as 10 x 22 "
+                                                            "fp32 partial sums per four voxels from the mask conv's in-tile kw sum: 2.5x the algorithmic 5.77 MB)",
+                                  "algorithmic_mb_per_frame": round(WARP_BYTES_PER_FRAME / 1e6, 2),
+                                  "achieved": round(WARP_BYTES_PER_FRAME * plan.n_local * K / (prof["warp_ms"] / 1e3) / 1e9, 1),
+                                  "peak": 8000.0, "unit": "GB/s",
+                                  "frac": round(WARP_BYTES_PER_FRAME * plan.n_local * K / (prof["warp_ms"] / 1e3) / 8e12, 4),
+                                  "avg_launch_us": round(prof["warp_ms"] * 1e3 / max(prof["warp_launches"], 1), 2), "traffic": warp_traffic,
+                                  "traffic_unit": "HBM bytes per warp launch (FETCH_SIZE x2 + WRITE_SIZE, profiles/hbm_traffic.json)"},
+                # the other HBM row SURVEY 8d names: the sparse-motion sampler (dense_motion.py:29-65: 22 deformed copies of the 4-channel compressed
+                # volume + 22 heat maps, concatenated) - per call 4 x 65536 x 2 B read + 22 x 4 x 65536 x 2 B written (the 17 MB grid is generated from
+                # the 21 key-points, never read) = 12.06 MB at 2-byte storage; two calls per frame
+                "sparse_roofline": {"bound": "hbm", "kernel": "dm_sparse_kernel (sparse motions + deformed features + heat maps + concat into the hourglass input)",
+                                    "algorithmic_mb_per_call": 12.06, "calls_per_frame": 2,
+                                    "achieved": round(12.06e6 * 2 * K * plan.n_local / max(sparse_ms, 1e-9) / 1e6, 1) if sparse_n else None,
+                                    "peak": 8000.0, "unit": "GB/s",
+                                    "frac": round(12.06e6 * 2 * K * plan.n_local / max(sparse_ms, 1e-9) / 1e6 / 8000.0, 4) if sparse_n else None,
+                                    "avg_launch_us": round(sparse_ms * 1e3 / sparse_n, 2) if sparse_n else None},
+                "cpu_baseline": cpu,
+            })
         if parity:
             line.update(parity)
         if fixed:

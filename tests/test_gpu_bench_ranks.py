@@ -26,7 +26,7 @@ def _run(cmd):
 
 
 def test_two_rank_fixed_size_job_equals_single_process(tmp_path):
-    common = ["--frames", "18", "--batch", "4", "--steps", "1", "--warmup", "0", "--no-cpu-baseline"]
+    common = ["--frames", "18", "--batch", "4", "--steps", "1", "--warmup", "0", "--full", "--no-cpu-baseline"]      # --full: the roofline pass
     crc1, crc2 = str(tmp_path / "one.json"), str(tmp_path / "two.json")
     one = _run([sys.executable, "bench.py", "--gpus", "1", *common, "--dump-crc", crc1])
     two = _run([sys.executable, "bench.py", "--gpus", "2", "--backend", "gloo", *common, "--dump-crc", crc2])      # self-spawned ranks
@@ -86,9 +86,10 @@ def test_rccl_world_of_one_runs_every_collective_and_equals_the_plain_run(tmp_pa
 
 
 def test_rccl_world_of_one_weak_scaling_line_and_stream_subcommunicators(tmp_path):
-    """The default (weak-scaling) line with its fixed-size job through RCCL at N = 1, and --streams 2 with dist.new_group sub-communicators
+    """The weak-scaling line with its fixed-size job (--full) through RCCL at N = 1, and --streams 2 with dist.new_group sub-communicators
     (one per stream, formed and barriered on the device) against the same streams without a process group."""
-    line = _run([sys.executable, "bench.py", "--gpus", "1", "--force-dist", "--batch", "4", "--steps", "2", "--warmup", "1", "--no-cpu-baseline"])
+    line = _run([sys.executable, "bench.py", "--gpus", "1", "--force-dist", "--batch", "4", "--steps", "2", "--warmup", "1", "--full",
+                 "--no-cpu-baseline"])
     assert line["backend"] == "nccl" and line["scaling"] == "weak" and line["fixed_job"]["frames"] == 300 and line["value"] > 0
     common = ["--streams", "2", "--frames", "6", "--batch", "4", "--steps", "1", "--warmup", "0", "--no-cpu-baseline"]
     c1, c2 = str(tmp_path / "plain"), str(tmp_path / "rccl")
@@ -136,3 +137,14 @@ def test_dump_outputs_are_the_last_timed_step(tmp_path):
         assert np.array_equal(f, np.round(f)) and f.min() >= 0 and f.max() <= 255
         assert zlib.crc32(f.astype(np.uint8).tobytes()) == crcs[j]
     assert np.array_equal(idx, np.load(d2 / "out_frame_index.npy")) and np.array_equal(frames, np.load(d2 / "out_frames.npy"))
+
+
+def test_plain_run_carries_the_headline_only():
+    """Without --full the run sets up, warms up, times the steps and prints the headline: no fixed-size job, one-frame engine, chain, roofline
+    pass, parity or CPU baseline."""
+    line = _run([sys.executable, "bench.py", "--gpus", "1", "--batch", "4", "--steps", "2", "--warmup", "1"])
+    assert line["metric"] == "frames/sec at 512x512 (generator hot path F->W->T->R->W->G)" and line["unit"] == "frames/s"
+    assert line["higher_is_better"] is True and line["dtype"] == "f16" and line["steps"] == 2 and line["warmup"] == 1
+    assert line["value"] > 0 and line["ms_per_step"] > 0 and abs(line["value"] * line["ms_per_step"] / 1e3 - 4) < 0.01
+    moved = ("roofline", "warp_roofline", "sparse_roofline", "cpu_baseline", "psnr_db_min", "fixed_job", "single_frame", "chain", "v2i_body")
+    assert not set(moved) & set(line), sorted(set(moved) & set(line))
