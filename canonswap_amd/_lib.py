@@ -27,6 +27,7 @@ ABI_SYMBOLS = [
     "cs_motion_extract", "cs_motion_keypoints", "cs_soft_erosion_frames", "cs_paste_back_batch", "cs_swap_frames", "cs_animate_frames", "cs_profile_begin", "cs_profile_end", "cs_profile_exec_flops", "cs_op_conv", "cs_op_grid_sample3d",
     "cs_op_chan_stats", "cs_op_chan_stats_partial_floats", "cs_op_pair_ragged", "cs_op_resblock3d", "cs_op_t_mask",
     "cs_op_m_stem", "cs_op_m_dwln", "cs_op_m_ln_s2d", "cs_op_m_grn", "cs_op_m_head", "cs_op_m_pointwise",
+    "cs_op_dm_compress", "cs_op_dm_sparse", "cs_op_dm_softmax_warp", "cs_op_occ_finish", "cs_op_dm_read",
 ]
 ABI_VERSION = 4          # CS_ABI_VERSION of include/canonswap_hip.h
 HIPCC_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wno-unused-value"]
@@ -414,6 +415,11 @@ def load():
     lib.cs_op_m_grn.argtypes = [vp, vp, vp, vp, vp, vp, ci, ci, ci, vp]
     lib.cs_op_m_head.argtypes = [vp, vp, vp, vp, vp, vp, ci, ci, vp]
     lib.cs_op_m_pointwise.argtypes = [vp, ci, vp, vp, vp, vp, ci, ci, ci, vp]
+    lib.cs_op_dm_compress.argtypes = [vp, vp, vp, vp, ci, ci, ci, ci, vp]
+    lib.cs_op_dm_sparse.argtypes = [vp, ci, vp, vp, ci, vp, ci, ci, ci, ci, ci, vp]
+    lib.cs_op_dm_softmax_warp.argtypes = [vp, vp, vp, vp, ci, vp, ci, vp, vp, vp, ci, ci, ci, ci, vp]
+    lib.cs_op_occ_finish.argtypes = [vp, ci, cf, vp, ci, ci, ci, vp]
+    lib.cs_op_dm_read.argtypes = [vp, ci, ci, vp, vp]
     lib.cs_op_resblock3d.argtypes = [vp, vp, vp, vp, ci, ci, ci, vp, vp, vp, vp, vp, vp, ci, cf, vp]
     lib.cs_op_chan_stats_partial_floats.argtypes = [ci, C.c_long, ci]
     lib.cs_op_chan_stats_partial_floats.restype = C.c_long

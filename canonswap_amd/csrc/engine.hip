@@ -1857,3 +1857,50 @@ extern "C" int cs_op_m_pointwise(cs_engine* e, int form, const void* in, const v
     ConvCall c = m_pointwise(L, form, (const half_t*)in, out, N, H, C);
     return go(e, c, (hipStream_t)stream);
 }
+
+// ---- operator level: the dense-motion kernels of W (csrc/kernels.hip) without an engine, and the engine's dense-motion buffers as the last
+// call left them (cs_op_dm_read): the tests run W through the public entry points and check each layer on the engine's own input
+extern "C" int cs_op_dm_compress(const float* f_hwdc, const float* w, const float* b, void* comp, int N, int D, int H, int W, void* stream)
+{
+    if (!f_hwdc || !w || !b || !comp || N < 1 || D < 1 || H < 1 || W < 1) { cs_set_error("cs_op_dm_compress: bad arguments"); return -1; }
+    return launch_dm_compress(f_hwdc, w, b, (half_t*)comp, N, D, H, W, (hipStream_t)stream);
+}
+
+extern "C" int cs_op_dm_sparse(const void* comp, int shared_comp, const float* kp_d, const float* kp_s, int shared_kps, void* out, int ostride,
+                               int N, int D, int H, int W, void* stream)
+{
+    if (!comp || !kp_d || !kp_s || !out || N < 1 || D < 2 || H < 2 || W < 2 || ostride < 112) { cs_set_error("cs_op_dm_sparse: bad arguments"); return -1; }
+    return launch_dm_sparse((const half_t*)comp, kp_d, kp_s, (half_t*)out, ostride, N, D, H, W, (hipStream_t)stream, shared_comp != 0, shared_kps != 0);
+}
+
+extern "C" int cs_op_dm_softmax_warp(const float* part, const float* bias, const float* kp_d, const float* kp_s, int shared_kps, const float* in_hwdc,
+                                     int shared_in, float* out32, void* out16, float* deform, int N, int D, int H, int W, void* stream)
+{
+    if (!part || !bias || !kp_d || !kp_s || !in_hwdc || N < 1 || H < 2) { cs_set_error("cs_op_dm_softmax_warp: bad arguments"); return -1; }
+    if (W & 3) { cs_set_error("cs_op_dm_softmax_warp: compact-2 partials need a width that is a multiple of 4"); return -1; }
+    return launch_dm_softmax_warp(part, bias, kp_d, kp_s, in_hwdc, out32, (half_t*)out16, deform, N, D, H, W, (hipStream_t)stream, 2,
+                                  shared_in != 0, shared_kps != 0);
+}
+
+extern "C" int cs_op_occ_finish(const float* part, int taps, float bias, float* occ, int N, int H, int W, void* stream)
+{
+    if (!part || !occ || N < 1 || H < 1 || W < 1) { cs_set_error("cs_op_occ_finish: bad arguments"); return -1; }
+    if (taps == 49) return launch_occ_finish49(part, bias, occ, N, H, W, (hipStream_t)stream);
+    if (taps == 7) return launch_occ_finish(part, bias, occ, N, H, W, (hipStream_t)stream);
+    cs_set_error("cs_op_occ_finish: taps %d (7 or 49)", taps);
+    return -1;
+}
+
+extern "C" int cs_op_dm_read(cs_engine* e, int which, int B, void* dst, void* stream)
+{
+    ENTER(e, B);
+    if (!dst) { cs_set_error("cs_op_dm_read: null destination"); return -1; }
+    static const long lsz[6] = {65536L * 144, 16L * 1024 * 128, 16L * 256 * 256, 16L * 64 * 512, 16L * 16 * 1024, 16L * 4 * 1024};
+    const void* src; size_t bytes;
+    if (which == CS_DM_COMP) { src = e->dm_comp; bytes = (size_t)B * VOX * 4 * sizeof(half_t); }
+    else if (which >= CS_DM_L0 && which <= CS_DM_L0 + 5) { src = e->dm_l[which - CS_DM_L0]; bytes = (size_t)B * lsz[which - CS_DM_L0] * sizeof(half_t); }
+    else if (which == CS_DM_PRED) { src = e->dm_pred; bytes = (size_t)B * VOX * 144 * sizeof(half_t); }
+    else if (which == CS_DM_LOGITS) { src = e->dm_logits; bytes = (size_t)B * VOX / 4 * 220 * sizeof(float); }
+    else { cs_set_error("cs_op_dm_read: no buffer %d", which); return -1; }
+    return copy_dd(dst, src, bytes, (hipStream_t)stream);
+}

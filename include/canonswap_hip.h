@@ -214,6 +214,33 @@ int cs_op_m_head(const float* x, const float* g, const float* be, const float* h
  * in split [N][H][H][8C] from cs_op_m_ln_s2d (H: the output grid) -> out fp32 [N][H][H][2C]. */
 int cs_op_m_pointwise(cs_engine* e, int form, const void* in, const void* wpacked, const float* bias, float* out, int N, int H, int C, void* stream);
 
+/* The dense-motion kernels of W one at a time (csrc/kernels.hip; weights as pack._pack_W lays them out).  Volumes are [N][D][H][W] voxels.
+ * compress: f fp32 HWDC [N][H][W][D][32] -> comp fp16 [N][D][H][W][4] = ReLU(conv1x1 + BN folded) (w: [4][32], b: [4]) */
+int cs_op_dm_compress(const float* f_hwdc, const float* w, const float* b, void* comp, int N, int D, int H, int W, void* stream);
+/* sparse motions + heat maps: comp fp16 [N][D][H][W][4] (shared_comp: one volume [1][D][H][W][4] for all N), kp_d [N][21][3], kp_s [N][21][3]
+ * (shared_kps: [1][21][3]) -> 112 fp16 channels per voxel at voxel stride ostride (a multiple of 8, 16-byte aligned): channel 5 k = heat map of
+ * slot k (0 for k = 0), 5 k + 1 .. 5 k + 4 = comp sampled at slot k's sparse motion, 110 / 111 = zero.  D, H >= 2, 2 <= W <= 64. */
+int cs_op_dm_sparse(const void* comp, int shared_comp, const float* kp_d, const float* kp_s, int shared_kps, void* out, int ostride,
+                    int N, int D, int H, int W, void* stream);
+/* mask softmax + deformation + feature warp: part = the mask conv's compact-2 partials fp32 [N][D][H][W/4][10][22] (tile T, j <-> output column
+ * 4 T - 3 + j, see cs_op_dm_read), bias [22]; in fp32 HWDC [N][H][W][D][32] (shared_in: one volume) -> out32 fp32 / out16 fp16 HWDC (either may
+ * be null), deform fp32 [N][D][H][W][3] (may be null).  D = 16, W a multiple of 16. */
+int cs_op_dm_softmax_warp(const float* part, const float* bias, const float* kp_d, const float* kp_s, int shared_kps, const float* in_hwdc,
+                          int shared_in, float* out32, void* out16, float* deform, int N, int D, int H, int W, void* stream);
+/* occlusion finish: occ fp32 [N][H][W] = sigmoid(bias + the shifted partial sums, zero padding).  taps 49: part [N][H][W][64] with channel
+ * ky * 7 + kx (the batched path's 1x1 conv); taps 7: part [N][H][W][16] with channel kx (latency mode's (7,1)-tap conv). */
+int cs_op_occ_finish(const float* part, int taps, float bias, float* occ, int N, int H, int W, void* stream);
+/* Copies one of the engine's dense-motion buffers, as the last call (cs_warp, cs_warp_forward, cs_animate_frames) left it, to dst on `stream`;
+ * B: samples to copy (<= max_batch).
+ *   CS_DM_COMP:    fp16 [B][16][64][64][4] (after a shared-volume call only sample 0 is valid)
+ *   CS_DM_L0 + i:  fp16 [B][16][S][S][lw], S = 64 >> i, lw = 144, 128, 256, 512, 1024, 1024 (i = 0 .. 5): channels [0, skip_off) the up-block
+ *                  output, [skip_off, skip_off + cin) the down-block input, skip_off = 32, 64, 128, 256, 512, 0, cin = 112, 64, 128, 256, 512,
+ *                  1024; in level 0 channels [32, 144) are the output of dm_sparse
+ *   CS_DM_PRED:    fp16 [B][16][64][64][144] (the hourglass output; channels 142, 143 zero)
+ *   CS_DM_LOGITS:  fp32 [B][16][64][16][10][22]: the mask conv's compact-2 partials (cs_op_dm_softmax_warp) */
+enum { CS_DM_COMP = 0, CS_DM_L0 = 1, CS_DM_PRED = 7, CS_DM_LOGITS = 8 };
+int cs_op_dm_read(cs_engine* e, int which, int B, void* dst, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

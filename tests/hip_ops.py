@@ -200,3 +200,82 @@ def unsplit(y):
     c = y.shape[-1] // 2
     hi, lo = y[..., :c], y[..., c:]
     return hi.double() + lo.double(), hi, lo
+
+
+# ---- the dense-motion kernels of W (cs_op_dm_*, cs_op_occ_finish; csrc/kernels.hip) and the engine's dense-motion buffers (cs_op_dm_read)
+DM_COMP, DM_L0, DM_PRED, DM_LOGITS = 0, 1, 7, 8
+DM_LW = (144, 128, 256, 512, 1024, 1024)          # concat width of level i (S = 64 >> i)
+
+
+def dm_compress(f_hwdc, w, b, comp):
+    """f fp32 [N, H, W, D, 32] -> comp (caller's fp16 buffer [N, D, H, W, 4])"""
+    assert f_hwdc.is_contiguous() and comp.is_contiguous()
+    N, Hh, Ww, D, _ = f_hwdc.shape
+    _lib.check(_lib.load().cs_op_dm_compress(_p(f_hwdc), _p(w), _p(b), _p(comp), N, D, Hh, Ww, _st()), "cs_op_dm_compress")
+    return comp
+
+
+def dm_sparse(comp, kp_d, kp_s, out, N, shared_comp=False, shared_kps=False):
+    """comp fp16 [1 or N, D, H, W, 4] -> out [N, D, H, W, ostride] fp16 view whose channels [0, 112) receive dm_sparse's output"""
+    assert comp.is_contiguous() and kp_d.is_contiguous() and kp_s.is_contiguous()
+    _, D, Hh, Ww, _ = comp.shape
+    _lib.check(_lib.load().cs_op_dm_sparse(_p(comp), int(shared_comp), _p(kp_d), _p(kp_s), int(shared_kps), _p(out), out.stride(3),
+                                           N, D, Hh, Ww, _st()), "cs_op_dm_sparse")
+    return out
+
+
+def dm_softmax_warp(part, bias, kp_d, kp_s, inp, N, D, Hh, Ww, shared_kps=False, shared_in=False, out32=None, out16=None, deform=None):
+    """part: compact-2 fp32 [N, D, H, W/4, 10, 22]; inp fp32 HWDC [1 or N, H, W, D, 32]"""
+    assert part.is_contiguous() and inp.is_contiguous()
+    _lib.check(_lib.load().cs_op_dm_softmax_warp(_p(part), _p(bias), _p(kp_d), _p(kp_s), int(shared_kps), _p(inp), int(shared_in), _p(out32),
+                                                 _p(out16), _p(deform), N, D, Hh, Ww, _st()), "cs_op_dm_softmax_warp")
+
+
+def occ_finish(part, taps, bias, occ):
+    """part fp32 [N, H, W, 64 (taps 49) or 16 (taps 7)] -> occ (caller's fp32 buffer [N, H, W])"""
+    assert part.is_contiguous() and occ.is_contiguous()
+    N, Hh, Ww, _ = part.shape
+    _lib.check(_lib.load().cs_op_occ_finish(_p(part), taps, float(bias), _p(occ), N, Hh, Ww, _st()), "cs_op_occ_finish")
+    return occ
+
+
+def dm_read(engine, which, B):
+    """One of the engine's dense-motion buffers as the last call left it (shapes: include/canonswap_hip.h, cs_op_dm_read)"""
+    dev = engine.device
+    if which == DM_COMP:
+        out = torch.empty(B, 16, 64, 64, 4, dtype=torch.float16, device=dev)
+    elif DM_L0 <= which < DM_L0 + 6:
+        S = 64 >> (which - DM_L0)
+        out = torch.empty(B, 16, S, S, DM_LW[which - DM_L0], dtype=torch.float16, device=dev)
+    elif which == DM_PRED:
+        out = torch.empty(B, 16, 64, 64, 144, dtype=torch.float16, device=dev)
+    else:
+        out = torch.empty(B, 16, 64, 16, 10, 22, dtype=torch.float32, device=dev)
+    _lib.check(engine.lib.cs_op_dm_read(engine.h, which, B, _p(out), _st()), "cs_op_dm_read")
+    return out
+
+
+def compact2(p):
+    """The mask conv's (kw, c) partials P [N, D, H, W, 7, 22] (P[.., x, kw, c]: input column x's product with tap kw) -> its compact-2
+    hand-over [N, D, H, W/4, 10, 22], as the ST == 9 kw_out epilogue of conv_halo_kernel.h stores it: tile T owns input columns
+    4 T .. 4 T + 3 and writes the 10 output columns o = 4 T - 3 + j it reaches, each the sum over its columns w' of P[4 T + w'][w' + 6 - j]
+    (the terms with 0 <= kw <= 6), w' ascending.  Computed in p's dtype; sum over the tiles reaching o (T ascending) + bias = logit at o."""
+    N, D, Hh, Ww = p.shape[:4]
+    q = p.reshape(N, D, Hh, Ww // 4, 4, 7, 22)
+    out = torch.zeros(N, D, Hh, Ww // 4, 10, 22, dtype=p.dtype, device=p.device)
+    for j in range(10):
+        for t in range(4):
+            kw = t + 6 - j
+            if 0 <= kw <= 6:
+                out[:, :, :, :, j] += q[:, :, :, :, t, kw]
+    return out
+
+
+def compact2_logits(part, bias):
+    """compact-2 partials [N, D, H, W/4, 10, 22] -> logits [N, D, H, W, 22] = bias + the sum over the (up to three) tiles reaching each column"""
+    N, D, Hh, nT = part.shape[:4]
+    Ww = 4 * nT
+    l = torch.zeros(N, D, Hh, Ww + 6, 22, dtype=part.dtype, device=part.device)     # output column o at index o + 3
+    for T in range(nT):
+        l[:, :, :, 4 * T:4 * T + 10] += part[:, :, :, T]
+    return l[:, :, :, 3:3 + Ww] + bias.to(part.dtype)

@@ -173,6 +173,73 @@ def test_upsampled_conv3d_phase_decomposition():
     assert np.abs(out - ref).max() < 1e-12
 
 
+@pytest.fixture(scope="module")
+def w_blobs():
+    """pack._pack_W's blobs of the synthetic warping module and its state dict (numpy)"""
+    from canonswap_amd import synth
+    sd = synth.make_state_dicts(0, modules=("warping_module",))["warping_module"]
+    out = {}
+    pack._pack_W(out, pack._np_sd(sd))
+    return out, pack._np_sd(sd)
+
+
+def _f16(w):
+    return torch.from_numpy(np.asarray(w, np.float64).astype(np.float16).astype(np.float64))
+
+
+def test_mask_conv_kw_split_decomposition(w_blobs):
+    """W.maskp, the (7,7,1)-tap conv with (kw, c) output channels, shifted by kw - 3 along W and summed over kw == the 7x7x7 mask conv."""
+    out, sd = w_blobs
+    w = _f16(sd["dense_motion_network.mask.weight"])                                          # [22][142][7][7][7]
+    wp = torch.from_numpy(pack.unpack_conv(out["W.maskp.w"], 154, 142, 7, 7, 1).astype(np.float64))
+    x = torch.from_numpy(np.random.Generator(np.random.PCG64(3)).standard_normal((1, 142, 5, 6, 9)))
+    ref = F.conv3d(x, w, padding=3)
+    part = F.conv3d(x, wp, padding=(3, 3, 0)).view(1, 7, 22, 5, 6, 9)                        # [.., kw, c, d, h, xin]
+    got = torch.zeros_like(ref)
+    for kw in range(7):
+        lo, hi = max(0, 3 - kw), min(9, 12 - kw)                                              # output x takes input x + kw - 3
+        got[..., lo:hi] += part[:, kw, :, :, :, lo + kw - 3:hi + kw - 3]
+    assert (got - ref).abs().max() < 1e-10 * ref.abs().max()
+
+
+def test_compact2_regrouping_sums_back_to_the_logits():
+    """tests/hip_ops.compact2 (the ST == 9 kw_out epilogue's layout) and compact2_logits == bias + sum_kw P[x + kw - 3][kw], zero padding."""
+    import hip_ops
+    r = np.random.Generator(np.random.PCG64(4))
+    for Wd in (4, 8, 24):
+        P = torch.from_numpy(r.standard_normal((2, 3, 5, Wd, 7, 22)))
+        bias = torch.from_numpy(r.standard_normal(22))
+        part = hip_ops.compact2(P)
+        assert part.shape == (2, 3, 5, Wd // 4, 10, 22)
+        ref = bias.expand(2, 3, 5, Wd, 22).clone()
+        for x in range(Wd):
+            for kw in range(7):
+                if 0 <= x + kw - 3 < Wd:
+                    ref[:, :, :, x] += P[:, :, :, x + kw - 3, kw]
+        assert (hip_ops.compact2_logits(part, bias) - ref).abs().max() < 1e-12
+
+
+def test_occlusion_conv_decompositions(w_blobs):
+    """W.occ49 (a 1x1 conv with the 49 taps as output channels, shifted and summed) and W.occp (7 vertical taps, the 7 horizontal taps as
+    output channels) == the 7x7 occlusion conv over the (c * 16 + d)-flattened prediction; input channel d * 160 + c of the grouped form."""
+    out, sd = w_blobs
+    w = _f16(sd["dense_motion_network.occlusion.weight"])                                     # [1][2272][7][7]
+    Hh, Ww = 9, 11
+    x = torch.from_numpy(np.random.Generator(np.random.PCG64(5)).standard_normal((1, 142, 16, Hh, Ww)))
+    ref = F.conv2d(x.reshape(1, 2272, Hh, Ww), w, padding=3)[0, 0]
+    xg = torch.zeros(1, 16, 160, Hh, Ww, dtype=torch.float64)
+    xg[:, :, :142] = x.permute(0, 2, 1, 3, 4)
+    xg = xg.reshape(1, 2560, Hh, Ww)
+    w49 = torch.from_numpy(pack.unpack_conv(out["W.occ49.w"], 49, 2560, 1, 1, 1).astype(np.float64)).view(49, 2560, 1, 1)
+    p49 = F.pad(F.conv2d(xg, w49)[0], (3, 3, 3, 3))                                            # [49][H + 6][W + 6]
+    got49 = sum(p49[ky * 7 + kx, ky:ky + Hh, kx:kx + Ww] for ky in range(7) for kx in range(7))
+    w7 = torch.from_numpy(pack.unpack_conv(out["W.occp.w"], 7, 2560, 1, 7, 1).astype(np.float64)).view(7, 2560, 7, 1)
+    p7 = F.pad(F.conv2d(xg, w7, padding=(3, 0))[0], (3, 3))                                    # [7][H][W + 6]
+    got7 = sum(p7[kx, :, kx:kx + Ww] for kx in range(7))
+    for got in (got49, got7):
+        assert (got - ref).abs().max() < 1e-10 * ref.abs().max()
+
+
 def test_getid_arithmetic_with_injected_network():
     """can_swap_e2e.py:102-107: nearest resize to 112x112 -> identity network -> L2 normalisation; the network is injected."""
     from canonswap_amd.can_swap_e2e import can_swapper
