@@ -12,11 +12,15 @@ the generator).
     :274      soft_mask(masks[i]) [D2H]                                        cs_soft_erosion_frames
     :279-282  prepare_paste_back + paste_back (two cv2.warpAffine) [host]      cs_paste_back_batch
 
+AnimateChain below is the same for the second program, inference_v2i.py (src/can_swap_pipeline_v2i.py: one source image animated by a
+driving video, the driving identity swapped in); its table stands in the class's docstring.
+
 What stays outside (out of scope): face detection / landmarks / the cropper's geometry (they produce the crops and
 M_c2o), SegFormer face parsing (it produces the 0/1 masks), video decode / encode.
 """
 from __future__ import annotations
 
+import numpy as np
 import torch
 
 from . import tail
@@ -118,4 +122,179 @@ class FrameChain:
         res = {"frames": frames}
         if keep:
             res.update(crops_out=gen, x_t=x_t, x_can=x_can, soft_mask=soft, I=I)
+        return res
+
+
+class AnimateChain:
+    """chain = AnimateChain(swapper);  chain.set_source(crop_u8, mask, M_c2o, img_ori, driving_id);  frames = chain(driving_crops_u8)["frames"]
+
+    The device-side frame of CanSwapPipeline.execute of src/can_swap_pipeline_v2i.py, B driving frames per call:
+
+        reference (host round trips in brackets)                                   here
+        once per source image and driving identity                                 set_source
+        :86-90    prepare_source, get_kp_info, extract_feature_3d, transform_keypoint   cs_prepare_crops, cs_motion_extract, cs_motion_keypoints,
+                                                                                   cs_extract_feature_3d
+        :92-97    warp(f_s, x_s, scale * kp)                                       cs_warp
+        :286-289  swap_module + conv_decode                                        cs_swap_ids, cs_warp_out + cs_spade_decode
+        :294      F.interpolate(swap_can, (256, 256), bilinear)                    cs_resize_half_bilinear
+        :297-298  get_kp_info + transform_keypoint of swap_can_256                 cs_motion_extract + cs_motion_keypoints
+        :308      extract_feature_3d(swap_can_256), there once per frame           cs_extract_feature_3d, once (loop-invariant)
+        :255-258  soft_mask + prepare_paste_back [D2H, cv2.warpAffine]             cs_soft_erosion_frames + cs_warp_affine_f32
+        per driving frame                                                          __call__
+        :223-238  cv2.resize + prepare_videos + make_motion_template [seven tensors D2H]   cs_prepare_crops + cs_motion_extract
+        :301-305  x_t_2 = scale_swap * (kp_swap @ R_swap + delta_t) + t_swap        cs_motion_keypoints_driven
+        :309      warp_decode(f_swap_can_2, x_swap, x_t_2)                         cs_animate_frames
+        :312-321  parse_output [sync + D2H] + paste_back into a copy of the image   (pack_u8 inside cs_animate_frames) cs_paste_back_shared
+
+    There is no refine module in this pipeline.  Outside: everything FrameChain leaves outside, getid (the driving identity is passed in) and
+    concat_frames."""
+
+    def __init__(self, swapper, kernel_size: int = 21, threshold: float = 0.9, iterations: int = 2):
+        self.sw = swapper
+        self.e: Engine = swapper.engine
+        if swapper.motion_extractor is None:
+            raise RuntimeError("AnimateChain: the loaded weights hold no 'motion_extractor' state-dict")
+        self.se = tail.SoftErosion(self.e, kernel_size, threshold, iterations)      # SoftErosion(21, 0.9, 2): can_swap_pipeline_v2i.py:43
+        self._buf = {}
+        self._src = None                                              # source_state()
+        self._side, self._free, self._pending = None, None, []        # prefetch(): side stream, double buffer (as FrameChain)
+
+    def _get(self, key, shape, dtype):
+        t = self._buf.get(key)
+        if t is None or tuple(t.shape) != tuple(shape) or t.dtype != dtype:
+            t = torch.empty(shape, dtype=dtype, device=self.e.device)
+            self._buf[key] = t
+        return t
+
+    # ---- once per (source image, driving identity)
+    def set_source(self, crop_u8, mask, M_c2o, img_ori, driving_id):
+        """crop_u8 (512,512,3) or (256,256,3) u8: the cropper's crop of the source image; mask (Hm,Wm) u8 0/1 or fp32: the parser's
+        `torch.isin(labels, valid)` of that crop; M_c2o 2x3 / 3x3 host, crop -> image; img_ori (Ho,Wo,3) u8; driving_id (1,512).
+        Everything on the device, on the caller's stream.  -> {"I_can" (512,512,3) u8, "swap_can" (1,3,512,512), "x_swap", "x_s" (1,21,3)}"""
+        e = self.e
+        self.drop_prefetches()                                                       # staged key-points were formed with the old kp_swap / pose
+        ori = torch.as_tensor(img_ori)
+        if ori.dtype != torch.uint8 or ori.dim() != 3 or ori.shape[2] != 3:
+            raise ValueError("img_ori: expected ONE HoxWox3 uint8 image")
+        ori = ori.to(e.device).contiguous()
+        m = torch.as_tensor(mask)
+        if m.dim() != 2:
+            raise ValueError("mask: expected ONE (H, W) mask in the crop's frame")
+        M = np.ascontiguousarray(np.asarray(M_c2o, dtype=np.float64).reshape(-1)[:6]).copy()
+        I_s = tail.prepare_crops(e, crop_u8)                                         # cropper.py:155 + :86
+        if I_s.shape[0] != 1:
+            raise ValueError("crop_u8: expected ONE crop")
+        raw_pose = e.motion_extract_raw(I_s)                                         # :87
+        x_s, x_d = e.motion_keypoints(raw_pose)                                      # :90, :92-94 (x_d_i_new = scale * kp)
+        f_s = e.extract_feature_3d(I_s)                                              # :89
+        f_s_can, occ = e.warp(f_s, x_s, x_d)                                         # :97
+        f_can_swap = e.swap(f_s_can, driving_id)                                     # :286
+        swap_can = e.spade_decode(e.warp_out(f_can_swap, occ))                       # :289 conv_decode
+        swap_can_256 = e.resize_half_bilinear(swap_can)                              # :294
+        raw_swap = e.motion_extract_raw(swap_can_256)                                # :297
+        x_swap, _ = e.motion_keypoints(raw_swap)                                     # :298
+        f_swap_can_2 = e.extract_feature_3d(swap_can_256)                            # :308, hoisted out of the loop
+        soft = tail.soft_erosion_frames(e, m[None], self.se.weight, self.se.kernel_size, self.se.threshold, self.se.iterations)      # :255
+        mask_ori = tail.prepare_paste_back(e, soft[0], M, (ori.shape[1], ori.shape[0]))      # :258
+        self._src = {"f_swap_can_2": f_swap_can_2, "x_swap": x_swap, "kp_swap": raw_swap[0, :63].view(21, 3), "raw_pose": raw_pose,
+                     "mask_ori": mask_ori, "img_ori": ori, "M_c2o": M}
+        return {"I_can": e.pack_u8(swap_can)[0], "swap_can": swap_can, "x_swap": x_swap, "x_s": x_s}      # :290 parse_output
+
+    def source_state(self):
+        """What the per-frame path reads: device tensors f_swap_can_2 (1,32,16,64,64), x_swap (1,21,3), kp_swap (21,3), raw_pose (1,328),
+        mask_ori (Ho,Wo) fp32, img_ori (Ho,Wo,3) u8, and the host matrix M_c2o (6 doubles).  A caller with several source images keeps one
+        dict per image and switches with load_source_state()."""
+        if self._src is None:
+            raise RuntimeError("AnimateChain: no source has been set (set_source / load_source_state)")
+        return dict(self._src)
+
+    def load_source_state(self, d):
+        e = self.e
+        want = {"f_swap_can_2": ((1, 32, 16, 64, 64), torch.float32), "x_swap": ((1, 21, 3), torch.float32), "kp_swap": ((21, 3), torch.float32),
+                "raw_pose": ((1, 328), torch.float32)}
+        src = {}
+        for k, (shape, dt) in want.items():
+            t = d[k]
+            if not isinstance(t, torch.Tensor) or t.dtype != dt or tuple(t.shape) != shape:
+                raise ValueError(f"load_source_state: {k} must be a {dt} tensor of shape {shape}")
+            src[k] = t.to(e.device).contiguous()
+        ori, mo = d["img_ori"], d["mask_ori"]
+        if not isinstance(ori, torch.Tensor) or ori.dtype != torch.uint8 or ori.dim() != 3 or ori.shape[2] != 3:
+            raise ValueError("load_source_state: img_ori must be an HoxWox3 uint8 tensor")
+        if not isinstance(mo, torch.Tensor) or mo.dtype != torch.float32 or tuple(mo.shape) != tuple(ori.shape[:2]):
+            raise ValueError("load_source_state: mask_ori must be an fp32 tensor of the size of img_ori")
+        src["img_ori"], src["mask_ori"] = ori.to(e.device).contiguous(), mo.to(e.device).contiguous()
+        src["M_c2o"] = np.ascontiguousarray(np.asarray(d["M_c2o"], dtype=np.float64).reshape(-1)[:6]).copy()
+        self.drop_prefetches()
+        self._src = src
+
+    # ---- stage A: what the generator needs from a batch of driving crops.  The reference runs it as a pre-pass over the whole driving video
+    # (prepare_videos + make_motion_template, can_swap_pipeline_v2i.py:235-238) and forms x_t_2 in the loop (:305)
+    def _stage_a(self, crops_u8, slot):
+        if self._src is None:
+            raise RuntimeError("AnimateChain: no source has been set (set_source / load_source_state)")
+        t = torch.as_tensor(crops_u8)
+        B = t.shape[0] if t.dim() == 4 else 1
+        I = tail.prepare_crops(self.e, t, out=self._get(("I", slot), (B, 3, 256, 256), torch.float32))      # :223 + :235
+        raw = self.e.motion_extract_raw(I, out=self._get(("raw", slot), (B, 328), torch.float32))           # :161
+        x_t = self.e.motion_keypoints_driven(raw, self._src["raw_pose"], self._src["kp_swap"],
+                                             out=self._get(("x_t", slot), (B, 21, 3), torch.float32))       # :301-305
+        return I, x_t
+
+    def prefetch(self, crops_u8):
+        """Stage A of the NEXT batch on a side stream beside the generator of the current one; the next __call__ with the same crops tensor
+        picks it up.  The rules of FrameChain.prefetch, for the same reasons: a double buffer, at most two batches staged, any
+        order; not on a latency-mode engine (split-K scratch shared by M and the generator)."""
+        e = self.e
+        if e.latency_mode:
+            raise RuntimeError("AnimateChain.prefetch: the engine is in latency mode (split-K scratch shared by M and the generator); "
+                               "run the chain in-line")
+        if self._src is None:
+            raise RuntimeError("AnimateChain: no source has been set (set_source / load_source_state)")
+        if len(self._pending) >= 2:
+            raise RuntimeError("AnimateChain.prefetch: two batches are already staged (double buffer); run one of them first")
+        if self._side is None:
+            self._side = torch.cuda.Stream(device=e.device)
+            self._free = [torch.cuda.Event(), torch.cuda.Event()]
+        slot = 1 - self._pending[0][1] if self._pending else 0      # the half no staged batch holds (they may be run out of order)
+        main = torch.cuda.current_stream(e.device)
+        self._side.wait_stream(main)                      # the crops and the source state were produced on the caller's stream
+        self._side.wait_event(self._free[slot])           # the generator that read this half of the double buffer is done
+        with torch.cuda.stream(self._side):
+            res = self._stage_a(crops_u8, slot)
+            ready = torch.cuda.Event()
+            ready.record(self._side)
+        self._pending.append((crops_u8, slot, res, ready))
+
+    def drop_prefetches(self):
+        """Forget staged batches that will not be run.  Their stage A may still be running on the side stream: the caller's stream waits for
+        it, as an in-line stage A must (both use the engine's M scratch)."""
+        self._pending = []
+        if self._side is not None:
+            torch.cuda.current_stream(self.e.device).wait_stream(self._side)
+
+    def __call__(self, crops_u8, out=None, keep=False):
+        """crops_u8 (B,512,512,3) or (B,256,256,3) u8: the cropper's crops of B driving frames
+        -> {"frames": (B,Ho,Wo,3) u8[, "crops_out" (B,512,512,3) u8, "x_t" (B,21,3), "I" (B,3,256,256) with keep=True]}"""
+        e = self.e
+        main = torch.cuda.current_stream(e.device)
+        slot = None
+        hit = [k for k, q in enumerate(self._pending) if q[0] is crops_u8]
+        if hit:
+            _, slot, (I, x_t), ready = self._pending.pop(hit[0])
+            main.wait_event(ready)
+        else:
+            if self._side is not None:
+                main.wait_stream(self._side)      # a prefetch in flight uses the same M scratch in the engine
+            I, x_t = self._stage_a(crops_u8, "inline")
+        src = self._src
+        B = I.shape[0]
+        gen = e.animate_frames(src["f_swap_can_2"], src["x_swap"], x_t, want_f32=False, want_u8=True,
+                               out_u8=self._get("gen", (B, 512, 512, 3), torch.uint8))["out_u8"]        # :309-312
+        frames = tail.paste_back_shared(e, gen, src["M_c2o"], src["img_ori"], src["mask_ori"], out=out)  # :317-321
+        if slot is not None:
+            self._free[slot].record(main)
+        res = {"frames": frames}
+        if keep:
+            res.update(crops_out=gen, x_t=x_t, I=I)
         return res

@@ -248,9 +248,13 @@ int launch_prepare_crops(const unsigned char* in, float* out, int B, int Hc, int
 int launch_paste(const unsigned char* crop, const float* mask_crop, const float* mask_ori, int Hc, int Wc, const double M[6],
                  const unsigned char* ori, unsigned char* out, int Ho, int Wo, hipStream_t st);
 int launch_warp_f32(const float* src, int Hs, int Ws, const double M[6], float* dst, int Hd, int Wd, hipStream_t st);
+int launch_resize_half(const float* in, float* out, long planes, int H, int W, hipStream_t st);
+int launch_paste_shared(const unsigned char* crops, int Hc, int Wc, const float* mask_ori, const double M[6], const unsigned char* ori,
+                        unsigned char* outs, int B, int Ho, int Wo, hipStream_t st);
 
 // ---- motion extractor pieces (motion.hip)
 int launch_m_keypoints(const float* raw, float* x_t, float* x_can, float* rot, int N, hipStream_t st);
+int launch_m_keypoints_driven(const float* raw_driving, const float* raw_pose, const float* kp, float* x_t, int N, hipStream_t st);
 int launch_m_stem(const float* img, const float* w, const float* b, const float* g, const float* be, float* x, int N, int HI, int WI, hipStream_t st);
 int launch_m_dwln(const float* x, const float* wt, const float* b, const float* g, const float* be, half_t* y, int N, int H, int W, int C, hipStream_t st);
 int launch_m_ln_s2d(const float* x, const float* g, const float* be, half_t* y, int N, int H, int W, int C, hipStream_t st);

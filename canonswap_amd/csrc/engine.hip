@@ -22,6 +22,8 @@ void cs_set_error(const char* fmt, ...)
     va_end(ap);
 }
 extern "C" const char* cs_last_error(void) { return g_err; }
+// 4, unchanged: cs_resize_half_bilinear, cs_motion_keypoints_driven, cs_paste_back_shared (the v2i device-side frame) were added; new entry points
+// alone change no struct, no existing entry point's meaning and no blob format, which is what the header bumps the version for.
 // 4 (round 6): cs_soft_erosion_frames, cs_paste_back_batch, cs_motion_keypoints.
 // 3 (round 4): cs_conv_desc grew (hilo, stat_out, xf_*, ep_general), cs_op_conv takes conv_halo / vol32 / conv_wide configurations only, the
 // packed weight blobs of F.down0 / down1 / second carry [W_hi | W_lo], W.occ49 exists; cs_conv_desc::pool_hw.  _lib.load() refuses any other value.
@@ -1679,6 +1681,39 @@ extern "C" int cs_motion_keypoints(cs_engine* e, int B, const float* raw, float*
     DevGuard guard(e->dev);
     hipStream_t st = (hipStream_t)stream;
     return e->run(1, st, [&] { return launch_m_keypoints(raw, x_t, x_can, rot, B, st); }, "m_keypoints");
+}
+
+// ---- the device-side frame of the video-to-image pipeline around cs_animate_frames (can_swap_pipeline_v2i.py:285-321)
+extern "C" int cs_resize_half_bilinear(cs_engine* e, int B, int C, const float* img, int H, int W, float* out, void* stream)
+{
+    if (!e || !img || !out || B < 1 || C < 1 || H < 2 || W < 2) { cs_set_error("cs_resize_half_bilinear: bad arguments"); return -1; }
+    if (H % 2 || W % 2) { cs_set_error("cs_resize_half_bilinear: H and W must be even (got %dx%d)", H, W); return -1; }
+    DevGuard guard(e->dev);
+    hipStream_t st = (hipStream_t)stream;
+    return e->run(1, st, [&] { return launch_resize_half(img, out, (long)B * C, H, W, st); }, "resize_half");
+}
+
+extern "C" int cs_motion_keypoints_driven(cs_engine* e, int B, const float* raw_driving, const float* raw_pose, const float* kp, float* x_t,
+                                          void* stream)
+{
+    if (!e || !raw_driving || !raw_pose || !kp || !x_t || B < 1) { cs_set_error("cs_motion_keypoints_driven: bad arguments"); return -1; }
+    DevGuard guard(e->dev);
+    hipStream_t st = (hipStream_t)stream;
+    return e->run(1, st, [&] { return launch_m_keypoints_driven(raw_driving, raw_pose, kp, x_t, B, st); }, "m_keypoints_driven");
+}
+
+extern "C" int cs_paste_back_shared(cs_engine* e, int B, const uint8_t* crops, int Hc, int Wc, const float* mask_ori, const double M_c2o[6],
+                                    const uint8_t* img_ori, uint8_t* out, int Ho, int Wo, void* stream)
+{
+    if (!e || !crops || !mask_ori || !M_c2o || !img_ori || !out || B < 1 || Hc < 1 || Wc < 1 || Ho < 1 || Wo < 1) {
+        cs_set_error("cs_paste_back_shared: bad arguments");
+        return -1;
+    }
+    // 32-bit byte offsets inside one crop; eight frames per grid row
+    if ((long)Hc * Wc * 3 >= (1L << 31) || B > 65535 * 8) { cs_set_error("cs_paste_back_shared: crop %dx%d or B = %d exceeds the kernel's limits", Hc, Wc, B); return -1; }
+    DevGuard guard(e->dev);
+    hipStream_t st = (hipStream_t)stream;
+    return e->run(1, st, [&] { return launch_paste_shared(crops, Hc, Wc, mask_ori, M_c2o, img_ori, out, B, Ho, Wo, st); }, "paste_back_shared");
 }
 
 extern "C" int cs_profile_begin(cs_engine* e)

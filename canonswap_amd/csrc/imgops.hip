@@ -313,6 +313,150 @@ __global__ void __launch_bounds__(256) paste_batch_kernel(const unsigned char* _
     out[0] = wv[0]; out[1] = wv[1]; out[2] = wv[2];
 }
 
+// ---- paste-back of B generated frames into ONE image under ONE mask and ONE matrix (can_swap_pipeline_v2i.py:317-321: every frame is
+// pasted into a fresh copy of the source image with the same mask_ori_float and source_M_c2o).  Per pixel the arithmetic of paste_kernel with
+// mask_ori given.  Everything that does not depend on the frame is formed once per thread - the fixed-point coordinates, the tap weights (kept
+// as fx, fy), the mask value, the image's pixels - and the thread then walks its group of frames (blockIdx.y), reading that frame's four crop
+// taps only.  A pixel with mask 0 (v = 0 * res + 1 * ori = ori) or with all four taps outside the crop (res = 0: v = m * 0 + (1 - m) * ori,
+// the same for every frame) never touches the crop; most of a 1080p frame is such pixels and is stored from registers, frame after frame.
+// PX pixels of a row per thread: 8 (24 bytes, 8-byte aligned: one 16-byte and one 8-byte store) or 4 (12 bytes, as paste_batch_kernel).
+// paste_kernel's blend `m * res + (1 - m) * ori` rounds both products and the sum (this file compiles with fp contraction off), so the second
+// product, which does not depend on the frame, may be formed apart (tests/test_gpu_v2i_chain.py holds the two kernels bit-equal).
+__device__ __forceinline__ unsigned blend_u8(float m, int res, float rest)
+{
+    return (unsigned)(unsigned char)fminf(fmaxf(m * (float)res + rest, 0.f), 255.f);
+}
+
+template <int PX>
+__device__ __forceinline__ void store_px(unsigned char* frame, long q, const unsigned (&w)[PX * 3 / 4])
+{
+    if constexpr (PX == 8) {
+        uint2* out = (uint2*)frame + q * 3;
+        out[0] = make_uint2(w[0], w[1]); out[1] = make_uint2(w[2], w[3]); out[2] = make_uint2(w[4], w[5]);
+    } else {
+        unsigned* out = (unsigned*)frame + q * (PX * 3 / 4);
+#pragma unroll
+        for (int j = 0; j < PX * 3 / 4; ++j) out[j] = w[j];
+    }
+}
+
+template <int PX>
+__global__ void __launch_bounds__(256) paste_shared_kernel(const unsigned char* __restrict__ crops, int Hc, int Wc, AffineInv A,
+                                                           const float* __restrict__ mask_ori, const unsigned char* __restrict__ ori,
+                                                           unsigned char* __restrict__ outs, int Ho, int Wo, int B, int frames_per_block)
+{
+    constexpr int NW = PX * 3 / 4;                                   // dwords of PX pixels
+    const long q = (long)blockIdx.x * 256 + threadIdx.x;             // group of PX pixels of one row
+    const long P = (long)Ho * Wo;
+    if (q * PX >= P) return;
+    const int f0 = blockIdx.y * frames_per_block, f1 = min(B, f0 + frames_per_block);
+    unsigned base[NW];                                               // the image's bytes; for pixels that never read the crop: the result
+    float m[PX];
+    if constexpr (PX == 8) {
+#pragma unroll
+        for (int j = 0; j < 3; ++j) {
+            const uint2 v = ((const uint2*)ori)[q * 3 + j];
+            base[2 * j] = v.x; base[2 * j + 1] = v.y;
+        }
+#pragma unroll
+        for (int j = 0; j < 2; ++j) {
+            const float4 v = ((const float4*)mask_ori)[q * 2 + j];
+            m[4 * j] = v.x; m[4 * j + 1] = v.y; m[4 * j + 2] = v.z; m[4 * j + 3] = v.w;
+        }
+    } else {
+#pragma unroll
+        for (int j = 0; j < NW; ++j) base[j] = ((const unsigned*)ori)[q * NW + j];
+#pragma unroll
+        for (int k = 0; k < PX; ++k) m[k] = mask_ori[q * PX + k];
+    }
+    const int y = (int)((q * PX) / Wo), xb = (int)((q * PX) % Wo);
+    int o00[PX], info[PX];      // info: fx | fy << 5 | (y0, y1, x0, x1) << 10 | live << 14
+    bool any = false;
+#pragma unroll
+    for (int k = 0; k < PX; ++k) {
+        o00[k] = 0; info[k] = 0;
+        if (m[k] == 0.f) continue;                                   // the original pixel
+        int sx, sy, fx, fy;
+        affine_coords(A, xb + k, y, sx, sy, fx, fy);
+        if (sx < -1 || sy < -1 || sx >= Wc || sy >= Hc) {            // all four taps outside: res = 0 for every frame
+#pragma unroll
+            for (int c = 0; c < 3; ++c) {
+                const int by = k * 3 + c, sh = (by & 3) * 8;
+                const float o = (float)((base[by >> 2] >> sh) & 0xffu);
+                base[by >> 2] = (base[by >> 2] & ~(0xffu << sh)) | (blend_u8(m[k], 0, (1.f - m[k]) * o) << sh);
+            }
+            continue;
+        }
+        const int y0 = (unsigned)sy < (unsigned)Hc, y1 = (unsigned)(sy + 1) < (unsigned)Hc;
+        const int x0 = (unsigned)sx < (unsigned)Wc, x1 = (unsigned)(sx + 1) < (unsigned)Wc;
+        o00[k] = sy * Wc + sx;                                       // sx, sy >= -1 and inside the crop otherwise: fits (the launcher bounds Hc * Wc)
+        info[k] = fx | fy << 5 | y0 << 10 | y1 << 11 | x0 << 12 | x1 << 13 | 1 << 14;
+        any = true;
+    }
+    if (!any) {                                                      // nothing of this group depends on the frame
+        for (int f = f0; f < f1; ++f) store_px<PX>(outs + (long)f * P * 3, q, base);
+        return;
+    }
+    for (int f = f0; f < f1; ++f) {
+        const unsigned char* crop = crops + (long)f * Hc * Wc * 3;
+        unsigned wv[NW];
+#pragma unroll
+        for (int j = 0; j < NW; ++j) wv[j] = base[j];
+#pragma unroll
+        for (int k = 0; k < PX; ++k) {
+            const int in = info[k];
+            if (!(in >> 14)) continue;
+            const int fx = in & 31, fy = (in >> 5) & 31;
+            const int w00 = (32 - fy) * (32 - fx) * 32, w01 = (32 - fy) * fx * 32, w10 = fy * (32 - fx) * 32, w11 = fy * fx * 32;
+            const bool y0 = in & (1 << 10), y1 = in & (1 << 11), x0 = in & (1 << 12), x1 = in & (1 << 13);
+            const unsigned char* t = crop + (long)o00[k] * 3;
+            const float mk = m[k], om = 1.f - mk;
+#pragma unroll
+            for (int c = 0; c < 3; ++c) {
+                const int t00 = (y0 && x0) ? t[c] : 0;
+                const int t01 = (y0 && x1) ? t[3 + c] : 0;
+                const int t10 = (y1 && x0) ? t[(long)Wc * 3 + c] : 0;
+                const int t11 = (y1 && x1) ? t[(long)Wc * 3 + 3 + c] : 0;
+                const int res = (t00 * w00 + t01 * w01 + t10 * w10 + t11 * w11 + (1 << 14)) >> 15;
+                const int by = k * 3 + c, sh = (by & 3) * 8;
+                const float o = (float)((base[by >> 2] >> sh) & 0xffu);
+                wv[by >> 2] = (wv[by >> 2] & ~(0xffu << sh)) | (blend_u8(mk, res, om * o) << sh);
+            }
+        }
+        store_px<PX>(outs + (long)f * P * 3, q, wv);
+    }
+}
+
+// ---- F.interpolate(x, size=(H/2, W/2), mode="bilinear", align_corners=False) at exactly one half (can_swap_pipeline_v2i.py:294): the
+// source coordinate of output i is 2 i + 0.5, so every weight is 1/2 * 1/2 and the result is the mean of a 2x2 block.  The order of the three
+// additions is the one of the GPU kernel the reference runs, 0.25f * ((a + b) + (c + d)) (rows first); the products by 1/2 are exact.
+__global__ void __launch_bounds__(256) resize_half_vec_kernel(const float* __restrict__ in, float* __restrict__ out, long planes, int Hd, int Wd)
+{
+    const long i = (long)blockIdx.x * 256 + threadIdx.x;          // four output columns
+    const int W4 = Wd / 4;
+    if (i >= planes * Hd * W4) return;
+    const long row = i / W4;                                       // plane * Hd + y
+    const int x4 = (int)(i % W4);
+    const float4* u = (const float4*)(in + row * 2 * (Wd * 2L)) + x4 * 2;
+    const float4* l = (const float4*)(in + (row * 2 + 1) * (Wd * 2L)) + x4 * 2;
+    const float4 u0 = u[0], u1 = u[1], l0 = l[0], l1 = l[1];
+    float4 r;
+    r.x = 0.25f * ((u0.x + u0.y) + (l0.x + l0.y)); r.y = 0.25f * ((u0.z + u0.w) + (l0.z + l0.w));
+    r.z = 0.25f * ((u1.x + u1.y) + (l1.x + l1.y)); r.w = 0.25f * ((u1.z + u1.w) + (l1.z + l1.w));
+    ((float4*)out)[i] = r;
+}
+
+__global__ void __launch_bounds__(256) resize_half_kernel(const float* __restrict__ in, float* __restrict__ out, long planes, int Hd, int Wd)
+{
+    const long i = (long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= planes * Hd * Wd) return;
+    const long row = i / Wd;
+    const int x = (int)(i % Wd);
+    const float* u = in + row * 2 * (Wd * 2L) + x * 2;
+    const float* l = u + Wd * 2L;
+    out[i] = 0.25f * ((u[0] + u[1]) + (l[0] + l[1]));
+}
+
 // float image (one channel) warped into the destination frame (prepare_paste_back, crop.py:515-521)
 __global__ void __launch_bounds__(256) warp_f32_kernel(const float* __restrict__ src, int Hs, int Ws, AffineInv A, float* __restrict__ dst,
                                                        int Hd, int Wd)
@@ -361,6 +505,44 @@ int launch_warp_f32(const float* src, int Hs, int Ws, const double M[6], float* 
     const long n = (long)Hd * Wd;
     hipLaunchKernelGGL(warp_f32_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, src, Hs, Ws, invert_affine(M), dst, Hd, Wd);
     LAUNCH_CHECK("warp_f32");
+    return 0;
+}
+
+int launch_resize_half(const float* in, float* out, long planes, int H, int W, hipStream_t st)
+{
+    const int Hd = H / 2, Wd = W / 2;
+    if (Wd % 4 == 0 && ((uintptr_t)in & 15) == 0 && ((uintptr_t)out & 15) == 0) {
+        const long n = planes * Hd * (Wd / 4);
+        hipLaunchKernelGGL(resize_half_vec_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, in, out, planes, Hd, Wd);
+    } else {
+        const long n = planes * Hd * Wd;
+        hipLaunchKernelGGL(resize_half_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, in, out, planes, Hd, Wd);
+    }
+    LAUNCH_CHECK("resize_half");
+    return 0;
+}
+
+// B frames into one image: eight pixels per thread where rows and buffers allow 8-byte accesses, four pixels (dwords) otherwise; odd widths /
+// unaligned buffers: the single-frame kernel per frame (same arithmetic).  The frame groups are grid rows, so B is not bound by a chunk size.
+int launch_paste_shared(const unsigned char* crops, int Hc, int Wc, const float* mask_ori, const double M[6], const unsigned char* ori,
+                        unsigned char* outs, int B, int Ho, int Wo, hipStream_t st)
+{
+    const long P = (long)Ho * Wo;
+    const uintptr_t al = (uintptr_t)ori | (uintptr_t)outs;
+    const int FPB = 8;                                               // frames a thread walks with its per-pixel state
+    const dim3 groups(1, (unsigned)((B + FPB - 1) / FPB));
+    if (Wo % 8 == 0 && (al & 7) == 0 && ((uintptr_t)mask_ori & 15) == 0) {
+        hipLaunchKernelGGL(paste_shared_kernel<8>, dim3((unsigned)((P / 8 + 255) / 256), groups.y), dim3(256), 0, st, crops, Hc, Wc, invert_affine(M),
+                           mask_ori, ori, outs, Ho, Wo, B, FPB);
+        LAUNCH_CHECK("paste_shared");
+    } else if (Wo % 4 == 0 && (al & 3) == 0) {
+        hipLaunchKernelGGL(paste_shared_kernel<4>, dim3((unsigned)((P / 4 + 255) / 256), groups.y), dim3(256), 0, st, crops, Hc, Wc, invert_affine(M),
+                           mask_ori, ori, outs, Ho, Wo, B, FPB);
+        LAUNCH_CHECK("paste_shared");
+    } else {
+        for (int i = 0; i < B; ++i)
+            if (launch_paste(crops + (long)i * Hc * Wc * 3, nullptr, mask_ori, Hc, Wc, M, ori, outs + (long)i * P * 3, Ho, Wo, st)) return -1;
+    }
     return 0;
 }
 

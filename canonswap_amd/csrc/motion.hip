@@ -410,6 +410,52 @@ __global__ void __launch_bounds__(64) m_keypoints_kernel(const float* __restrict
     xc[0] = scale * k0; xc[1] = scale * k1; xc[2] = scale * k2;
 }
 
+// The driven key-points of the video-to-image loop (can_swap_pipeline_v2i.py:301-305): scale, pose and t of ONE row (the source crop's raw
+// heads), the canonical key-points of the swapped canonical image, the expression of each driving frame:
+//     x_t[b] = scale_pose * (kp R_pose + exp[b]) + (t_x, t_y, 0)
+// One wavefront per KPD_FRAMES frames: the rotation does not depend on the frame and is formed once per wavefront, exactly as above.
+// (get_rotation_matrix is restated here and not shared with m_keypoints_kernel: moving it into a function changed that kernel's machine code,
+// and its bits are what every recorded parity figure of the e2e chain was measured with.)
+constexpr int KPD_FRAMES = 16;
+__device__ __forceinline__ void pose_rotation(const float* r, int lane, float m[3][3])      // m = Rz Ry Rx; R = m^T
+{
+    const float PI = 3.14159265358979323846f;
+    const float x = bins_to_degree(r + 64, lane) / 180.f * PI, y = bins_to_degree(r + 130, lane) / 180.f * PI,
+                z = bins_to_degree(r + 196, lane) / 180.f * PI;
+    const float cx = cosf(x), sx = sinf(x), cy = cosf(y), sy = sinf(y), cz = cosf(z), sz = sinf(z);
+    const float zy[3][3] = {{cz * cy, -sz, cz * sy}, {sz * cy, cz, sz * sy}, {-sy, 0.f, cy}};      // rz @ ry, then @ rx (camera.py:53-71)
+#pragma unroll
+    for (int i = 0; i < 3; ++i) {
+        m[i][0] = zy[i][0];
+        m[i][1] = zy[i][1] * cx + zy[i][2] * sx;
+        m[i][2] = zy[i][1] * -sx + zy[i][2] * cx;
+    }
+}
+
+__global__ void __launch_bounds__(64) m_keypoints_driven_kernel(const float* __restrict__ raw_driving, const float* __restrict__ pose,
+                                                                const float* __restrict__ kp, float* __restrict__ x_t, int N)
+{
+    const int lane = threadIdx.x;
+    float m[3][3];
+    pose_rotation(pose, lane, m);
+    if (lane >= 21) return;
+    const float scale = pose[63];
+    const float k0 = kp[lane * 3], k1 = kp[lane * 3 + 1], k2 = kp[lane * 3 + 2];
+    float rot[3];
+#pragma unroll
+    for (int j = 0; j < 3; ++j) rot[j] = (k0 * m[j][0] + k1 * m[j][1]) + k2 * m[j][2];
+    const int n1 = min(N, ((int)blockIdx.x + 1) * KPD_FRAMES);
+    for (int n = blockIdx.x * KPD_FRAMES; n < n1; ++n) {
+        const float* ex = raw_driving + (long)n * 328 + 265 + lane * 3;
+        float* xt = x_t + ((long)n * 21 + lane) * 3;
+#pragma unroll
+        for (int j = 0; j < 3; ++j) {
+            const float v = (rot[j] + ex[j]) * scale;
+            xt[j] = j < 2 ? v + pose[262 + j] : v;
+        }
+    }
+}
+
 }  // namespace
 
 #define M_LAUNCH_CHECK(name) do { hipError_t e_ = hipGetLastError(); if (e_ != hipSuccess) { cs_set_error(name ": %s", hipGetErrorString(e_)); return -1; } } while (0)
@@ -475,5 +521,12 @@ int launch_m_keypoints(const float* raw, float* x_t, float* x_can, float* rot, i
 {
     hipLaunchKernelGGL(m_keypoints_kernel, dim3(N), dim3(64), 0, st, raw, x_t, x_can, rot);
     M_LAUNCH_CHECK("m_keypoints");
+    return 0;
+}
+
+int launch_m_keypoints_driven(const float* raw_driving, const float* raw_pose, const float* kp, float* x_t, int N, hipStream_t st)
+{
+    hipLaunchKernelGGL(m_keypoints_driven_kernel, dim3((N + KPD_FRAMES - 1) / KPD_FRAMES), dim3(64), 0, st, raw_driving, raw_pose, kp, x_t, N);
+    M_LAUNCH_CHECK("m_keypoints_driven");
     return 0;
 }

@@ -306,6 +306,35 @@ class Engine:
                                               _ptr(out_f32), _ptr(out_u8), self._stream()), "cs_animate_frames")
         return {"out": out_f32, "out_u8": out_u8}
 
+    def resize_half_bilinear(self, img, out=None):
+        """F.interpolate(img, size=(H/2, W/2), mode="bilinear", align_corners=False) at exactly one half (can_swap_pipeline_v2i.py:294):
+        (B,C,H,W) fp32, H and W even -> (B,C,H/2,W/2); the 2x2 mean summed rows first, 0.25 * ((a + b) + (c + d))."""
+        if not isinstance(img, torch.Tensor) or img.dim() != 4:
+            raise ValueError("expected a (B, C, H, W) tensor")
+        img = img.to(self.device).contiguous().float()
+        B, Cc, H, W = img.shape
+        if B < 1 or Cc < 1 or H < 2 or W < 2 or H % 2 or W % 2:
+            raise ValueError(f"resize_half_bilinear: H and W must be even and the tensor not empty, got {tuple(img.shape)}")
+        out = self._out(out, (B, Cc, H // 2, W // 2), torch.float32)
+        _lib.check(self.lib.cs_resize_half_bilinear(self.h, B, Cc, _ptr(img), H, W, _ptr(out), self._stream()), "cs_resize_half_bilinear")
+        return out
+
+    def motion_keypoints_driven(self, raw_driving, raw_pose, kp, out=None):
+        """The driven key-points of can_swap_pipeline_v2i.py:301-305 on the device: raw_driving (B,328) raw heads of the driving frames,
+        raw_pose (1,328) raw heads of the source crop (scale, pose, t), kp (21,3) or (1,21,3) canonical key-points of the swapped canonical
+        image -> x_t (B,21,3) = scale_pose * (kp @ R_pose + exp[b]) + (t_x, t_y, 0)."""
+        raw_driving = self._in(raw_driving, (328,))
+        B = raw_driving.shape[0]
+        for name, t, n in (("raw_pose", raw_pose, 328), ("kp", kp, 63)):
+            if not isinstance(t, torch.Tensor) or t.numel() != n:
+                raise ValueError(f"{name} must hold {n} values (one row)")
+        raw_pose = raw_pose.to(self.device).contiguous().float()
+        kp = kp.to(self.device).contiguous().float()
+        x_t = self._out(out, (B, 21, 3), torch.float32)
+        _lib.check(self.lib.cs_motion_keypoints_driven(self.h, B, _ptr(raw_driving), _ptr(raw_pose), _ptr(kp), _ptr(x_t), self._stream()),
+                   "cs_motion_keypoints_driven")
+        return x_t
+
     # ---------------------------------------------------------------- measurement
     def profile_begin(self):
         _lib.check(self.lib.cs_profile_begin(self.h), "cs_profile_begin")

@@ -7,6 +7,7 @@ per-frame loop (src/can_swap_pipeline_e2e.py:223-283) no longer leaves the GPU b
 * ``prepare_paste_back``     src/utils/crop.py:515-521          (cv2.warpAffine of the float mask)
 * ``paste_back``             src/utils/crop.py:523-529          (cv2.warpAffine of the crop + blend)
 * ``paste_back_fused``       both of the above in one kernel launch per frame
+* ``paste_back_shared``      paste_back of B frames into one image under one mask (can_swap_pipeline_v2i.py:317-321)
 * ``prepare_crops``          src/utils/cropper.py:209 + src/can_swap_e2e.py:126-163 (INTER_AREA 512 -> 256, /255, HWC -> CHW)
 * ``FrameStreamer``          streamed upload of the uint8 crops instead of the whole-video residency of prepare_videos
 
@@ -100,6 +101,35 @@ def paste_back_batch(e: Engine, crops, masks_crop, M_c2o, imgs_ori, out=None):
     with torch.cuda.device(e.device):
         _lib.check(e.lib.cs_paste_back_batch(e.h, B, _ptr(crops), _ptr(mc), crops.shape[1], crops.shape[2], M.ctypes.data_as(C.POINTER(C.c_double)),
                                              _ptr(ori), _ptr(out), ori.shape[1], ori.shape[2], e._stream()), "cs_paste_back_batch")
+    return out
+
+
+def paste_back_shared(e: Engine, crops, M_c2o, img_ori, mask_ori, out=None):
+    """paste_back (crop.py:523-529) of B generated frames into ONE image, as the loop of can_swap_pipeline_v2i.py:317-321 does on a fresh copy
+    of the source image per frame: crops (B,Hc,Wc,3) u8, M_c2o 2x3 / 3x3 host, img_ori (Ho,Wo,3) u8, mask_ori (Ho,Wo) fp32 (prepare_paste_back's
+    result, :255-258) -> (B,Ho,Wo,3) u8, frame b bit-equal to paste_back(crops[b], M_c2o, img_ori, mask_ori)."""
+    crops, ori = torch.as_tensor(crops), torch.as_tensor(img_ori)
+    if crops.dtype != torch.uint8 or crops.dim() != 4 or crops.shape[3] != 3 or crops.shape[0] < 1:
+        raise ValueError("expected BxHcxWcx3 uint8 crops")
+    if ori.dtype != torch.uint8 or ori.dim() != 3 or ori.shape[2] != 3:
+        raise ValueError("expected ONE HoxWox3 uint8 image")
+    crops, ori = crops.to(e.device).contiguous(), ori.to(e.device).contiguous()
+    mo = torch.as_tensor(mask_ori)
+    if mo.dim() == 3:
+        mo = mo[..., 0]
+    mo = mo.to(e.device).float().contiguous()
+    if tuple(mo.shape) != tuple(ori.shape[:2]):
+        raise ValueError("mask_ori must have the size of img_ori")
+    B = crops.shape[0]
+    shape = (B,) + tuple(ori.shape)
+    if out is None:
+        out = torch.empty(shape, dtype=torch.uint8, device=e.device)
+    elif not isinstance(out, torch.Tensor) or out.dtype != torch.uint8 or tuple(out.shape) != shape or not out.is_contiguous() or out.device != e.device:
+        raise ValueError("out must be a contiguous (B, Ho, Wo, 3) uint8 tensor on the engine's device")
+    mm, mp = _m6(M_c2o)
+    with torch.cuda.device(e.device):
+        _lib.check(e.lib.cs_paste_back_shared(e.h, B, _ptr(crops), crops.shape[1], crops.shape[2], _ptr(mo), mp, _ptr(ori), _ptr(out),
+                                              ori.shape[0], ori.shape[1], e._stream()), "cs_paste_back_shared")
     return out
 
 

@@ -131,6 +131,25 @@ int cs_paste_back_batch(cs_engine* e, int B, const uint8_t* crops, const float* 
  * Replaces make_motion_template's per-frame D2H of seven tensors (can_swap_pipeline_e2e.py:111-125). */
 int cs_motion_keypoints(cs_engine* e, int B, const float* raw, float* x_t, float* x_can, float* rot, void* stream);
 
+/* ---- the device-side frame of the video-to-image pipeline around cs_animate_frames (can_swap_pipeline_v2i.py; chain.py AnimateChain) ---- */
+/* F.interpolate(img, size=(H/2, W/2), mode="bilinear", align_corners=False) at exactly one half (can_swap_pipeline_v2i.py:294, swap_can
+ * 512 -> 256): img BxCxHxW fp32 -> out BxCx(H/2)x(W/2) fp32, H and W even.  The source coordinate of output i is 2i + 0.5, all four weights are
+ * 1/4; the summation order is the one of the GPU kernel the reference executes: out = 0.25f * ((a + b) + (c + d)), a b the upper row's
+ * two pixels, c d the lower row's. */
+int cs_resize_half_bilinear(cs_engine* e, int B, int C, const float* img, int H, int W, float* out, void* stream);
+/* The driven key-points of B driving frames (can_swap_pipeline_v2i.py:301-305): raw_driving Bx328 (cs_motion_extract's raw heads of the
+ * driving frames; only their exp is read), raw_pose 1x328 (the raw heads of the SOURCE crop: its scale, its three 66-bin pose logits, its
+ * t), kp 21x3 (x_swap_info['kp'], the canonical key-points of the swapped canonical image) -> x_t Bx21x3:
+ * x_t[b] = scale_pose * (kp @ R_pose + exp[b]) + (t_x, t_y, 0)   (t_swap[..., 2].fill_(0), :303), R_pose formed as in cs_motion_keypoints. */
+int cs_motion_keypoints_driven(cs_engine* e, int B, const float* raw_driving, const float* raw_pose, const float* kp, float* x_t, void* stream);
+/* paste_back of B generated frames into ONE source image (src/utils/crop.py:523-529 as the loop of can_swap_pipeline_v2i.py:317-321 calls
+ * it, on a fresh copy of the image per frame): crops BxHcxWcx3 u8, mask_ori HoxWo fp32 (the soft mask already in the image's frame:
+ * cs_warp_affine_f32 = prepare_paste_back, can_swap_pipeline_v2i.py:255-258), M_c2o 2x3 (host), img_ori HoxWox3 u8 -> out BxHoxWox3 u8,
+ * out[b] bit-equal to cs_paste_back of crops[b] with mask_ori given.  Coordinates, tap weights, the mask value and the image's pixels are
+ * formed once per pixel group and reused for every frame; any B >= 1 (not bound to max_batch). */
+int cs_paste_back_shared(cs_engine* e, int B, const uint8_t* crops, int Hc, int Wc, const float* mask_ori, const double M_c2o[6],
+                         const uint8_t* img_ori, uint8_t* out, int Ho, int Wo, void* stream);
+
 /* ---- measurement: per-kernel-family HIP-event timing on the launch stream */
 int cs_profile_begin(cs_engine* e);
 /* ms[0] = convolution kernels (conv_halo / conv_igemm), ms[1] = all other kernels except ms[2] = the feature warp
