@@ -20,24 +20,25 @@ M_c2o), SegFormer face parsing (it produces the 0/1 masks), video decode / encod
 """
 from __future__ import annotations
 
-import numpy as np
 import torch
 
 from . import tail
 from .engine import Engine
 
 
-class FrameChain:
-    """chain = FrameChain(swapper);  frames = chain(crops_u8, masks, M_c2o, frames_ori, source_id)["frames"]"""
+class _StagedChain:
+    """What the two chains share: engine, SoftErosion module, named buffers and the staging pipeline.  Stage A of a batch (`_stage_a`, the
+    subclass's own: everything the generator needs from the crops) runs in-line on the caller's stream, or ahead of time on a side stream
+    into one half of a double buffer.  Every stream-ordering rule of FrameChain and AnimateChain stands here, once."""
 
-    def __init__(self, swapper, kernel_size: int = 21, threshold: float = 0.9, iterations: int = 3):
+    def __init__(self, swapper, kernel_size, threshold, iterations):
         self.sw = swapper
         self.e: Engine = swapper.engine
         if swapper.motion_extractor is None:
-            raise RuntimeError("FrameChain: the loaded weights hold no 'motion_extractor' state-dict")
-        self.se = tail.SoftErosion(self.e, kernel_size, threshold, iterations)      # SoftErosion(21, 0.9, 3): can_swap_pipeline_e2e.py:42
+            raise RuntimeError(f"{type(self).__name__}: the loaded weights hold no 'motion_extractor' state-dict")
+        self.se = tail.SoftErosion(self.e, kernel_size, threshold, iterations)
         self._buf = {}
-        self._side, self._free, self._pending = None, None, []        # prefetch(): side stream, double buffer
+        self._side, self._free, self._pending = None, None, []        # _stage_ahead(): side stream, double buffer
 
     def _get(self, key, shape, dtype):
         t = self._buf.get(key)
@@ -45,6 +46,64 @@ class FrameChain:
             t = torch.empty(shape, dtype=dtype, device=self.e.device)
             self._buf[key] = t
         return t
+
+    def _check_stageable(self):
+        """Raises where stage A cannot run yet (AnimateChain: no source)."""
+
+    def _stage_ahead(self, crops_u8, *args):
+        """prefetch() of both chains: _stage_a(crops_u8, *args, slot) on the side stream, into the half of the double buffer no staged
+        batch holds; the call with the same crops tensor picks the result up (_resolve)."""
+        e, name = self.e, type(self).__name__
+        if e.latency_mode:
+            raise RuntimeError(f"{name}.prefetch: the engine is in latency mode (split-K scratch shared by M and the generator); "
+                               "run the chain in-line")
+        self._check_stageable()
+        if len(self._pending) >= 2:
+            raise RuntimeError(f"{name}.prefetch: two batches are already staged (double buffer); run one of them first")
+        if self._side is None:
+            self._side = torch.cuda.Stream(device=e.device)      # (a high-priority side stream measured the same: 0.933 either way)
+            self._free = [torch.cuda.Event(), torch.cuda.Event()]
+        slot = 1 - self._pending[0][1] if self._pending else 0      # the half no staged batch holds (they may be run out of order)
+        main = torch.cuda.current_stream(e.device)
+        self._side.wait_stream(main)                      # the crops (and AnimateChain's source state) were produced on the caller's stream
+        self._side.wait_event(self._free[slot])           # the generator that read this half of the double buffer is done
+        with torch.cuda.stream(self._side):
+            res = self._stage_a(crops_u8, *args, slot)
+            ready = torch.cuda.Event()
+            ready.record(self._side)
+        self._pending.append((crops_u8, slot, res, ready))
+
+    def drop_prefetches(self):
+        """Forget staged batches that will not be run (their buffers are reused by the next prefetch).  Their stage A may still be running
+        on the side stream: the caller's stream waits for it, as an in-line stage A must (both use the engine's M and SoftErosion scratch)."""
+        self._pending = []
+        if self._side is not None:
+            torch.cuda.current_stream(self.e.device).wait_stream(self._side)
+
+    def _resolve(self, crops_u8, *args):
+        """Head of __call__ -> (slot, stage A's result): the staged batch whose crops tensor is this one (slot = its half of the double
+        buffer), else stage A in-line (slot None)."""
+        main = torch.cuda.current_stream(self.e.device)
+        hit = [k for k, q in enumerate(self._pending) if q[0] is crops_u8]
+        if hit:
+            _, slot, res, ready = self._pending.pop(hit[0])
+            main.wait_event(ready)
+            return slot, res
+        if self._side is not None:
+            main.wait_stream(self._side)      # a prefetch in flight uses the same M and SoftErosion scratch in the engine
+        return None, self._stage_a(crops_u8, *args, "inline")
+
+    def _release(self, slot):
+        """End of __call__, the generator queued: the next prefetch into this half of the double buffer waits for it."""
+        if slot is not None:
+            self._free[slot].record(torch.cuda.current_stream(self.e.device))
+
+
+class FrameChain(_StagedChain):
+    """chain = FrameChain(swapper);  frames = chain(crops_u8, masks, M_c2o, frames_ori, source_id)["frames"]"""
+
+    def __init__(self, swapper, kernel_size: int = 21, threshold: float = 0.9, iterations: int = 3):
+        super().__init__(swapper, kernel_size, threshold, iterations)      # SoftErosion(21, 0.9, 3): can_swap_pipeline_e2e.py:42
 
     def keypoints(self, I, slot=0):
         """(B,3,256,256) fp32 -> x_t, x_can (B,21,3): make_motion_template's get_kp_info + transform_keypoint and the loop's
@@ -72,60 +131,26 @@ class FrameChain:
         the same crops tensor picks the result up (the soft masks of that batch included: they depend on the parser's labels only).  M's workspace is its own, the batch's inputs land in the other half of a double buffer.
         Staged batches may be run in any order.  Not on a latency-mode engine: there every small plain conv (M's and the generator's
         alike) runs split-K on the engine's one partial-sum buffer, which M on the side stream and the generator would share."""
-        e = self.e
-        if e.latency_mode:
-            raise RuntimeError("FrameChain.prefetch: the engine is in latency mode (split-K scratch shared by M and the generator); "
-                               "run the chain in-line")
-        if len(self._pending) >= 2:
-            raise RuntimeError("FrameChain.prefetch: two batches are already staged (double buffer); run one of them first")
-        if self._side is None:
-            self._side = torch.cuda.Stream(device=e.device)      # (a high-priority side stream measured the same: 0.933 either way)
-            self._free = [torch.cuda.Event(), torch.cuda.Event()]
-        slot = 1 - self._pending[0][1] if self._pending else 0      # the half no staged batch holds (they may be run out of order)
-        main = torch.cuda.current_stream(e.device)
-        self._side.wait_stream(main)                      # the crops were produced on the caller's stream
-        self._side.wait_event(self._free[slot])           # the generator that read this half of the double buffer is done
-        with torch.cuda.stream(self._side):
-            res = self._stage_a(crops_u8, masks, slot)
-            ready = torch.cuda.Event()
-            ready.record(self._side)
-        self._pending.append((crops_u8, slot, res, ready))
-
-    def drop_prefetches(self):
-        """Forget staged batches that will not be run (their buffers are reused by the next prefetch).  Their stage A may still be running
-        on the side stream: the caller's stream waits for it, as an in-line stage A must (both use the engine's M and SoftErosion scratch)."""
-        self._pending = []
-        if self._side is not None:
-            torch.cuda.current_stream(self.e.device).wait_stream(self._side)
+        self._stage_ahead(crops_u8, masks)
 
     def __call__(self, crops_u8, masks, M_c2o, frames_ori, source_id=None, slots=None, out=None, keep=False):
         """crops_u8 (B,512,512,3) or (B,256,256,3) u8; masks (B,512,512) u8 0/1 or fp32 (the parser's `torch.isin(labels, valid)`);
         M_c2o (B,2,3)/(B,3,3) host; frames_ori (B,Ho,Wo,3) u8; source_id (1,512)/(B,512) or identity slots.
         -> {"frames": (B,Ho,Wo,3) u8[, "crops_out", "x_t", "x_can", "soft_mask" with keep=True]}"""
         e = self.e
-        main = torch.cuda.current_stream(e.device)
-        slot = None
-        hit = [k for k, q in enumerate(self._pending) if q[0] is crops_u8]
-        if hit:
-            _, slot, (I, x_t, x_can, soft), ready = self._pending.pop(hit[0])
-            main.wait_event(ready)
-        else:
-            if self._side is not None:
-                main.wait_stream(self._side)      # a prefetch in flight uses the same M and SoftErosion scratch in the engine
-            I, x_t, x_can, soft = self._stage_a(crops_u8, masks, "inline")
+        slot, (I, x_t, x_can, soft) = self._resolve(crops_u8, masks)
         B = I.shape[0]
         gen = e.swap_frames(I, x_t, x_can, source_id, want_f32=False, want_u8=True, slots=slots,
                             out_u8=self._get("gen", (B, 512, 512, 3), torch.uint8))["out_u8"]   # :242-267
         frames = tail.paste_back_batch(e, gen, soft, M_c2o, frames_ori, out=out)                # :279-282
-        if slot is not None:
-            self._free[slot].record(main)
+        self._release(slot)
         res = {"frames": frames}
         if keep:
             res.update(crops_out=gen, x_t=x_t, x_can=x_can, soft_mask=soft, I=I)
         return res
 
 
-class AnimateChain:
+class AnimateChain(_StagedChain):
     """chain = AnimateChain(swapper);  chain.set_source(crop_u8, mask, M_c2o, img_ori, driving_id);  frames = chain(driving_crops_u8)["frames"]
 
     The device-side frame of CanSwapPipeline.execute of src/can_swap_pipeline_v2i.py, B driving frames per call:
@@ -150,21 +175,8 @@ class AnimateChain:
     concat_frames."""
 
     def __init__(self, swapper, kernel_size: int = 21, threshold: float = 0.9, iterations: int = 2):
-        self.sw = swapper
-        self.e: Engine = swapper.engine
-        if swapper.motion_extractor is None:
-            raise RuntimeError("AnimateChain: the loaded weights hold no 'motion_extractor' state-dict")
-        self.se = tail.SoftErosion(self.e, kernel_size, threshold, iterations)      # SoftErosion(21, 0.9, 2): can_swap_pipeline_v2i.py:43
-        self._buf = {}
+        super().__init__(swapper, kernel_size, threshold, iterations)      # SoftErosion(21, 0.9, 2): can_swap_pipeline_v2i.py:43
         self._src = None                                              # source_state()
-        self._side, self._free, self._pending = None, None, []        # prefetch(): side stream, double buffer (as FrameChain)
-
-    def _get(self, key, shape, dtype):
-        t = self._buf.get(key)
-        if t is None or tuple(t.shape) != tuple(shape) or t.dtype != dtype:
-            t = torch.empty(shape, dtype=dtype, device=self.e.device)
-            self._buf[key] = t
-        return t
 
     # ---- once per (source image, driving identity)
     def set_source(self, crop_u8, mask, M_c2o, img_ori, driving_id):
@@ -180,7 +192,7 @@ class AnimateChain:
         m = torch.as_tensor(mask)
         if m.dim() != 2:
             raise ValueError("mask: expected ONE (H, W) mask in the crop's frame")
-        M = np.ascontiguousarray(np.asarray(M_c2o, dtype=np.float64).reshape(-1)[:6]).copy()
+        M = tail._m6(M_c2o)[0].copy()                                                # not the caller's array
         I_s = tail.prepare_crops(e, crop_u8)                                         # cropper.py:155 + :86
         if I_s.shape[0] != 1:
             raise ValueError("crop_u8: expected ONE crop")
@@ -200,12 +212,15 @@ class AnimateChain:
                      "mask_ori": mask_ori, "img_ori": ori, "M_c2o": M}
         return {"I_can": e.pack_u8(swap_can)[0], "swap_can": swap_can, "x_swap": x_swap, "x_s": x_s}      # :290 parse_output
 
+    def _check_stageable(self):
+        if self._src is None:
+            raise RuntimeError("AnimateChain: no source has been set (set_source / load_source_state)")
+
     def source_state(self):
         """What the per-frame path reads: device tensors f_swap_can_2 (1,32,16,64,64), x_swap (1,21,3), kp_swap (21,3), raw_pose (1,328),
         mask_ori (Ho,Wo) fp32, img_ori (Ho,Wo,3) u8, and the host matrix M_c2o (6 doubles).  A caller with several source images keeps one
         dict per image and switches with load_source_state()."""
-        if self._src is None:
-            raise RuntimeError("AnimateChain: no source has been set (set_source / load_source_state)")
+        self._check_stageable()
         return dict(self._src)
 
     def load_source_state(self, d):
@@ -224,15 +239,14 @@ class AnimateChain:
         if not isinstance(mo, torch.Tensor) or mo.dtype != torch.float32 or tuple(mo.shape) != tuple(ori.shape[:2]):
             raise ValueError("load_source_state: mask_ori must be an fp32 tensor of the size of img_ori")
         src["img_ori"], src["mask_ori"] = ori.to(e.device).contiguous(), mo.to(e.device).contiguous()
-        src["M_c2o"] = np.ascontiguousarray(np.asarray(d["M_c2o"], dtype=np.float64).reshape(-1)[:6]).copy()
+        src["M_c2o"] = tail._m6(d["M_c2o"])[0].copy()
         self.drop_prefetches()
         self._src = src
 
     # ---- stage A: what the generator needs from a batch of driving crops.  The reference runs it as a pre-pass over the whole driving video
     # (prepare_videos + make_motion_template, can_swap_pipeline_v2i.py:235-238) and forms x_t_2 in the loop (:305)
     def _stage_a(self, crops_u8, slot):
-        if self._src is None:
-            raise RuntimeError("AnimateChain: no source has been set (set_source / load_source_state)")
+        self._check_stageable()
         t = torch.as_tensor(crops_u8)
         B = t.shape[0] if t.dim() == 4 else 1
         I = tail.prepare_crops(self.e, t, out=self._get(("I", slot), (B, 3, 256, 256), torch.float32))      # :223 + :235
@@ -245,55 +259,19 @@ class AnimateChain:
         """Stage A of the NEXT batch on a side stream beside the generator of the current one; the next __call__ with the same crops tensor
         picks it up.  The rules of FrameChain.prefetch, for the same reasons: a double buffer, at most two batches staged, any
         order; not on a latency-mode engine (split-K scratch shared by M and the generator)."""
-        e = self.e
-        if e.latency_mode:
-            raise RuntimeError("AnimateChain.prefetch: the engine is in latency mode (split-K scratch shared by M and the generator); "
-                               "run the chain in-line")
-        if self._src is None:
-            raise RuntimeError("AnimateChain: no source has been set (set_source / load_source_state)")
-        if len(self._pending) >= 2:
-            raise RuntimeError("AnimateChain.prefetch: two batches are already staged (double buffer); run one of them first")
-        if self._side is None:
-            self._side = torch.cuda.Stream(device=e.device)
-            self._free = [torch.cuda.Event(), torch.cuda.Event()]
-        slot = 1 - self._pending[0][1] if self._pending else 0      # the half no staged batch holds (they may be run out of order)
-        main = torch.cuda.current_stream(e.device)
-        self._side.wait_stream(main)                      # the crops and the source state were produced on the caller's stream
-        self._side.wait_event(self._free[slot])           # the generator that read this half of the double buffer is done
-        with torch.cuda.stream(self._side):
-            res = self._stage_a(crops_u8, slot)
-            ready = torch.cuda.Event()
-            ready.record(self._side)
-        self._pending.append((crops_u8, slot, res, ready))
-
-    def drop_prefetches(self):
-        """Forget staged batches that will not be run.  Their stage A may still be running on the side stream: the caller's stream waits for
-        it, as an in-line stage A must (both use the engine's M scratch)."""
-        self._pending = []
-        if self._side is not None:
-            torch.cuda.current_stream(self.e.device).wait_stream(self._side)
+        self._stage_ahead(crops_u8)
 
     def __call__(self, crops_u8, out=None, keep=False):
         """crops_u8 (B,512,512,3) or (B,256,256,3) u8: the cropper's crops of B driving frames
         -> {"frames": (B,Ho,Wo,3) u8[, "crops_out" (B,512,512,3) u8, "x_t" (B,21,3), "I" (B,3,256,256) with keep=True]}"""
         e = self.e
-        main = torch.cuda.current_stream(e.device)
-        slot = None
-        hit = [k for k, q in enumerate(self._pending) if q[0] is crops_u8]
-        if hit:
-            _, slot, (I, x_t), ready = self._pending.pop(hit[0])
-            main.wait_event(ready)
-        else:
-            if self._side is not None:
-                main.wait_stream(self._side)      # a prefetch in flight uses the same M scratch in the engine
-            I, x_t = self._stage_a(crops_u8, "inline")
+        slot, (I, x_t) = self._resolve(crops_u8)
         src = self._src
         B = I.shape[0]
         gen = e.animate_frames(src["f_swap_can_2"], src["x_swap"], x_t, want_f32=False, want_u8=True,
                                out_u8=self._get("gen", (B, 512, 512, 3), torch.uint8))["out_u8"]        # :309-312
         frames = tail.paste_back_shared(e, gen, src["M_c2o"], src["img_ori"], src["mask_ori"], out=out)  # :317-321
-        if slot is not None:
-            self._free[slot].record(main)
+        self._release(slot)
         res = {"frames": frames}
         if keep:
             res.update(crops_out=gen, x_t=x_t, I=I)

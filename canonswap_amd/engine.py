@@ -222,9 +222,7 @@ class Engine:
 
     def motion_extract(self, img):
         """MotionExtractor.forward (motion_extractor.py:33-35): Bx3x256x256 in [0,1] -> dict of raw head outputs."""
-        img = self._in(img, (3, 256, 256))
-        out = self._new(img.shape[0], 328)
-        _lib.check(self.lib.cs_motion_extract(self.h, img.shape[0], _ptr(img), _ptr(out), self._stream()), "cs_motion_extract")
+        out = self.motion_extract_raw(img)
         res, o = {}, 0
         for k, n in pack.M_HEADS:
             res[k] = out[:, o:o + n].contiguous()

@@ -24,9 +24,19 @@ from . import _lib
 from .engine import Engine, _ptr
 
 
-def _m6(M):
-    m = np.ascontiguousarray(np.asarray(M, dtype=np.float64).reshape(-1)[:6])      # 2x3 or the top rows of a 3x3
+def _m6(M, B=None):
+    """One host matrix, 2x3 or 3x3 (its top rows) -> (six doubles, their pointer); with B: B matrices -> (B, 6)."""
+    a = np.asarray(M, dtype=np.float64)
+    m = np.ascontiguousarray(a.reshape(-1)[:6] if B is None else a.reshape(B, -1)[:, :6])
     return m, m.ctypes.data_as(C.POINTER(C.c_double))
+
+
+def _mask_hw(e: Engine, mask):
+    """A float mask, HxW or HxWx3 (the reference stacks three identical channels), host or device -> contiguous fp32 HxW on the device."""
+    m = torch.as_tensor(mask)
+    if m.dim() == 3:
+        m = m[..., 0]
+    return m.to(e.device).float().contiguous()
 
 
 class SoftErosion:
@@ -70,10 +80,7 @@ def soft_erosion_frames(e: Engine, masks, weight, kernel_size=21, threshold=0.9,
         m = m.to(torch.uint8) if not m.dtype.is_floating_point else m.float()
     m = m.to(e.device).contiguous()
     B, H, W = m.shape
-    if out is None:
-        out = torch.empty((B, H, W), dtype=torch.float32, device=e.device)
-    elif out.dtype != torch.float32 or tuple(out.shape) != (B, H, W) or not out.is_contiguous() or out.device != e.device:
-        raise ValueError("out must be a contiguous (B, H, W) fp32 tensor of the masks' shape on the engine's device")
+    out = e._out(out, (B, H, W), torch.float32)
     if weight.dtype != torch.float32 or weight.numel() != kernel_size * kernel_size or not weight.is_contiguous() or weight.device != e.device:
         raise ValueError("weight must be the contiguous kernel_size x kernel_size fp32 kernel on the engine's device")
     with torch.cuda.device(e.device):
@@ -93,13 +100,10 @@ def paste_back_batch(e: Engine, crops, masks_crop, M_c2o, imgs_ori, out=None):
     mc = torch.as_tensor(masks_crop).to(e.device).float().contiguous()
     if tuple(mc.shape) != tuple(crops.shape[:3]) or ori.shape[0] != B:
         raise ValueError("masks_crop must be (B, Hc, Wc) and imgs_ori must hold B frames")
-    M = np.ascontiguousarray(np.asarray(M_c2o, dtype=np.float64).reshape(B, -1)[:, :6])
-    if out is None:
-        out = torch.empty_like(ori)
-    elif out.dtype != torch.uint8 or tuple(out.shape) != tuple(ori.shape) or not out.is_contiguous() or out.device != ori.device:
-        raise ValueError("out must be a contiguous uint8 tensor of the shape of imgs_ori on the engine's device")
+    mm, mp = _m6(M_c2o, B)
+    out = e._out(out, ori.shape, torch.uint8)
     with torch.cuda.device(e.device):
-        _lib.check(e.lib.cs_paste_back_batch(e.h, B, _ptr(crops), _ptr(mc), crops.shape[1], crops.shape[2], M.ctypes.data_as(C.POINTER(C.c_double)),
+        _lib.check(e.lib.cs_paste_back_batch(e.h, B, _ptr(crops), _ptr(mc), crops.shape[1], crops.shape[2], mp,
                                              _ptr(ori), _ptr(out), ori.shape[1], ori.shape[2], e._stream()), "cs_paste_back_batch")
     return out
 
@@ -114,18 +118,11 @@ def paste_back_shared(e: Engine, crops, M_c2o, img_ori, mask_ori, out=None):
     if ori.dtype != torch.uint8 or ori.dim() != 3 or ori.shape[2] != 3:
         raise ValueError("expected ONE HoxWox3 uint8 image")
     crops, ori = crops.to(e.device).contiguous(), ori.to(e.device).contiguous()
-    mo = torch.as_tensor(mask_ori)
-    if mo.dim() == 3:
-        mo = mo[..., 0]
-    mo = mo.to(e.device).float().contiguous()
+    mo = _mask_hw(e, mask_ori)
     if tuple(mo.shape) != tuple(ori.shape[:2]):
         raise ValueError("mask_ori must have the size of img_ori")
     B = crops.shape[0]
-    shape = (B,) + tuple(ori.shape)
-    if out is None:
-        out = torch.empty(shape, dtype=torch.uint8, device=e.device)
-    elif not isinstance(out, torch.Tensor) or out.dtype != torch.uint8 or tuple(out.shape) != shape or not out.is_contiguous() or out.device != e.device:
-        raise ValueError("out must be a contiguous (B, Ho, Wo, 3) uint8 tensor on the engine's device")
+    out = e._out(out, (B,) + tuple(ori.shape), torch.uint8)
     mm, mp = _m6(M_c2o)
     with torch.cuda.device(e.device):
         _lib.check(e.lib.cs_paste_back_shared(e.h, B, _ptr(crops), crops.shape[1], crops.shape[2], _ptr(mo), mp, _ptr(ori), _ptr(out),
@@ -154,10 +151,7 @@ def warp_affine_u8(e: Engine, img, M, dsize):
 def prepare_paste_back(e: Engine, mask_crop, crop_M_c2o, dsize):
     """crop.py:515-521 with if_float=True (the call of can_swap_pipeline_e2e.py:279): float mask -> frame of the original image.
     mask_crop: HxW or HxWx3 (the reference stacks three identical channels); returns HoxWo float32 on the device."""
-    m = torch.as_tensor(mask_crop)
-    if m.dim() == 3:
-        m = m[..., 0]
-    m = m.to(e.device).float().contiguous()
+    m = _mask_hw(e, mask_crop)
     Wd, Hd = int(dsize[0]), int(dsize[1])
     dst = torch.empty((Hd, Wd), dtype=torch.float32, device=e.device)
     mm, mp = _m6(crop_M_c2o)
@@ -169,10 +163,7 @@ def prepare_paste_back(e: Engine, mask_crop, crop_M_c2o, dsize):
 def paste_back(e: Engine, img_crop, M_c2o, img_ori, mask_ori):
     """crop.py:523-529: result = warp(img_crop); clip(mask_ori * result + (1 - mask_ori) * img_ori, 0, 255) as uint8."""
     crop, ori = _u8_hwc(e, img_crop), _u8_hwc(e, img_ori)
-    mo = torch.as_tensor(mask_ori)
-    if mo.dim() == 3:
-        mo = mo[..., 0]
-    mo = mo.to(e.device).float().contiguous()
+    mo = _mask_hw(e, mask_ori)
     if tuple(mo.shape) != tuple(ori.shape[:2]):
         raise ValueError("mask_ori must have the size of img_ori")
     out = torch.empty_like(ori)
@@ -186,10 +177,7 @@ def paste_back(e: Engine, img_crop, M_c2o, img_ori, mask_ori):
 def paste_back_fused(e: Engine, img_crop, mask_crop, M_c2o, img_ori):
     """prepare_paste_back + paste_back in one launch: the soft mask stays in the crop frame (HcxWc float32)."""
     crop, ori = _u8_hwc(e, img_crop), _u8_hwc(e, img_ori)
-    mc = torch.as_tensor(mask_crop)
-    if mc.dim() == 3:
-        mc = mc[..., 0]
-    mc = mc.to(e.device).float().contiguous()
+    mc = _mask_hw(e, mask_crop)
     if tuple(mc.shape) != tuple(crop.shape[:2]):
         raise ValueError("mask_crop must have the size of img_crop")
     out = torch.empty_like(ori)
@@ -210,10 +198,7 @@ def prepare_crops(e: Engine, crops_u8, out=None) -> torch.Tensor:
         raise ValueError("expected BxHxWx3 uint8 crops")
     t = t.to(e.device).contiguous()
     B, H, W, _ = t.shape
-    if out is None:
-        out = torch.empty((B, 3, 256, 256), dtype=torch.float32, device=e.device)
-    elif out.dtype != torch.float32 or tuple(out.shape) != (B, 3, 256, 256) or not out.is_contiguous() or out.device != e.device:
-        raise ValueError("out must be a contiguous (B, 3, 256, 256) fp32 tensor on the engine's device")
+    out = e._out(out, (B, 3, 256, 256), torch.float32)
     with torch.cuda.device(e.device):
         _lib.check(e.lib.cs_prepare_crops(e.h, B, _ptr(t), H, W, _ptr(out), e._stream()), "cs_prepare_crops")
     return out

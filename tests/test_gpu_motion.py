@@ -9,19 +9,19 @@ import numpy as np
 import pytest
 import torch
 
+import chain_helpers
+
 pytestmark = pytest.mark.gpu
 
 
 @pytest.fixture(scope="module")
 def sds_m():
-    from canonswap_amd import synth
-    return synth.to_torch(synth.make_state_dicts(0, modules=synth.MODULES + ("motion_extractor",)))
+    return chain_helpers.motion_state_dicts()
 
 
 @pytest.fixture(scope="module")
 def swapper_m(sds_m):
-    from canonswap_amd.can_swap_e2e import can_swapper
-    return can_swapper(None, state_dicts=sds_m, max_batch=4)
+    return chain_helpers.swapper_b4(sds_m)
 
 
 @pytest.fixture(scope="module")

@@ -7,35 +7,20 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+import chain_helpers
+from chain_helpers import _affine, _masks, _occupy, _timed
+
 pytestmark = pytest.mark.gpu
 
 
 @pytest.fixture(scope="module")
 def sds_m():
-    from canonswap_amd import synth
-    return synth.to_torch(synth.make_state_dicts(0, modules=synth.MODULES + ("motion_extractor",)))
+    return chain_helpers.motion_state_dicts()
 
 
 @pytest.fixture(scope="module")
 def swapper_m(sds_m):
-    from canonswap_amd.can_swap_e2e import can_swapper
-    return can_swapper(None, state_dicts=sds_m, max_batch=4)
-
-
-def _affine(k, Ho, Wo):
-    th, sc = 0.1 * k - 0.15, 0.8 + 0.12 * k
-    tx, ty = 0.3 * Wo - 40.5 * k, 0.1 * Ho + 33.25 * k
-    return np.array([[sc * np.cos(th), -sc * np.sin(th), tx], [sc * np.sin(th), sc * np.cos(th), ty], [0, 0, 1]], np.float64)
-
-
-def _masks(n, seed=5):
-    r = np.random.Generator(np.random.PCG64(seed))
-    yy, xx = np.mgrid[0:512, 0:512].astype(np.float32)
-    out = []
-    for k in range(n):
-        cx, cy, a, b = r.uniform(200, 312), r.uniform(200, 312), r.uniform(120, 200), r.uniform(150, 220)
-        out.append((((xx - cx) / a) ** 2 + ((yy - cy) / b) ** 2 <= 1).astype(np.uint8))
-    return np.stack(out)
+    return chain_helpers.swapper_b4(sds_m)
 
 
 def _crops(n, seed):
@@ -414,24 +399,6 @@ def test_chain_equals_its_stages(swapper_m, case):
 
 
 # ------------------------------------------------------------------------------------------------ stream rules
-def _timed():
-    return torch.cuda.Event(enable_timing=True)
-
-
-def _occupy(stream, ms):
-    """Keep `stream` busy for about `ms` milliseconds with one bounded spin kernel (calibrated first), so that work queued behind it on that
-    stream is certainly still pending while the caller's stream runs."""
-    a, b = _timed(), _timed()
-    with torch.cuda.stream(stream):
-        a.record()
-        torch.cuda._sleep(1_000_000)
-        b.record()
-    b.synchronize()
-    per_ms = 1e6 / max(a.elapsed_time(b), 1e-3)
-    with torch.cuda.stream(stream):
-        torch.cuda._sleep(int(min(min(ms, 200.0) * per_ms, 1e9)))
-
-
 def _drv(seed, B=2):
     return torch.from_numpy(_crops(B, seed)).cuda()
 
