@@ -27,6 +27,7 @@ ABI_SYMBOLS = [
     "cs_motion_extract", "cs_motion_keypoints", "cs_soft_erosion_frames", "cs_paste_back_batch", "cs_swap_frames", "cs_animate_frames", 
     "cs_resize_half_bilinear", "cs_motion_keypoints_driven", "cs_paste_back_shared", "cs_profile_begin", "cs_profile_end", "cs_profile_exec_flops", "cs_op_conv", "cs_op_grid_sample3d",
     "cs_op_chan_stats", "cs_op_chan_stats_partial_floats", "cs_op_pair_ragged", "cs_op_resblock3d", "cs_op_t_mask",
+    "cs_op_t_style", "cs_op_t_modulate", "cs_op_t_read", "cs_op_t_layer",
     "cs_op_m_stem", "cs_op_m_dwln", "cs_op_m_ln_s2d", "cs_op_m_grn", "cs_op_m_head", "cs_op_m_pointwise",
     "cs_op_dm_compress", "cs_op_dm_sparse", "cs_op_dm_softmax_warp", "cs_op_occ_finish", "cs_op_dm_read",
 ]
@@ -413,6 +414,10 @@ def load():
     lib.cs_op_chan_stats.argtypes = [vp, ci, ci, C.c_long, ci, cf, vp, vp, vp]
     lib.cs_op_pair_ragged.argtypes = [vp, ci, ci, ci, ci, ci, vp]
     lib.cs_op_t_mask.argtypes = [vp, vp, vp, vp, ci, ci, ci, vp]
+    lib.cs_op_t_style.argtypes = [vp, vp, vp, ci, vp]
+    lib.cs_op_t_modulate.argtypes = [vp, vp, vp, vp]
+    lib.cs_op_t_read.argtypes = [vp, ci, ci, ci, vp, vp]
+    lib.cs_op_t_layer.argtypes = [vp, ci, ci, C.POINTER(ci), vp, vp, vp, vp, vp, vp]
     lib.cs_op_m_stem.argtypes = [vp, vp, vp, vp, vp, vp, ci, ci, ci, vp]
     lib.cs_op_m_dwln.argtypes = [vp, vp, vp, vp, vp, vp, ci, ci, ci, ci, vp]
     lib.cs_op_m_ln_s2d.argtypes = [vp, vp, vp, vp, ci, ci, ci, ci, vp]

@@ -699,18 +699,16 @@ int run_warp_out(cs_engine* e, int B, const half_t* vol16, const float* occ, hip
 }
 
 // ------------------------------------------------------------------------------------------------ T
-// transfer_model2.forward (adaptive_modulate.py:522-554). x: fp32 vs[*cur] + fp16 copy va[0].
-// On exit: fp32 result in vs[*cur], fp16 copy in va[0].
-// slots: B host ints (identity slot per sample)
-int run_T(cs_engine* e, int B, const int* slots, int* cur, hipStream_t st)
+// Checks the slots of a batch (B host ints, the identity slot per sample) and, when they differ, uploads the per-sample slot vector; *mixed: the launches read e->slot_dev
+int t_slots(cs_engine* e, int B, const int* slots, bool* mixed, hipStream_t st)
 {
-    bool mixed = false;
+    *mixed = false;
     for (int b = 0; b < B; ++b) {
         if (slots[b] < 0 || slots[b] >= MAX_SLOTS) { cs_set_error("cs_swap: identity slot %d outside [0, %d)", slots[b], MAX_SLOTS); return -1; }
         if (!e->slot_set[slots[b]]) { cs_set_error("cs_swap: cs_set_identity has not been called for slot %d", slots[b]); return -1; }
-        mixed |= slots[b] != slots[0];
+        *mixed |= slots[b] != slots[0];
     }
-    if (mixed) {    // upload the per-sample slot vector when it changed (pinned ring: earlier async copies may still be pending)
+    if (*mixed) {    // upload the per-sample slot vector when it changed (pinned ring: earlier async copies may still be pending)
         if (e->slot_cur.size() != (size_t)B || memcmp(e->slot_cur.data(), slots, sizeof(int) * B) != 0) {
             int* stage = e->slot_pin + (size_t)(e->slot_ring++ % 16) * e->maxB;
             memcpy(stage, slots, sizeof(int) * B);
@@ -719,37 +717,56 @@ int run_T(cs_engine* e, int B, const int* slots, int* cur, hipStream_t st)
             e->slot_cur.assign(slots, slots + B);
         }
     }
+    return 0;
+}
+
+// One AdaptiveSharedWeightConv2d layer of T (layer = 2 * block + (conv2 ? 1 : 0)) on [B][64][64][512] tensors: the mask conv into tmask, then
+// the fused [W ; w_mod] conv with the blend epilogue.  conv1: out16 = relu(blend); conv2: out32 = res32 + blend and out16 its fp16 copy, on the
+// last block through resblocks_3d.3dr0's norm1 + ReLU.  run_T and cs_op_t_layer both launch a layer here, so the operator test runs the
+// engine's routing.
+int t_layer(cs_engine* e, int layer, int B, const int* slots, bool mixed, const half_t* in, const float* res32, float* tmask, half_t* out16,
+            float* out32, hipStream_t st)
+{
+    TLayer& L = e->t_l[layer];
+    // mask_conv + sigmoid (:118-121,176): 512 -> 1 channel, a memory-bound dot product - its own VALU kernel (t_mask_kernel: 65 -> 4x us
+    // per launch against one row of sixteen on the MFMA kernel)
+    {
+        const double mfl = 2.0 * L.mask.macs_per_pos * (double)B * 4096;
+        e->flops += mfl; e->flops_exec += mfl;
+        TRY(e->run(0, st, [&] { return launch_t_mask(in, L.mask.w, L.mask.b, tmask, B, 64, 64, st); }, L.mask.name.c_str(), mfl));
+    }
+    ConvCall fc = mk(L.fused, in, hwdc2(nullptr), B, 1, 64, 64);      // [W ; w_mod] fused, blend epilogue
+    fc.mode = MODE_TBLEND;
+    if (mixed) { fc.p.wgt = L.wset[0]; fc.p.wofs = L.wofs; fc.p.wslot = e->slot_dev; }   // per-sample w_mod (groups=N, :157-167)
+    else fc.p.wgt = L.wset[slots[0]];
+    fc.p.Cout = 512;
+    fc.p.bias = L.bias;
+    fc.p.pixscale = tmask; fc.p.ps_stride = 4;
+    if (layer % 2 == 0) {
+        fc.p.act0 = ACT_RELU;
+        fc.p.out0 = hwdc2(out16);
+    } else {
+        fc.p.res = hwdc2((void*)res32); fc.p.res_f32 = 1;
+        fc.p.out0 = hwdc2(out32); fc.p.out0_f32 = 1;
+        fc.p.out1 = hwdc2(out16);
+        if (layer == 13) { fc.p.s2 = e->t_pre0.s; fc.p.t2 = e->t_pre0.t; fc.p.act1 = ACT_RELU; }
+    }
+    return go(e, fc, st);
+}
+
+// transfer_model2.forward (adaptive_modulate.py:522-554). x: fp32 vs[*cur] + fp16 copy va[0].
+// On exit: fp32 result in vs[*cur], fp16 copy in va[0].
+// slots: B host ints (identity slot per sample)
+int run_T(cs_engine* e, int B, const int* slots, int* cur, hipStream_t st)
+{
+    bool mixed = false;
+    TRY(t_slots(e, B, slots, &mixed, st));
     for (int i = 0; i < 7; ++i) {
-        for (int j = 0; j < 2; ++j) {   // ResnetBlock_Adaptive2D: conv1 -> ReLU -> conv2, + x (:337-349)
-            TLayer& L = e->t_l[i * 2 + j];
-            const half_t* in = e->va[j];
-            // mask_conv + sigmoid (:118-121,176): 512 -> 1 channel, a memory-bound dot product - its own VALU kernel (t_mask_kernel: 65 -> 4x us
-            // per launch against one row of sixteen on the MFMA kernel)
-            {
-                const double mfl = 2.0 * L.mask.macs_per_pos * (double)B * 4096;
-                e->flops += mfl; e->flops_exec += mfl;
-                TRY(e->run(0, st, [&] { return launch_t_mask(in, L.mask.w, L.mask.b, e->tmask, B, 64, 64, st); }, L.mask.name.c_str(), mfl));
-            }
-            ConvCall fc = mk(L.fused, in, hwdc2(nullptr), B, 1, 64, 64);      // [W ; w_mod] fused, blend epilogue
-            fc.mode = MODE_TBLEND;
-            if (mixed) { fc.p.wgt = L.wset[0]; fc.p.wofs = L.wofs; fc.p.wslot = e->slot_dev; }   // per-sample w_mod (groups=N, :157-167)
-            else fc.p.wgt = L.wset[slots[0]];
-            fc.p.Cout = 512;
-            fc.p.bias = L.bias;
-            fc.p.pixscale = e->tmask; fc.p.ps_stride = 4;
-            if (j == 0) {
-                fc.p.act0 = ACT_RELU;
-                fc.p.out0 = hwdc2(e->va[1]);
-            } else {
-                const int nxt = (*cur + 1) % 3;
-                fc.p.res = hwdc2(e->vs[*cur]); fc.p.res_f32 = 1;
-                fc.p.out0 = hwdc2(e->vs[nxt]); fc.p.out0_f32 = 1;
-                fc.p.out1 = hwdc2(e->va[0]);
-                if (i == 6) { fc.p.s2 = e->t_pre0.s; fc.p.t2 = e->t_pre0.t; fc.p.act1 = ACT_RELU; }
-                *cur = nxt;
-            }
-            TRY(go(e, fc, st));
-        }
+        // ResnetBlock_Adaptive2D: conv1 -> ReLU -> conv2, + x (:337-349)
+        TRY(t_layer(e, 2 * i, B, slots, mixed, e->va[0], nullptr, e->tmask, e->va[1], nullptr, st));
+        const int nxt = (*cur + 1) % 3;
+        TRY(t_layer(e, 2 * i + 1, B, slots, mixed, e->va[1], e->vs[*cur], e->tmask, e->va[0], e->vs[nxt], st));
+        *cur = nxt;
     }
     return run_resblocks3d(e, e->t_rb, B, cur, nullptr, ACT_NONE, st);   // last block leaves the raw fp16 copy in va[0]
 }
@@ -1824,6 +1841,50 @@ extern "C" int cs_op_resblock3d(const void* a, const float* x, float* out0, void
 extern "C" int cs_op_t_mask(const void* x, const void* wpacked, const float* bias, float* tmask, int N, int H, int W, void* stream)
 {
     return launch_t_mask((const half_t*)x, (const half_t*)wpacked, bias, tmask, N, H, W, (hipStream_t)stream);
+}
+
+// ---- operator level: T's per-identity precompute (csrc/kernels.hip) without an engine, what cs_set_identity left in an engine (cs_op_t_read), and
+// one blend layer of T on the caller's buffers through the engine's routing (cs_op_t_layer)
+extern "C" int cs_op_t_style(const float* id, const float* fc, float* style, int nlayers, void* stream)
+{
+    if (!id || !fc || !style || nlayers < 1) { cs_set_error("cs_op_t_style: bad arguments"); return -1; }
+    return launch_t_style(id, fc, style, nlayers, (hipStream_t)stream);
+}
+
+extern "C" int cs_op_t_modulate(const float* wraw, const float* style, void* packed, void* stream)
+{
+    if (!wraw || !style || !packed) { cs_set_error("cs_op_t_modulate: bad arguments"); return -1; }
+    return launch_t_modulate(wraw, style, (half_t*)packed, 0, (hipStream_t)stream);
+}
+
+extern "C" int cs_op_t_read(cs_engine* e, int layer, int slot, int which, void* dst, void* stream)
+{
+    if (!e || !e->finalized) { cs_set_error("cs_op_t_read: engine not finalized"); return -1; }
+    if (!dst) { cs_set_error("cs_op_t_read: null destination"); return -1; }
+    if (layer < 0 || layer >= 14) { cs_set_error("cs_op_t_read: layer %d outside [0, 14)", layer); return -1; }
+    if (slot < 0 || slot >= MAX_SLOTS) { cs_set_error("cs_op_t_read: identity slot %d outside [0, %d)", slot, MAX_SLOTS); return -1; }
+    if (!e->slot_set[slot]) { cs_set_error("cs_op_t_read: cs_set_identity has not been called for slot %d", slot); return -1; }
+    DevGuard guard(e->dev);
+    if (which == CS_T_WSET) return copy_dd(dst, e->t_l[layer].wset[slot], (size_t)144 * 1024 * 32 * sizeof(half_t), (hipStream_t)stream);
+    if (which == CS_T_STYLE) return copy_dd(dst, e->style + layer * 512, 512 * sizeof(float), (hipStream_t)stream);
+    cs_set_error("cs_op_t_read: no buffer %d", which);
+    return -1;
+}
+
+extern "C" int cs_op_t_layer(cs_engine* e, int layer, int B, const int* slots, const void* in16, const float* res32, float* tmask_out, void* out16,
+                             float* out32, void* stream)
+{
+    ENTER(e, B);
+    if (layer < 0 || layer >= 14) { cs_set_error("cs_op_t_layer: layer %d outside [0, 14)", layer); return -1; }
+    const bool conv2 = layer % 2 == 1;
+    if (!slots || !in16 || !tmask_out || !out16 || (conv2 && (!res32 || !out32)) || (!conv2 && (res32 || out32))) {
+        cs_set_error("cs_op_t_layer: bad arguments (conv2 layers take res32 and out32, conv1 layers neither)");
+        return -1;
+    }
+    hipStream_t st = (hipStream_t)stream;
+    bool mixed = false;
+    TRY(t_slots(e, B, slots, &mixed, st));
+    return t_layer(e, layer, B, slots, mixed, (const half_t*)in16, res32, tmask_out, (half_t*)out16, out32, st);
 }
 
 extern "C" int cs_op_pair_ragged(void* w, int Cout_pad, int nchunks, int KD, int KH, int KW, void* stream)

@@ -205,6 +205,28 @@ int cs_op_pair_ragged(void* w, int Cout_pad, int nchunks, int KD, int KH, int KW
 /* T's mask conv + sigmoid (adaptive_modulate.py:118-121,176: Conv2d(512, 1, 3, padding 1)) as a memory-bound VALU kernel: x fp16 [N][H][W][512],
  * w the layer's packed conv weight [16 chunks * 9 taps][16][32] (row 0 is the output channel), tmask[(n H W + h W + w) * 4] = sigmoid(conv + bias[0]) */
 int cs_op_t_mask(const void* x, const void* wpacked, const float* bias, float* tmask, int N, int H, int W, void* stream);
+/* T's per-identity precompute one kernel at a time (csrc/kernels.hip; blobs as pack._pack_T lays them out).
+ * style: id 512 fp32, fc = nlayers x [W1 512x512][b1 512][W2 512x512][b2 512] fp32 (the ".fc" blobs back to back) -> style fp32 [nlayers][512]
+ * = W2 lrelu(W1 id + b1, 0.2) + b2; the ".fc" blob carries W2 / b2 in memory channel order, so style does too.
+ * modulate: wraw fp32 [512 o][9 taps][512 i] (the ".raw" blob, memory channel order), style 512 fp32 -> the 512 x 4608 values
+ * wraw[o][t][i] style[i] / sqrt(sum_{t,i} (wraw[o][t][i] style[i])^2 + 1e-8) as fp16 into packed [144 = (i / 32) * 9 + t][1024][32 = i % 32] at
+ * row ((o / 16) * 2 + 1) * 16 + o % 16; the rows ((o / 16) * 2) * 16 + o % 16 (the shared weight W) are not written. */
+int cs_op_t_style(const float* id, const float* fc, float* style, int nlayers, void* stream);
+int cs_op_t_modulate(const float* wraw, const float* style, void* packed, void* stream);
+/* Copies to dst on `stream` what cs_set_identity left in the engine for layer 0 .. 13 (2 * block + conv - 1) and an identity slot that has been set:
+ *   CS_T_WSET:   fp16 [144][1024][32], the slot's fused [W ; w_mod] set of the layer (rows as cs_op_t_modulate describes them)
+ *   CS_T_STYLE:  fp32 [512], the style vector the LAST cs_set_identity call (whatever its slot) computed for the layer, memory channel order */
+enum { CS_T_WSET = 0, CS_T_STYLE = 1 };
+int cs_op_t_read(cs_engine* e, int layer, int slot, int which, void* dst, void* stream);
+/* One AdaptiveSharedWeightConv2d layer of T (adaptive_modulate.py:128-193) on caller buffers, launched as cs_swap_ids launches it on this engine
+ * (tile configuration by batch, the wide kernel, latency mode's conv_lat, per-sample weight sets): slots: B host ints; in16 fp16 [B][64][64][512]
+ * (channel d * 32 + c); tmask_out fp32 [B][64][64][4], element 0 of each group receives sigmoid(mask_conv), the others are not written;
+ * blend = mask * (conv(in, w_mod[slot]) + bias) + (1 - mask) * conv(in, W).
+ * Even layers (conv1): out16 fp16 [B][64][64][512] = relu(blend); res32 and out32 must be NULL.
+ * Odd layers (conv2): res32 fp32 [B][64][64][512] -> out32 fp32 = res32 + blend, out16 = fp16(out32), for layer 13 out16 = relu(out32 * s + t)
+ * with the "T.pre0" affine (resblocks_3d.3dr0.norm1 folded). */
+int cs_op_t_layer(cs_engine* e, int layer, int B, const int* slots, const void* in16, const float* res32, float* tmask_out, void* out16,
+                  float* out32, void* stream);
 /* one ResBlock3d of a feature volume (util.py:80-102, BatchNorms folded): contiguous [N][H][W][16][32] volumes a (fp16), x (fp32) ->
  * out0 (fp32) = conv2(relu(conv1(a) + b1)) + b2 + x, out1 (fp16) = act1(out0 * s2 + t2); w1 / w2 packed like every 3x3x3 32 -> 32 weight */
 int cs_op_resblock3d(const void* a, const float* x, float* out0, void* out1, int N, int H, int W, const void* w1, const void* w2,

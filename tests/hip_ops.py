@@ -279,3 +279,44 @@ def compact2_logits(part, bias):
     for T in range(nT):
         l[:, :, :, 4 * T:4 * T + 10] += part[:, :, :, T]
     return l[:, :, :, 3:3 + Ww] + bias.to(part.dtype)
+
+
+# ---- T's identity path (cs_op_t_*; csrc/kernels.hip t_style / t_modulate, the engine's per-slot weight sets and its blend layers)
+T_WSET, T_STYLE = 0, 1
+
+
+def t_style(idv, fc, style, nlayers):
+    """idv fp32 [512], fc fp32 nlayers x (2 * (512 * 512 + 512)) -> style (caller's fp32 buffer of nlayers * 512 values)"""
+    assert idv.is_contiguous() and fc.is_contiguous() and style.is_contiguous()
+    _lib.check(_lib.load().cs_op_t_style(_p(idv), _p(fc), _p(style), nlayers, _st()), "cs_op_t_style")
+    return style
+
+
+def t_modulate(wraw, style, packed):
+    """wraw fp32 [512, 9, 512], style fp32 [512] -> the modulated rows of packed (caller's fp16 buffer [144, 1024, 32])"""
+    assert wraw.is_contiguous() and style.is_contiguous() and packed.is_contiguous()
+    _lib.check(_lib.load().cs_op_t_modulate(_p(wraw), _p(style), _p(packed), _st()), "cs_op_t_modulate")
+    return packed
+
+
+def t_read(engine, layer, slot, which):
+    """The slot's fused weight set fp16 [144, 1024, 32] (T_WSET) or the layer's last style vector fp32 [512] (T_STYLE) of a live engine"""
+    out = torch.empty((144, 1024, 32), dtype=torch.float16, device=engine.device) if which == T_WSET else \
+        torch.empty(512, dtype=torch.float32, device=engine.device)
+    _lib.check(engine.lib.cs_op_t_read(engine.h, layer, slot, which, _p(out), _st()), "cs_op_t_read")
+    return out
+
+
+def t_layer(engine, layer, slots, x16, res32, tmask, out16, out32):
+    """One blend layer of T through the engine's routing (cs_op_t_layer): x16 fp16 [B, 64, 64, 512]; tmask fp32 [B, 64, 64, 4], out16 fp16 and
+    (odd layers) res32 / out32 fp32 [B, 64, 64, 512] are the caller's buffers"""
+    B = x16.shape[0]
+    assert len(slots) == B and all(t is None or t.is_contiguous() for t in (x16, res32, tmask, out16, out32))
+    arr = (C.c_int * B)(*[int(s) for s in slots])
+    _lib.check(engine.lib.cs_op_t_layer(engine.h, layer, B, arr, _p(x16), _p(res32), _p(tmask), _p(out16), _p(out32), _st()), "cs_op_t_layer")
+
+
+def t_rows(kind):
+    """Row indices, in a fused [W ; w_mod] set of 1024 rows, of the 512 memory out-channels' shared (kind 0) or modulated (kind 1) rows"""
+    o = np.arange(512)
+    return ((o // 16) * 2 + kind) * 16 + o % 16

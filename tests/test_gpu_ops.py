@@ -459,6 +459,38 @@ def test_t_mask_segment_length_does_not_change_bits():
         assert torch.equal(one[0], big[n])
 
 
+def test_t_mask_16_column_segments():
+    """N = 2, H = 66, W = 128: 1056 items and H % 4 != 0, so launch_t_mask takes t_mask_kernel<16> (no 64 x 64 launch reaches it: from 1024 items
+    up those go to t_mask_rows_kernel).  Against float64 of the fp16 operands at a derived bound: along any path to an output lie 36 fdot2 (two
+    roundings each at most), 16 sequential adds, 2 exchanges and the bias, 91 roundings: |dy| <= 91 u sum |x w|, u = 2^-24; the sigmoid's slope is at
+    most 1/4, and 8 u cover __expf and the division on a result below 1.  Per output the bits of the other two instantiations: each sample
+    alone (528 items: <4>), and the same maps with two zero rows appended (H = 68: t_mask_rows_kernel; explicit zero rows are the zero padding)."""
+    import hip_ops as ops
+    r = _rng(7766)
+    N, H, W = 2, 66, 128
+    x = F.relu(_randn(r, N, 512, H, W))
+    w = _randn(r, 1, 512, 3, 3, scale=2.0 / np.sqrt(512 * 9))
+    b = _randn(r, 4, scale=0.1)
+    xq, wq = x.half().double(), w.half().double()
+    y = F.conv2d(xq, wq, b[:1].double(), padding=1)[:, 0]
+    bound = 0.25 * 91 * 2.0 ** -24 * (F.conv2d(xq.abs(), wq.abs(), b[:1].double().abs(), padding=1)[:, 0]) + 8 * 2.0 ** -24
+    xd = x.permute(0, 2, 3, 1).contiguous().half().to(DEV)
+    wp = ops.packed_weight(w.unsqueeze(2), 16, DEV)
+    out = ops.t_mask(xd, wp, b.to(DEV))
+    torch.cuda.synchronize()
+    err = (out[..., 0].cpu().double() - torch.sigmoid(y)).abs()
+    print(f"\nt_mask<16>: max err {float(err.max()):.3e}, max err / bound {float((err / bound).max()):.3f}")
+    assert bool(torch.all(err <= bound))
+    assert float((out[..., 1:] + 1.0).abs().max()) == 0.0
+    for n in range(N):
+        one = ops.t_mask(xd[n:n + 1].contiguous(), wp, b.to(DEV))
+        assert torch.equal(one[0], out[n]), n
+    x68 = torch.cat([xd, torch.zeros(N, 2, W, 512, dtype=torch.float16, device=DEV)], 1).contiguous()
+    rows = ops.t_mask(x68, wp, b.to(DEV))
+    torch.cuda.synchronize()
+    assert torch.equal(rows[:, :H], out)
+
+
 @pytest.mark.parametrize("stat", [False, True])
 def test_conv_256x64_tile_2d(stat):
     """3x3, 128 -> 64 (G's last up block / F's first down block) on the 2-D 256-position x 64-channel tile (16x16) against the 128x64

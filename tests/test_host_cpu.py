@@ -258,3 +258,55 @@ def test_getid_arithmetic_with_injected_network():
     host.netArc = None
     with pytest.raises(RuntimeError, match="identity network"):
         can_swapper.getid(host, img)
+
+
+def test_unpack_conv_deinterleaves_the_fused_t_rows():
+    """unpack_conv(pack_conv(interleave16(a, b))) gives a and b back at rows ((o / 16) * 2 + kind) * 16 + o % 16: the row formula of
+    t_modulate_kernel (csrc/kernels.hip) for the fused [W ; w_mod] set"""
+    r = np.random.Generator(np.random.PCG64(31))
+    a = r.standard_normal((64, 96, 3, 3)).astype(np.float16).astype(np.float32)
+    b = r.standard_normal((64, 96, 3, 3)).astype(np.float16).astype(np.float32)
+    p = pack.pack_conv(pack.interleave16(a, b), 128)
+    assert p.shape == (3 * 9, 128, 32)
+    u = pack.unpack_conv(p, 128, 96, 1, 3, 3)[:, :, 0]
+    o = np.arange(64)
+    assert np.array_equal(u[((o // 16) * 2) * 16 + o % 16], a) and np.array_equal(u[((o // 16) * 2 + 1) * 16 + o % 16], b)
+    v = u.reshape(4, 2, 16, 96, 3, 3)
+    assert np.array_equal(v[:, 0].reshape(64, 96, 3, 3), a) and np.array_equal(v[:, 1].reshape(64, 96, 3, 3), b)
+
+
+def t_precompute_f32(fc, raw, idv):
+    """fp32 numpy restatement of t_style_kernel + t_modulate_kernel on pack._pack_T's ".fc" / ".raw" blobs -> (style [512], w_mod [512, 9, 512])"""
+    f = np.float32
+    n = 512 * 512
+    w1, b1, w2, b2 = fc[:n].reshape(512, 512), fc[n:n + 512], fc[n + 512:2 * n + 512].reshape(512, 512), fc[2 * n + 512:]
+    h = w1 @ idv.astype(f) + b1
+    h = np.where(h > 0, h, f(0.2) * h).astype(f)
+    style = (w2 @ h + b2).astype(f)
+    m = raw * style[None, None, :]
+    ss = (m * m).reshape(512, -1).sum(1, dtype=f)
+    return style, m * (f(1) / np.sqrt(ss + f(1e-8)))[:, None, None]
+
+
+@pytest.mark.parametrize("layer", ["T.b0.c1", "T.b0.c2", "T.b3.c2", "T.b6.c1", "T.b6.c2"])
+def test_t_blobs_restated_in_fp32_match_the_oracles_modulated_weight(state_dicts_np, state_dicts, layer):
+    """The ".fc" blob is [W1][b1][W2][b2] with fc.2 (rows and bias) in memory channel order and fc.0 untouched, ".raw" is [o][tap][i] in memory
+    order: an fp32 restatement of the two kernels on them lands within one fp16 ulp of the oracle's float64 modulated_weight, its style within
+    1e-6 of the oracle's style (|style| is O(1))."""
+    from canonswap_amd import synth
+    from oracle import canonswap_ref as O
+    blobs = {}
+    pack._pack_T(blobs, state_dicts_np["transfer"])
+    sdd = {k: v.double() for k, v in state_dicts["transfer"].items()}
+    idv = synth.make_identity(7)
+    p = "BottleNeck_2d.%s.conv%s" % (layer[3], layer[6])
+    style, wm = t_precompute_f32(blobs[layer + ".fc"], blobs[layer + ".raw"], idv[0])
+    lat = torch.from_numpy(idv).double()
+    ref_s = O.style_vector(sdd, p, lat)[0].numpy()[pack.MEM2REF]
+    assert np.abs(style - ref_s).max() < 1e-6
+    assert np.abs(style - O.style_vector(sdd, p, lat)[0].numpy()).max() > 1e-2      # (the permutation is not the identity on this vector)
+    ref = O.modulated_weight(sdd, p, lat)[0].numpy()[pack.MEM2REF][:, pack.MEM2REF].transpose(0, 2, 3, 1).reshape(512, 9, 512)
+    ulp = np.abs(np.spacing(np.abs(ref).astype(np.float16))).astype(np.float64)
+    err = np.abs(wm.astype(np.float16).astype(np.float64) - ref) / ulp
+    print(f"\n{layer}: max error {err.max():.3f} fp16 ulp, style {np.abs(style - ref_s).max():.2e}")
+    assert err.max() <= 1.0
