@@ -1,8 +1,10 @@
 """The whole device-side frame: the per-frame work of CanSwapPipeline.execute (src/can_swap_pipeline_e2e.py) for B frames per call
-without leaving the GPU between the cropper's uint8 crop and the pasted-back uint8 frame (SURVEY.md section 8f rows N1-N3 around
+without leaving the GPU between the decoded uint8 frame and the pasted-back uint8 frame (SURVEY.md section 8f rows N1-N3 around
 the generator).
 
     reference (per frame, host round trips in brackets)                       here (B frames per launch, all on the device)
+    cropper.py:196-204  crop_image: landmarks -> M_o2c, cv2.warpAffine        chain.crop: crop.crop_matrices (host, no image) +
+                              of the 1080p frame [host, then upload]           cs_crop_frames
     cropper.py:209  cv2.resize(crop 512 -> 256, INTER_AREA) [host]            cs_prepare_crops
     can_swap_e2e.py:147-163  prepare_videos -> fp32 NCHW [upload]               "
     can_swap_pipeline_e2e.py:111-125  get_kp_info + transform_keypoint         cs_motion_extract + cs_motion_keypoints
@@ -12,11 +14,14 @@ the generator).
     :274      soft_mask(masks[i]) [D2H]                                        cs_soft_erosion_frames
     :279-282  prepare_paste_back + paste_back (two cv2.warpAffine) [host]      cs_paste_back_batch
 
+The loop of a caller:  c = chain.crop(frames, lmk);  masks = <the caller's parser on c["crops"]>;
+frames_out = chain(c["crops"], masks, c["M_c2o"], frames, source_id)["frames"].
+
 AnimateChain below is the same for the second program, inference_v2i.py (src/can_swap_pipeline_v2i.py: one source image animated by a
 driving video, the driving identity swapped in); its table stands in the class's docstring.
 
-What stays outside (out of scope): face detection / landmarks / the cropper's geometry (they produce the crops and
-M_c2o), SegFormer face parsing (it produces the 0/1 masks), video decode / encode.
+What stays outside (out of scope): face detection and the landmark network (they produce the landmarks), SegFormer
+face parsing (it produces the 0/1 masks), video decode / encode.
 """
 from __future__ import annotations
 
@@ -46,6 +51,13 @@ class _StagedChain:
             t = torch.empty(shape, dtype=dtype, device=self.e.device)
             self._buf[key] = t
         return t
+
+    def crop(self, frames_ori, lmk, **cfg):
+        """The cropper's step in front of the chain (cropper.py:196-204, crop.py:429-455): frames_ori (B,Ho,Wo,3) u8 on the device, lmk (B,N,2)
+        tracked landmarks (host) -> {"crops" (B,512,512,3) u8 on the device, "M_c2o", "M_o2c" (B,3,3) host, "lmk_crop"}: tail.crop_frames with
+        CropConfig's defaults (cfg: dsize, scale, vy_ratio, flag_do_rot, out, want_I).  A new crops tensor per call, so a batch may be cropped
+        and prefetched while the one before it runs; stage A reads the crops as it would a caller's."""
+        return tail.crop_frames(self.e, frames_ori, lmk, **cfg)
 
     def _check_stageable(self):
         """Raises where stage A cannot run yet (AnimateChain: no source)."""
@@ -171,8 +183,9 @@ class AnimateChain(_StagedChain):
         :309      warp_decode(f_swap_can_2, x_swap, x_t_2)                         cs_animate_frames
         :312-321  parse_output [sync + D2H] + paste_back into a copy of the image   (pack_u8 inside cs_animate_frames) cs_paste_back_shared
 
-    There is no refine module in this pipeline.  Outside: everything FrameChain leaves outside, getid (the driving identity is passed in) and
-    concat_frames."""
+    There is no refine module in this pipeline.  The crops, the source's and the driving frames', come from chain.crop (cropper.py:144-152,
+    196-204): `c = chain.crop(img[None], lmk)`, then `set_source(c["crops"][0], mask, c["M_c2o"][0], img, driving_id)`.  Outside: everything
+    FrameChain leaves outside, getid (the driving identity is passed in) and concat_frames."""
 
     def __init__(self, swapper, kernel_size: int = 21, threshold: float = 0.9, iterations: int = 2):
         super().__init__(swapper, kernel_size, threshold, iterations)      # SoftErosion(21, 0.9, 2): can_swap_pipeline_v2i.py:43

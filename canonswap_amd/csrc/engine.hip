@@ -22,7 +22,7 @@ void cs_set_error(const char* fmt, ...)
     va_end(ap);
 }
 extern "C" const char* cs_last_error(void) { return g_err; }
-// 4, unchanged: cs_resize_half_bilinear, cs_motion_keypoints_driven, cs_paste_back_shared (the v2i device-side frame) were added; new entry points
+// 4, unchanged: cs_resize_half_bilinear, cs_motion_keypoints_driven, cs_paste_back_shared (the v2i device-side frame) and cs_crop_frames (the crop in front of both chains) were added; new entry points
 // alone change no struct, no existing entry point's meaning and no blob format, which is what the header bumps the version for.
 // 4 (round 6): cs_soft_erosion_frames, cs_paste_back_batch, cs_motion_keypoints.
 // 3 (round 4): cs_conv_desc grew (hilo, stat_out, xf_*, ep_general), cs_op_conv takes conv_halo / vol32 / conv_wide configurations only, the
@@ -1731,6 +1731,18 @@ extern "C" int cs_paste_back_shared(cs_engine* e, int B, const uint8_t* crops, i
     DevGuard guard(e->dev);
     hipStream_t st = (hipStream_t)stream;
     return e->run(1, st, [&] { return launch_paste_shared(crops, Hc, Wc, mask_ori, M_c2o, img_ori, out, B, Ho, Wo, st); }, "paste_back_shared");
+}
+
+// ---- the crop in front of both chains (crop.py:429-455 per frame, cropper.py:196-209)
+extern "C" int cs_crop_frames(cs_engine* e, int B, const uint8_t* frames, int Ho, int Wo, const double* M_o2c, int dsize, uint8_t* crops, float* I_out,
+                              void* stream)
+{
+    if (!e || !frames || !M_o2c || !crops || B < 1 || Ho < 1 || Wo < 1) { cs_set_error("cs_crop_frames: bad arguments"); return -1; }
+    if (dsize < 4 || dsize % 4 || dsize > 16384) { cs_set_error("cs_crop_frames: dsize %d (a multiple of 4 from 4 to 16384)", dsize); return -1; }
+    if (I_out && dsize != 256 && dsize != 512) { cs_set_error("cs_crop_frames: I_out goes with dsize 256 or 512 (got %d)", dsize); return -1; }
+    DevGuard guard(e->dev);
+    hipStream_t st = (hipStream_t)stream;
+    return e->run(1, st, [&] { return launch_crop_batch(frames, Ho, Wo, M_o2c, dsize, crops, I_out, B, st); }, "crop_frames");
 }
 
 extern "C" int cs_profile_begin(cs_engine* e)

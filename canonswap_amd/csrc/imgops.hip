@@ -567,3 +567,106 @@ int launch_paste_batch(const unsigned char* crops, const float* masks, int Hc, i
     }
     return 0;
 }
+
+// ---------------------------------------------------------------------------------------------- the crop itself
+// crop_image's image step (src/utils/crop.py:429-455 as src/utils/cropper.py:196-209 calls it per frame): cv2.warpAffine(frame, M_o2c[:2],
+// (dsize, dsize), INTER_LINEAR), BORDER_CONSTANT 0, for B frames in one launch; blockIdx.y = frame, the matrices are kernel arguments as in
+// paste_batch_kernel.  Per pixel the arithmetic of paste_kernel without an original image: fixed-point coordinates, 15-bit weights, taps outside
+// the frame are 0.  The reads are a rotated gather of bytes that the L2 serves (a crop row walks a slanted line through the frame, 4 x 3 bytes
+// per pixel, neighbouring lanes on neighbouring pixels); what can be made wide is the store: a thread owns four consecutive crop pixels of a
+// row = 12 bytes = three dwords, a wave's stores of one row are contiguous.
+// STAGE != 0: the thread owns a 4 x 2 block and also writes what prepare_crops_kernel would make of it, from its registers - the crop is not
+// read back: STAGE 2 (dsize 512): the two 2 x 2 means (a + b + c + d + 2) >> 2, / 255, as one float2 per channel of the NCHW fp32 input;
+// STAGE 1 (dsize 256): / 255 only, one float4 per row and channel.
+__device__ __forceinline__ void crop_pixel(const unsigned char* __restrict__ frame, int Ho, int Wo, const AffineInv& A, int x, int y, int (&res)[3])
+{
+    int sx, sy, fx, fy;
+    affine_coords(A, x, y, sx, sy, fx, fy);
+    res[0] = res[1] = res[2] = 0;
+    if (sx < -1 || sy < -1 || sx >= Wo || sy >= Ho) return;          // all four taps outside the frame: the border value
+    const int w00 = (32 - fy) * (32 - fx) * 32, w01 = (32 - fy) * fx * 32, w10 = fy * (32 - fx) * 32, w11 = fy * fx * 32;   // sum 1 << 15
+    const bool y0 = (unsigned)sy < (unsigned)Ho, y1 = (unsigned)(sy + 1) < (unsigned)Ho;
+    const bool x0 = (unsigned)sx < (unsigned)Wo, x1 = (unsigned)(sx + 1) < (unsigned)Wo;
+    const unsigned char* t = frame + ((long)sy * Wo + sx) * 3;       // dereferenced only where the tap lies inside
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+        const int t00 = (y0 && x0) ? t[c] : 0;
+        const int t01 = (y0 && x1) ? t[3 + c] : 0;
+        const int t10 = (y1 && x0) ? t[(long)Wo * 3 + c] : 0;
+        const int t11 = (y1 && x1) ? t[(long)Wo * 3 + 3 + c] : 0;
+        res[c] = (t00 * w00 + t01 * w01 + t10 * w10 + t11 * w11 + (1 << 14)) >> 15;
+    }
+}
+
+__device__ __forceinline__ float staged_value(int v) { return fminf(fmaxf((float)v / 255.f, 0.f), 1.f); }      // prepare_crops_kernel's
+
+template <int STAGE>
+__global__ void __launch_bounds__(256) crop_batch_kernel(const unsigned char* __restrict__ frames, int Ho, int Wo, AffineBatch AB, int dsize,
+                                                         unsigned char* __restrict__ crops, float* __restrict__ I)
+{
+    constexpr int ROWS = STAGE ? 2 : 1;
+    const int n = blockIdx.y;
+    const int gw = dsize >> 2;                                        // groups of four pixels in a row
+    const int g = blockIdx.x * 256 + threadIdx.x;
+    if (g >= gw * (dsize / ROWS)) return;
+    const int yb = (g / gw) * ROWS, xb = (g % gw) * 4;
+    const AffineInv& A = AB.a[n];
+    const unsigned char* frame = frames + (long)n * Ho * Wo * 3;
+    int v[ROWS][4][3];
+#pragma unroll
+    for (int r = 0; r < ROWS; ++r)
+#pragma unroll
+        for (int k = 0; k < 4; ++k) crop_pixel(frame, Ho, Wo, A, xb + k, yb + r, v[r][k]);
+#pragma unroll
+    for (int r = 0; r < ROWS; ++r) {
+        unsigned w[3] = {0u, 0u, 0u};
+#pragma unroll
+        for (int j = 0; j < 12; ++j) w[j >> 2] |= (unsigned)v[r][j / 3][j % 3] << ((j & 3) * 8);
+        unsigned* out = (unsigned*)(crops + (((long)n * dsize + yb + r) * dsize + xb) * 3);
+        out[0] = w[0]; out[1] = w[1]; out[2] = w[2];
+    }
+    if constexpr (STAGE == 2) {
+        const int Wd = dsize >> 1;
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+            const int a = (v[0][0][c] + v[0][1][c] + v[1][0][c] + v[1][1][c] + 2) >> 2;
+            const int b = (v[0][2][c] + v[0][3][c] + v[1][2][c] + v[1][3][c] + 2) >> 2;
+            *(float2*)(I + (((long)n * 3 + c) * Wd + (yb >> 1)) * Wd + (xb >> 1)) = make_float2(staged_value(a), staged_value(b));
+        }
+    } else if constexpr (STAGE == 1) {
+#pragma unroll
+        for (int c = 0; c < 3; ++c)
+#pragma unroll
+            for (int r = 0; r < 2; ++r)
+                *(float4*)(I + (((long)n * 3 + c) * dsize + yb + r) * dsize + xb) =
+                    make_float4(staged_value(v[r][0][c]), staged_value(v[r][1][c]), staged_value(v[r][2][c]), staged_value(v[r][3][c]));
+    }
+}
+
+// dsize: a multiple of 4 (the caller checks); I != nullptr: dsize 256 or 512.  B is chunked by the 64 matrices of a launch, so it is not bound
+// by anything.  Buffers that do not allow the wide stores (a crop buffer off a 4-byte, an I off a 16-byte boundary): the single-frame kernel per
+// frame and prepare_crops_kernel behind it - the same arithmetic.
+int launch_crop_batch(const unsigned char* frames, int Ho, int Wo, const double* M, int dsize, unsigned char* crops, float* I, int B, hipStream_t st)
+{
+    const long P = (long)Ho * Wo * 3, C = (long)dsize * dsize * 3;
+    if (((uintptr_t)crops & 3) != 0 || ((uintptr_t)I & 15) != 0) {
+        for (int i = 0; i < B; ++i)
+            if (launch_paste(frames + i * P, nullptr, nullptr, Ho, Wo, M + (long)i * 6, nullptr, crops + i * C, dsize, dsize, st)) return -1;
+        return I ? launch_prepare_crops(crops, I, B, dsize, dsize, dsize / 256, st) : 0;
+    }
+    const int stage = I ? dsize / 256 : 0, rows = stage ? 2 : 1;
+    const dim3 grid((unsigned)(((long)(dsize / 4) * (dsize / rows) + 255) / 256));
+    for (int b0 = 0; b0 < B; b0 += 64) {
+        const int nb = B - b0 < 64 ? B - b0 : 64;
+        AffineBatch AB;
+        for (int i = 0; i < nb; ++i) AB.a[i] = invert_affine(M + (long)(b0 + i) * 6);
+        const unsigned char* f = frames + b0 * P;
+        unsigned char* c = crops + b0 * C;
+        float* Ib = I ? I + (long)b0 * 3 * 256 * 256 : nullptr;
+        if (stage == 2) hipLaunchKernelGGL(crop_batch_kernel<2>, dim3(grid.x, nb), dim3(256), 0, st, f, Ho, Wo, AB, dsize, c, Ib);
+        else if (stage == 1) hipLaunchKernelGGL(crop_batch_kernel<1>, dim3(grid.x, nb), dim3(256), 0, st, f, Ho, Wo, AB, dsize, c, Ib);
+        else hipLaunchKernelGGL(crop_batch_kernel<0>, dim3(grid.x, nb), dim3(256), 0, st, f, Ho, Wo, AB, dsize, c, Ib);
+        LAUNCH_CHECK("crop_batch");
+    }
+    return 0;
+}

@@ -8,6 +8,8 @@ per-frame loop (src/can_swap_pipeline_e2e.py:223-283) no longer leaves the GPU b
 * ``paste_back``             src/utils/crop.py:523-529          (cv2.warpAffine of the crop + blend)
 * ``paste_back_fused``       both of the above in one kernel launch per frame
 * ``paste_back_shared``      paste_back of B frames into one image under one mask (can_swap_pipeline_v2i.py:317-321)
+* ``crop_frames``            src/utils/crop.py:429-455 per frame (cropper.py:196-209): landmark geometry on the host (crop.py of this
+                             package), cv2.warpAffine of B frames in one launch; ``crop_frames_M``: the same with the caller's matrices
 * ``prepare_crops``          src/utils/cropper.py:209 + src/can_swap_e2e.py:126-163 (INTER_AREA 512 -> 256, /255, HWC -> CHW)
 * ``FrameStreamer``          streamed upload of the uint8 crops instead of the whole-video residency of prepare_videos
 
@@ -21,6 +23,7 @@ import numpy as np
 import torch
 
 from . import _lib
+from . import crop as crop_geometry
 from .engine import Engine, _ptr
 
 
@@ -202,6 +205,39 @@ def prepare_crops(e: Engine, crops_u8, out=None) -> torch.Tensor:
     with torch.cuda.device(e.device):
         _lib.check(e.lib.cs_prepare_crops(e.h, B, _ptr(t), H, W, _ptr(out), e._stream()), "cs_prepare_crops")
     return out
+
+
+def crop_frames_M(e: Engine, frames, M_o2c, dsize, out=None, want_I=False, out_I=None):
+    """crop_image_mo2c's image step (crop.py:457-461) of B frames in one launch: frames (B,Ho,Wo,3) u8, M_o2c (B,2,3) or (B,3,3) host matrices original ->
+    crop, dsize a multiple of 4 -> {"crops": (B,dsize,dsize,3) u8 on the device, crops[b] = cv2.warpAffine(frames[b], M_o2c[b][:2], (dsize, dsize),
+    INTER_LINEAR)[, "I": (B,3,256,256) fp32 = prepare_crops(crops), from the same launch; dsize 256 or 512 only]}."""
+    fr = torch.as_tensor(frames)
+    if fr.dtype != torch.uint8 or fr.dim() != 4 or fr.shape[3] != 3 or fr.shape[0] < 1:
+        raise ValueError("expected BxHoxWox3 uint8 frames")
+    fr = fr.to(e.device).contiguous()
+    B, dsize = fr.shape[0], int(dsize)
+    if tuple(np.shape(M_o2c)) not in ((B, 2, 3), (B, 3, 3)):
+        raise ValueError(f"M_o2c must be (B,2,3) or (B,3,3) for the {B} frames, got {tuple(np.shape(M_o2c))}")
+    mm, mp = _m6(M_o2c, B)
+    want_I = want_I or out_I is not None
+    crops = e._out(out, (B, dsize, dsize, 3), torch.uint8)
+    I = e._out(out_I, (B, 3, 256, 256), torch.float32) if want_I else None
+    with torch.cuda.device(e.device):
+        _lib.check(e.lib.cs_crop_frames(e.h, B, _ptr(fr), fr.shape[1], fr.shape[2], mp, dsize, _ptr(crops), _ptr(I), e._stream()), "cs_crop_frames")
+    return {"crops": crops, "I": I} if want_I else {"crops": crops}
+
+
+def crop_frames(e: Engine, frames, lmk, dsize=512, scale=2.3, vy_ratio=-0.125, flag_do_rot=True, out=None, want_I=False, out_I=None):
+    """crop_image (crop.py:429-455) of B frames, as the cropper runs it per frame (cropper.py:196-204; defaults: CropConfig's): frames
+    (B,Ho,Wo,3) u8, lmk (B,N,2) tracked landmarks in the frame (host; (N,2) for one frame) -> {"crops" (B,dsize,dsize,3) u8 on the device,
+    "M_o2c", "M_c2o" (B,3,3) float32 on the host, "lmk_crop" (B,N,2) on the host[, "I" (B,3,256,256) fp32 with want_I]}.  The matrices come from
+    crop.crop_matrices on the host (a few hundred flops per frame), the image step is one launch."""
+    M_o2c, M_c2o, lmk_crop = crop_geometry.crop_matrices(lmk, dsize=dsize, scale=scale, vy_ratio=vy_ratio, flag_do_rot=flag_do_rot)
+    if M_o2c.shape[0] != np.shape(frames)[0]:
+        raise ValueError(f"{M_o2c.shape[0]} landmark sets for {np.shape(frames)[0]} frames")
+    res = crop_frames_M(e, frames, M_o2c, dsize, out=out, want_I=want_I, out_I=out_I)
+    res.update(M_o2c=M_o2c, M_c2o=M_c2o, lmk_crop=lmk_crop)
+    return res
 
 
 class FrameStreamer:

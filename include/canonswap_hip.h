@@ -150,6 +150,17 @@ int cs_motion_keypoints_driven(cs_engine* e, int B, const float* raw_driving, co
 int cs_paste_back_shared(cs_engine* e, int B, const uint8_t* crops, int Hc, int Wc, const float* mask_ori, const double M_c2o[6],
                          const uint8_t* img_ori, uint8_t* out, int Ho, int Wo, void* stream);
 
+/* ---- the crop in front of both chains ---- */
+/* crop_image's image step (src/utils/crop.py:429-455, called per frame by src/utils/cropper.py:196-209; the landmark runner's 224x224 crop,
+ * human_landmark_runner.py:62, is the same call) for B frames in one launch: crops[b] = cv2.warpAffine(frames[b], M_o2c[b], (dsize, dsize),
+ * INTER_LINEAR), BORDER_CONSTANT 0, bit-equal to cs_warp_affine_u8 of that frame.  frames BxHoxWox3 u8; M_o2c: HOST, B x 6 doubles (2x3 row
+ * major, original -> crop: the matrices of canonswap_amd/crop.py crop_matrices, or a caller's own = crop_image_mo2c); crops B x dsize x dsize x 3 u8,
+ * dsize a multiple of 4 from 4 to 16384.  I_out (NULL, or Bx3x256x256 fp32; dsize 256 or 512 only): what cs_prepare_crops makes of the crops
+ * (cropper.py:209 + can_swap_e2e.py:126-163), bit-equal, written from the same registers instead of a second pass.  Any B >= 1 (not bound to
+ * max_batch). */
+int cs_crop_frames(cs_engine* e, int B, const uint8_t* frames, int Ho, int Wo, const double* M_o2c, int dsize, uint8_t* crops, float* I_out,
+                   void* stream);
+
 /* ---- measurement: per-kernel-family HIP-event timing on the launch stream */
 int cs_profile_begin(cs_engine* e);
 /* ms[0] = convolution kernels (conv_halo / conv_igemm), ms[1] = all other kernels except ms[2] = the feature warp
