@@ -2,7 +2,8 @@
 //   * SoftErosion of the face-parsing mask (src/utils/crop.py:21-47),
 //   * paste-back of the generated crop into the original frame: cv2.warpAffine of crop and mask + blend
 //     (src/utils/crop.py:49-63, 515-529, driven from can_swap_pipeline_e2e.py:267-283),
-//   * input staging: cv2.resize(crop, (256,256), INTER_AREA) + /255 + HWC->CHW (src/utils/cropper.py:209, can_swap_e2e.py:126-163).
+//   * input staging: cv2.resize(crop, (256,256), INTER_AREA) + /255 + HWC->CHW (src/utils/cropper.py:209, can_swap_e2e.py:126-163),
+//   * the crop itself: cv2.warpAffine of the frame into the crop's frame (src/utils/crop.py:429-455, src/utils/cropper.py:196-209).
 // All of them are HBM-bound byte / float work: one thread per output pixel, coalesced along the row.  The OpenCV steps follow
 // OpenCV's published fixed-point algorithm (restated in oracle/cv_ref.py, which the tests compare against bit for bit).
 #include "common.h"
@@ -172,6 +173,8 @@ int launch_soft_erosion(const void* mask, int mask_u8, float* tmp_a, float* tmp_
 
 // ---------------------------------------------------------------------------------------------- input staging
 // cv2.resize(INTER_AREA) by exactly 2 in both directions for 8-bit images: (a + b + c + d + 2) >> 2; then / 255, clip, CHW
+__device__ __forceinline__ float staged_value(int v) { return fminf(fmaxf((float)v / 255.f, 0.f), 1.f); }
+
 __global__ void __launch_bounds__(256) prepare_crops_kernel(const unsigned char* __restrict__ in, float* __restrict__ out, int B, int Hd, int Wd,
                                                             int factor)
 {
@@ -186,7 +189,7 @@ __global__ void __launch_bounds__(256) prepare_crops_kernel(const unsigned char*
         int v;
         if (factor == 2) v = (s[c] + s[3 + c] + s[(long)Ws * 3 + c] + s[(long)Ws * 3 + 3 + c] + 2) >> 2;
         else v = s[c];
-        out[((long)n * 3 + c) * P + (long)y * Wd + x] = fminf(fmaxf((float)v / 255.f, 0.f), 1.f);
+        out[((long)n * 3 + c) * P + (long)y * Wd + x] = staged_value(v);
     }
 }
 
@@ -216,8 +219,77 @@ __device__ __forceinline__ void affine_coords(const AffineInv& A, int x, int y, 
     sx = (int)ix; sy = (int)iy; fx = (int)(X & 31); fy = (int)(Y & 31);
 }
 
-// crop (u8, 3 channels) warped into the destination frame; with a mask (warped from the crop frame, or given in the
-// destination frame) and the original image: out = clip(mask * warped + (1 - mask) * ori, 0, 255) truncated (crop.py:523-529)
+// The bilinear read of one destination pixel (remapBilinear, BORDER_CONSTANT 0): the taps are the source elements (sy, sx), (sy, sx + 1),
+// (sy + 1, sx), (sy + 1, sx + 1) with the 5-bit fractions fx, fy; a tap outside the source reads 0.  Every warp, paste and crop kernel below
+// forms its taps here and reads them through tap_u8x3 / tap_f32.
+struct Tap {
+    long o00;                   // element offset of tap (sy, sx); dereferenced only where a tap lies inside
+    int fx, fy;
+    bool y0, y1, x0, x1;        // rows sy, sy + 1 and columns sx, sx + 1 inside the source
+    bool outside;               // all four taps outside: an 8-bit read gives 0, a float read 0.f
+};
+
+__device__ __forceinline__ Tap tap_at(const AffineInv& A, int x, int y, int Hs, int Ws)
+{
+    Tap t;
+    int sx, sy;
+    affine_coords(A, x, y, sx, sy, t.fx, t.fy);
+    t.o00 = (long)sy * Ws + sx;
+    t.y0 = (unsigned)sy < (unsigned)Hs; t.y1 = (unsigned)(sy + 1) < (unsigned)Hs;
+    t.x0 = (unsigned)sx < (unsigned)Ws; t.x1 = (unsigned)(sx + 1) < (unsigned)Ws;
+    t.outside = sx < -1 || sy < -1 || sx >= Ws || sy >= Hs;
+    return t;
+}
+
+// paste_shared_kernel keeps a tap per pixel across its frames as two ints (its launcher bounds the offset): the offset, and
+// fx | fy << 5 | (y0, y1, x0, x1) << 10 | !outside << 14.  The word 0 is a pixel that reads nothing.
+__device__ __forceinline__ int tap_pack(const Tap& t)
+{
+    return t.fx | t.fy << 5 | t.y0 << 10 | t.y1 << 11 | t.x0 << 12 | t.x1 << 13 | !t.outside << 14;
+}
+
+__device__ __forceinline__ Tap tap_unpack(int o00, int w)
+{
+    return Tap{o00, w & 31, (w >> 5) & 31, (bool)(w & 1 << 10), (bool)(w & 1 << 11), (bool)(w & 1 << 12), (bool)(w & 1 << 13), !(w >> 14)};
+}
+
+// 8-bit image, 3 interleaved channels, rows of Ws pixels: 15-bit weights (sum 1 << 15), rounded to nearest (remapBilinear, uchar)
+__device__ __forceinline__ void tap_u8x3(const unsigned char* __restrict__ src, int Ws, const Tap& t, int (&res)[3])
+{
+    const int w00 = (32 - t.fy) * (32 - t.fx) * 32, w01 = (32 - t.fy) * t.fx * 32, w10 = t.fy * (32 - t.fx) * 32, w11 = t.fy * t.fx * 32;
+    const unsigned char* p = src + t.o00 * 3;
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+        const int t00 = (t.y0 && t.x0) ? p[c] : 0;
+        const int t01 = (t.y0 && t.x1) ? p[3 + c] : 0;
+        const int t10 = (t.y1 && t.x0) ? p[(long)Ws * 3 + c] : 0;
+        const int t11 = (t.y1 && t.x1) ? p[(long)Ws * 3 + 3 + c] : 0;
+        res[c] = (t00 * w00 + t01 * w01 + t10 * w10 + t11 * w11 + (1 << 14)) >> 15;
+    }
+}
+
+// float image, one channel: table weights (1 - a)(1 - b) ... in float, left-to-right sum without contraction (remapBilinear, float)
+__device__ __forceinline__ float tap_f32(const float* __restrict__ src, int Ws, const Tap& t)
+{
+    const float ax = (float)t.fx * 0.03125f, ay = (float)t.fy * 0.03125f;
+    const float f00 = (1.f - ay) * (1.f - ax), f01 = (1.f - ay) * ax;
+    const float f10 = ay * (1.f - ax), f11 = ay * ax;
+    const float* p = src + t.o00;
+    const float t00 = (t.y0 && t.x0) ? p[0] : 0.f, t01 = (t.y0 && t.x1) ? p[1] : 0.f;
+    const float t10 = (t.y1 && t.x0) ? p[Ws] : 0.f, t11 = (t.y1 && t.x1) ? p[(long)Ws + 1] : 0.f;
+    return ((t00 * f00 + t01 * f01) + t10 * f10) + t11 * f11;
+}
+
+// out = clip(m * warped + (1 - m) * ori, 0, 255) truncated (crop.py:523-529; np.clip(...).astype(np.uint8)), `rest` = (1 - m) * ori.
+// The blend rounds both products and the sum (this file compiles with fp contraction off), so the second product, which in
+// paste_shared_kernel does not depend on the frame, may be formed apart (tests/test_gpu_v2i_chain.py holds the kernels bit-equal).
+__device__ __forceinline__ unsigned blend_u8(float m, int res, float rest)
+{
+    return (unsigned)(unsigned char)fminf(fmaxf(m * (float)res + rest, 0.f), 255.f);
+}
+
+// crop (u8, 3 channels) warped into the destination frame; with the original image: blended into it under a mask, warped from the
+// crop frame here (mask_crop) or given in the destination frame (mask_ori)
 __global__ void __launch_bounds__(256) paste_kernel(const unsigned char* __restrict__ crop, const float* __restrict__ mask_crop,
                                                     const float* __restrict__ mask_ori, int Hc, int Wc, AffineInv A,
                                                     const unsigned char* __restrict__ ori, unsigned char* __restrict__ out, int Ho, int Wo)
@@ -225,40 +297,17 @@ __global__ void __launch_bounds__(256) paste_kernel(const unsigned char* __restr
     const long i = (long)blockIdx.x * 256 + threadIdx.x;
     if (i >= (long)Ho * Wo) return;
     const int y = (int)(i / Wo), x = (int)(i % Wo);
-    int sx, sy, fx, fy;
-    affine_coords(A, x, y, sx, sy, fx, fy);
-    const int w00 = (32 - fy) * (32 - fx) * 32, w01 = (32 - fy) * fx * 32, w10 = fy * (32 - fx) * 32, w11 = fy * fx * 32;   // sum 1 << 15
-    const bool y0 = (unsigned)sy < (unsigned)Hc, y1 = (unsigned)(sy + 1) < (unsigned)Hc;
-    const bool x0 = (unsigned)sx < (unsigned)Wc, x1 = (unsigned)(sx + 1) < (unsigned)Wc;
+    const Tap t = tap_at(A, x, y, Hc, Wc);
     int res[3];
-#pragma unroll
-    for (int c = 0; c < 3; ++c) {
-        const int t00 = (y0 && x0) ? crop[((long)sy * Wc + sx) * 3 + c] : 0;
-        const int t01 = (y0 && x1) ? crop[((long)sy * Wc + sx + 1) * 3 + c] : 0;
-        const int t10 = (y1 && x0) ? crop[((long)(sy + 1) * Wc + sx) * 3 + c] : 0;
-        const int t11 = (y1 && x1) ? crop[((long)(sy + 1) * Wc + sx + 1) * 3 + c] : 0;
-        res[c] = (t00 * w00 + t01 * w01 + t10 * w10 + t11 * w11 + (1 << 14)) >> 15;
-    }
+    tap_u8x3(crop, Wc, t, res);
     if (!ori) {
 #pragma unroll
         for (int c = 0; c < 3; ++c) out[i * 3 + c] = (unsigned char)res[c];
         return;
     }
-    float m;
-    if (mask_ori) m = mask_ori[i];
-    else {      // float image: table weights (1 - a)(1 - b) ... in float, left-to-right sum without contraction (remapBilinear, float)
-        const float ax = (float)fx * 0.03125f, ay = (float)fy * 0.03125f;
-        const float f00 = (1.f - ay) * (1.f - ax), f01 = (1.f - ay) * ax;
-        const float f10 = ay * (1.f - ax), f11 = ay * ax;
-        const float t00 = (y0 && x0) ? mask_crop[(long)sy * Wc + sx] : 0.f, t01 = (y0 && x1) ? mask_crop[(long)sy * Wc + sx + 1] : 0.f;
-        const float t10 = (y1 && x0) ? mask_crop[(long)(sy + 1) * Wc + sx] : 0.f, t11 = (y1 && x1) ? mask_crop[(long)(sy + 1) * Wc + sx + 1] : 0.f;
-        m = ((t00 * f00 + t01 * f01) + t10 * f10) + t11 * f11;
-    }
+    const float m = mask_ori ? mask_ori[i] : tap_f32(mask_crop, Wc, t);
 #pragma unroll
-    for (int c = 0; c < 3; ++c) {
-        const float v = m * (float)res[c] + (1.f - m) * (float)ori[i * 3 + c];
-        out[i * 3 + c] = (unsigned char)fminf(fmaxf(v, 0.f), 255.f);       // np.clip(...).astype(np.uint8): truncation
-    }
+    for (int c = 0; c < 3; ++c) out[i * 3 + c] = blend_u8(m, res[c], (1.f - m) * (float)ori[i * 3 + c]);
 }
 
 // ---- the paste-back step of B frames in one launch (can_swap_pipeline_e2e.py:273-283 per frame: SoftErosion mask -> prepare_paste_back ->
@@ -286,29 +335,13 @@ __global__ void __launch_bounds__(256) paste_batch_kernel(const unsigned char* _
     const int y = (int)((q * 4) / Wo), xb = (int)((q * 4) % Wo);
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
-        int sx, sy, fx, fy;
-        affine_coords(A, xb + k, y, sx, sy, fx, fy);
-        if (sx < -1 || sy < -1 || sx >= Wc || sy >= Hc) continue;          // all four taps outside: the original pixel
-        const int w00 = (32 - fy) * (32 - fx) * 32, w01 = (32 - fy) * fx * 32, w10 = fy * (32 - fx) * 32, w11 = fy * fx * 32;
-        const bool y0 = (unsigned)sy < (unsigned)Hc, y1 = (unsigned)(sy + 1) < (unsigned)Hc;
-        const bool x0 = (unsigned)sx < (unsigned)Wc, x1 = (unsigned)(sx + 1) < (unsigned)Wc;
-        const long o00 = (long)sy * Wc + sx;
-        const float ax = (float)fx * 0.03125f, ay = (float)fy * 0.03125f;
-        const float f00 = (1.f - ay) * (1.f - ax), f01 = (1.f - ay) * ax;
-        const float f10 = ay * (1.f - ax), f11 = ay * ax;
-        const float m00 = (y0 && x0) ? mask_crop[o00] : 0.f, m01 = (y0 && x1) ? mask_crop[o00 + 1] : 0.f;
-        const float m10 = (y1 && x0) ? mask_crop[o00 + Wc] : 0.f, m11 = (y1 && x1) ? mask_crop[o00 + Wc + 1] : 0.f;
-        const float m = ((m00 * f00 + m01 * f01) + m10 * f10) + m11 * f11;
+        const Tap t = tap_at(A, xb + k, y, Hc, Wc);
+        if (t.outside) continue;                                           // the original pixel
+        const float m = tap_f32(mask_crop, Wc, t);
+        int res[3];
+        tap_u8x3(crop, Wc, t, res);
 #pragma unroll
-        for (int c = 0; c < 3; ++c) {
-            const int t00 = (y0 && x0) ? crop[o00 * 3 + c] : 0;
-            const int t01 = (y0 && x1) ? crop[(o00 + 1) * 3 + c] : 0;
-            const int t10 = (y1 && x0) ? crop[(o00 + Wc) * 3 + c] : 0;
-            const int t11 = (y1 && x1) ? crop[(o00 + Wc + 1) * 3 + c] : 0;
-            const int res = (t00 * w00 + t01 * w01 + t10 * w10 + t11 * w11 + (1 << 14)) >> 15;
-            const float v = m * (float)res + (1.f - m) * (float)px[k * 3 + c];
-            px[k * 3 + c] = (unsigned char)fminf(fmaxf(v, 0.f), 255.f);
-        }
+        for (int c = 0; c < 3; ++c) px[k * 3 + c] = blend_u8(m, res[c], (1.f - m) * (float)px[k * 3 + c]);
     }
     out[0] = wv[0]; out[1] = wv[1]; out[2] = wv[2];
 }
@@ -320,13 +353,6 @@ __global__ void __launch_bounds__(256) paste_batch_kernel(const unsigned char* _
 // taps only.  A pixel with mask 0 (v = 0 * res + 1 * ori = ori) or with all four taps outside the crop (res = 0: v = m * 0 + (1 - m) * ori,
 // the same for every frame) never touches the crop; most of a 1080p frame is such pixels and is stored from registers, frame after frame.
 // PX pixels of a row per thread: 8 (24 bytes, 8-byte aligned: one 16-byte and one 8-byte store) or 4 (12 bytes, as paste_batch_kernel).
-// paste_kernel's blend `m * res + (1 - m) * ori` rounds both products and the sum (this file compiles with fp contraction off), so the second
-// product, which does not depend on the frame, may be formed apart (tests/test_gpu_v2i_chain.py holds the two kernels bit-equal).
-__device__ __forceinline__ unsigned blend_u8(float m, int res, float rest)
-{
-    return (unsigned)(unsigned char)fminf(fmaxf(m * (float)res + rest, 0.f), 255.f);
-}
-
 template <int PX>
 __device__ __forceinline__ void store_px(unsigned char* frame, long q, const unsigned (&w)[PX * 3 / 4])
 {
@@ -370,15 +396,14 @@ __global__ void __launch_bounds__(256) paste_shared_kernel(const unsigned char* 
         for (int k = 0; k < PX; ++k) m[k] = mask_ori[q * PX + k];
     }
     const int y = (int)((q * PX) / Wo), xb = (int)((q * PX) % Wo);
-    int o00[PX], info[PX];      // info: fx | fy << 5 | (y0, y1, x0, x1) << 10 | live << 14
+    int o00[PX], info[PX];      // the pixel's tap, packed (tap_pack)
     bool any = false;
 #pragma unroll
     for (int k = 0; k < PX; ++k) {
         o00[k] = 0; info[k] = 0;
         if (m[k] == 0.f) continue;                                   // the original pixel
-        int sx, sy, fx, fy;
-        affine_coords(A, xb + k, y, sx, sy, fx, fy);
-        if (sx < -1 || sy < -1 || sx >= Wc || sy >= Hc) {            // all four taps outside: res = 0 for every frame
+        const Tap t = tap_at(A, xb + k, y, Hc, Wc);
+        if (t.outside) {                                             // res = 0 for every frame
 #pragma unroll
             for (int c = 0; c < 3; ++c) {
                 const int by = k * 3 + c, sh = (by & 3) * 8;
@@ -387,10 +412,8 @@ __global__ void __launch_bounds__(256) paste_shared_kernel(const unsigned char* 
             }
             continue;
         }
-        const int y0 = (unsigned)sy < (unsigned)Hc, y1 = (unsigned)(sy + 1) < (unsigned)Hc;
-        const int x0 = (unsigned)sx < (unsigned)Wc, x1 = (unsigned)(sx + 1) < (unsigned)Wc;
-        o00[k] = sy * Wc + sx;                                       // sx, sy >= -1 and inside the crop otherwise: fits (the launcher bounds Hc * Wc)
-        info[k] = fx | fy << 5 | y0 << 10 | y1 << 11 | x0 << 12 | x1 << 13 | 1 << 14;
+        o00[k] = (int)t.o00;                                         // sx, sy >= -1 and inside the crop otherwise: fits (the launcher bounds Hc * Wc)
+        info[k] = tap_pack(t);
         any = true;
     }
     if (!any) {                                                      // nothing of this group depends on the frame
@@ -404,23 +427,16 @@ __global__ void __launch_bounds__(256) paste_shared_kernel(const unsigned char* 
         for (int j = 0; j < NW; ++j) wv[j] = base[j];
 #pragma unroll
         for (int k = 0; k < PX; ++k) {
-            const int in = info[k];
-            if (!(in >> 14)) continue;
-            const int fx = in & 31, fy = (in >> 5) & 31;
-            const int w00 = (32 - fy) * (32 - fx) * 32, w01 = (32 - fy) * fx * 32, w10 = fy * (32 - fx) * 32, w11 = fy * fx * 32;
-            const bool y0 = in & (1 << 10), y1 = in & (1 << 11), x0 = in & (1 << 12), x1 = in & (1 << 13);
-            const unsigned char* t = crop + (long)o00[k] * 3;
+            const Tap t = tap_unpack(o00[k], info[k]);
+            if (t.outside) continue;
+            int res[3];
+            tap_u8x3(crop, Wc, t, res);
             const float mk = m[k], om = 1.f - mk;
 #pragma unroll
             for (int c = 0; c < 3; ++c) {
-                const int t00 = (y0 && x0) ? t[c] : 0;
-                const int t01 = (y0 && x1) ? t[3 + c] : 0;
-                const int t10 = (y1 && x0) ? t[(long)Wc * 3 + c] : 0;
-                const int t11 = (y1 && x1) ? t[(long)Wc * 3 + 3 + c] : 0;
-                const int res = (t00 * w00 + t01 * w01 + t10 * w10 + t11 * w11 + (1 << 14)) >> 15;
                 const int by = k * 3 + c, sh = (by & 3) * 8;
                 const float o = (float)((base[by >> 2] >> sh) & 0xffu);
-                wv[by >> 2] = (wv[by >> 2] & ~(0xffu << sh)) | (blend_u8(mk, res, om * o) << sh);
+                wv[by >> 2] = (wv[by >> 2] & ~(0xffu << sh)) | (blend_u8(mk, res[c], om * o) << sh);
             }
         }
         store_px<PX>(outs + (long)f * P * 3, q, wv);
@@ -464,16 +480,7 @@ __global__ void __launch_bounds__(256) warp_f32_kernel(const float* __restrict__
     const long i = (long)blockIdx.x * 256 + threadIdx.x;
     if (i >= (long)Hd * Wd) return;
     const int y = (int)(i / Wd), x = (int)(i % Wd);
-    int sx, sy, fx, fy;
-    affine_coords(A, x, y, sx, sy, fx, fy);
-    const bool y0 = (unsigned)sy < (unsigned)Hs, y1 = (unsigned)(sy + 1) < (unsigned)Hs;
-    const bool x0 = (unsigned)sx < (unsigned)Ws, x1 = (unsigned)(sx + 1) < (unsigned)Ws;
-    const float ax = (float)fx * 0.03125f, ay = (float)fy * 0.03125f;
-    const float f00 = (1.f - ay) * (1.f - ax), f01 = (1.f - ay) * ax;
-    const float f10 = ay * (1.f - ax), f11 = ay * ax;
-    const float t00 = (y0 && x0) ? src[(long)sy * Ws + sx] : 0.f, t01 = (y0 && x1) ? src[(long)sy * Ws + sx + 1] : 0.f;
-    const float t10 = (y1 && x0) ? src[(long)(sy + 1) * Ws + sx] : 0.f, t11 = (y1 && x1) ? src[(long)(sy + 1) * Ws + sx + 1] : 0.f;
-    dst[i] = ((t00 * f00 + t01 * f01) + t10 * f10) + t11 * f11;
+    dst[i] = tap_f32(src, Ws, tap_at(A, x, y, Hs, Ws));
 }
 
 static AffineInv invert_affine(const double M[6])      // imgwarp.cpp warpAffine, !WARP_INVERSE_MAP
@@ -488,6 +495,19 @@ static AffineInv invert_affine(const double M[6])      // imgwarp.cpp warpAffine
     const double b2 = -A.m[3] * A.m[2] - A.m[4] * A.m[5];
     A.m[2] = b1; A.m[5] = b2;
     return A;
+}
+
+// B matrices, inverted, in chunks of the 64 that one launch takes as kernel arguments: launch(first frame, frames, matrices) per chunk
+template <typename F>
+static int for_affine_batches(const double* M, int B, F launch)
+{
+    for (int b0 = 0; b0 < B; b0 += 64) {
+        const int nb = B - b0 < 64 ? B - b0 : 64;
+        AffineBatch AB;
+        for (int i = 0; i < nb; ++i) AB.a[i] = invert_affine(M + (long)(b0 + i) * 6);
+        if (launch(b0, nb, AB)) return -1;
+    }
+    return 0;
 }
 
 int launch_paste(const unsigned char* crop, const float* mask_crop, const float* mask_ori, int Hc, int Wc, const double M[6],
@@ -550,55 +570,36 @@ int launch_paste_batch(const unsigned char* crops, const float* masks, int Hc, i
                        unsigned char* outs, int B, int Ho, int Wo, hipStream_t st)
 {
     const long P = (long)Ho * Wo;
-    const bool vec = Wo % 4 == 0 && ((uintptr_t)oris & 3) == 0 && ((uintptr_t)outs & 3) == 0;
-    for (int b0 = 0; b0 < B; b0 += 64) {
-        const int nb = B - b0 < 64 ? B - b0 : 64;
-        if (vec) {
-            AffineBatch AB;
-            for (int i = 0; i < nb; ++i) AB.a[i] = invert_affine(M + (long)(b0 + i) * 6);
-            hipLaunchKernelGGL(paste_batch_kernel, dim3((unsigned)((P / 4 + 255) / 256), nb), dim3(256), 0, st, crops + (long)b0 * Hc * Wc * 3,
-                               masks + (long)b0 * Hc * Wc, Hc, Wc, AB, oris + (long)b0 * P * 3, outs + (long)b0 * P * 3, Ho, Wo);
-            LAUNCH_CHECK("paste_batch");
-        } else {      // odd widths / unaligned buffers: the single-frame kernel per frame (same arithmetic)
-            for (int i = b0; i < b0 + nb; ++i)
-                if (launch_paste(crops + (long)i * Hc * Wc * 3, masks + (long)i * Hc * Wc, nullptr, Hc, Wc, M + (long)i * 6, oris + (long)i * P * 3,
-                                 outs + (long)i * P * 3, Ho, Wo, st)) return -1;
-        }
+    if (Wo % 4 != 0 || ((uintptr_t)oris & 3) != 0 || ((uintptr_t)outs & 3) != 0) {
+        // odd widths / unaligned buffers: the single-frame kernel per frame (same arithmetic)
+        for (int i = 0; i < B; ++i)
+            if (launch_paste(crops + (long)i * Hc * Wc * 3, masks + (long)i * Hc * Wc, nullptr, Hc, Wc, M + (long)i * 6, oris + (long)i * P * 3,
+                             outs + (long)i * P * 3, Ho, Wo, st)) return -1;
+        return 0;
     }
-    return 0;
+    return for_affine_batches(M, B, [&](int b0, int nb, const AffineBatch& AB) {
+        hipLaunchKernelGGL(paste_batch_kernel, dim3((unsigned)((P / 4 + 255) / 256), nb), dim3(256), 0, st, crops + (long)b0 * Hc * Wc * 3,
+                           masks + (long)b0 * Hc * Wc, Hc, Wc, AB, oris + (long)b0 * P * 3, outs + (long)b0 * P * 3, Ho, Wo);
+        LAUNCH_CHECK("paste_batch");
+        return 0;
+    });
 }
 
 // ---------------------------------------------------------------------------------------------- the crop itself
 // crop_image's image step (src/utils/crop.py:429-455 as src/utils/cropper.py:196-209 calls it per frame): cv2.warpAffine(frame, M_o2c[:2],
 // (dsize, dsize), INTER_LINEAR), BORDER_CONSTANT 0, for B frames in one launch; blockIdx.y = frame, the matrices are kernel arguments as in
-// paste_batch_kernel.  Per pixel the arithmetic of paste_kernel without an original image: fixed-point coordinates, 15-bit weights, taps outside
-// the frame are 0.  The reads are a rotated gather of bytes that the L2 serves (a crop row walks a slanted line through the frame, 4 x 3 bytes
-// per pixel, neighbouring lanes on neighbouring pixels); what can be made wide is the store: a thread owns four consecutive crop pixels of a
-// row = 12 bytes = three dwords, a wave's stores of one row are contiguous.
+// paste_batch_kernel.  Per pixel the arithmetic of paste_kernel without an original image.  The reads are a rotated gather of bytes that the L2
+// serves (a crop row walks a slanted line through the frame, 4 x 3 bytes per pixel, neighbouring lanes on neighbouring pixels); what can be
+// made wide is the store: a thread owns four consecutive crop pixels of a row = 12 bytes = three dwords, a wave's stores of one row are contiguous.
 // STAGE != 0: the thread owns a 4 x 2 block and also writes what prepare_crops_kernel would make of it, from its registers - the crop is not
 // read back: STAGE 2 (dsize 512): the two 2 x 2 means (a + b + c + d + 2) >> 2, / 255, as one float2 per channel of the NCHW fp32 input;
 // STAGE 1 (dsize 256): / 255 only, one float4 per row and channel.
 __device__ __forceinline__ void crop_pixel(const unsigned char* __restrict__ frame, int Ho, int Wo, const AffineInv& A, int x, int y, int (&res)[3])
 {
-    int sx, sy, fx, fy;
-    affine_coords(A, x, y, sx, sy, fx, fy);
-    res[0] = res[1] = res[2] = 0;
-    if (sx < -1 || sy < -1 || sx >= Wo || sy >= Ho) return;          // all four taps outside the frame: the border value
-    const int w00 = (32 - fy) * (32 - fx) * 32, w01 = (32 - fy) * fx * 32, w10 = fy * (32 - fx) * 32, w11 = fy * fx * 32;   // sum 1 << 15
-    const bool y0 = (unsigned)sy < (unsigned)Ho, y1 = (unsigned)(sy + 1) < (unsigned)Ho;
-    const bool x0 = (unsigned)sx < (unsigned)Wo, x1 = (unsigned)(sx + 1) < (unsigned)Wo;
-    const unsigned char* t = frame + ((long)sy * Wo + sx) * 3;       // dereferenced only where the tap lies inside
-#pragma unroll
-    for (int c = 0; c < 3; ++c) {
-        const int t00 = (y0 && x0) ? t[c] : 0;
-        const int t01 = (y0 && x1) ? t[3 + c] : 0;
-        const int t10 = (y1 && x0) ? t[(long)Wo * 3 + c] : 0;
-        const int t11 = (y1 && x1) ? t[(long)Wo * 3 + 3 + c] : 0;
-        res[c] = (t00 * w00 + t01 * w01 + t10 * w10 + t11 * w11 + (1 << 14)) >> 15;
-    }
+    const Tap t = tap_at(A, x, y, Ho, Wo);
+    res[0] = res[1] = res[2] = 0;                                    // all four taps outside the frame: the border value
+    if (!t.outside) tap_u8x3(frame, Wo, t, res);
 }
-
-__device__ __forceinline__ float staged_value(int v) { return fminf(fmaxf((float)v / 255.f, 0.f), 1.f); }      // prepare_crops_kernel's
 
 template <int STAGE>
 __global__ void __launch_bounds__(256) crop_batch_kernel(const unsigned char* __restrict__ frames, int Ho, int Wo, AffineBatch AB, int dsize,
@@ -656,10 +657,7 @@ int launch_crop_batch(const unsigned char* frames, int Ho, int Wo, const double*
     }
     const int stage = I ? dsize / 256 : 0, rows = stage ? 2 : 1;
     const dim3 grid((unsigned)(((long)(dsize / 4) * (dsize / rows) + 255) / 256));
-    for (int b0 = 0; b0 < B; b0 += 64) {
-        const int nb = B - b0 < 64 ? B - b0 : 64;
-        AffineBatch AB;
-        for (int i = 0; i < nb; ++i) AB.a[i] = invert_affine(M + (long)(b0 + i) * 6);
+    return for_affine_batches(M, B, [&](int b0, int nb, const AffineBatch& AB) {
         const unsigned char* f = frames + b0 * P;
         unsigned char* c = crops + b0 * C;
         float* Ib = I ? I + (long)b0 * 3 * 256 * 256 : nullptr;
@@ -667,6 +665,6 @@ int launch_crop_batch(const unsigned char* frames, int Ho, int Wo, const double*
         else if (stage == 1) hipLaunchKernelGGL(crop_batch_kernel<1>, dim3(grid.x, nb), dim3(256), 0, st, f, Ho, Wo, AB, dsize, c, Ib);
         else hipLaunchKernelGGL(crop_batch_kernel<0>, dim3(grid.x, nb), dim3(256), 0, st, f, Ho, Wo, AB, dsize, c, Ib);
         LAUNCH_CHECK("crop_batch");
-    }
-    return 0;
+        return 0;
+    });
 }

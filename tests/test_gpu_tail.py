@@ -175,3 +175,87 @@ def test_soft_erosion_edges_vs_oracle(swapper, size, ks):
             soft, hard_got = se(mf[:, None])
             want, hard = R.soft_erosion(mf[:, None], ks, thr, iters)
             _compare(soft.cpu().numpy()[:, 0], want.numpy()[:, 0], hard_got.cpu().numpy()[:, 0], hard.numpy()[:, 0], m, what + ("module",))
+
+
+# ---- the shared bilinear tap of imgops.hip (tap_at / tap_u8x3 / tap_f32) on shapes so small that every class of tap occurs: every entry
+# point that reads through it, straight against oracle/cv_ref.py
+_TAP_SRC = (6, 10)            # source H x W
+_TAP_THETAS = (0.3, -0.5)
+
+
+def _tap_matrix(theta, Hd, Wd, s=2.0):
+    """Scale 2 and a rotation about the source's centre (5, 3), which lands (0.3, -0.2) off the destination's centre."""
+    c, sn = np.cos(theta), np.sin(theta)
+    tx = Wd / 2 - s * (5 * c - 3 * sn) + 0.3
+    ty = Hd / 2 - s * (5 * sn + 3 * c) - 0.2
+    return np.array([[s * c, -s * sn, tx], [s * sn, s * c, ty]], np.float64)
+
+
+def _tap_classes(M, Hd, Wd):
+    """From the oracle's fixed-point coordinates: (counts of the nine classes (rows both in / only the lower in / only the upper in) x
+    (columns likewise) among the pixels with fx > 0 and fy > 0, the map of pixels whose four taps are all outside)."""
+    from oracle import cv_ref as R
+    Hs, Ws = _TAP_SRC
+    sx, sy, fx, fy = R._coords(R.invert_affine(M), Hd, Wd)
+    rows = [(sy >= 0) & (sy + 1 < Hs), sy == -1, sy == Hs - 1]
+    cols = [(sx >= 0) & (sx + 1 < Ws), sx == -1, sx == Ws - 1]
+    frac = (fx > 0) & (fy > 0)
+    counts = np.array([[int((rw & cl & frac).sum()) for cl in cols] for rw in rows])
+    outside = (sx < -1) | (sy < -1) | (sx >= Ws) | (sy >= Hs)
+    return counts, outside
+
+
+@pytest.mark.parametrize("dest", ["24x32", "24x28", "23x29", "crop24"])
+def test_shared_tap_every_class_vs_oracle(swapper, dest):
+    """Destinations: 24x32 (paste_shared's 8-pixel path, paste_batch's dword path), 24x28 (the 4-pixel path), 23x29 (the single-frame fallback
+    of both), and cs_crop_frames at dsize 24.  Bit for bit against the cv_ref composition; the inputs are checked to hold every tap class."""
+    from canonswap_amd import tail
+    from oracle import cv_ref as R
+    e = swapper.engine
+    Hs, Ws = _TAP_SRC
+    r = np.random.Generator(np.random.PCG64(2718))
+    crops = r.integers(0, 256, size=(3, Hs, Ws, 3), dtype=np.uint8)          # crops[0] is "the source"
+    masks = r.random(size=(3, Hs, Ws), dtype=np.float32)
+
+    def same(got, want, what):
+        got = got.cpu().numpy()
+        assert got.shape == want.shape and got.dtype == want.dtype, (what, got.shape, got.dtype)
+        d = got != want
+        assert not d.any(), (dest, what, int(d.sum()), np.argwhere(d)[:3].tolist())
+
+    def covered(M, Hd, Wd):
+        counts, outside = _tap_classes(M, Hd, Wd)
+        print(dest, "tap classes with fx, fy > 0 (rows: both / lower / upper x columns likewise)", counts.tolist(), "all outside", int(outside.sum()))
+        assert counts.min() >= 1 and outside.sum() >= 1, (dest, counts.tolist(), int(outside.sum()))
+        return outside
+
+    if dest == "crop24":
+        Ms = np.stack([_tap_matrix(th, 24, 24) for th in _TAP_THETAS])
+        for M in Ms:
+            covered(M, 24, 24)
+        got = tail.crop_frames_M(e, crops[:2], Ms, 24)["crops"]
+        same(got, np.stack([R.warp_affine_u8(crops[b], Ms[b], (24, 24)) for b in range(2)]), "crop_frames_M")
+        return
+
+    Hd, Wd = (int(v) for v in dest.split("x"))
+    oris = r.integers(0, 256, size=(3, Hd, Wd, 3), dtype=np.uint8)
+    mask_ori = r.random(size=(Hd, Wd), dtype=np.float32)
+    mask_ori[1, 1] = 1.0                                                      # seeded values in [0, 1], both ends included
+    mask_ori[10:14, 12:18] = 0.0                                              # exact zeros over pixels that would read the crop
+    mask_ori[0:2, 0:4] = 1.0                                                  # ones over pixels whose taps are all outside (asserted below)
+    want_fused = {}
+    for th in _TAP_THETAS:
+        M = _tap_matrix(th, Hd, Wd)
+        outside = covered(M, Hd, Wd)
+        assert outside[0:2, 0:4].all() and not outside[10:14, 12:18].any(), (dest, th)
+        same(tail.warp_affine_u8(e, crops[0], M, (Wd, Hd)), R.warp_affine_u8(crops[0], M, (Wd, Hd)), ("warp_affine_u8", th))
+        for b in range(3):
+            want_fused[th, b] = R.paste_back(crops[b], M, oris[b], R.prepare_paste_back(masks[b], M, (Wd, Hd))[..., None])
+        same(tail.prepare_paste_back(e, masks[0], M, (Wd, Hd)), R.prepare_paste_back(masks[0], M, (Wd, Hd)), ("prepare_paste_back", th))
+        same(tail.paste_back(e, crops[0], M, oris[0], mask_ori), R.paste_back(crops[0], M, oris[0], mask_ori[..., None]), ("paste_back", th))
+        same(tail.paste_back_fused(e, crops[0], masks[0], M, oris[0]), want_fused[th, 0], ("paste_back_fused", th))
+        same(tail.paste_back_shared(e, crops, M, oris[0], mask_ori),
+             np.stack([R.paste_back(crops[b], M, oris[0], mask_ori[..., None]) for b in range(3)]), ("paste_back_shared", th))
+    ths = (_TAP_THETAS[0], _TAP_THETAS[1], _TAP_THETAS[0])                    # both matrices and one repeated
+    same(tail.paste_back_batch(e, crops, masks, np.stack([_tap_matrix(th, Hd, Wd) for th in ths]), oris),
+         np.stack([want_fused[ths[b], b] for b in range(3)]), "paste_back_batch")

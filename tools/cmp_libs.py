@@ -1,5 +1,5 @@
 """GPU box: the same frames through two builds of the library, compared bit for bit (stage outputs of the whole loop body, default and latency mode,
-and the motion extractor's raw head outputs):
+the motion extractor's raw head outputs, and the crop / warp / paste-back entry points on 1080p frames):
     python tools/cmp_libs.py tools/bin/base.so ""        ("" = the shipped library)
 Each build runs in its own process (the library is chosen at import: CANONSWAP_LIB)."""
 import os
@@ -29,6 +29,27 @@ for lat in (False, True):
 sdm = synth.to_torch(synth.make_state_dicts(0, modules=synth.MODULES + ("motion_extractor",)))
 swm = can_swapper(None, state_dicts=sdm, max_batch=5)
 out["M.raw"] = swm.engine.motion_extract_raw(torch.from_numpy(synth.make_smooth_images(5, seed=77, size=256)).cuda()).cpu()
+# the image-space tail (csrc/imgops.hip) at the sizes tools/time_crop.py and tools/time_v2i_chain.py time: 1080 x 1920 frames, 512 x 512 crops
+import numpy as np
+from canonswap_amd import tail
+e = swm.engine
+r = np.random.Generator(np.random.PCG64(4242))
+Bt, Ho, Wo = 4, 1080, 1920
+frames = torch.from_numpy(r.integers(0, 256, size=(Bt, Ho, Wo, 3), dtype=np.uint8)).cuda()
+crops = torch.from_numpy(r.integers(0, 256, size=(Bt, 512, 512, 3), dtype=np.uint8)).cuda()
+masks = torch.from_numpy(r.random(size=(Bt, 512, 512), dtype=np.float32)).cuda()
+# crop -> frame: inside the frame, rotated and enlarged, hanging over the left and over the right edge
+M_c2o = np.stack([[[sc * np.cos(th), -sc * np.sin(th), tx], [sc * np.sin(th), sc * np.cos(th), ty], [0, 0, 1]] for sc, th, tx, ty in
+                  ((0.45 * Ho / 512, 0.1, 0.35 * Wo, 0.2 * Ho), (1.3, -0.3, 900.0, 300.0), (0.6, 0.25, -150.5, 700.3), (1.0, 0.0, 1500.25, 600.75))])
+c = tail.crop_frames_M(e, frames, np.linalg.inv(M_c2o), 512, want_I=True)
+out["tail.crop_frames_M"], out["tail.crop_frames_M.I"] = c["crops"].cpu(), c["I"].cpu()
+out["tail.paste_back_batch"] = tail.paste_back_batch(e, crops, masks, M_c2o, frames).cpu()
+mask_ori = tail.prepare_paste_back(e, masks[0], M_c2o[0], (Wo, Ho))
+out["tail.prepare_paste_back"] = mask_ori.cpu()
+out["tail.paste_back_shared"] = tail.paste_back_shared(e, crops, M_c2o[0], frames[0], mask_ori).cpu()
+out["tail.paste_back"] = tail.paste_back(e, crops[0], M_c2o[0], frames[0], mask_ori).cpu()
+out["tail.paste_back_fused"] = tail.paste_back_fused(e, crops[0], masks[0], M_c2o[0], frames[0]).cpu()
+out["tail.warp_affine_u8"] = tail.warp_affine_u8(e, crops[0], M_c2o[0], (Wo, Ho)).cpu()
 torch.save(out, sys.argv[1])
 ''' % ROOT
 
