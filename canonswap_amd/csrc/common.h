@@ -201,15 +201,15 @@ int launch_conv_lat(const ConvParams& p, int mode, hipStream_t st);
 const half_t* cs_zero_page();   // per-process device buffer of zeros (lazily allocated on the current device)
 
 int launch_conv_first(const float* img, const float* w, const float* b, half_t* out, int N, int H, int W, hipStream_t st);
-int launch_avgpool(const half_t* in, int N, int D, int H, int W, int C, TDesc out, hipStream_t st);
 int launch_dm_compress(const float* f, const float* w, const float* b, half_t* comp, int N, int D, int H, int W, hipStream_t st);
 // shared_*: one compressed / feature volume, one kp_s set for all N samples (sample stride 0: the v2i body warps ONE swapped canonical volume)
 int launch_dm_sparse(const half_t* comp, const float* kp_d, const float* kp_s, half_t* out, int out_stride, int N, int D,
                      int H, int W, hipStream_t st, bool shared_comp = false, bool shared_kps = false);
-int launch_dm_softmax(const float* part, const float* bias, const float* kp_d, const float* kp_s, float* deform, float* mask_out,
-                      int N, int D, int H, int W, hipStream_t st, int compact = 0, bool shared_kps = false);
+// part: the mask conv's 4-column-tile sums (ConvParams::kw_out on 4 x 8 x 8 tiles; kernels.hip dm_logits)
+int launch_dm_softmax(const float* part, const float* bias, const float* kp_d, const float* kp_s, float* deform,
+                      int N, int D, int H, int W, hipStream_t st, bool shared_kps = false);
 int launch_dm_softmax_warp(const float* part, const float* bias, const float* kp_d, const float* kp_s, const float* in, float* out32,
-                           half_t* out16, float* deform, int N, int D, int H, int W, hipStream_t st, int compact = 0, bool shared_in = false,
+                           half_t* out16, float* deform, int N, int D, int H, int W, hipStream_t st, bool shared_in = false,
                            bool shared_kps = false);
 int launch_occ_finish(const float* part, float bias, float* occ, int N, int H, int W, hipStream_t st);
 int launch_occ_finish49(const float* part, float bias, float* occ, int N, int H, int W, hipStream_t st);
@@ -226,8 +226,7 @@ int launch_splitk_finish(const ConvParams& p, hipStream_t st);
 // re-pack the last chunk of a packed conv weight [chunk * taps][Cout_pad][32] for ConvParams::ragged (in place, via a scratch copy)
 int launch_pair_ragged(half_t* w, int Cout_pad, int nchunks, int KD, int KH, int KW, hipStream_t st);
 int launch_absmax16(const half_t* x, TDesc t, int N, int D, int H, int W, int C, unsigned* slot, hipStream_t st);
-int launch_ncdhw_to_hwdc(const float* in, float* out32, half_t* out16, const float* s2, const float* t2, int act2, float slope2,
-                         int N, int C, int D, int H, int W, hipStream_t st);
+int launch_ncdhw_to_hwdc(const float* in, float* out32, half_t* out16, int N, int C, int D, int H, int W, hipStream_t st);
 int launch_hwdc_to_ncdhw(const float* in, float* out, int N, int C, int D, int H, int W, hipStream_t st);
 int launch_nchw_to_nhwc16(const float* in, half_t* out, int N, int C, int HW, hipStream_t st);
 int launch_nhwc16_to_nchw(const half_t* in, float* out, int N, int C, int HW, hipStream_t st);
@@ -235,8 +234,6 @@ int launch_t_mask(const half_t* x, const half_t* wpacked, const float* bias, flo
 int launch_t_style(const float* id, const float* fc, float* style, int nlayers, hipStream_t st);
 int launch_t_modulate(const float* wraw, const float* style, half_t* packed, int layer, hipStream_t st);
 int launch_pack_u8(const float* img, uint8_t* out, int N, int C, int H, int W, hipStream_t st);
-int launch_lrelu16(const half_t* in, half_t* out, long n, float slope, hipStream_t st);
-
 int launch_unpack_u8(const uint8_t* in, float* out, int N, int C, int H, int W, hipStream_t st);
 
 // ---- image-space steps around the generator (imgops.hip)

@@ -36,6 +36,11 @@ namespace {
 constexpr int FD = 16, FH = 64, FW = 64, FC = 32;            // feature volume 32x16x64x64
 constexpr long VOL = (long)FD * FH * FW * FC;                 // 2,097,152 elements
 constexpr long VOX = (long)FD * FH * FW;                      // 65,536 voxels
+// dense motion's hourglass: level i is a [FD][S][S][DM_LW[i]] fp16 concat buffer per sample, S = 64 >> i (cs_engine::dm_l)
+constexpr int DM_LW[6] = {144, 128, 256, 512, 1024, 1024};    // concat widths per level
+constexpr long dm_level_elems(int i) { return (long)FD * (64 >> i) * (64 >> i) * DM_LW[i]; }
+static_assert(dm_level_elems(0) == 65536L * 144 && dm_level_elems(3) == 16L * 64 * 512 && dm_level_elems(5) == 16L * 4 * 1024, "hourglass level sizes");
+constexpr long DM_LOGIT_FLOATS = VOX / 4 * 220;                     // floats per sample of the mask conv's hand-over (ConvParams::kw_out, 4-column tiles)
 constexpr int IMG = 256;
 
 struct Blob { void* p = nullptr; size_t bytes = 0; bool paired = false; };     // paired: launch_pair_ragged already ran on it
@@ -470,7 +475,7 @@ int do_stats(cs_engine* e, const void* x, int is_f32, int B, long P, int C, floa
 // whole ResBlock3d per launch (vol32_fused.hip; CANONSWAP_VOL32_FUSED=0: A/B knob, two vol32 / conv_halo launches per block)
 bool vol32_fused_on() { static const bool on = [] { const char* s = getenv("CANONSWAP_VOL32_FUSED"); return !s || atoi(s) != 0; }(); return on && vol32_enabled(); }
 
-int run_resblocks3d(cs_engine* e, cs_engine::RB3* rb, int B, int* cur, const Affine* final_post, int final_act, hipStream_t st)
+int run_resblocks3d(cs_engine* e, cs_engine::RB3* rb, int B, int* cur, hipStream_t st)
 {
     // util.py:94-102; a = relu(bn1(x)) is already in va[0]; x (fp32 residual stream) in vs[*cur]
     if (vol32_fused_on()) {      // at every batch size (one frame: 2-row segments, launch_vol32_fused); the same bits as the two-launch path below
@@ -484,7 +489,6 @@ int run_resblocks3d(cs_engine* e, cs_engine::RB3* rb, int B, int* cur, const Aff
             c.w1 = rb[i].c1.w; c.w2 = rb[i].c2.w; c.b1 = rb[i].c1.b; c.b2 = rb[i].c2.b;
             c.s2 = nullptr; c.t2 = nullptr; c.act1 = ACT_NONE; c.slope1 = 0.f;
             if (i < 5) { c.s2 = rb[i].post.s; c.t2 = rb[i].post.t; c.act1 = ACT_RELU; }
-            else if (final_post) { c.s2 = final_post->s; c.t2 = final_post->t; c.act1 = final_act; }
             c.N = B; c.H = FH; c.W = FW;
             const double fl = 2.0 * (rb[i].c1.macs_per_pos + rb[i].c2.macs_per_pos) * (double)B * VOX;
             e->flops += fl;
@@ -506,7 +510,6 @@ int run_resblocks3d(cs_engine* e, cs_engine::RB3* rb, int B, int* cur, const Aff
         c2.p.out0 = hwdc3(e->vs[nxt]); c2.p.out0_f32 = 1;
         c2.p.out1 = hwdc3(e->va[0]);
         if (i < 5) { c2.p.s2 = rb[i].post.s; c2.p.t2 = rb[i].post.t; c2.p.act1 = ACT_RELU; }
-        else if (final_post) { c2.p.s2 = final_post->s; c2.p.t2 = final_post->t; c2.p.act1 = final_act; }
         c2.hcfg = cfg_v32();
         TRY(go(e, c2, st, 4, 4));
         *cur = nxt;
@@ -544,7 +547,7 @@ int run_F(cs_engine* e, int B, const float* img, int* cur, hipStream_t st)
     s.p.out0 = hwdc2(e->vs[0]); s.p.out0_f32 = 1;
     s.p.out1 = hwdc2(e->va[0]); s.p.s2 = e->f_pre0.s; s.p.t2 = e->f_pre0.t; s.p.act1 = ACT_RELU; wsplit_in(s, 256);
     TRY(go(e, s, st));
-    return run_resblocks3d(e, e->f_rb, B, cur, nullptr, ACT_NONE, st);
+    return run_resblocks3d(e, e->f_rb, B, cur, st);
 }
 
 // ------------------------------------------------------------------------------------------------ W
@@ -558,7 +561,7 @@ bool warp_fused() { static const bool on = [] { const char* s = getenv("CANONSWA
 // CANONSWAP_DEC_PHASES_DEEP=0: A/B knob (up-blocks 0 - 2 of the hourglass as 27-tap convs on the up-sampled grid, the form of rounds 1-5)
 static bool dec_phases_deep() { static const bool on = [] { const char* s = getenv("CANONSWAP_DEC_PHASES_DEEP"); return !s || atoi(s) != 0; }(); return on; }
 
-int run_dense_motion(cs_engine* e, int B, const float* feat, const float* kp_d, const float* kp_s, float* mask_out, hipStream_t st,
+int run_dense_motion(cs_engine* e, int B, const float* feat, const float* kp_d, const float* kp_s, hipStream_t st,
                      const float* warp_in = nullptr, float* warp_o32 = nullptr, half_t* warp_o16 = nullptr, bool want_deform = false,
                      bool shared_feat = false, bool shared_kps = false)
 {
@@ -568,17 +571,15 @@ int run_dense_motion(cs_engine* e, int B, const float* feat, const float* kp_d, 
     e->flops += 2.0 * 32 * 4 * VOX * B;
     // hourglass input lands in channels [32,144) of the level-0 concat buffer (util.py:255-264 cat order)
     TRY(e->run(1, st, [&] { return launch_dm_sparse(e->dm_comp, kp_d, kp_s, e->dm_l[0] + 32, 144, B, FD, FH, FW, st, shared_feat, shared_kps); }, "dm_sparse"));
-    static const int cin[5] = {112, 64, 128, 256, 512}, cout[5] = {64, 128, 256, 512, 1024};
-    static const int lw[6] = {144, 128, 256, 512, 1024, 1024};   // concat widths per level
+    static const int cout[5] = {64, 128, 256, 512, 1024};
     static const int skip_off[6] = {32, 64, 128, 256, 512, 0};   // channel offset of the skip part
     for (int i = 0; i < 5; ++i) {       // Encoder: DownBlock3d (util.py:185-190)
         const int S = 64 >> i;
-        ConvCall c = mk(e->w_enc[i], e->dm_l[i] + skip_off[i], dhwc(nullptr, FD, S, S, lw[i]), B, FD, S, S);
-        (void)cin;
+        ConvCall c = mk(e->w_enc[i], e->dm_l[i] + skip_off[i], dhwc(nullptr, FD, S, S, DM_LW[i]), B, FD, S, S);
         c.p.act0 = ACT_RELU;
         c.p.out0 = dhwc(e->dm_pre, FD, S, S, cout[i]);
         if (i == 0) c.hcfg = CFG_H_256x64;      // 64 channels at 64x64: 256-position tiles (0.65 -> 0.47 ms per 16 frames)
-        TDesc o = dhwc(e->dm_l[i + 1] + skip_off[i + 1], FD, S / 2, S / 2, lw[i + 1]);
+        TDesc o = dhwc(e->dm_l[i + 1] + skip_off[i + 1], FD, S / 2, S / 2, DM_LW[i + 1]);
         // AvgPool3d((1,2,2)) of the block (util.py:189) inside the conv's epilogue: the average of the four fp32 values, rounded once, goes
         // straight into the next level's concat buffer - no full-resolution tensor, no pooling launch.  In latency mode
         // too: the finishing launch of a split-K conv averages the same way (splitk_finish_pool_kernel).
@@ -587,9 +588,9 @@ int run_dense_motion(cs_engine* e, int B, const float* feat, const float* kp_d, 
     }
     for (int i = 0; i < 5; ++i) {       // Decoder: UpBlock3d (util.py:142-147), nearest x(1,2,2) folded into addressing
         const int lv = 5 - i, S = 64 >> (lv - 1), Si = S / 2;
-        ConvCall c = mk(e->w_dec[i], e->dm_l[lv], dhwc(nullptr, FD, Si, Si, lw[lv]), B, FD, S, S, 1);
+        ConvCall c = mk(e->w_dec[i], e->dm_l[lv], dhwc(nullptr, FD, Si, Si, DM_LW[lv]), B, FD, S, S, 1);
         c.p.act0 = ACT_RELU;
-        c.p.out0 = dhwc(e->dm_l[lv - 1], FD, S, S, lw[lv - 1]);
+        c.p.out0 = dhwc(e->dm_l[lv - 1], FD, S, S, DM_LW[lv - 1]);
         // Round 6: also up-blocks 0, 1 and 2 (1024 -> 512 from the 4 x 4 grid, 1024 -> 256 from the 8 x 8 one, 512 -> 128 from the 16 x 16 one) in
         // the batched mode - on 128x128 tiles (4x4x8 / 8x8x2 positions, static shapes 17 / 13): 12 of 27 taps, 0.66 -> 0.32 ms per 64-frame launch
         // for up-block 2.  In latency mode these three keep the 27-tap form: their launches are 8 - 64 workgroups there and run split-K, which a
@@ -601,12 +602,12 @@ int run_dense_motion(cs_engine* e, int B, const float* feat, const float* kp_d, 
             // phase (ConvParams::nphase).  One frame: 128 / 256 workgroups that run their whole K loop instead of four split-K launches of
             // 32 / 64 tiles each with a finishing launch behind it (8 launches of 14 + 7 us per level: profiles/r05_l_phase_group.txt); the
             // same bits as four launches at every batch size (tests/test_gpu_ops.py).
-            const int lwo = lw[lv - 1];
+            const int lwo = DM_LW[lv - 1];
             static const bool grouped = [] { const char* s = getenv("CANONSWAP_PHASE_GROUP"); return !s || atoi(s) != 0; }();      // =0: four launches (tests: same bits)
             if (!grouped) {
                 for (int ab = 0; ab < 4; ++ab) {
                     const int a = ab >> 1, b = ab & 1;
-                    ConvCall q1 = mk(e->w_dec_p[i][ab], e->dm_l[lv], dhwc(nullptr, FD, Si, Si, lw[lv]), B, FD, Si, Si);
+                    ConvCall q1 = mk(e->w_dec_p[i][ab], e->dm_l[lv], dhwc(nullptr, FD, Si, Si, DM_LW[lv]), B, FD, Si, Si);
                     q1.p.PH = a == 0; q1.p.PW = b == 0;
                     q1.p.act0 = ACT_RELU;
                     q1.p.out0 = td(e->dm_l[lv - 1] + ((long)a * S + b) * lwo, (long)FD * S * S * lwo, (long)S * S * lwo, 2L * S * lwo, 2L * lwo);
@@ -615,7 +616,7 @@ int run_dense_motion(cs_engine* e, int B, const float* feat, const float* kp_d, 
                 }
                 continue;
             }
-            ConvCall q = mk(e->w_dec_p[i][0], e->dm_l[lv], dhwc(nullptr, FD, Si, Si, lw[lv]), B, FD, Si, Si);
+            ConvCall q = mk(e->w_dec_p[i][0], e->dm_l[lv], dhwc(nullptr, FD, Si, Si, DM_LW[lv]), B, FD, Si, Si);
             q.p.act0 = ACT_RELU;
             q.p.out0 = td(e->dm_l[lv - 1], (long)FD * S * S * lwo, (long)S * S * lwo, 2L * S * lwo, 2L * lwo);
             q.p.nphase = 4;
@@ -642,21 +643,18 @@ int run_dense_motion(cs_engine* e, int B, const float* feat, const float* kp_d, 
     t.hcfg = CFG_H_256x160;
     TRY(go(e, t, st));
     ConvCall m = mk(e->w_mask, e->dm_pred, dhwc(nullptr, FD, 64, 64, 144), B, FD, 64, 64);   // dense_motion.py:88
-    m.p.out0 = dhwc(e->dm_logits, FD, 64, 64, 160); m.p.out0_f32 = 1;     // (kw, c) partials, finished by dm_softmax
-    // ... or, on the 256-position tiles (2 x 8 x 16), summed over kw inside the tile as far as the tile reaches: 8 logit vectors per 2 columns
-    // instead of 14 (ConvParams::kw_out): another, fixed summation order of the 7 partials of a logit.
-    // ... on 4-column tiles (4 x 8 x 8): 10 logit vectors per 4 columns instead of 8 per 2 - the hand-over to the softmax is 0.92 GB per 64-frame
-    // call instead of 1.48 GB, for 27 % more halo (784 voxels per 256 positions instead of 616).  A caller that wants the mask itself
-    // (cs_warp's debug output) gets the plain (kw, c) partials on 2-column tiles.
-    const int compact = mask_out ? 0 : 2;
-    if (compact) { m.p.kw_out = e->dm_logits; m.p.out0.p = nullptr; }
+    // The (kw, c) partials never leave the conv: on its 256-position tiles (4 x 8 x 8) they are summed over kw inside the tile as far as the
+    // tile reaches - 10 logit vectors per 4 columns instead of 28 (ConvParams::kw_out): a fixed summation order of the 7 partials of a logit,
+    // finished by dm_logits().  Against 2-column tiles (8 vectors per 2 columns) the hand-over to the softmax is 0.92 GB per 64-frame call
+    // instead of 1.48 GB, for 27 % more halo (784 voxels per 256 positions instead of 616).
+    m.p.kw_out = e->dm_logits;
     m.hcfg = CFG_H_256x160;
-    TRY(go(e, m, st, compact == 2 ? 4 : 2, 8));     // no halo along W (KW = 1)
-    if (warp_in && !mask_out && warp_fused()) {
-        TRY(e->run(2, st, [&] { return launch_dm_softmax_warp(e->dm_logits, e->mask_b, kp_d, kp_s, warp_in, warp_o32, warp_o16, want_deform ? e->dm_deform : nullptr, B, FD, FH, FW, st, compact, shared_feat, shared_kps); },
+    TRY(go(e, m, st, 4, 8));     // no halo along W (KW = 1)
+    if (warp_in && warp_fused()) {
+        TRY(e->run(2, st, [&] { return launch_dm_softmax_warp(e->dm_logits, e->mask_b, kp_d, kp_s, warp_in, warp_o32, warp_o16, want_deform ? e->dm_deform : nullptr, B, FD, FH, FW, st, shared_feat, shared_kps); },
                    "dm_softmax_warp"));
     } else {
-        TRY(e->run(1, st, [&] { return launch_dm_softmax(e->dm_logits, e->mask_b, kp_d, kp_s, e->dm_deform, mask_out, B, FD, FH, FW, st, compact, shared_kps); }, "dm_softmax"));
+        TRY(e->run(1, st, [&] { return launch_dm_softmax(e->dm_logits, e->mask_b, kp_d, kp_s, e->dm_deform, B, FD, FH, FW, st, shared_kps); }, "dm_softmax"));
         if (warp_in) TRY(e->run(2, st, [&] { return launch_grid_sample(warp_in, e->dm_deform, warp_o32, warp_o16, B, FD, FH, FW, st, shared_feat); }, "grid_sample"));
     }
     // occlusion (dense_motion.py:98-102): the (c,d)-flattened 2272-channel 7x7 conv runs as a 2-D (7,1)-tap conv whose
@@ -768,7 +766,7 @@ int run_T(cs_engine* e, int B, const int* slots, int* cur, hipStream_t st)
         TRY(t_layer(e, 2 * i + 1, B, slots, mixed, e->va[1], e->vs[*cur], e->tmask, e->va[0], e->vs[nxt], st));
         *cur = nxt;
     }
-    return run_resblocks3d(e, e->t_rb, B, cur, nullptr, ACT_NONE, st);   // last block leaves the raw fp16 copy in va[0]
+    return run_resblocks3d(e, e->t_rb, B, cur, st);   // last block leaves the raw fp16 copy in va[0]
 }
 
 // ------------------------------------------------------------------------------------------------ R
@@ -1136,7 +1134,7 @@ int copy_dd(void* dst, const void* src, size_t bytes, hipStream_t st)
 
 int to_hwdc(cs_engine* e, int B, const float* f, float* out32, half_t* out16, hipStream_t st)
 {
-    return e->run(1, st, [&] { return launch_ncdhw_to_hwdc(f, out32, out16, nullptr, nullptr, ACT_NONE, 0.f, B, FC, FD, FH, FW, st); }, "ncdhw_to_hwdc");
+    return e->run(1, st, [&] { return launch_ncdhw_to_hwdc(f, out32, out16, B, FC, FD, FH, FW, st); }, "ncdhw_to_hwdc");
 }
 int from_hwdc(cs_engine* e, int B, const float* in, float* out, hipStream_t st)
 {
@@ -1166,10 +1164,9 @@ extern "C" int cs_create(int device_id, int max_batch, cs_engine** out)
     for (int i = 0; i < 2; ++i) A(va[i], B * VOL);
     for (int i = 0; i < 2; ++i) A(vsp[i], B * VOL * 2);
     A(dm_comp, B * VOX * 4);
-    static const long lsz[6] = {65536L * 144, 16L * 1024 * 128, 16L * 256 * 256, 16L * 64 * 512, 16L * 16 * 1024, 16L * 4 * 1024};
-    for (int i = 0; i < 6; ++i) A(dm_l[i], B * lsz[i]);
+    for (int i = 0; i < 6; ++i) A(dm_l[i], B * dm_level_elems(i));
     A(dm_pre, B * VOX * 64); A(dm_pred, B * VOX * 144);
-    A(dm_logits, B * VOX * 160); A(dm_deform, B * VOX * 3); A(dm_occ, B * 4096);
+    A(dm_logits, B * DM_LOGIT_FLOATS); A(dm_deform, B * VOX * 3); A(dm_occ, B * 4096);
     A(kpbuf, B * 21 * 3 * 2);
     A(w_t3, B * 4096 * 256); A(seg16, B * 4096 * 256);
     A(tmask, B * 4096 * 4); A(style, 14 * 512);
@@ -1191,7 +1188,7 @@ extern "C" int cs_create(int device_id, int max_batch, cs_engine** out)
     A(img_a, B * 3 * 512 * 512); A(img_b, B * 3 * 512 * 512);
 #undef A
     // the concat buffers carry zero pad channels that are never written: clear once
-    CS_CHECK_HIP(hipMemset(e->dm_l[0], 0, B * lsz[0] * sizeof(half_t)));
+    CS_CHECK_HIP(hipMemset(e->dm_l[0], 0, B * dm_level_elems(0) * sizeof(half_t)));
     CS_CHECK_HIP(hipMemset(e->dm_pred, 0, B * VOX * 144 * sizeof(half_t)));
     *out = e;
     return 0;
@@ -1261,7 +1258,7 @@ extern "C" int cs_finalize_weights(cs_engine* e)
     }
     // ---- F
     TRY(get_f32(e, "F.first.w", 64 * 27, &e->first_w)); TRY(get_f32(e, "F.first.b", 64, &e->first_b));
-    // packed as [W_hi | W_lo] over twice the input channels (run_F: wsplit_in); with the knob off only the W_hi chunks (the first half) are used
+    // packed as [W_hi | W_lo] over twice the input channels (run_F: wsplit_in)
     TRY(get_conv(e, "F.down0", 128, 128, 128, 1, 3, 3, 128, 64.0 * 128 * 9, &e->f_down0));
     TRY(get_conv(e, "F.down1", 256, 256, 256, 1, 3, 3, 256, 128.0 * 256 * 9, &e->f_down1));
     TRY(get_conv(e, "F.second", 512, 512, 512, 1, 1, 1, 512, 256.0 * 512, &e->f_second));
@@ -1275,7 +1272,6 @@ extern "C" int cs_finalize_weights(cs_engine* e)
             if (i < 5) { snprintf(n, sizeof n, "%s.rb%d.post", pre, i); TRY(get_affine(e, n, 32, &rb[i].post)); }
         }
     }
-    // first conv of F (3->64 @256^2) is outside launch_conv: account its FLOPs where it is launched? keep simple: not counted
     // ---- W
     TRY(get_f32(e, "W.compress.w", 128, &e->cmp_w)); TRY(get_f32(e, "W.compress.b", 4, &e->cmp_b));
     static const int eci[5] = {112, 64, 128, 256, 512}, eco[5] = {64, 128, 256, 512, 1024};
@@ -1460,7 +1456,7 @@ extern "C" int cs_warp(cs_engine* e, int B, const float* f, const float* kp_sour
     ENTER(e, B);
     hipStream_t st = (hipStream_t)stream;
     TRY(to_hwdc(e, B, f, e->vs[0], nullptr, st));
-    TRY(run_dense_motion(e, B, e->vs[0], kp_driving, kp_source, nullptr, st, e->vs[0], e->vs[1], nullptr));      // dense motion + the feature warp it drives
+    TRY(run_dense_motion(e, B, e->vs[0], kp_driving, kp_source, st, e->vs[0], e->vs[1], nullptr));      // dense motion + the feature warp it drives
     TRY(from_hwdc(e, B, e->vs[1], f_out, st));
     if (occ_out) TRY(copy_dd(occ_out, e->dm_occ, (size_t)B * 4096 * 4, st));
     return 0;
@@ -1509,7 +1505,7 @@ extern "C" int cs_warp_forward(cs_engine* e, int B, const float* f, const float*
     ENTER(e, B);
     hipStream_t st = (hipStream_t)stream;
     TRY(to_hwdc(e, B, f, e->vs[0], nullptr, st));
-    TRY(run_dense_motion(e, B, e->vs[0], kp_driving, kp_source, nullptr, st, e->vs[0], nullptr, e->va[0], deformation_out != nullptr));      // dense motion + the feature warp it drives
+    TRY(run_dense_motion(e, B, e->vs[0], kp_driving, kp_source, st, e->vs[0], nullptr, e->va[0], deformation_out != nullptr));      // dense motion + the feature warp it drives
     TRY(run_warp_out(e, B, e->va[0], e->dm_occ, st));
     if (seg_out) TRY(e->run(1, st, [&] { return launch_nhwc16_to_nchw(e->seg16, seg_out, B, 256, 4096, st); }, "nhwc16_to_nchw"));
     if (occ_out) TRY(copy_dd(occ_out, e->dm_occ, (size_t)B * 4096 * 4, st));
@@ -1565,7 +1561,7 @@ extern "C" int cs_swap_frames_ids(cs_engine* e, const int* slots, int B, const f
     TRY(run_F(e, B, img, &cur, st));                                                      // :242 f_s
     // :244 warp(f_s, kp_source = x_t, kp_driving = x_can)
     const int nxt = (cur + 1) % 3;
-    TRY(run_dense_motion(e, B, e->vs[cur], /*kp_d*/ x_can, /*kp_s*/ x_t, nullptr, st, e->vs[cur], e->vs[nxt], e->va[0]));      // dense motion + the feature warp it drives
+    TRY(run_dense_motion(e, B, e->vs[cur], /*kp_d*/ x_can, /*kp_s*/ x_t, st, e->vs[cur], e->vs[nxt], e->va[0]));      // dense motion + the feature warp it drives
     cur = nxt;
     // the first warp's occlusion map is reused by the debug decodes (:248,:257); keep a copy in tmask-free storage
     float* occ1 = e->img_b;   // B*4096 floats fit easily
@@ -1581,7 +1577,7 @@ extern "C" int cs_swap_frames_ids(cs_engine* e, const int* slots, int B, const f
     }
     TRY(run_R(e, B, &cur, st));                                                             // :262
     // :263 warp_decode(f, kp_source = x_can, kp_driving = x_t)
-    TRY(run_dense_motion(e, B, e->vs[cur], /*kp_d*/ x_t, /*kp_s*/ x_can, nullptr, st, e->vs[cur], nullptr, e->va[0]));      // dense motion + the feature warp it drives
+    TRY(run_dense_motion(e, B, e->vs[cur], /*kp_d*/ x_t, /*kp_s*/ x_can, st, e->vs[cur], nullptr, e->va[0]));      // dense motion + the feature warp it drives
     TRY(run_warp_out(e, B, e->va[0], e->dm_occ, st));
     float* dst = out_f32 ? out_f32 : e->img_a;
     TRY(run_G(e, B, e->seg16, dst, st));
@@ -1600,7 +1596,7 @@ extern "C" int cs_animate_frames(cs_engine* e, int B, const float* f, int nf, co
     TRY(to_hwdc(e, nf, f, e->vs[0], nullptr, st));
     // nf == 1 / ns == 1: the one volume / key-point set is broadcast by a zero sample stride in the kernels that read it (round 6; before: B - 1
     // device copies of 8.4 MB and B of 252 bytes per call)
-    TRY(run_dense_motion(e, B, e->vs[0], kp_driving, kp_source, nullptr, st, e->vs[0], nullptr, e->va[0], false, nf == 1 && B > 1, ns == 1 && B > 1));
+    TRY(run_dense_motion(e, B, e->vs[0], kp_driving, kp_source, st, e->vs[0], nullptr, e->va[0], false, nf == 1 && B > 1, ns == 1 && B > 1));
     TRY(run_warp_out(e, B, e->va[0], e->dm_occ, st));
     float* dst = out_f32 ? out_f32 : e->img_a;
     TRY(run_G(e, B, e->seg16, dst, st));
@@ -1986,8 +1982,7 @@ extern "C" int cs_op_dm_softmax_warp(const float* part, const float* bias, const
 {
     if (!part || !bias || !kp_d || !kp_s || !in_hwdc || N < 1 || H < 2) { cs_set_error("cs_op_dm_softmax_warp: bad arguments"); return -1; }
     if (W & 3) { cs_set_error("cs_op_dm_softmax_warp: compact-2 partials need a width that is a multiple of 4"); return -1; }
-    return launch_dm_softmax_warp(part, bias, kp_d, kp_s, in_hwdc, out32, (half_t*)out16, deform, N, D, H, W, (hipStream_t)stream, 2,
-                                  shared_in != 0, shared_kps != 0);
+    return launch_dm_softmax_warp(part, bias, kp_d, kp_s, in_hwdc, out32, (half_t*)out16, deform, N, D, H, W, (hipStream_t)stream, shared_in != 0, shared_kps != 0);
 }
 
 extern "C" int cs_op_occ_finish(const float* part, int taps, float bias, float* occ, int N, int H, int W, void* stream)
@@ -2003,12 +1998,11 @@ extern "C" int cs_op_dm_read(cs_engine* e, int which, int B, void* dst, void* st
 {
     ENTER(e, B);
     if (!dst) { cs_set_error("cs_op_dm_read: null destination"); return -1; }
-    static const long lsz[6] = {65536L * 144, 16L * 1024 * 128, 16L * 256 * 256, 16L * 64 * 512, 16L * 16 * 1024, 16L * 4 * 1024};
     const void* src; size_t bytes;
     if (which == CS_DM_COMP) { src = e->dm_comp; bytes = (size_t)B * VOX * 4 * sizeof(half_t); }
-    else if (which >= CS_DM_L0 && which <= CS_DM_L0 + 5) { src = e->dm_l[which - CS_DM_L0]; bytes = (size_t)B * lsz[which - CS_DM_L0] * sizeof(half_t); }
+    else if (which >= CS_DM_L0 && which <= CS_DM_L0 + 5) { src = e->dm_l[which - CS_DM_L0]; bytes = (size_t)B * dm_level_elems(which - CS_DM_L0) * sizeof(half_t); }
     else if (which == CS_DM_PRED) { src = e->dm_pred; bytes = (size_t)B * VOX * 144 * sizeof(half_t); }
-    else if (which == CS_DM_LOGITS) { src = e->dm_logits; bytes = (size_t)B * VOX / 4 * 220 * sizeof(float); }
+    else if (which == CS_DM_LOGITS) { src = e->dm_logits; bytes = (size_t)B * DM_LOGIT_FLOATS * sizeof(float); }
     else { cs_set_error("cs_op_dm_read: no buffer %d", which); return -1; }
     return copy_dd(dst, src, bytes, (hipStream_t)stream);
 }

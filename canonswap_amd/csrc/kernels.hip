@@ -27,6 +27,16 @@ const half_t* cs_zero_page()
 
 static inline unsigned cdiv(long a, long b) { return (unsigned)((a + b - 1) / b); }
 
+// XCD-aware block order: hardware places workgroup b on XCD b % 8 (each with its own L2); every XCD walks a contiguous eighth of the
+// grid, so the source lines that neighbouring workgroups share (the 8 corners of adjacent output voxels of a warp, the three input rows of
+// neighbouring output rows of T's mask conv) are fetched into ONE L2 instead of up to eight (r02: 2.1x over-fetch on the warp's read side,
+// profiles/r02_i_pmc_summary.csv).  A grid that is no multiple of 8 is walked in launch order.
+__device__ __forceinline__ long xcd_block()
+{
+    if ((gridDim.x & 7) == 0) return (long)(blockIdx.x & 7) * (gridDim.x >> 3) + (blockIdx.x >> 3);
+    return blockIdx.x;
+}
+
 // ------------------------------------------------------------------------------------------------
 // first encoder layer: conv 3x3 3->64 + folded BN + ReLU (appearance_feature_extractor.py:22,39;
 // util.py:207-211). K = 27 is too small for MFMA: direct convolution, fp32 NCHW in, fp16 NHWC out.
@@ -70,38 +80,6 @@ int launch_conv_first(const float* img, const float* w, const float* b, half_t* 
 {
     hipLaunchKernelGGL(conv_first_kernel, dim3(cdiv((long)N * H * W, 64)), dim3(256), 0, st, img, w, b, out, N, H, W);
     LAUNCH_CHECK("conv_first");
-    return 0;
-}
-
-// ------------------------------------------------------------------------------------------------
-// AvgPool over (H,W) 2x2 (nn.AvgPool2d(2) util.py:158,165; nn.AvgPool3d((1,2,2)) util.py:183,189)
-// in: contiguous [N][D][H][W][C] fp16; out: strided view (so it can land inside a concat buffer)
-// ------------------------------------------------------------------------------------------------
-__global__ void __launch_bounds__(256) avgpool_kernel(const half_t* __restrict__ in, int N, int D, int H, int W, int C, TDesc out)
-{
-    const int C8 = C >> 3, Ho = H >> 1, Wo = W >> 1;
-    const long total = (long)N * D * Ho * Wo * C8;
-    long i = (long)blockIdx.x * 256 + threadIdx.x;
-    if (i >= total) return;
-    const int c8 = i % C8; i /= C8;
-    const int x = i % Wo; i /= Wo;
-    const int y = i % Ho; i /= Ho;
-    const int d = i % D;
-    const int n = i / D;
-    const half_t* src = in + ((((long)n * D + d) * H + 2 * y) * W + 2 * x) * C + c8 * 8;
-    const h8_t a = *(const h8_t*)src, b = *(const h8_t*)(src + C), c = *(const h8_t*)(src + (long)W * C),
-               e = *(const h8_t*)(src + (long)W * C + C);
-    h8_t o;
-#pragma unroll
-    for (int j = 0; j < 8; ++j) o[j] = (half_t)(((float)a[j] + (float)b[j] + (float)c[j] + (float)e[j]) * 0.25f);
-    *(h8_t*)((half_t*)out.p + (long)n * out.sN + (long)d * out.sD + (long)y * out.sH + (long)x * out.sW + c8 * 8) = o;
-}
-
-int launch_avgpool(const half_t* in, int N, int D, int H, int W, int C, TDesc out, hipStream_t st)
-{
-    const long total = (long)N * D * (H / 2) * (W / 2) * (C / 8);
-    hipLaunchKernelGGL(avgpool_kernel, dim3(cdiv(total, 256)), dim3(256), 0, st, in, N, D, H, W, C, out);
-    LAUNCH_CHECK("avgpool");
     return 0;
 }
 
@@ -300,73 +278,36 @@ int launch_dm_sparse(const half_t* comp, const float* kp_d, const float* kp_s, h
 
 // mask conv finish + softmax over the 22 mask logits + deformation = sum_k mask_k * sparse_motion_k
 // (dense_motion.py:88-94). The 7x7x7 mask conv runs on the MFMA kernel as a (7,7,1)-tap conv whose 154 output
-// channels are (kw, c): part[voxel][kw*22+c] = sum_{kd,kh,cin} pred[d+kd-3][h+kh-3][w][cin] * Wm[c][cin][kd][kh][kw]
-// (row stride 160 floats). This kernel adds the seven horizontally shifted partials:
-//     logit_c(d,h,w) = bias_c + sum_kw part[(d,h,w+kw-3)][kw*22+c]   (zero padding in w),
-// then softmax and the motion blend. deformation out: fp32 [N][D][H][W][3]; optional mask out [N][22][D][H][W].
-// the 22 mask logits of voxel v = (n, d, y, x): bias + the mask conv's partials.  compact 0: part[voxel][kw * 22 + c] of the 7 voxels
-// x - 3 .. x + 3 (ConvParams::out0 of the kw-split conv);  compact 1: the in-tile sums part[((n D + d) H + y) * (W / 2) + T][j][22] of the
-// (up to) four 2-column tiles T whose 8 output columns 2 T - 3 .. 2 T + 4 include x (ConvParams::kw_out), T ascending: a fixed order
-__device__ __forceinline__ void dm_logits(float (&l)[22], const float* __restrict__ part, const float* __restrict__ bias, long v, int x, int W,
-                                          int compact)
+// channels are (kw, c): P[voxel][kw*22+c] = sum_{kd,kh,cin} pred[d+kd-3][h+kh-3][w][cin] * Wm[c][cin][kd][kh][kw], and
+//     logit_c(d,h,w) = bias_c + sum_kw P[(d,h,w+kw-3)][kw*22+c]   (zero padding in w).
+// The conv's epilogue sums over kw inside its 4-column tiles as far as a tile reaches (ConvParams::kw_out) and hands over
+// part[((n D + d) H + y) * (W / 4) + T][j][22], j <-> output column 4 T - 3 + j (10 per tile): the 22 mask logits of voxel
+// v = (n, d, y, x) are the bias + the sums of the (up to) three tiles whose reach includes x, T ascending: a fixed order.
+__device__ __forceinline__ void dm_logits(float (&l)[22], const float* __restrict__ part, const float* __restrict__ bias, long v, int x, int W)
 {
 #pragma unroll
     for (int k = 0; k < 22; ++k) l[k] = bias[k];
-    if (compact == 2) {
-        // the 4-column tiles' sums: part[((n D + d) H + y) * (W / 4) + T][j][22], j <-> output column 4 T - 3 + j (10 per tile); x lies in the
-        // reach of (up to) three tiles, T ascending: a fixed order
-        const long row = (v - x) / 4 * 220;
-        const int T0 = (x + 1) / 4 - 1;                      // = ceil((x - 6) / 4): the smallest T with 4 T + 6 >= x
+    const long row = (v - x) / 4 * 220;                  // first tile of this (n, d, y) row: (v - x) is the row's first voxel, W / 4 tiles x 220
+    const int T0 = (x + 1) / 4 - 1;                      // = ceil((x - 6) / 4): the smallest T with 4 T + 6 >= x
 #pragma unroll
-        for (int dt = 0; dt < 3; ++dt) {
-            const int T = T0 + dt, j = x - 4 * T + 3;
-            if ((unsigned)T < (unsigned)(W >> 2) && (unsigned)j < 10u) {
-                const float2* src = (const float2*)(part + row + (long)T * 220 + j * 22);
+    for (int dt = 0; dt < 3; ++dt) {
+        const int T = T0 + dt, j = x - 4 * T + 3;
+        if ((unsigned)T < (unsigned)(W >> 2) && (unsigned)j < 10u) {
+            const float2* src = (const float2*)(part + row + (long)T * 220 + j * 22);
 #pragma unroll
-                for (int k = 0; k < 11; ++k) { const float2 q = src[k]; l[2 * k] += q.x; l[2 * k + 1] += q.y; }
-            }
-        }
-        return;
-    }
-    if (compact) {
-        const long row = (v - x) / 2 * 176;                  // first tile of this (n, d, y) row: (v - x) is the row's first voxel, W / 2 tiles x 176
-        const int T0 = (x >> 1) - 2 + (x & 1);
-#pragma unroll
-        for (int dt = 0; dt < 4; ++dt) {
-            const int T = T0 + dt;
-            if ((unsigned)T < (unsigned)(W >> 1)) {
-                const float2* src = (const float2*)(part + row + (long)T * 176 + (x - 2 * T + 3) * 22);
-#pragma unroll
-                for (int j = 0; j < 11; ++j) { const float2 q = src[j]; l[2 * j] += q.x; l[2 * j + 1] += q.y; }
-            }
-        }
-        return;
-    }
-#pragma unroll
-    for (int kw = 0; kw < 7; ++kw) {
-        const int xx = x + kw - 3;
-        if ((unsigned)xx < (unsigned)W) {
-            const float2* src = (const float2*)(part + (v + kw - 3) * 160 + kw * 22);
-#pragma unroll
-            for (int j = 0; j < 11; ++j) { const float2 q = src[j]; l[2 * j] += q.x; l[2 * j + 1] += q.y; }
+            for (int k = 0; k < 11; ++k) { const float2 q = src[k]; l[2 * k] += q.x; l[2 * k + 1] += q.y; }
         }
     }
 }
 
-__global__ void __launch_bounds__(256) dm_softmax_kernel(const float* __restrict__ part, const float* __restrict__ bias,
-                                                         const float* __restrict__ kp_d, const float* __restrict__ kp_s,
-                                                         float* __restrict__ deform, float* __restrict__ mask_out, int N, int D, int H, int W,
-                                                         int compact, int kps_sN)
+// the deformation (x, y, z) of voxel v = (n, d, y, x): softmax over its 22 logits, then the blend of the identity grid (slot 0) and the 21
+// key-point motions in slot order.  The one statement of this arithmetic: dm_softmax_kernel and dm_softmax_warp_kernel give the same bits.
+__device__ __forceinline__ void dm_deformation(float (&o)[3], const float* __restrict__ part, const float* __restrict__ bias,
+                                               const float* __restrict__ kp_d, const float* __restrict__ kp_s, long v, int n, int d, int y, int x,
+                                               int D, int H, int W, int kps_sN)
 {
-    const long total = (long)N * D * H * W;
-    const long v = (long)blockIdx.x * 256 + threadIdx.x;
-    if (v >= total) return;
-    const int x = v % W; long r = v / W;
-    const int y = r % H; r /= H;
-    const int d = r % D;
-    const int n = r / D;
     float l[22];
-    dm_logits(l, part, bias, v, x, W, compact);
+    dm_logits(l, part, bias, v, x, W);
     float mx = l[0];
 #pragma unroll
     for (int k = 1; k < 22; ++k) mx = fmaxf(mx, l[k]);
@@ -385,119 +326,124 @@ __global__ void __launch_bounds__(256) dm_softmax_kernel(const float* __restrict
         oy = fmaf(m, (gy - pd[1]) + ps[1], oy);
         oz = fmaf(m, (gz - pd[2]) + ps[2], oz);
     }
-    float* o = deform + v * 3;
     o[0] = ox; o[1] = oy; o[2] = oz;
-    if (mask_out) {
-        const long dhw = (long)D * H * W, sp = ((long)d * H + y) * W + x;
+}
+
+// F.grid_sample(..., align_corners=False), trilinear, zeros padding, of the 4 channels at `base` (a sample's HWDC volume + the lane's channel
+// group) at the point (gx, gy, gz).  All eight corners are fetched back to back (clamped address, weight 0 outside: the same bits as skipping
+// them; see dm_sparse_kernel).  The one statement of the gather: grid_sample_kernel and dm_softmax_warp_kernel give the same bits.
+__device__ __forceinline__ void trilinear4(float (&a)[4], const float* base, float gx, float gy, float gz, int D, int H, int W)
+{
+    const float ix = ((gx + 1.f) * W - 1.f) * 0.5f, iy = ((gy + 1.f) * H - 1.f) * 0.5f, iz = ((gz + 1.f) * D - 1.f) * 0.5f;
+    const float fx = floorf(ix), fy = floorf(iy), fz = floorf(iz);
+    const int x0 = (int)fx, y0 = (int)fy, z0 = (int)fz;
+    const float tx = ix - fx, ty = iy - fy, tz = iz - fz;
+    a[0] = 0.f; a[1] = 0.f; a[2] = 0.f; a[3] = 0.f;
+    float4 cv[8]; float wv[8];
 #pragma unroll
-        for (int k = 0; k < 22; ++k) mask_out[((long)n * 22 + k) * dhw + sp] = l[k] * inv;
+    for (int dz = 0; dz < 2; ++dz)
+#pragma unroll
+        for (int dy = 0; dy < 2; ++dy)
+#pragma unroll
+            for (int dx = 0; dx < 2; ++dx) {
+                const int xc = x0 + dx, yc = y0 + dy, zc = z0 + dz;
+                const bool inb = (unsigned)xc < (unsigned)W && (unsigned)yc < (unsigned)H && (unsigned)zc < (unsigned)D;
+                const float wgt = (dx ? tx : 1.f - tx) * (dy ? ty : 1.f - ty) * (dz ? tz : 1.f - tz);
+                const int xq = min(max(xc, 0), W - 1), yq = min(max(yc, 0), H - 1), zq = min(max(zc, 0), D - 1);
+                cv[dz * 4 + dy * 2 + dx] = *(const float4*)(base + (((long)yq * W + xq) * D + zq) * 32);
+                wv[dz * 4 + dy * 2 + dx] = inb ? wgt : 0.f;
+            }
+#pragma unroll
+    for (int c8 = 0; c8 < 8; ++c8) {
+        a[0] = fmaf(wv[c8], cv[c8].x, a[0]); a[1] = fmaf(wv[c8], cv[c8].y, a[1]);
+        a[2] = fmaf(wv[c8], cv[c8].z, a[2]); a[3] = fmaf(wv[c8], cv[c8].w, a[3]);
     }
 }
 
-int launch_dm_softmax(const float* part, const float* bias, const float* kp_d, const float* kp_s, float* deform, float* mask_out,
-                      int N, int D, int H, int W, hipStream_t st, int compact, bool shared_kps)
+__device__ __forceinline__ void store_warped4(const float (&a)[4], float* out32, half_t* out16, long o)
 {
-    if ((compact == 1 && (W & 1)) || (compact == 2 && (W & 3))) { cs_set_error("dm_softmax: the compact partial layouts need a width that is a multiple of the tile's columns"); return -1; }
+    if (out32) *(float4*)(out32 + o) = make_float4(a[0], a[1], a[2], a[3]);
+    if (out16) {
+        h4_t h; h[0] = (half_t)a[0]; h[1] = (half_t)a[1]; h[2] = (half_t)a[2]; h[3] = (half_t)a[3];
+        *(h4_t*)(out16 + o) = h;
+    }
+}
+
+// deformation out: fp32 [N][D][H][W][3]
+__global__ void __launch_bounds__(256) dm_softmax_kernel(const float* __restrict__ part, const float* __restrict__ bias,
+                                                         const float* __restrict__ kp_d, const float* __restrict__ kp_s,
+                                                         float* __restrict__ deform, int N, int D, int H, int W, int kps_sN)
+{
+    const long total = (long)N * D * H * W;
+    const long v = (long)blockIdx.x * 256 + threadIdx.x;
+    if (v >= total) return;
+    const int x = v % W; long r = v / W;
+    const int y = r % H; r /= H;
+    const int d = r % D;
+    const int n = r / D;
+    float g[3];
+    dm_deformation(g, part, bias, kp_d, kp_s, v, n, d, y, x, D, H, W, kps_sN);
+    float* o = deform + v * 3;
+    o[0] = g[0]; o[1] = g[1]; o[2] = g[2];
+}
+
+int launch_dm_softmax(const float* part, const float* bias, const float* kp_d, const float* kp_s, float* deform,
+                      int N, int D, int H, int W, hipStream_t st, bool shared_kps)
+{
+    if (W & 3) { cs_set_error("dm_softmax: compact-2 partials need a width that is a multiple of 4"); return -1; }
     hipLaunchKernelGGL(dm_softmax_kernel, dim3(cdiv((long)N * D * H * W, 256)), dim3(256), 0, st, part, bias, kp_d, kp_s,
-                       deform, mask_out, N, D, H, W, compact, shared_kps ? 0 : 63);
+                       deform, N, D, H, W, shared_kps ? 0 : 63);
     LAUNCH_CHECK("dm_softmax");
     return 0;
 }
 
 // dm_softmax + the feature warp that consumes its deformation in ONE kernel (dense_motion.py:88-94 -> warping_network.py:46-62): the
 // sampling grid never goes through HBM (SURVEY 8d prices it at 0 bytes then) and one dependent launch disappears.  A workgroup owns the
-// 16 (w) x 16 (d) voxels of one (n, h): phase 1, one thread per voxel, is dm_softmax_kernel's arithmetic verbatim (same order of
-// operations: same bits) and leaves (x, y, z) in LDS; phase 2 gathers with 8 lanes x float4 per voxel exactly like grid_sample_kernel,
-// voxels in (w, d) order so that a wave writes 8 consecutive depth slices of one column = 1 KiB contiguous.  XCD-aware block order:
-// every XCD walks a contiguous eighth of the output (neighbouring voxels share source lines: they meet in one L2).
-__global__ void __launch_bounds__(256) dm_softmax_warp_kernel(const float* __restrict__ part, const float* __restrict__ bias,
+// 16 (w) x 16 (d) voxels of one (n, h): phase 1, one thread per voxel, is dm_softmax_kernel's dm_deformation and leaves (x, y, z) in LDS;
+// phase 2 is grid_sample_kernel's trilinear4 with 8 lanes x float4 per voxel, voxels in (w, d) order so that a wave writes 8 consecutive
+// depth slices of one column = 1 KiB contiguous.  Blocks in xcd_block() order (neighbouring voxels share source lines).
+// (256, 8): eight waves per SIMD, 63 VGPRs - with dm_logits' one layout left and no bound the compiler keeps all three tiles' loads of phase 1 in
+// flight at 66 VGPRs, one wave fewer)
+__global__ void __launch_bounds__(256, 8) dm_softmax_warp_kernel(const float* __restrict__ part, const float* __restrict__ bias,
                                                               const float* __restrict__ kp_d, const float* __restrict__ kp_s,
                                                               const float* __restrict__ in, float* __restrict__ out32, half_t* __restrict__ out16,
-                                                              float* __restrict__ deform, int N, int D, int H, int W, int compact,
-                                                              long in_sN, int kps_sN)
+                                                              float* __restrict__ deform, int N, int D, int H, int W, long in_sN, int kps_sN)
 {
     __shared__ float defs[256 * 3];
-    long blk = blockIdx.x;
-    if ((gridDim.x & 7) == 0) blk = (long)(blockIdx.x & 7) * (gridDim.x >> 3) + (blockIdx.x >> 3);
+    const long blk = xcd_block();
     const int nwb = W >> 4;
     const int wb = (int)(blk % nwb); long r = blk / nwb;
     const int y = (int)(r % H);
     const int n = (int)(r / H);
     const int t = threadIdx.x;
-    {   // ---- phase 1: softmax over the 22 mask logits and the motion blend for voxel (d, x) = (t >> 4, wb * 16 + (t & 15))
+    {   // ---- phase 1: the deformation of voxel (d, x) = (t >> 4, wb * 16 + (t & 15))
         const int d = t >> 4, x = wb * 16 + (t & 15);
         const long v = (((long)n * D + d) * H + y) * W + x;
-        float l[22];
-        dm_logits(l, part, bias, v, x, W, compact);
-        float mx = l[0];
-#pragma unroll
-        for (int k = 1; k < 22; ++k) mx = fmaxf(mx, l[k]);
-        float sum = 0.f;
-#pragma unroll
-        for (int k = 0; k < 22; ++k) { l[k] = __expf(l[k] - mx); sum += l[k]; }
-        const float inv = 1.f / sum;
-        const float gx = grid_coord(x, W), gy = grid_coord(y, H), gz = grid_coord(d, D);
-        float ox = gx * (l[0] * inv), oy = gy * (l[0] * inv), oz = gz * (l[0] * inv);
-#pragma unroll
-        for (int k = 1; k < 22; ++k) {
-            const float* pd = kp_d + ((long)n * 21 + (k - 1)) * 3;
-            const float* ps = kp_s + (long)n * kps_sN + (k - 1) * 3;
-            const float m = l[k] * inv;
-            ox = fmaf(m, (gx - pd[0]) + ps[0], ox);
-            oy = fmaf(m, (gy - pd[1]) + ps[1], oy);
-            oz = fmaf(m, (gz - pd[2]) + ps[2], oz);
-        }
-        defs[t * 3] = ox; defs[t * 3 + 1] = oy; defs[t * 3 + 2] = oz;
-        if (deform) { float* o = deform + v * 3; o[0] = ox; o[1] = oy; o[2] = oz; }
+        float g[3];
+        dm_deformation(g, part, bias, kp_d, kp_s, v, n, d, y, x, D, H, W, kps_sN);
+        defs[t * 3] = g[0]; defs[t * 3 + 1] = g[1]; defs[t * 3 + 2] = g[2];
+        if (deform) { float* o = deform + v * 3; o[0] = g[0]; o[1] = g[1]; o[2] = g[2]; }
     }
     __syncthreads();
-    // ---- phase 2: trilinear gather (grid_sample_kernel's arithmetic), voxel j = (w, d) = (j >> 4, j & 15) -> 8 lanes x float4
+    // ---- phase 2: trilinear gather, voxel j = (w, d) = (j >> 4, j & 15) -> 8 lanes x float4
     const int cg = t & 7;
     const float* base = in + (long)n * in_sN + cg * 4;         // in_sN = 0: every sample warps the one shared volume (v2i)
 #pragma unroll 1
     for (int it = 0; it < 8; ++it) {
         const int j = it * 32 + (t >> 3), wl = j >> 4, d = j & 15;
         const float* g = defs + ((d << 4) | wl) * 3;
-        const float ix = ((g[0] + 1.f) * W - 1.f) * 0.5f, iy = ((g[1] + 1.f) * H - 1.f) * 0.5f, iz = ((g[2] + 1.f) * D - 1.f) * 0.5f;
-        const float fx = floorf(ix), fy = floorf(iy), fz = floorf(iz);
-        const int x0 = (int)fx, y0 = (int)fy, z0 = (int)fz;
-        const float tx = ix - fx, ty = iy - fy, tz = iz - fz;
-        float a[4] = {0.f, 0.f, 0.f, 0.f};
-        // all eight corners fetched back to back (clamped address, weight 0 outside: the same bits as skipping them; see dm_sparse_kernel)
-        float4 cv[8]; float wv[8];
-#pragma unroll
-        for (int dz = 0; dz < 2; ++dz)
-#pragma unroll
-            for (int dy = 0; dy < 2; ++dy)
-#pragma unroll
-                for (int dx = 0; dx < 2; ++dx) {
-                    const int xc = x0 + dx, yc = y0 + dy, zc = z0 + dz;
-                    const bool inb = (unsigned)xc < (unsigned)W && (unsigned)yc < (unsigned)H && (unsigned)zc < (unsigned)D;
-                    const float wgt = (dx ? tx : 1.f - tx) * (dy ? ty : 1.f - ty) * (dz ? tz : 1.f - tz);
-                    const int xq = min(max(xc, 0), W - 1), yq = min(max(yc, 0), H - 1), zq = min(max(zc, 0), D - 1);
-                    cv[dz * 4 + dy * 2 + dx] = *(const float4*)(base + (((long)yq * W + xq) * D + zq) * 32);
-                    wv[dz * 4 + dy * 2 + dx] = inb ? wgt : 0.f;
-                }
-#pragma unroll
-        for (int c8 = 0; c8 < 8; ++c8) {
-            a[0] = fmaf(wv[c8], cv[c8].x, a[0]); a[1] = fmaf(wv[c8], cv[c8].y, a[1]);
-            a[2] = fmaf(wv[c8], cv[c8].z, a[2]); a[3] = fmaf(wv[c8], cv[c8].w, a[3]);
-        }
-        const long vo = ((((long)n * H + y) * W + wb * 16 + wl) * D + d) * 32 + cg * 4;
-        if (out32) *(float4*)(out32 + vo) = make_float4(a[0], a[1], a[2], a[3]);
-        if (out16) {
-            h4_t o; o[0] = (half_t)a[0]; o[1] = (half_t)a[1]; o[2] = (half_t)a[2]; o[3] = (half_t)a[3];
-            *(h4_t*)(out16 + vo) = o;
-        }
+        float a[4];
+        trilinear4(a, base, g[0], g[1], g[2], D, H, W);
+        store_warped4(a, out32, out16, ((((long)n * H + y) * W + wb * 16 + wl) * D + d) * 32 + cg * 4);
     }
 }
 
 int launch_dm_softmax_warp(const float* part, const float* bias, const float* kp_d, const float* kp_s, const float* in, float* out32,
-                           half_t* out16, float* deform, int N, int D, int H, int W, hipStream_t st, int compact, bool shared_in, bool shared_kps)
+                           half_t* out16, float* deform, int N, int D, int H, int W, hipStream_t st, bool shared_in, bool shared_kps)
 {
     if (D != 16 || (W & 15)) { cs_set_error("dm_softmax_warp: depth 16 and a width that is a multiple of 16"); return -1; }
     hipLaunchKernelGGL(dm_softmax_warp_kernel, dim3((unsigned)((long)N * H * (W >> 4))), dim3(256), 0, st, part, bias, kp_d, kp_s, in,
-                       out32, out16, deform, N, D, H, W, compact, shared_in ? 0L : (long)H * W * D * 32, shared_kps ? 0 : 63);
+                       out32, out16, deform, N, D, H, W, shared_in ? 0L : (long)H * W * D * 32, shared_kps ? 0 : 63);
     LAUNCH_CHECK("dm_softmax_warp");
     return 0;
 }
@@ -566,12 +512,7 @@ __global__ void __launch_bounds__(256) grid_sample_kernel(const float* __restric
                                                           float* __restrict__ out32, half_t* __restrict__ out16, int N, int D, int H, int W, long in_sN)
 {
     const long total = (long)N * H * W * D * 8;
-    // XCD-aware block order: hardware places workgroup b on XCD b % 8 (each with its own L2); every XCD walks a contiguous eighth of the
-    // output, so the source lines that neighbouring output voxels share (the 8 corners of adjacent voxels overlap) are fetched into ONE
-    // L2 instead of up to eight (r02: 2.1x over-fetch on the read side, profiles/r02_i_pmc_summary.csv)
-    long blk = blockIdx.x;
-    if ((gridDim.x & 7) == 0) blk = (long)(blockIdx.x & 7) * (gridDim.x >> 3) + (blockIdx.x >> 3);
-    long i = blk * 256 + threadIdx.x;
+    const long i = xcd_block() * 256 + threadIdx.x;
     if (i >= total) return;
     const int cg = i & 7; long v = i >> 3;     // v: voxel index in HWDC order
     const int d = v % D; long r = v / D;
@@ -579,36 +520,9 @@ __global__ void __launch_bounds__(256) grid_sample_kernel(const float* __restric
     const int y = r % H;
     const int n = r / H;
     const float* g = grid + ((((long)n * D + d) * H + y) * W + x) * 3;
-    const float ix = ((g[0] + 1.f) * W - 1.f) * 0.5f, iy = ((g[1] + 1.f) * H - 1.f) * 0.5f, iz = ((g[2] + 1.f) * D - 1.f) * 0.5f;
-    const float fx = floorf(ix), fy = floorf(iy), fz = floorf(iz);
-    const int x0 = (int)fx, y0 = (int)fy, z0 = (int)fz;
-    const float tx = ix - fx, ty = iy - fy, tz = iz - fz;
-    float a[4] = {0.f, 0.f, 0.f, 0.f};
-    const float* base = in + (long)n * in_sN + cg * 4;
-    float4 cv[8]; float wv[8];           // all eight corners fetched back to back (see dm_sparse_kernel)
-#pragma unroll
-    for (int dz = 0; dz < 2; ++dz)
-#pragma unroll
-        for (int dy = 0; dy < 2; ++dy)
-#pragma unroll
-            for (int dx = 0; dx < 2; ++dx) {
-                const int xc = x0 + dx, yc = y0 + dy, zc = z0 + dz;
-                const bool inb = (unsigned)xc < (unsigned)W && (unsigned)yc < (unsigned)H && (unsigned)zc < (unsigned)D;
-                const float wgt = (dx ? tx : 1.f - tx) * (dy ? ty : 1.f - ty) * (dz ? tz : 1.f - tz);
-                const int xq = min(max(xc, 0), W - 1), yq = min(max(yc, 0), H - 1), zq = min(max(zc, 0), D - 1);
-                cv[dz * 4 + dy * 2 + dx] = *(const float4*)(base + (((long)yq * W + xq) * D + zq) * 32);
-                wv[dz * 4 + dy * 2 + dx] = inb ? wgt : 0.f;
-            }
-#pragma unroll
-    for (int c8 = 0; c8 < 8; ++c8) {
-        a[0] = fmaf(wv[c8], cv[c8].x, a[0]); a[1] = fmaf(wv[c8], cv[c8].y, a[1]);
-        a[2] = fmaf(wv[c8], cv[c8].z, a[2]); a[3] = fmaf(wv[c8], cv[c8].w, a[3]);
-    }
-    if (out32) *(float4*)(out32 + v * 32 + cg * 4) = make_float4(a[0], a[1], a[2], a[3]);
-    if (out16) {
-        h4_t o; o[0] = (half_t)a[0]; o[1] = (half_t)a[1]; o[2] = (half_t)a[2]; o[3] = (half_t)a[3];
-        *(h4_t*)(out16 + v * 32 + cg * 4) = o;
-    }
+    float a[4];
+    trilinear4(a, in + (long)n * in_sN + cg * 4, g[0], g[1], g[2], D, H, W);
+    store_warped4(a, out32, out16, v * 32 + cg * 4);
 }
 
 int launch_grid_sample(const float* in, const float* grid, float* out32, half_t* out16, int N, int D, int H, int W, hipStream_t st, bool shared_in)
@@ -824,11 +738,9 @@ int launch_norm_act(const float* y, const float* stats, const float* gamma, cons
 // ------------------------------------------------------------------------------------------------
 // API-boundary layout conversion (the reference passes fp32 NCDHW / NCHW tensors between stages)
 // ------------------------------------------------------------------------------------------------
-// fp32 NCDHW [N][C][D][H][W] -> fp32 HWDC (+ optional fp16 pre-activation copy act2(x*s2[c]+t2[c]))
+// fp32 NCDHW [N][C][D][H][W] -> fp32 HWDC (+ optional fp16 copy)
 __global__ void __launch_bounds__(256) ncdhw_to_hwdc_kernel(const float* __restrict__ in, float* __restrict__ out32,
-                                                            half_t* __restrict__ out16, const float* __restrict__ s2,
-                                                            const float* __restrict__ t2, int act2, float slope2, int N, int C, int D,
-                                                            int H, int W)
+                                                            half_t* __restrict__ out16, int N, int C, int D, int H, int W)
 {
     // tile: one (n, d, y) row: transpose [C][W] -> [W][C] through LDS
     __shared__ float tile[32][65];
@@ -845,19 +757,17 @@ __global__ void __launch_bounds__(256) ncdhw_to_hwdc_kernel(const float* __restr
                 const float v = tile[c][x];
                 const long o = ((((long)n * H + y) * W + x0 + x) * D + d) * C + c;
                 if (out32) out32[o] = v;
-                if (out16) out16[o] = (half_t)act_f(s2 ? v * s2[c] + t2[c] : v, act2, slope2);
+                if (out16) out16[o] = (half_t)v;
             }
         }
         __syncthreads();
     }
 }
 
-int launch_ncdhw_to_hwdc(const float* in, float* out32, half_t* out16, const float* s2, const float* t2, int act2, float slope2,
-                         int N, int C, int D, int H, int W, hipStream_t st)
+int launch_ncdhw_to_hwdc(const float* in, float* out32, half_t* out16, int N, int C, int D, int H, int W, hipStream_t st)
 {
     if (C != 32) { cs_set_error("ncdhw_to_hwdc: C must be 32"); return -1; }
-    hipLaunchKernelGGL(ncdhw_to_hwdc_kernel, dim3((unsigned)((long)N * D * H)), dim3(256), 0, st, in, out32, out16, s2, t2, act2, slope2,
-                       N, C, D, H, W);
+    hipLaunchKernelGGL(ncdhw_to_hwdc_kernel, dim3((unsigned)((long)N * D * H)), dim3(256), 0, st, in, out32, out16, N, C, D, H, W);
     LAUNCH_CHECK("ncdhw_to_hwdc");
     return 0;
 }
@@ -973,97 +883,29 @@ __device__ __forceinline__ float tm_dot8(const uint4& v, const uint4& q, float a
     a = __builtin_amdgcn_fdot2(__builtin_bit_cast(tm_h2, v.z), __builtin_bit_cast(tm_h2, q.z), a, false);
     return __builtin_amdgcn_fdot2(__builtin_bit_cast(tm_h2, v.w), __builtin_bit_cast(tm_h2, q.w), a, false);
 }
-// SEG: output columns a wave marches over (16; 4 for launches of fewer than 1024 waves - one or two frames -, where 64 x 4 waves of 18 dependent
-// column steps leave three quarters of the CUs idle: 10 -> 5 us per launch at one frame).  Per output the same sums in the same order: same bits.
-template <int SEG>
-__global__ void __launch_bounds__(256, 4) t_mask_kernel(const half_t* __restrict__ x, const half_t* __restrict__ wp, const float* __restrict__ bias,
-                                                        float* __restrict__ tmask, int N, int H, int W)
+// SEG: output columns a wave marches over; RH: output rows it owns.
+// RH = 1, SEG = 16 is the form described above; SEG = 4 for launches of fewer than 1024 waves - one or two frames -, where 64 x 4 waves of 18
+// dependent column steps leave three quarters of the CUs idle: 10 -> 5 us per launch at one frame.
+// RH = 4, SEG = 8 is the form with vertical reuse for launches of many frames: a wave marches over the columns of its RH + 2 input rows, so a
+// fetched 16 bytes feed up to nine dot products instead of three and the read out of the L2 per output drops from 3 x 18 / 16 = 3.4 KiB to
+// (RH + 2) / RH x (SEG + 2) / SEG = 1.9 KiB: with RH = 1 the kernel runs at the L2's rate (10.5 TB/s of reads at 64 frames; more columns in
+// flight made it slower, profiles/r06_v_dec_phases.txt).
+// Per output every instance forms the same dot products in the same order (column by column, kh ascending within a column; the lanes'
+// partial sums reduced the same way): the same bits, so that the launcher may choose by launch size (tests/test_gpu_ops.py).
+template <int SEG, int RH>
+__global__ void __launch_bounds__(256, RH == 1 ? 4 : 2) t_mask_kernel(const half_t* __restrict__ x, const half_t* __restrict__ wp, const float* __restrict__ bias,
+                                                                      float* __restrict__ tmask, int N, int H, int W)
 {
     constexpr int RS = 65;                                  // LDS row stride 65 floats: the reduction's reads are conflict-free
-    __shared__ float part[4][SEG * RS];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int nseg = W / SEG;
-    // XCD-aware order: hardware places workgroup b on XCD b % 8; every XCD walks a contiguous range of rows (the three input rows of
-    // neighbouring output rows are then fetched into one L2)
-    long blk = blockIdx.x;
-    if ((gridDim.x & 7) == 0) blk = (long)(blockIdx.x & 7) * (gridDim.x >> 3) + (blockIdx.x >> 3);
-    const long item = blk * 4 + wave;                       // (n, h, segment); the launcher makes the item count a multiple of 4
-    const int sg = (int)(item % nseg); long r = item / nseg;
-    const int h = (int)(r % H);
-    const int n = (int)(r / H);
-    const int w0 = sg * SEG;
-    // this lane's weights: tap t, channels lane * 8 .. + 7 = packed chunk j = lane / 4, k = (lane % 4) * 8
-    uint4 wt[9];
-#pragma unroll
-    for (int t = 0; t < 9; ++t) wt[t] = *(const uint4*)(wp + ((long)((lane >> 2) * 9 + t) * 16) * 32 + (lane & 3) * 8);
-    const half_t* xb = x + (long)n * H * W * 512 + lane * 8;
-    const bool hok0 = h > 0, hok2 = h + 1 < H;
-    const long r0 = (long)(hok0 ? h - 1 : h) * W, r1 = (long)h * W, r2 = (long)(hok2 ? h + 1 : h) * W;
-    auto fetch = [&](int c, uint4 (&v)[3]) {               // input column w0 - 1 + c of the three rows (zero outside the map)
-        const int wi = w0 - 1 + c;
-        const bool cin = (unsigned)wi < (unsigned)W;
-        const int wq = cin ? wi : w0;
-        v[0] = *(const uint4*)(xb + (r0 + wq) * 512);
-        v[1] = *(const uint4*)(xb + (r1 + wq) * 512);
-        v[2] = *(const uint4*)(xb + (r2 + wq) * 512);
-        const uint4 z = make_uint4(0u, 0u, 0u, 0u);
-        if (!cin || !hok0) v[0] = z;
-        if (!cin) v[1] = z;
-        if (!cin || !hok2) v[2] = z;
-    };
-    // rolling accumulators: a2 = output c (kw = 0 so far), a1 = output c - 1, a0 = output c - 2 (complete after this column)
-    float a0 = 0.f, a1 = 0.f, a2 = 0.f;
-    uint4 cur[3], nxt[3];
-    fetch(0, cur);
-#pragma unroll 2
-    for (int c = 0; c < SEG + 2; ++c) {
-        if (c + 1 < SEG + 2) fetch(c + 1, nxt);
-#pragma unroll
-        for (int kh = 0; kh < 3; ++kh) {
-            a2 = tm_dot8(cur[kh], wt[kh * 3 + 0], a2);
-            a1 = tm_dot8(cur[kh], wt[kh * 3 + 1], a1);
-            a0 = tm_dot8(cur[kh], wt[kh * 3 + 2], a0);
-        }
-        if (c >= 2) part[wave][(c - 2) * RS + lane] = a0;
-        a0 = a1; a1 = a2; a2 = 0.f;
-#pragma unroll
-        for (int k = 0; k < 3; ++k) cur[k] = nxt[k];
-    }
-    __builtin_amdgcn_s_waitcnt(0xc07f);                    // lgkmcnt(0): the wave's own LDS writes (no other wave reads them)
-    // lane = output o (lane / 4), quarter q of the 64 channel lanes: 16 partials in a fixed order, then the four quarters
-    const int o = lane >> 2, q = lane & 3;
-    float sum = 0.f;
-#pragma unroll
-    for (int i = 0; i < 16; ++i) sum += part[wave][(o < SEG ? o : 0) * RS + q * 16 + i];
-    sum += __shfl_xor(sum, 1, 64);
-    sum += __shfl_xor(sum, 2, 64);
-    if (q == 0 && o < SEG) {
-        const float y = sum + bias[0];
-        tmask[(((long)n * H + h) * W + w0 + o) * 4] = 1.f / (1.f + __expf(-y));
-    }
-}
-
-// The same layer with vertical reuse for launches of many frames: a wave owns RH output rows of a SEG-column segment and marches over the columns
-// of its RH + 2 input rows, so a fetched 16 bytes feed up to nine dot products instead of three and the read out of the L2 per output drops from
-// 3 x 18 / 16 = 3.4 KiB to (RH + 2) / RH x (SEG + 2) / SEG = 1.9 KiB (RH = 4, SEG = 8): t_mask_kernel runs at the L2's rate (10.5 TB/s of reads at
-// 64 frames; more columns in flight made it slower, profiles/r06_v_dec_phases.txt).  Per output the same dot products in the same order as in
-// t_mask_kernel (column by column, kh ascending within a column; the lanes' partial sums reduced the same way): the same bits, so that the
-// launcher may choose by launch size (tests/test_gpu_ops.py).
-template <int SEG, int RH>
-__global__ void __launch_bounds__(256, 2) t_mask_rows_kernel(const half_t* __restrict__ x, const half_t* __restrict__ wp, const float* __restrict__ bias,
-                                                             float* __restrict__ tmask, int N, int H, int W)
-{
-    constexpr int RS = 65;
     __shared__ float part[4][RH][SEG * RS];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int nseg = W / SEG, nhb = H / RH;
-    long blk = blockIdx.x;
-    if ((gridDim.x & 7) == 0) blk = (long)(blockIdx.x & 7) * (gridDim.x >> 3) + (blockIdx.x >> 3);
-    const long item = blk * 4 + wave;
+    const long item = xcd_block() * 4 + wave;               // (n, row block, segment); the launcher makes the item count a multiple of 4
     const int sg = (int)(item % nseg); long r = item / nseg;
     const int h0 = (int)(r % nhb) * RH;
     const int n = (int)(r / nhb);
     const int w0 = sg * SEG;
+    // this lane's weights: tap t, channels lane * 8 .. + 7 = packed chunk j = lane / 4, k = (lane % 4) * 8
     uint4 wt[9];
 #pragma unroll
     for (int t = 0; t < 9; ++t) wt[t] = *(const uint4*)(wp + ((long)((lane >> 2) * 9 + t) * 16) * 32 + (lane & 3) * 8);
@@ -1085,6 +927,7 @@ __global__ void __launch_bounds__(256, 2) t_mask_rows_kernel(const half_t* __res
 #pragma unroll
         for (int i = 0; i < RH + 2; ++i) if (!cin || !rok[i]) v[i] = z;
     };
+    // rolling accumulators per output row: a2 = output c (kw = 0 so far), a1 = output c - 1, a0 = output c - 2 (complete after this column)
     float a0[RH], a1[RH], a2[RH];
 #pragma unroll
     for (int j = 0; j < RH; ++j) { a0[j] = 0.f; a1[j] = 0.f; a2[j] = 0.f; }
@@ -1108,6 +951,7 @@ __global__ void __launch_bounds__(256, 2) t_mask_rows_kernel(const half_t* __res
         for (int k = 0; k < RH + 2; ++k) cur[k] = nxt[k];
     }
     __builtin_amdgcn_s_waitcnt(0xc07f);                    // lgkmcnt(0): the wave's own LDS writes (no other wave reads them)
+    // lane = output o (lane / 4), quarter q of the 64 channel lanes: 16 partials in a fixed order, then the four quarters
     const int o = lane >> 2, q = lane & 3;
 #pragma unroll
     for (int j = 0; j < RH; ++j) {
@@ -1130,17 +974,14 @@ int launch_t_mask(const half_t* x, const half_t* wpacked, const float* bias, flo
     if (W % 16 != 0 || ((uintptr_t)x & 15) || ((uintptr_t)wpacked & 15)) { cs_set_error("t_mask: width a multiple of 16, 16-byte aligned tensors"); return -1; }
     const long items = (long)N * H * (W / 16);
     if (items % 4 != 0) { cs_set_error("t_mask: N * H * W / 16 must be a multiple of 4"); return -1; }
-    // (the segment length may depend on N: it does not change a bit of the result, tests/test_gpu_ops.py)
-    // from four frames of a 64 x 64 map up: 4 output rows x 8 columns per wave (the same bits; 76 -> 58 us per 64-frame launch, and faster at
+    // (the instance may depend on N: it does not change a bit of the result, tests/test_gpu_ops.py)
+    // from four frames of a 64 x 64 map up: 4 output rows x 8 columns per wave (76 -> 58 us per 64-frame launch, and faster at
     // 4, 8, 16 and 32 frames too: profiles/r06_x_t_mask_rows.txt)
     const long ritems = (long)N * (H / 4) * (W / 8);
-    if (items >= 1024 && H % 4 == 0 && W % 8 == 0 && ritems % 4 == 0) {
-        hipLaunchKernelGGL((t_mask_rows_kernel<8, 4>), dim3((unsigned)(ritems / 4)), dim3(256), 0, st, x, wpacked, bias, tmask, N, H, W);
-        LAUNCH_CHECK("t_mask_rows");
-        return 0;
-    }
-    if (items < 1024) hipLaunchKernelGGL(t_mask_kernel<4>, dim3((unsigned)items), dim3(256), 0, st, x, wpacked, bias, tmask, N, H, W);
-    else hipLaunchKernelGGL(t_mask_kernel<16>, dim3((unsigned)cdiv(items, 4)), dim3(256), 0, st, x, wpacked, bias, tmask, N, H, W);
+    if (items >= 1024 && H % 4 == 0 && W % 8 == 0 && ritems % 4 == 0)
+        hipLaunchKernelGGL((t_mask_kernel<8, 4>), dim3((unsigned)(ritems / 4)), dim3(256), 0, st, x, wpacked, bias, tmask, N, H, W);
+    else if (items < 1024) hipLaunchKernelGGL((t_mask_kernel<4, 1>), dim3((unsigned)items), dim3(256), 0, st, x, wpacked, bias, tmask, N, H, W);
+    else hipLaunchKernelGGL((t_mask_kernel<16, 1>), dim3((unsigned)cdiv(items, 4)), dim3(256), 0, st, x, wpacked, bias, tmask, N, H, W);
     LAUNCH_CHECK("t_mask");
     return 0;
 }
@@ -1230,23 +1071,6 @@ int launch_unpack_u8(const uint8_t* in, float* out, int N, int C, int H, int W, 
 {
     hipLaunchKernelGGL(unpack_u8_kernel, dim3(cdiv((long)N * H * W, 256)), dim3(256), 0, st, in, out, N, C, H, W);
     LAUNCH_CHECK("unpack_u8");
-    return 0;
-}
-
-__global__ void __launch_bounds__(256) lrelu16_kernel(const half_t* __restrict__ in, half_t* __restrict__ out, long n8, float slope)
-{
-    const long i = (long)blockIdx.x * 256 + threadIdx.x;
-    if (i >= n8) return;
-    h8_t v = ((const h8_t*)in)[i];
-#pragma unroll
-    for (int j = 0; j < 8; ++j) { const float f = (float)v[j]; v[j] = (half_t)(f > 0.f ? f : f * slope); }
-    ((h8_t*)out)[i] = v;
-}
-
-int launch_lrelu16(const half_t* in, half_t* out, long n, float slope, hipStream_t st)
-{
-    hipLaunchKernelGGL(lrelu16_kernel, dim3(cdiv(n / 8, 256)), dim3(256), 0, st, in, out, n / 8, slope);
-    LAUNCH_CHECK("lrelu16");
     return 0;
 }
 

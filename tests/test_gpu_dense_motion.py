@@ -330,10 +330,12 @@ def _column_classes(Ww):
     return cls
 
 
-@pytest.mark.parametrize("shape", [(1, 16, 64, 64), (2, 16, 24, 48)], ids=lambda s: "x".join(map(str, s)))
+@pytest.mark.parametrize("shape", [(1, 16, 64, 64), (2, 16, 24, 48), (1, 16, 3, 16)], ids=lambda s: "x".join(map(str, s)))
 @pytest.mark.parametrize("pattern", ["ordinary", "dominant", "equal", "negative"])
 def test_dm_softmax_warp(shape, pattern):
-    """compact-2 hand-over -> softmax -> deformation -> warp, per column class (x mod 4 and the three border columns on each side)."""
+    """compact-2 hand-over -> softmax -> deformation -> warp, per column class (x mod 4 and the three border columns on each side).
+    (1, 16, 3, 16) is 3 workgroups: the block walk of a grid that is no multiple of 8 (the other shapes' grids are).  The stand-alone
+    gather (grid_sample_kernel) fed the kernel's own deformation gives the fused kernel's bits: one function behind both."""
     N, D, Hh, Ww = shape
     P, bias, kd, ks = _logit_case(pattern, N, D, Hh, Ww, 10 + Ww)
     part = H.compact2(P).float()
@@ -358,6 +360,8 @@ def test_dm_softmax_warp(shape, pattern):
         # measured: deformation 1.1e-6 (all logits near -400), warp fp32 5.5e-6 (the fp32 sampling point), fp16 4.2e-4 (storage)
         _gate(f"dm_softmax_warp {shape} {pattern} {what} (worst class {w})", errs[w][i], (4e-6, 2e-5, 1.8e-3)[i])
     assert torch.equal(o16, o32.half())
+    g32, g16 = H.grid_sample(inp.cuda(), de.cuda())
+    assert torch.equal(g32.cpu(), o32) and torch.equal(g16.cpu(), o16)
 
 
 @pytest.mark.parametrize("shared", ["in", "kps", "both"])

@@ -460,11 +460,11 @@ def test_t_mask_segment_length_does_not_change_bits():
 
 
 def test_t_mask_16_column_segments():
-    """N = 2, H = 66, W = 128: 1056 items and H % 4 != 0, so launch_t_mask takes t_mask_kernel<16> (no 64 x 64 launch reaches it: from 1024 items
-    up those go to t_mask_rows_kernel).  Against float64 of the fp16 operands at a derived bound: along any path to an output lie 36 fdot2 (two
+    """N = 2, H = 66, W = 128: 1056 items and H % 4 != 0, so launch_t_mask takes t_mask_kernel<16, 1> (no 64 x 64 launch reaches it: from 1024 items
+    up those go to t_mask_kernel<8, 4>).  Against float64 of the fp16 operands at a derived bound: along any path to an output lie 36 fdot2 (two
     roundings each at most), 16 sequential adds, 2 exchanges and the bias, 91 roundings: |dy| <= 91 u sum |x w|, u = 2^-24; the sigmoid's slope is at
     most 1/4, and 8 u cover __expf and the division on a result below 1.  Per output the bits of the other two instantiations: each sample
-    alone (528 items: <4>), and the same maps with two zero rows appended (H = 68: t_mask_rows_kernel; explicit zero rows are the zero padding)."""
+    alone (528 items: <4, 1>), and the same maps with two zero rows appended (H = 68: <8, 4>; explicit zero rows are the zero padding)."""
     import hip_ops as ops
     r = _rng(7766)
     N, H, W = 2, 66, 128

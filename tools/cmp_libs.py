@@ -1,5 +1,6 @@
 """GPU box: the same frames through two builds of the library, compared bit for bit (stage outputs of the whole loop body, default and latency mode,
-the motion extractor's raw head outputs, and the crop / warp / paste-back entry points on 1080p frames):
+W's own entry points - warp, warp_forward, animate_frames on one shared volume -, the motion extractor's raw head outputs, and the crop / warp /
+paste-back entry points on 1080p frames); the environment (an A/B knob such as CANONSWAP_WARP_FUSED=0) reaches both children:
     python tools/cmp_libs.py tools/bin/base.so ""        ("" = the shipped library)
 Each build runs in its own process (the library is chosen at import: CANONSWAP_LIB)."""
 import os
@@ -26,6 +27,16 @@ for lat in (False, True):
     for k, v in r.items():
         if torch.is_tensor(v):
             out[("lat." if lat else "") + k] = v.cpu()
+    if not lat:
+        # W's entry points beyond the loop body, on the same engine: cs_warp (f_out and occ), cs_warp_forward (the fused kernel also stores its
+        # deformation), cs_animate_frames with ONE volume and ONE source key-point set for 3 frames (sample stride 0 in dm_sparse and in the
+        # softmax / warp kernels)
+        e, (img, kd, ks) = sw.engine, (a[:3] for a in args)
+        f = e.extract_feature_3d(img)
+        out["engine.warp.f_out"], out["engine.warp.occ"] = (t.cpu() for t in e.warp(f, ks, kd))
+        for k, v in e.warp_forward(f, kd, ks).items():
+            out["engine.warp_forward." + k] = v.cpu()
+        out["engine.animate_frames.shared"] = e.animate_frames(f[:1], ks[:1], kd)["out"].cpu()
 sdm = synth.to_torch(synth.make_state_dicts(0, modules=synth.MODULES + ("motion_extractor",)))
 swm = can_swapper(None, state_dicts=sdm, max_batch=5)
 out["M.raw"] = swm.engine.motion_extract_raw(torch.from_numpy(synth.make_smooth_images(5, seed=77, size=256)).cuda()).cpu()
