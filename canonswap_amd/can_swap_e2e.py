@@ -206,6 +206,9 @@ class can_swapper(object):
     def paste_back_fused(self, img_crop, mask_crop, M_c2o, img_ori):
         return tail.paste_back_fused(self.engine, img_crop, mask_crop, M_c2o, img_ori)
 
+    def face_masks(self, logits, **kw):                                                 # can_swap_pipeline_e2e.py:183-190: logits -> 0/1 masks
+        return tail.face_masks(self.engine, logits, **kw)
+
     def crop_frames(self, frames, lmk, **kw):                                           # crop.py:429-455 of B frames (cropper.py:196-204)
         return tail.crop_frames(self.engine, frames, lmk, **kw)
 

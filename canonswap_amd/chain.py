@@ -11,17 +11,21 @@ the generator).
                               [seven tensors to the host and back per frame]
     :242-263  F -> warp -> T -> R -> warp_decode                               cs_swap_frames_ids
     :267      parse_output [sync + D2H]                                        (pack_u8 inside cs_swap_frames_ids)
+    :183-190  F.interpolate(logits, 512 x 512) -> argmax -> isin               cs_face_masks (with logits=: the parser's logits go in as they
+                              [19.9 MB of up-sampled logits per frame]          are; with masks: the caller has run these lines)
     :274      soft_mask(masks[i]) [D2H]                                        cs_soft_erosion_frames
     :279-282  prepare_paste_back + paste_back (two cv2.warpAffine) [host]      cs_paste_back_batch
 
-The loop of a caller:  c = chain.crop(frames, lmk);  masks = <the caller's parser on c["crops"]>;
-frames_out = chain(c["crops"], masks, c["M_c2o"], frames, source_id)["frames"].
+The loop of a caller:  c = chain.crop(frames, lmk);  logits = <the caller's parser on c["crops"]>, (B,19,128,128);
+frames_out = chain(c["crops"], None, c["M_c2o"], frames, source_id, logits=logits)["frames"]
+(or, with 0/1 masks the caller has made of them: chain(c["crops"], masks, c["M_c2o"], frames, source_id)).
 
 AnimateChain below is the same for the second program, inference_v2i.py (src/can_swap_pipeline_v2i.py: one source image animated by a
 driving video, the driving identity swapped in); its table stands in the class's docstring.
 
 What stays outside (out of scope): face detection and the landmark network (they produce the landmarks), SegFormer
-face parsing (it produces the 0/1 masks), video decode / encode.
+face parsing (the network and its image processor: it produces the logits; what the pipelines do with them is cs_face_masks), video decode /
+encode.
 """
 from __future__ import annotations
 
@@ -36,8 +40,10 @@ class _StagedChain:
     subclass's own: everything the generator needs from the crops) runs in-line on the caller's stream, or ahead of time on a side stream
     into one half of a double buffer.  Every stream-ordering rule of FrameChain and AnimateChain stands here, once."""
 
-    def __init__(self, swapper, kernel_size, threshold, iterations):
+    def __init__(self, swapper, kernel_size, threshold, iterations, valid):
         self.sw = swapper
+        tail.valid_bits(valid)                                        # raises on a class id the mask word cannot hold
+        self.valid = tuple(valid)
         self.e: Engine = swapper.engine
         if swapper.motion_extractor is None:
             raise RuntimeError(f"{type(self).__name__}: the loaded weights hold no 'motion_extractor' state-dict")
@@ -61,6 +67,12 @@ class _StagedChain:
 
     def _check_stageable(self):
         """Raises where stage A cannot run yet (AnimateChain: no source)."""
+
+    @staticmethod
+    def _mask_or_logits(masks, logits, who):
+        """The parser's result comes as 0/1 masks or as logits (tail.face_masks makes the masks of them), never both, never neither."""
+        if (masks is None) == (logits is None):
+            raise ValueError(f"{who}: pass either masks or logits=" + (", not both" if masks is not None else " (got neither)"))
 
     def _stage_ahead(self, crops_u8, *args):
         """prefetch() of both chains: _stage_a(crops_u8, *args, slot) on the side stream, into the half of the double buffer no staged
@@ -114,8 +126,8 @@ class _StagedChain:
 class FrameChain(_StagedChain):
     """chain = FrameChain(swapper);  frames = chain(crops_u8, masks, M_c2o, frames_ori, source_id)["frames"]"""
 
-    def __init__(self, swapper, kernel_size: int = 21, threshold: float = 0.9, iterations: int = 3):
-        super().__init__(swapper, kernel_size, threshold, iterations)      # SoftErosion(21, 0.9, 3): can_swap_pipeline_e2e.py:42
+    def __init__(self, swapper, kernel_size: int = 21, threshold: float = 0.9, iterations: int = 3, valid=tail.FACE_VALID):
+        super().__init__(swapper, kernel_size, threshold, iterations, valid)      # SoftErosion(21, 0.9, 3): can_swap_pipeline_e2e.py:42; valid_list :189
 
     def keypoints(self, I, slot=0):
         """(B,3,256,256) fp32 -> x_t, x_can (B,21,3): make_motion_template's get_kp_info + transform_keypoint and the loop's
@@ -126,31 +138,37 @@ class FrameChain(_StagedChain):
 
     # ---- stage A: everything the generator needs from a batch of crops (input staging + motion extractor).  The reference runs it as a
     # pre-pass over the whole video (prepare_videos + make_motion_template, can_swap_pipeline_e2e.py:196-197) before the swapping loop
-    # ... and the soft mask, which depends on the parser's labels only (:274)
-    def _stage_a(self, crops_u8, masks, slot):
+    # ... and the soft mask, which depends on the parser's labels only (:274); given the logits, the labels' mask first (:183-190)
+    def _stage_a(self, crops_u8, masks, logits, slot):
         t = torch.as_tensor(crops_u8)
         B = t.shape[0] if t.dim() == 4 else 1
         I = tail.prepare_crops(self.e, t, out=self._get(("I", slot), (B, 3, 256, 256), torch.float32))      # cropper.py:209 + can_swap_e2e.py:147-163
         x_t, x_can = self.keypoints(I, slot)                                                              # can_swap_pipeline_e2e.py:111-125, 243
-        m = torch.as_tensor(masks)
+        if logits is not None:
+            m = tail.face_masks(self.e, logits, self.valid, out=self._get(("mask", slot), (B, 512, 512), torch.uint8))
+        else:
+            m = torch.as_tensor(masks)
         soft = tail.soft_erosion_frames(self.e, m, self.se.weight, self.se.kernel_size, self.se.threshold, self.se.iterations,
                                         out=self._get(("soft", slot), (B,) + tuple(m.shape[-2:]), torch.float32))      # :274
         return I, x_t, x_can, soft
 
-    def prefetch(self, crops_u8, masks):
-        """Stage A of the NEXT batch on a side stream, so that it runs beside the generator of the current one (M and the staging are
-        bandwidth / latency bound, the generator is matrix-pipe bound): call it before __call__ of the current batch; the next __call__ with
+    def prefetch(self, crops_u8, masks=None, logits=None):
+        """Stage A of the NEXT batch on a side stream (masks or logits= as in __call__), so that it runs beside the generator of the current one
+        (M and the staging are bandwidth / latency bound, the generator is matrix-pipe bound): call it before __call__ of the current batch; the next __call__ with
         the same crops tensor picks the result up (the soft masks of that batch included: they depend on the parser's labels only).  M's workspace is its own, the batch's inputs land in the other half of a double buffer.
         Staged batches may be run in any order.  Not on a latency-mode engine: there every small plain conv (M's and the generator's
         alike) runs split-K on the engine's one partial-sum buffer, which M on the side stream and the generator would share."""
-        self._stage_ahead(crops_u8, masks)
+        self._mask_or_logits(masks, logits, "FrameChain.prefetch")
+        self._stage_ahead(crops_u8, masks, logits)
 
-    def __call__(self, crops_u8, masks, M_c2o, frames_ori, source_id=None, slots=None, out=None, keep=False):
-        """crops_u8 (B,512,512,3) or (B,256,256,3) u8; masks (B,512,512) u8 0/1 or fp32 (the parser's `torch.isin(labels, valid)`);
+    def __call__(self, crops_u8, masks, M_c2o, frames_ori, source_id=None, slots=None, out=None, keep=False, logits=None):
+        """crops_u8 (B,512,512,3) or (B,256,256,3) u8; masks (B,512,512) u8 0/1 or fp32 (the parser's `torch.isin(labels, valid)`), or None
+        with logits= (B,C,128,128), (B,C,256,256) or (B,C,512,512) fp32: the parser's logits, masked here (tail.face_masks with the chain's valid);
         M_c2o (B,2,3)/(B,3,3) host; frames_ori (B,Ho,Wo,3) u8; source_id (1,512)/(B,512) or identity slots.
         -> {"frames": (B,Ho,Wo,3) u8[, "crops_out", "x_t", "x_can", "soft_mask" with keep=True]}"""
         e = self.e
-        slot, (I, x_t, x_can, soft) = self._resolve(crops_u8, masks)
+        self._mask_or_logits(masks, logits, "FrameChain")
+        slot, (I, x_t, x_can, soft) = self._resolve(crops_u8, masks, logits)
         B = I.shape[0]
         gen = e.swap_frames(I, x_t, x_can, source_id, want_f32=False, want_u8=True, slots=slots,
                             out_u8=self._get("gen", (B, 512, 512, 3), torch.uint8))["out_u8"]   # :242-267
@@ -176,6 +194,7 @@ class AnimateChain(_StagedChain):
         :294      F.interpolate(swap_can, (256, 256), bilinear)                    cs_resize_half_bilinear
         :297-298  get_kp_info + transform_keypoint of swap_can_256                 cs_motion_extract + cs_motion_keypoints
         :308      extract_feature_3d(swap_can_256), there once per frame           cs_extract_feature_3d, once (loop-invariant)
+        :76-83    F.interpolate(logits, 512 x 512) -> argmax -> isin               cs_face_masks (set_source(..., logits=))
         :255-258  soft_mask + prepare_paste_back [D2H, cv2.warpAffine]             cs_soft_erosion_frames + cs_warp_affine_f32
         per driving frame                                                          __call__
         :223-238  cv2.resize + prepare_videos + make_motion_template [seven tensors D2H]   cs_prepare_crops + cs_motion_extract
@@ -187,14 +206,15 @@ class AnimateChain(_StagedChain):
     196-204): `c = chain.crop(img[None], lmk)`, then `set_source(c["crops"][0], mask, c["M_c2o"][0], img, driving_id)`.  Outside: everything
     FrameChain leaves outside, getid (the driving identity is passed in) and concat_frames."""
 
-    def __init__(self, swapper, kernel_size: int = 21, threshold: float = 0.9, iterations: int = 2):
-        super().__init__(swapper, kernel_size, threshold, iterations)      # SoftErosion(21, 0.9, 2): can_swap_pipeline_v2i.py:43
+    def __init__(self, swapper, kernel_size: int = 21, threshold: float = 0.9, iterations: int = 2, valid=tail.FACE_VALID):
+        super().__init__(swapper, kernel_size, threshold, iterations, valid)      # SoftErosion(21, 0.9, 2): can_swap_pipeline_v2i.py:43; valid_list :82
         self._src = None                                              # source_state()
 
     # ---- once per (source image, driving identity)
-    def set_source(self, crop_u8, mask, M_c2o, img_ori, driving_id):
+    def set_source(self, crop_u8, mask, M_c2o, img_ori, driving_id, logits=None):
         """crop_u8 (512,512,3) or (256,256,3) u8: the cropper's crop of the source image; mask (Hm,Wm) u8 0/1 or fp32: the parser's
-        `torch.isin(labels, valid)` of that crop; M_c2o 2x3 / 3x3 host, crop -> image; img_ori (Ho,Wo,3) u8; driving_id (1,512).
+        `torch.isin(labels, valid)` of that crop, or None with logits= (C,h,w) / (1,C,h,w): the parser's logits of that crop (:76-83 run
+        here); M_c2o 2x3 / 3x3 host, crop -> image; img_ori (Ho,Wo,3) u8; driving_id (1,512).
         Everything on the device, on the caller's stream.  -> {"I_can" (512,512,3) u8, "swap_can" (1,3,512,512), "x_swap", "x_s" (1,21,3)}"""
         e = self.e
         self.drop_prefetches()                                                       # staged key-points were formed with the old kp_swap / pose
@@ -202,7 +222,14 @@ class AnimateChain(_StagedChain):
         if ori.dtype != torch.uint8 or ori.dim() != 3 or ori.shape[2] != 3:
             raise ValueError("img_ori: expected ONE HoxWox3 uint8 image")
         ori = ori.to(e.device).contiguous()
-        m = torch.as_tensor(mask)
+        self._mask_or_logits(mask, logits, "AnimateChain.set_source")
+        if logits is not None:
+            lg = torch.as_tensor(logits)
+            if lg.dim() not in (3, 4) or (lg.dim() == 4 and lg.shape[0] != 1):
+                raise ValueError("logits: expected ONE (C, h, w) set of logits of the crop")
+            m = tail.face_masks(e, lg, self.valid)[0]                                # :76-83
+        else:
+            m = torch.as_tensor(mask)
         if m.dim() != 2:
             raise ValueError("mask: expected ONE (H, W) mask in the crop's frame")
         M = tail._m6(M_c2o)[0].copy()                                                # not the caller's array

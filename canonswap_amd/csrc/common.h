@@ -249,6 +249,8 @@ int launch_resize_half(const float* in, float* out, long planes, int H, int W, h
 int launch_paste_shared(const unsigned char* crops, int Hc, int Wc, const float* mask_ori, const double M[6], const unsigned char* ori,
                         unsigned char* outs, int B, int Ho, int Wo, hipStream_t st);
 int launch_crop_batch(const unsigned char* frames, int Ho, int Wo, const double* M, int dsize, unsigned char* crops, float* I, int B, hipStream_t st);
+int launch_face_masks(const float* logits, int B, int C, int h, int w, int scale, unsigned valid_bits, unsigned char* masks, unsigned char* labels,
+                      hipStream_t st);
 
 // ---- motion extractor pieces (motion.hip)
 int launch_m_keypoints(const float* raw, float* x_t, float* x_can, float* rot, int N, hipStream_t st);

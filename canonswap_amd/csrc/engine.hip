@@ -22,7 +22,7 @@ void cs_set_error(const char* fmt, ...)
     va_end(ap);
 }
 extern "C" const char* cs_last_error(void) { return g_err; }
-// 4, unchanged: cs_resize_half_bilinear, cs_motion_keypoints_driven, cs_paste_back_shared (the v2i device-side frame) and cs_crop_frames (the crop in front of both chains) were added; new entry points
+// 4, unchanged: cs_resize_half_bilinear, cs_motion_keypoints_driven, cs_paste_back_shared (the v2i device-side frame) cs_crop_frames (the crop in front of both chains) and cs_face_masks (the parser's logits -> 0/1 masks) were added; new entry points
 // alone change no struct, no existing entry point's meaning and no blob format, which is what the header bumps the version for.
 // 4 (round 6): cs_soft_erosion_frames, cs_paste_back_batch, cs_motion_keypoints.
 // 3 (round 4): cs_conv_desc grew (hilo, stat_out, xf_*, ep_general), cs_op_conv takes conv_halo / vol32 / conv_wide configurations only, the
@@ -1739,6 +1739,20 @@ extern "C" int cs_crop_frames(cs_engine* e, int B, const uint8_t* frames, int Ho
     DevGuard guard(e->dev);
     hipStream_t st = (hipStream_t)stream;
     return e->run(1, st, [&] { return launch_crop_batch(frames, Ho, Wo, M_o2c, dsize, crops, I_out, B, st); }, "crop_frames");
+}
+
+// ---- the face mask from the parser's logits (can_swap_pipeline_e2e.py:183-190, can_swap_pipeline_v2i.py:76-83)
+extern "C" int cs_face_masks(cs_engine* e, int B, int C, const float* logits, int h, int w, int scale, uint32_t valid_bits, uint8_t* masks,
+                             uint8_t* labels, void* stream)
+{
+    if (!e || !logits) { cs_set_error("cs_face_masks: bad arguments"); return -1; }
+    if (scale != 1 && scale != 2 && scale != 4) { cs_set_error("cs_face_masks: scale %d (1, 2 and 4 are built)", scale); return -1; }
+    if (C < 1 || C > 32) { cs_set_error("cs_face_masks: %d classes outside [1, 32]", C); return -1; }
+    if (B < 1 || h < 1 || w < 1) { cs_set_error("cs_face_masks: B = %d, h = %d, w = %d (each at least 1)", B, h, w); return -1; }
+    if (!masks && !labels) { cs_set_error("cs_face_masks: both outputs are NULL"); return -1; }
+    DevGuard guard(e->dev);
+    hipStream_t st = (hipStream_t)stream;
+    return e->run(1, st, [&] { return launch_face_masks(logits, B, C, h, w, scale, valid_bits, masks, labels, st); }, "face_masks");
 }
 
 extern "C" int cs_profile_begin(cs_engine* e)

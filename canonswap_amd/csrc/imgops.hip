@@ -668,3 +668,137 @@ int launch_crop_batch(const unsigned char* frames, int Ho, int Wo, const double*
         return 0;
     });
 }
+
+// ---------------------------------------------------------------------------------------------- face mask from the parser's logits
+// The torch lines between SegFormer and SoftErosion (can_swap_pipeline_e2e.py:183-190, can_swap_pipeline_v2i.py:76-83) in one launch for B frames:
+//   up = F.interpolate(logits, size=(S h, S w), mode="bilinear", align_corners=False);  labels = up.argmax(1);  mask = isin(labels, valid)
+// The up-sampled logits exist in registers only.  A thread owns the S x S output pixels of ONE source cell (yc, xc), aligned to it, and walks the
+// classes with S x S running maxima and labels.  Output column S xc + k has the source coordinate src = (S xc + k + 0.5) / S - 0.5 clamped below at 0,
+// i0 = floor(src), i1 = min(i0 + 1, w - 1), l1 = src - i0, l0 = 1 - l1 (exact in fp32 for S = 1, 2, 4): i0 is xc - 1 for k < S / 2 and xc otherwise,
+// so per class the block reads the 3 x 3 cells about (yc, xc), indices clamped to the plane, and takes taps (TAP0(k), TAP0(k) + 1) of them.
+// At the low border the clamp of src gives i0 = 0 with l1 = 0, where this reads cell 0 for both taps: l0 a + 0 b is a either way (finite logits).
+// The value is formed in the expression order of torch's GPU kernel (upsample_bilinear2d_out_frame), every product and sum rounded (no
+// contraction in this file):   v = hl0 * (wl0 * a + wl1 * b) + hl1 * (wl0 * c + wl1 * d)
+// so the two parentheses, which depend on the tap row and the column only, are formed once per row (3 S of them) and shared by the S output rows.
+// argmax: classes in order, strict >: the first maximum, as torch.  NaN logits are outside the contract.
+// Lanes of a wave are 64 consecutive cells of a row: every load is contiguous along w, the three columns and three rows of neighbouring threads
+// and waves (a workgroup is 64 x 4 cells) come from the L1 / L2, so HBM sees each logit about once.  The next class's nine cells are fetched
+// while this one's are used.  Per output row the block's S bytes go out as one S-byte store (S = 4: aligned dwords, 256 contiguous bytes per wave),
+// byte by byte where a buffer is not S-byte aligned.
+template <int S>
+__device__ __forceinline__ void store_packed(unsigned char* p, unsigned v, int wide)
+{
+    if (S == 4 && wide) *(unsigned*)p = v;
+    else if (S == 2 && wide) *(unsigned short*)p = (unsigned short)v;
+    else {
+#pragma unroll
+        for (int k = 0; k < S; ++k) p[k] = (unsigned char)(v >> (8 * k));
+    }
+}
+
+// the 3 x 3 cells of one class about the thread's cell: cls is the class's plane, off the cells' offsets inside a plane, already clamped to
+// it (32-bit: the launcher bounds h * w)
+__device__ __forceinline__ void face_taps(const float* __restrict__ cls, const unsigned (&off)[3][3], float (&t)[3][3])
+{
+#pragma unroll
+    for (int r = 0; r < 3; ++r)
+#pragma unroll
+        for (int q = 0; q < 3; ++q) t[r][q] = cls[off[r][q]];
+}
+
+// class c's S x S up-sampled values from its cells, in the expression order stated above, into the running first maximum
+template <int S>
+__device__ __forceinline__ void face_class(const float (&t)[3][3], int c, const float (&wl0)[S], const float (&wl1)[S], const float (&hl0)[S],
+                                           const float (&hl1)[S], float (&best)[S][S], int (&lab)[S][S])
+{
+    float hx[3][S];
+#pragma unroll
+    for (int r = 0; r < 3; ++r)
+#pragma unroll
+        for (int k = 0; k < S; ++k) {
+            const int q = k < S / 2 ? 0 : 1;                            // TAP0(k)
+            hx[r][k] = wl0[k] * t[r][q] + wl1[k] * t[r][q + 1];
+        }
+#pragma unroll
+    for (int ky = 0; ky < S; ++ky) {
+        const int r = ky < S / 2 ? 0 : 1;
+#pragma unroll
+        for (int kx = 0; kx < S; ++kx) {
+            const float v = hl0[ky] * hx[r][kx] + hl1[ky] * hx[r + 1][kx];
+            if (v > best[ky][kx]) { best[ky][kx] = v; lab[ky][kx] = c; }
+        }
+    }
+}
+
+// grid: (tiles of 64 x 4 cells, frames)
+template <int S>
+__global__ void __launch_bounds__(256) face_mask_kernel(const float* __restrict__ logits, int C, int h, int w, int tiles_x, unsigned valid_bits,
+                                                        unsigned char* __restrict__ masks, unsigned char* __restrict__ labels, int wide)
+{
+    const long n = blockIdx.y;
+    const int xc = (int)(blockIdx.x % tiles_x) * 64 + (threadIdx.x & 63), yc = (int)(blockIdx.x / tiles_x) * 4 + (threadIdx.x >> 6);
+    if (xc >= w || yc >= h) return;
+    float wl0[S], wl1[S], hl0[S], hl1[S];
+#pragma unroll
+    for (int k = 0; k < S; ++k) {
+        const float sx = fmaxf(((float)(xc * S + k) + 0.5f) / (float)S - 0.5f, 0.f), sy = fmaxf(((float)(yc * S + k) + 0.5f) / (float)S - 0.5f, 0.f);
+        wl1[k] = sx - floorf(sx); wl0[k] = 1.f - wl1[k];
+        hl1[k] = sy - floorf(sy); hl0[k] = 1.f - hl1[k];
+    }
+    const long plane = (long)h * w;
+    const int xo[3] = {max(xc - 1, 0), xc, min(xc + 1, w - 1)}, yo[3] = {max(yc - 1, 0), yc, min(yc + 1, h - 1)};
+    unsigned off[3][3];
+#pragma unroll
+    for (int i = 0; i < 9; ++i) off[i / 3][i % 3] = (unsigned)yo[i / 3] * (unsigned)w + (unsigned)xo[i % 3];
+    const float* src = logits + n * C * plane;
+    float best[S][S], ta[3][3], tb[3][3];
+    int lab[S][S];
+#pragma unroll
+    for (int i = 0; i < S * S; ++i) { best[i / S][i % S] = -INFINITY; lab[i / S][i % S] = 0; }
+    // two classes per trip, their cells in two register sets that are fetched one class ahead of their use; a fetch past the last class reads
+    // the last class again (no branch, nothing out of bounds)
+    face_taps(src, off, ta);
+    for (int c = 0; c < C; c += 2) {
+        face_taps(src + min(c + 1, C - 1) * plane, off, tb);
+        face_class<S>(ta, c, wl0, wl1, hl0, hl1, best, lab);
+        face_taps(src + min(c + 2, C - 1) * plane, off, ta);
+        if (c + 1 < C) face_class<S>(tb, c + 1, wl0, wl1, hl0, hl1, best, lab);
+    }
+    const int W = w * S;
+#pragma unroll
+    for (int ky = 0; ky < S; ++ky) {
+        unsigned lw = 0, mw = 0;
+#pragma unroll
+        for (int kx = 0; kx < S; ++kx) {
+            lw |= (unsigned)lab[ky][kx] << (8 * kx);
+            mw |= ((valid_bits >> lab[ky][kx]) & 1u) << (8 * kx);
+        }
+        const long o = ((n * h + yc) * S + ky) * W + (long)xc * S;
+        if (masks) store_packed<S>(masks + o, mw, wide);
+        if (labels) store_packed<S>(labels + o, lw, wide);
+    }
+}
+
+// scale 1, 2 or 4, 1 <= C <= 32, B, h, w >= 1 and an output given: the caller checks (cs_face_masks).  Frame, class and output offsets are 64-bit,
+// a cell's offset inside its class plane is 32-bit: h * w < 2^30, which also bounds a frame's tiles.  Frames are grid rows,
+// 65535 of them per launch, so B is not bound by anything.
+int launch_face_masks(const float* logits, int B, int C, int h, int w, int scale, unsigned valid_bits, unsigned char* masks, unsigned char* labels,
+                      hipStream_t st)
+{
+    const int tiles_x = (w + 63) / 64;
+    const long tiles = (long)tiles_x * ((h + 3) / 4);
+    if ((long)h * w >= (1L << 30)) { cs_set_error("face_masks: %dx%d logits: a class plane must hold fewer than 2^30 cells", h, w); return -1; }
+    const int wide = (((uintptr_t)masks | (uintptr_t)labels) & (uintptr_t)(scale - 1)) == 0;
+    const long in_frame = (long)C * h * w, out_frame = (long)h * scale * w * scale;
+    for (int b0 = 0; b0 < B; b0 += 65535) {
+        const dim3 grid((unsigned)tiles, (unsigned)(B - b0 < 65535 ? B - b0 : 65535)), block(256);
+        const float* lg = logits + b0 * in_frame;
+        unsigned char* m = masks ? masks + b0 * out_frame : nullptr;
+        unsigned char* l = labels ? labels + b0 * out_frame : nullptr;
+        if (scale == 4) hipLaunchKernelGGL(face_mask_kernel<4>, grid, block, 0, st, lg, C, h, w, tiles_x, valid_bits, m, l, wide);
+        else if (scale == 2) hipLaunchKernelGGL(face_mask_kernel<2>, grid, block, 0, st, lg, C, h, w, tiles_x, valid_bits, m, l, wide);
+        else hipLaunchKernelGGL(face_mask_kernel<1>, grid, block, 0, st, lg, C, h, w, tiles_x, valid_bits, m, l, wide);
+        LAUNCH_CHECK("face_masks");
+    }
+    return 0;
+}

@@ -3,6 +3,8 @@
 Counterparts of the reference's host-side helpers, same names and argument meaning, operating on device tensors so the
 per-frame loop (src/can_swap_pipeline_e2e.py:223-283) no longer leaves the GPU between the generator and the final frame:
 
+* ``face_masks``             src/can_swap_pipeline_e2e.py:183-190, src/can_swap_pipeline_v2i.py:76-83: the parser's logits -> 0/1 masks
+                             (F.interpolate to 512 x 512, argmax, isin) of B frames in one launch, nothing up-sampled in memory
 * ``SoftErosion``            src/utils/crop.py:21-47            (the reference runs it with .cuda() too: pure torch)
 * ``prepare_paste_back``     src/utils/crop.py:515-521          (cv2.warpAffine of the float mask)
 * ``paste_back``             src/utils/crop.py:523-529          (cv2.warpAffine of the crop + blend)
@@ -40,6 +42,47 @@ def _mask_hw(e: Engine, mask):
     if m.dim() == 3:
         m = m[..., 0]
     return m.to(e.device).float().contiguous()
+
+
+FACE_VALID = (1, 2, 4, 5, 6, 7, 10, 11, 12)      # valid_list of can_swap_pipeline_e2e.py:189 / can_swap_pipeline_v2i.py:82: the face's classes
+
+
+def valid_bits(valid) -> int:
+    """Class ids -> the 32-bit set cs_face_masks takes (bit c: class c is part of the mask)."""
+    ids = [int(c) for c in valid]
+    if any(c != v for c, v in zip(ids, valid)) or any(not 0 <= c < 32 for c in ids):
+        raise ValueError(f"valid: class ids must be integers in [0, 32), got {tuple(valid)}")
+    bits = 0
+    for c in ids:
+        bits |= 1 << c
+    return bits
+
+
+def face_masks(e: Engine, logits, valid=FACE_VALID, size=(512, 512), out=None, want_labels=False, out_labels=None):
+    """The lines between the parser and SoftErosion (can_swap_pipeline_e2e.py:183-190, can_swap_pipeline_v2i.py:76-83) of B frames in one launch:
+    logits (B,C,h,w), or (C,h,w) for one frame, the parser's output (anything but contiguous fp32 is converted with .float().contiguous()) ->
+    (B,H,W) uint8 0/1 on the device = isin(argmax(F.interpolate(logits, size, mode="bilinear", align_corners=False), 1), valid); with want_labels
+    (or out_labels) {"masks", "labels"}, labels (B,H,W) uint8 class ids.  size = s * (h, w), s 1, 2 or 4; C <= 32; valid: class ids in [0, 32)."""
+    t = torch.as_tensor(logits)
+    if t.dim() == 3:
+        t = t[None]
+    if t.dim() != 4 or min(t.shape) < 1:
+        raise ValueError("face_masks expects (B, C, h, w) logits")
+    B, Cn, h, w = t.shape
+    if Cn > 32:
+        raise ValueError(f"face_masks: {Cn} classes (at most 32: the valid set is a 32-bit word)")
+    H, W = int(size[0]), int(size[1])
+    s = H // h
+    if s not in (1, 2, 4) or (H, W) != (s * h, s * w):
+        raise ValueError(f"face_masks: size {(H, W)} is not s * {(h, w)} with s in (1, 2, 4)")
+    bits = valid_bits(valid)
+    t = t.to(e.device).float().contiguous()
+    want_labels = want_labels or out_labels is not None
+    masks = e._out(out, (B, H, W), torch.uint8)
+    labels = e._out(out_labels, (B, H, W), torch.uint8) if want_labels else None
+    with torch.cuda.device(e.device):
+        _lib.check(e.lib.cs_face_masks(e.h, B, Cn, _ptr(t), h, w, s, bits, _ptr(masks), _ptr(labels), e._stream()), "cs_face_masks")
+    return {"masks": masks, "labels": labels} if want_labels else masks
 
 
 class SoftErosion:

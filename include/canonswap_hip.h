@@ -161,6 +161,21 @@ int cs_paste_back_shared(cs_engine* e, int B, const uint8_t* crops, int Hc, int 
 int cs_crop_frames(cs_engine* e, int B, const uint8_t* frames, int Ho, int Wo, const double* M_o2c, int dsize, uint8_t* crops, float* I_out,
                    void* stream);
 
+/* ---- the face mask from the parser's logits, in front of cs_soft_erosion_frames ---- */
+/* What both pipelines do between SegFormer and SoftErosion (can_swap_pipeline_e2e.py:183-190 per frame, can_swap_pipeline_v2i.py:76-83 per
+ * source image) for B frames in one launch, without materialising the up-sampled logits:
+ *   up = F.interpolate(logits, size=(scale*h, scale*w), mode="bilinear", align_corners=False); labels = up.argmax(dim=1);
+ *   mask = torch.isin(labels, valid_list)
+ * logits BxCxhxw fp32 (NCHW, contiguous), 1 <= C <= 32, scale 1, 2 or 4 on both axes; masks and labels B x scale*h x scale*w uint8, either may
+ * be NULL but not both: labels = the class id, masks = bit `label` of valid_bits (0/1; the pipelines' valid_list [1, 2, 4, 5, 6, 7, 10, 11, 12]
+ * is 0x1cf6).  Per pixel: src = (dst + 0.5) / scale - 0.5 clamped below at 0, i0 = floor(src), i1 = min(i0 + 1, n - 1), l1 = src - i0, l0 = 1 - l1,
+ * v = hl0 * (wl0 * a + wl1 * b) + hl1 * (wl0 * c + wl1 * d) with every product and sum rounded to fp32 (the expression of the GPU kernel
+ * the reference executes); the label is the FIRST maximum over the classes (strict >, classes in order), as torch.argmax.  Logits are assumed
+ * finite: how a NaN orders is not part of the contract.  Asynchronous on the stream, allocates nothing, any B >= 1 (not bound to max_batch).
+ * Returns nonzero and sets cs_last_error() for scale outside {1, 2, 4}, C outside [1, 32], B, h or w below 1, or both outputs NULL. */
+int cs_face_masks(cs_engine* e, int B, int C, const float* logits, int h, int w, int scale, uint32_t valid_bits, uint8_t* masks, uint8_t* labels,
+                  void* stream);
+
 /* ---- measurement: per-kernel-family HIP-event timing on the launch stream */
 int cs_profile_begin(cs_engine* e);
 /* ms[0] = convolution kernels (conv_halo / conv_igemm), ms[1] = all other kernels except ms[2] = the feature warp
