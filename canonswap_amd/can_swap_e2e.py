@@ -209,6 +209,9 @@ class can_swapper(object):
     def face_masks(self, logits, **kw):                                                 # can_swap_pipeline_e2e.py:183-190: logits -> 0/1 masks
         return tail.face_masks(self.engine, logits, **kw)
 
+    def parser_input(self, crops, **kw):                                                # can_swap_pipeline_e2e.py:171 + :180: crops -> the parser's pixel_values
+        return tail.parser_input(self.engine, crops, **kw)
+
     def crop_frames(self, frames, lmk, **kw):                                           # crop.py:429-455 of B frames (cropper.py:196-204)
         return tail.crop_frames(self.engine, frames, lmk, **kw)
 

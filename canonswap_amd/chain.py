@@ -11,21 +11,23 @@ the generator).
                               [seven tensors to the host and back per frame]
     :242-263  F -> warp -> T -> R -> warp_decode                               cs_swap_frames_ids
     :267      parse_output [sync + D2H]                                        (pack_u8 inside cs_swap_frames_ids)
+    :171, :180  cv2.resize(crop, 256 x 256) + SegformerImageProcessor          chain.parser_input: cs_parser_input (PIL's two integer passes,
+                              [D2H, PIL resize, three numpy passes, upload]     rescale + normalize as a table, fp32 NCHW)
     :183-190  F.interpolate(logits, 512 x 512) -> argmax -> isin               cs_face_masks (with logits=: the parser's logits go in as they
                               [19.9 MB of up-sampled logits per frame]          are; with masks: the caller has run these lines)
     :274      soft_mask(masks[i]) [D2H]                                        cs_soft_erosion_frames
     :279-282  prepare_paste_back + paste_back (two cv2.warpAffine) [host]      cs_paste_back_batch
 
-The loop of a caller:  c = chain.crop(frames, lmk);  logits = <the caller's parser on c["crops"]>, (B,19,128,128);
+The loop of a caller:  c = chain.crop(frames, lmk);  logits = model(pixel_values=chain.parser_input(c["crops"])).logits, (B,19,128,128);
 frames_out = chain(c["crops"], None, c["M_c2o"], frames, source_id, logits=logits)["frames"]
 (or, with 0/1 masks the caller has made of them: chain(c["crops"], masks, c["M_c2o"], frames, source_id)).
 
 AnimateChain below is the same for the second program, inference_v2i.py (src/can_swap_pipeline_v2i.py: one source image animated by a
 driving video, the driving identity swapped in); its table stands in the class's docstring.
 
-What stays outside (out of scope): face detection and the landmark network (they produce the landmarks), SegFormer
-face parsing (the network and its image processor: it produces the logits; what the pipelines do with them is cs_face_masks), video decode /
-encode.
+What stays outside (out of scope): face detection and the landmark network (they produce the landmarks), the SegFormer
+network (a third-party model: it turns pixel_values into the logits; its image processor is cs_parser_input, what the pipelines do with its logits
+is cs_face_masks), video decode / encode.
 """
 from __future__ import annotations
 
@@ -64,6 +66,13 @@ class _StagedChain:
         CropConfig's defaults (cfg: dsize, scale, vy_ratio, flag_do_rot, out, want_I).  A new crops tensor per call, so a batch may be cropped
         and prefetched while the one before it runs; stage A reads the crops as it would a caller's."""
         return tail.crop_frames(self.e, frames_ori, lmk, **cfg)
+
+    def parser_input(self, crops_u8, **kw):
+        """What the caller's face parsing network takes (can_swap_pipeline_e2e.py:171 + :180, can_swap_pipeline_v2i.py:73): crops_u8 (B,512,512,3) or
+        (B,256,256,3) u8 -> pixel_values (B,3,512,512) fp32 on the device, tail.parser_input (kw: halve, mean, std, rescale, out, want_u8,
+        out_u8).  One launch on the caller's stream that reads the crops and a 3 KB table and writes its own output: it uses no engine scratch,
+        so it may run on the caller's stream while a prefetch is in flight on the side stream."""
+        return tail.parser_input(self.e, crops_u8, **kw)
 
     def _check_stageable(self):
         """Raises where stage A cannot run yet (AnimateChain: no source)."""
@@ -194,6 +203,7 @@ class AnimateChain(_StagedChain):
         :294      F.interpolate(swap_can, (256, 256), bilinear)                    cs_resize_half_bilinear
         :297-298  get_kp_info + transform_keypoint of swap_can_256                 cs_motion_extract + cs_motion_keypoints
         :308      extract_feature_3d(swap_can_256), there once per frame           cs_extract_feature_3d, once (loop-invariant)
+        :73       image_processor(img_crop_256x256) [host: PIL, numpy, upload]     cs_parser_input (chain.parser_input(crop): the parser's pixel_values)
         :76-83    F.interpolate(logits, 512 x 512) -> argmax -> isin               cs_face_masks (set_source(..., logits=))
         :255-258  soft_mask + prepare_paste_back [D2H, cv2.warpAffine]             cs_soft_erosion_frames + cs_warp_affine_f32
         per driving frame                                                          __call__

@@ -22,7 +22,7 @@ void cs_set_error(const char* fmt, ...)
     va_end(ap);
 }
 extern "C" const char* cs_last_error(void) { return g_err; }
-// 4, unchanged: cs_resize_half_bilinear, cs_motion_keypoints_driven, cs_paste_back_shared (the v2i device-side frame) cs_crop_frames (the crop in front of both chains) and cs_face_masks (the parser's logits -> 0/1 masks) were added; new entry points
+// 4, unchanged: cs_resize_half_bilinear, cs_motion_keypoints_driven, cs_paste_back_shared (the v2i device-side frame) cs_crop_frames (the crop in front of both chains), cs_face_masks (the parser's logits -> 0/1 masks) and cs_parser_input (crops -> the parser's pixel_values) were added; new entry points
 // alone change no struct, no existing entry point's meaning and no blob format, which is what the header bumps the version for.
 // 4 (round 6): cs_soft_erosion_frames, cs_paste_back_batch, cs_motion_keypoints.
 // 3 (round 4): cs_conv_desc grew (hilo, stat_out, xf_*, ep_general), cs_op_conv takes conv_halo / vol32 / conv_wide configurations only, the
@@ -1753,6 +1753,22 @@ extern "C" int cs_face_masks(cs_engine* e, int B, int C, const float* logits, in
     DevGuard guard(e->dev);
     hipStream_t st = (hipStream_t)stream;
     return e->run(1, st, [&] { return launch_face_masks(logits, B, C, h, w, scale, valid_bits, masks, labels, st); }, "face_masks");
+}
+
+// ---- the parser's input (can_swap_pipeline_e2e.py:171 + :180, can_swap_pipeline_v2i.py:73): everything is refused before any launch
+extern "C" int cs_parser_input(cs_engine* e, int B, const uint8_t* crops, int Hc, int Wc, int halve, const float* lut, float* pixel_values,
+                               uint8_t* resized_u8, void* stream)
+{
+    if (!e || !crops || !lut) { cs_set_error("cs_parser_input: NULL %s", !e ? "engine" : !crops ? "crops" : "lut"); return -1; }
+    if (!pixel_values && !resized_u8) { cs_set_error("cs_parser_input: both outputs are NULL"); return -1; }
+    if (B < 1 || Hc < 1 || Wc < 1) { cs_set_error("cs_parser_input: B = %d, Hc = %d, Wc = %d (each at least 1)", B, Hc, Wc); return -1; }
+    if (halve != 0 && halve != 1) { cs_set_error("cs_parser_input: halve %d (0 or 1)", halve); return -1; }
+    if (halve && ((Hc | Wc) & 1)) { cs_set_error("cs_parser_input: %dx%d crops cannot be halved (odd size)", Hc, Wc); return -1; }
+    const long Ho = halve ? Hc : 2L * Hc, Wo = halve ? Wc : 2L * Wc;
+    if (Ho > 16384 || Wo > 16384) { cs_set_error("cs_parser_input: output %ldx%ld above 16384 a side", Ho, Wo); return -1; }
+    DevGuard guard(e->dev);
+    hipStream_t st = (hipStream_t)stream;
+    return e->run(1, st, [&] { return launch_parser_input(crops, B, Hc, Wc, halve, lut, pixel_values, resized_u8, st); }, "parser_input");
 }
 
 extern "C" int cs_profile_begin(cs_engine* e)

@@ -4,6 +4,8 @@
 //     (src/utils/crop.py:49-63, 515-529, driven from can_swap_pipeline_e2e.py:267-283),
 //   * input staging: cv2.resize(crop, (256,256), INTER_AREA) + /255 + HWC->CHW (src/utils/cropper.py:209, can_swap_e2e.py:126-163),
 //   * the crop itself: cv2.warpAffine of the frame into the crop's frame (src/utils/crop.py:429-455, src/utils/cropper.py:196-209).
+//   * the face parser's input: cv2.resize to one half + SegformerImageProcessor (PIL resize x 2, rescale, normalize) of a crop
+//     (src/can_swap_pipeline_e2e.py:171, 180, src/can_swap_pipeline_v2i.py:73).
 // All of them are HBM-bound byte / float work: one thread per output pixel, coalesced along the row.  The OpenCV steps follow
 // OpenCV's published fixed-point algorithm (restated in oracle/cv_ref.py, which the tests compare against bit for bit).
 #include "common.h"
@@ -799,6 +801,126 @@ int launch_face_masks(const float* logits, int B, int C, int h, int w, int scale
         else if (scale == 2) hipLaunchKernelGGL(face_mask_kernel<2>, grid, block, 0, st, lg, C, h, w, tiles_x, valid_bits, m, l, wide);
         else hipLaunchKernelGGL(face_mask_kernel<1>, grid, block, 0, st, lg, C, h, w, tiles_x, valid_bits, m, l, wide);
         LAUNCH_CHECK("face_masks");
+    }
+    return 0;
+}
+
+// ---------------------------------------------------------------------------------------------- the parser's input
+// What both pipelines do to a crop before SegFormer sees it (can_swap_pipeline_e2e.py:171 + :180, can_swap_pipeline_v2i.py:73: cv2.resize to
+// 256 x 256, then SegformerImageProcessor of transformers 4.38: PIL resize to 512 x 512 BILINEAR, rescale, normalize, HWC -> CHW) in one launch
+// for B crops, in integers:
+//   HALVE: x = (a + b + c + d + 2) >> 2 of each 2 x 2 block of the crop (cv2.resize by exactly one half, as prepare_crops_kernel), else x = the crop;
+//   PIL's Resample.c by exactly 2 (coefficients 0.75 / 0.25, 1.0 at both ends, exact in its 22-bit fixed point), the horizontal pass FIRST and
+//   its result rounded to uint8, the vertical pass on that; one axis pass n -> 2 n:
+//     out[2 j] = (3 in[j] + in[max(j - 1, 0)] + 2) >> 2,   out[2 j + 1] = (3 in[j] + in[min(j + 1, n - 1)] + 2) >> 2;
+//   pixel_values[c][y][x] = lut[c][byte]: rescale + normalize are a function of one byte per channel, tabulated on the host with the
+//   processor's own numpy lines (tail.parser_lut).  Nothing is computed in float here.
+// A workgroup owns 128 x 32 output pixels = 64 x 16 source pixels.  It stages those with a one-sample halo, indices clamped to the image (the
+// clamp is the filter's own border rule: a clamped neighbour equals the sample, (3 a + a + 2) >> 2 = a), filters every staged row horizontally
+// ONCE into LDS as bytes, one plane per channel (18 rows: the two output rows of a source row and its neighbours' share them), and then a
+// thread owns four consecutive output pixels of four output rows: per row and channel one dword of each of the two filtered rows it blends,
+// four table reads from LDS and one 16-byte store - the 32 lanes of a half-wave store 512 contiguous bytes of a plane's row.  The uint8
+// image goes out as three dwords per thread and row.  No intermediate in global memory.
+template <bool HALVE>
+__global__ void __launch_bounds__(256) parser_input_kernel(const unsigned char* __restrict__ crops, int Hc, int Wc, const float* __restrict__ lut,
+                                                           float* __restrict__ pv, unsigned char* __restrict__ u8, int tiles_x, int wide_f, int wide_u)
+{
+    constexpr int SX = 64, SY = 16, LR = SY + 2, SROW = (SX + 2) * 3, NS = LR * SROW, HW = SX * 2 / 4;
+    __shared__ float tab[3 * 256];
+    __shared__ unsigned char src[NS];
+    __shared__ unsigned hf[3][LR][HW];
+    const long n = blockIdx.y;
+    const int h = HALVE ? Hc >> 1 : Hc, w = HALVE ? Wc >> 1 : Wc, Ho = 2 * h, Wo = 2 * w;
+    const int sx0 = (int)(blockIdx.x % tiles_x) * SX, sy0 = (int)(blockIdx.x / tiles_x) * SY;
+    const unsigned char* in = crops + n * Hc * Wc * 3;
+    for (int i = threadIdx.x; i < 3 * 256; i += 256) tab[i] = lut[i];
+    for (int i = threadIdx.x; i < NS; i += 256) {                       // source tile + halo, interleaved as in memory
+        const int row = i / SROW, b = i % SROW, col = b / 3, c = b % 3;
+        const int gy = min(max(sy0 - 1 + row, 0), h - 1), gx = min(max(sx0 - 1 + col, 0), w - 1);
+        int v;
+        if (HALVE) {
+            const unsigned char* p = in + ((long)(2 * gy) * Wc + 2 * gx) * 3 + c;
+            v = (p[0] + p[3] + p[(long)Wc * 3] + p[(long)Wc * 3 + 3] + 2) >> 2;
+        } else {
+            v = in[((long)gy * Wc + gx) * 3 + c];
+        }
+        src[i] = (unsigned char)v;
+    }
+    __syncthreads();
+    for (int q = threadIdx.x; q < 3 * LR * HW; q += 256) {              // horizontal pass: four output columns = two source columns per dword
+        const int t = q % HW, row = (q / HW) % LR, c = q / (HW * LR);
+        const unsigned char* p = src + row * SROW + 2 * t * 3 + c;       // staged columns 2 t .. 2 t + 3 = source columns 2 t - 1 .. 2 t + 2 of the tile
+        const unsigned p0 = p[0], p1 = p[3], p2 = p[6], p3 = p[9];
+        hf[c][row][t] = ((3 * p1 + p0 + 2) >> 2) | ((3 * p1 + p2 + 2) >> 2) << 8 | ((3 * p2 + p1 + 2) >> 2) << 16 | ((3 * p2 + p3 + 2) >> 2) << 24;
+    }
+    __syncthreads();
+    const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;
+    const int x = 2 * sx0 + 4 * tx;
+    if (x >= Wo) return;
+    const int nx = min(4, Wo - x);
+    unsigned R[4][3];                                                   // filtered rows of source rows 2 ty - 1 .. 2 ty + 2 of the tile
+#pragma unroll
+    for (int r = 0; r < 4; ++r)
+#pragma unroll
+        for (int c = 0; c < 3; ++c) R[r][c] = hf[c][2 * ty + r][tx];
+    const long plane = (long)Ho * Wo;
+#pragma unroll
+    for (int o = 0; o < 4; ++o) {                                       // output row 2 j + (o & 1) of source row j = 2 ty + (o >> 1): 3 j's row + its neighbour's
+        const int y = 2 * (sy0 + 2 * ty) + o;
+        if (y >= Ho) break;
+        const int ra = (o >> 1) + 1, rb = (o & 1) ? ra + 1 : ra - 1;
+        unsigned v[3][4];
+#pragma unroll
+        for (int c = 0; c < 3; ++c)
+#pragma unroll
+            for (int k = 0; k < 4; ++k) v[c][k] = (3 * ((R[ra][c] >> (8 * k)) & 255u) + ((R[rb][c] >> (8 * k)) & 255u) + 2) >> 2;
+        if (pv) {
+#pragma unroll
+            for (int c = 0; c < 3; ++c) {
+                float* d = pv + (n * 3 + c) * plane + (long)y * Wo + x;
+                const float4 f = make_float4(tab[c * 256 + v[c][0]], tab[c * 256 + v[c][1]], tab[c * 256 + v[c][2]], tab[c * 256 + v[c][3]]);
+                if (wide_f) *(float4*)d = f;                            // Wo % 4 == 0: the group is whole
+                else {
+                    d[0] = f.x;
+                    if (nx > 1) d[1] = f.y;
+                    if (nx > 2) d[2] = f.z;
+                    if (nx > 3) d[3] = f.w;
+                }
+            }
+        }
+        if (u8) {
+            unsigned char* d = u8 + ((n * Ho + y) * Wo + x) * 3;
+            if (wide_u) {
+                unsigned wv[3] = {0u, 0u, 0u};
+#pragma unroll
+                for (int j = 0; j < 12; ++j) wv[j >> 2] |= v[j % 3][j / 3] << ((j & 3) * 8);
+                unsigned* dw = (unsigned*)d;
+                dw[0] = wv[0]; dw[1] = wv[1]; dw[2] = wv[2];
+            } else {
+#pragma unroll
+                for (int j = 0; j < 12; ++j) if (j / 3 < nx) d[j] = (unsigned char)v[j % 3][j / 3];
+            }
+        }
+    }
+}
+
+// B, Hc, Wc >= 1, even with halve, an output given, output sides <= 16384: the caller checks (cs_parser_input).  Frame and plane offsets are
+// 64-bit; frames are grid rows, 65535 of them per launch, so B is not bound by anything.  The wide stores need whole groups of four
+// pixels (Wo % 4 == 0) and aligned buffers; everything else takes element stores with the same values.
+int launch_parser_input(const unsigned char* crops, int B, int Hc, int Wc, int halve, const float* lut, float* pv, unsigned char* u8, hipStream_t st)
+{
+    const int h = halve ? Hc / 2 : Hc, w = halve ? Wc / 2 : Wc, Ho = 2 * h, Wo = 2 * w;
+    const int tiles_x = (w + 63) / 64, tiles = tiles_x * ((h + 15) / 16);
+    const int wide_f = Wo % 4 == 0 && ((uintptr_t)pv & 15) == 0, wide_u = Wo % 4 == 0 && ((uintptr_t)u8 & 3) == 0;
+    const long in_frame = (long)Hc * Wc * 3, out_frame = (long)Ho * Wo * 3;
+    for (int b0 = 0; b0 < B; b0 += 65535) {
+        const dim3 grid((unsigned)tiles, (unsigned)(B - b0 < 65535 ? B - b0 : 65535)), block(256);
+        const unsigned char* c = crops + b0 * in_frame;
+        float* p = pv ? pv + b0 * out_frame : nullptr;
+        unsigned char* u = u8 ? u8 + b0 * out_frame : nullptr;
+        if (halve) hipLaunchKernelGGL(parser_input_kernel<true>, grid, block, 0, st, c, Hc, Wc, lut, p, u, tiles_x, wide_f, wide_u);
+        else hipLaunchKernelGGL(parser_input_kernel<false>, grid, block, 0, st, c, Hc, Wc, lut, p, u, tiles_x, wide_f, wide_u);
+        LAUNCH_CHECK("parser_input");
     }
     return 0;
 }

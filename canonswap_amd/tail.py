@@ -5,6 +5,8 @@ per-frame loop (src/can_swap_pipeline_e2e.py:223-283) no longer leaves the GPU b
 
 * ``face_masks``             src/can_swap_pipeline_e2e.py:183-190, src/can_swap_pipeline_v2i.py:76-83: the parser's logits -> 0/1 masks
                              (F.interpolate to 512 x 512, argmax, isin) of B frames in one launch, nothing up-sampled in memory
+* ``parser_input``           src/can_swap_pipeline_e2e.py:171 + :180, src/can_swap_pipeline_v2i.py:73: crops -> the face parser's pixel_values
+                             (cv2.resize to one half, SegformerImageProcessor's PIL resize x 2, rescale, normalize, CHW) of B crops in one launch
 * ``SoftErosion``            src/utils/crop.py:21-47            (the reference runs it with .cuda() too: pure torch)
 * ``prepare_paste_back``     src/utils/crop.py:515-521          (cv2.warpAffine of the float mask)
 * ``paste_back``             src/utils/crop.py:523-529          (cv2.warpAffine of the crop + blend)
@@ -83,6 +85,72 @@ def face_masks(e: Engine, logits, valid=FACE_VALID, size=(512, 512), out=None, w
     with torch.cuda.device(e.device):
         _lib.check(e.lib.cs_face_masks(e.h, B, Cn, _ptr(t), h, w, s, bits, _ptr(masks), _ptr(labels), e._stream()), "cs_face_masks")
     return {"masks": masks, "labels": labels} if want_labels else masks
+
+
+# SegformerImageProcessor's class defaults (transformers 4.38: IMAGENET_DEFAULT_MEAN / _STD, rescale_factor 1 / 255, size 512 x 512); a checkpoint's
+# preprocessor_config.json may name others, hence parameters
+PARSER_MEAN = (0.485, 0.456, 0.406)
+PARSER_STD = (0.229, 0.224, 0.225)
+PARSER_RESCALE = 1 / 255
+
+
+def parser_lut(mean=PARSER_MEAN, std=PARSER_STD, rescale=PARSER_RESCALE) -> np.ndarray:
+    """(3, 256) fp32: what the processor's rescale and normalize make of byte v in channel c, by its own numpy lines (transformers 4.38
+    image_transforms.py): rescale = (image * scale).astype(np.float32), the product of a uint8 array and a Python float taken in float64;
+    normalize = (image - mean) / std with mean and std cast to the image's float32.  cs_parser_input looks this up and computes nothing in float
+    (a folded v * scale + bias differs from it in most entries)."""
+    mean, std = [float(m) for m in mean], [float(s) for s in std]
+    if len(mean) != 3 or len(std) != 3 or any(s == 0 for s in std):
+        raise ValueError("parser_lut: mean and std are three numbers each, std nonzero")
+    image = np.arange(256, dtype=np.uint8)
+    r = (image * float(rescale)).astype(np.float32)
+    m, s = np.array(mean, dtype=r.dtype), np.array(std, dtype=r.dtype)
+    lut = (r[None, :] - m[:, None]) / s[:, None]
+    assert lut.dtype == np.float32 and lut.shape == (3, 256)
+    return np.ascontiguousarray(lut)
+
+
+def _parser_lut_on(e: Engine, mean, std, rescale):
+    """The table on the engine's device, uploaded once per engine and set of constants."""
+    key = (tuple(float(m) for m in mean), tuple(float(s) for s in std), float(rescale))
+    cache = e.__dict__.setdefault("_parser_luts", {})
+    t = cache.get(key)
+    if t is None:
+        t = torch.from_numpy(parser_lut(*key)).to(e.device)
+        torch.cuda.current_stream(e.device).synchronize()      # once: later calls may come from any stream
+        cache[key] = t
+    return t
+
+
+def parser_input(e: Engine, crops_u8, halve=None, mean=PARSER_MEAN, std=PARSER_STD, rescale=PARSER_RESCALE, out=None, want_u8=False, out_u8=None):
+    """What both pipelines feed the face parser (can_swap_pipeline_e2e.py:171 + :180, can_swap_pipeline_v2i.py:73) for B crops in one launch:
+    crops_u8 (B,H,W,3), or (H,W,3) for one crop, uint8, host or device -> pixel_values (B,3,Ho,Wo) fp32 on the device =
+    SegformerImageProcessor(size 2h x 2w)(x), x = cv2.resize(crop, (W/2, H/2)) with halve, the crop itself without; (Ho, Wo) = (H, W) with
+    halve, (2H, 2W) without.  halve=None: halve iff the crop is 512 x 512 (the pipelines' 256 x 256 parser crop, 512 x 512 pixel_values, from
+    either crop size).  Bit-equal to PIL's two-pass fixed-point bilinear resize and the processor's numpy lines (parser_lut).  With want_u8 (or
+    out_u8) {"pixel_values", "resized_u8"}, resized_u8 (B,Ho,Wo,3) uint8: the resized image before rescale / normalize."""
+    t = torch.as_tensor(crops_u8)
+    if t.dim() == 3:
+        t = t[None]
+    if t.dtype != torch.uint8 or t.dim() != 4 or t.shape[3] != 3 or min(t.shape) < 1:
+        raise ValueError("parser_input expects (B, H, W, 3) uint8 crops")
+    B, H, W, _ = t.shape
+    if halve is None:
+        halve = (H, W) == (512, 512)
+    halve = bool(halve)
+    if halve and (H % 2 or W % 2):
+        raise ValueError(f"parser_input: {H}x{W} crops cannot be halved (odd size)")
+    Ho, Wo = (H, W) if halve else (2 * H, 2 * W)
+    if max(Ho, Wo) > 16384:
+        raise ValueError(f"parser_input: output {Ho}x{Wo} above 16384 a side")
+    t = t.to(e.device).contiguous()
+    want_u8 = want_u8 or out_u8 is not None
+    pv = e._out(out, (B, 3, Ho, Wo), torch.float32)
+    u8 = e._out(out_u8, (B, Ho, Wo, 3), torch.uint8) if want_u8 else None
+    lut = _parser_lut_on(e, mean, std, rescale)
+    with torch.cuda.device(e.device):
+        _lib.check(e.lib.cs_parser_input(e.h, B, _ptr(t), H, W, int(halve), _ptr(lut), _ptr(pv), _ptr(u8), e._stream()), "cs_parser_input")
+    return {"pixel_values": pv, "resized_u8": u8} if want_u8 else pv
 
 
 class SoftErosion:

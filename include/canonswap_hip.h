@@ -176,6 +176,26 @@ int cs_crop_frames(cs_engine* e, int B, const uint8_t* frames, int Ho, int Wo, c
 int cs_face_masks(cs_engine* e, int B, int C, const float* logits, int h, int w, int scale, uint32_t valid_bits, uint8_t* masks, uint8_t* labels,
                   void* stream);
 
+/* ---- the parser's input, in front of the caller's SegFormer network ---- */
+/* What both pipelines do to a crop before the face parser sees it (can_swap_pipeline_e2e.py:171 and :180 per frame, can_swap_pipeline_v2i.py:73
+ * per source image; SegformerImageProcessor of transformers 4.38: resize -> rescale -> normalize -> channels first) for B crops in one launch,
+ * without an intermediate in memory.  crops BxHcxWcx3 u8.
+ *   1. halve = 1: x = cv2.resize(crop, (Wc/2, Hc/2)) = (a + b + c + d + 2) >> 2 per 2x2 block and channel (INTER_LINEAR and INTER_AREA agree at
+ *      exactly one half: :171, cropper.py:209); halve = 0: x = the crop.  x is h x w.
+ *   2. PIL's image.resize((2w, 2h), BILINEAR) (Resample.c, PRECISION_BITS 22; at exactly x2 every coefficient is 0.75 / 0.25, 1.0 at both
+ *      ends, exact in fixed point): the HORIZONTAL pass first, its result rounded to uint8, the vertical pass on that.  One axis pass n -> 2n:
+ *        out[2j] = (3 in[j] + in[max(j - 1, 0)] + 2) >> 2,  out[2j + 1] = (3 in[j] + in[min(j + 1, n - 1)] + 2) >> 2.
+ *   3. rescale + normalize (image_transforms.py: (u8 * rescale).astype(float32), then (r - mean) / std in float32) as a table look-up:
+ *      lut: DEVICE, 3 x 256 fp32, lut[c][v] built on the host with exactly those numpy lines (canonswap_amd/tail.py parser_lut; the class defaults
+ *      are mean (0.485, 0.456, 0.406), std (0.229, 0.224, 0.225), rescale 1/255).  The device computes nothing in float.
+ *   4. pixel_values Bx3xHoxWo fp32 (NCHW), resized_u8 BxHoxWox3 (step 2's image); (Ho, Wo) = halve ? (Hc, Wc) : (2 Hc, 2 Wc).  Either output may be
+ *      NULL, not both.
+ * Any Hc, Wc >= 1 (even with halve), any B >= 1 (not bound to max_batch); asynchronous on the stream, no engine scratch, allocates nothing.
+ * Returns nonzero and sets cs_last_error() before any launch for a NULL e, crops or lut, both outputs NULL, B, Hc or Wc below 1, odd sizes with
+ * halve, halve outside {0, 1}, or an output side above 16384. */
+int cs_parser_input(cs_engine* e, int B, const uint8_t* crops, int Hc, int Wc, int halve, const float* lut, float* pixel_values,
+                    uint8_t* resized_u8, void* stream);
+
 /* ---- measurement: per-kernel-family HIP-event timing on the launch stream */
 int cs_profile_begin(cs_engine* e);
 /* ms[0] = convolution kernels (conv_halo / conv_igemm), ms[1] = all other kernels except ms[2] = the feature warp
