@@ -212,6 +212,9 @@ class can_swapper(object):
     def parser_input(self, crops, **kw):                                                # can_swap_pipeline_e2e.py:171 + :180: crops -> the parser's pixel_values
         return tail.parser_input(self.engine, crops, **kw)
 
+    def concat_frames(self, panels, **kw):                                              # video.py:84-109: the side-by-side frames, panels left to right
+        return tail.concat_frames(self.engine, panels, **kw)
+
     def crop_frames(self, frames, lmk, **kw):                                           # crop.py:429-455 of B frames (cropper.py:196-204)
         return tail.crop_frames(self.engine, frames, lmk, **kw)
 

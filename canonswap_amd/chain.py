@@ -17,6 +17,8 @@ the generator).
                               [19.9 MB of up-sampled logits per frame]          are; with masks: the caller has run these lines)
     :274      soft_mask(masks[i]) [D2H]                                        cs_soft_erosion_frames
     :279-282  prepare_paste_back + paste_back (two cv2.warpAffine) [host]      cs_paste_back_batch
+    :248-250, :257-259, :290  rec_can, I_can, concat_frames (video.py:84-109)  chain(..., concat=True): the two debug decodes of
+                              [three images per frame D2H, cv2.resize, hstack]  cs_swap_frames_ids + cs_concat_frames
 
 The loop of a caller:  c = chain.crop(frames, lmk);  logits = model(pixel_values=chain.parser_input(c["crops"])).logits, (B,19,128,128);
 frames_out = chain(c["crops"], None, c["M_c2o"], frames, source_id, logits=logits)["frames"]
@@ -73,6 +75,16 @@ class _StagedChain:
         out_u8).  One launch on the caller's stream that reads the crops and a 3 KB table and writes its own output: it uses no engine scratch,
         so it may run on the caller's stream while a prefetch is in flight on the side stream."""
         return tail.parser_input(self.e, crops_u8, **kw)
+
+    def _concat(self, crops_u8, middle, gen, out):
+        """The pipelines' side-by-side frame (video.py:84-109): driving crop | middle panels | gen, tail.concat_frames.  The driving panel is
+        the reference's driving_rgb_crop_256x256_lst resized back to 512 (can_swap_pipeline_e2e.py:171 then video.py:99): kind 2 for 512 x 512
+        crops (halved, then x 2), kind 1 for 256 x 256 crops (x 2).  middle: [(panel, kind, shared)].  One launch on the caller's stream behind the
+        generator; no engine scratch."""
+        drv = torch.as_tensor(crops_u8)
+        drv = drv[None] if drv.dim() == 3 else drv
+        panels = [(drv, 2 if drv.shape[1] == 512 else 1, 0)] + list(middle) + [(gen, 0, 0)]
+        return tail.concat_frames(self.e, [p for p, _, _ in panels], kinds=[k for _, k, _ in panels], shared=[f for _, _, f in panels], out=out)
 
     def _check_stageable(self):
         """Raises where stage A cannot run yet (AnimateChain: no source)."""
@@ -170,22 +182,33 @@ class FrameChain(_StagedChain):
         self._mask_or_logits(masks, logits, "FrameChain.prefetch")
         self._stage_ahead(crops_u8, masks, logits)
 
-    def __call__(self, crops_u8, masks, M_c2o, frames_ori, source_id=None, slots=None, out=None, keep=False, logits=None):
+    def __call__(self, crops_u8, masks, M_c2o, frames_ori, source_id=None, slots=None, out=None, keep=False, logits=None, concat=False,
+                 concat_out=None):
         """crops_u8 (B,512,512,3) or (B,256,256,3) u8; masks (B,512,512) u8 0/1 or fp32 (the parser's `torch.isin(labels, valid)`), or None
         with logits= (B,C,128,128), (B,C,256,256) or (B,C,512,512) fp32: the parser's logits, masked here (tail.face_masks with the chain's valid);
         M_c2o (B,2,3)/(B,3,3) host; frames_ori (B,Ho,Wo,3) u8; source_id (1,512)/(B,512) or identity slots.
-        -> {"frames": (B,Ho,Wo,3) u8[, "crops_out", "x_t", "x_can", "soft_mask" with keep=True]}"""
+        concat=True: also the frames of the pipeline's side-by-side video (:290, video.py:84-109), "concat" (B,512,2048,3) u8 (into concat_out):
+        driving crop | rec_can (:248-250) | I_can (:257-259) | I_p.  The generator then runs its two debug decodes, into chain-owned buffers; without
+        concat it runs neither.
+        -> {"frames": (B,Ho,Wo,3) u8[, "concat"][, "crops_out", "x_t", "x_can", "soft_mask" with keep=True, and "rec_can", "swap_can"
+        (B,3,512,512) fp32 with keep and concat]}"""
         e = self.e
         self._mask_or_logits(masks, logits, "FrameChain")
         slot, (I, x_t, x_can, soft) = self._resolve(crops_u8, masks, logits)
         B = I.shape[0]
+        rec = self._get("rec_can", (B, 3, 512, 512), torch.float32) if concat else None
+        swp = self._get("swap_can", (B, 3, 512, 512), torch.float32) if concat else None
         gen = e.swap_frames(I, x_t, x_can, source_id, want_f32=False, want_u8=True, slots=slots,
-                            out_u8=self._get("gen", (B, 512, 512, 3), torch.uint8))["out_u8"]   # :242-267
+                            out_u8=self._get("gen", (B, 512, 512, 3), torch.uint8), out_rec=rec, out_swap=swp)["out_u8"]   # :242-267
         frames = tail.paste_back_batch(e, gen, soft, M_c2o, frames_ori, out=out)                # :279-282
         self._release(slot)
         res = {"frames": frames}
+        if concat:
+            res["concat"] = self._concat(crops_u8, [(rec, 3, 0), (swp, 3, 0)], gen, concat_out)  # :290
         if keep:
             res.update(crops_out=gen, x_t=x_t, x_can=x_can, soft_mask=soft, I=I)
+            if concat:
+                res.update(rec_can=rec, swap_can=swp)
         return res
 
 
@@ -211,14 +234,16 @@ class AnimateChain(_StagedChain):
         :301-305  x_t_2 = scale_swap * (kp_swap @ R_swap + delta_t) + t_swap        cs_motion_keypoints_driven
         :309      warp_decode(f_swap_can_2, x_swap, x_t_2)                         cs_animate_frames
         :312-321  parse_output [sync + D2H] + paste_back into a copy of the image   (pack_u8 inside cs_animate_frames) cs_paste_back_shared
+        :328      concat_frames (video.py:84-109) [cv2.resize, hstack on the host]  chain(..., concat=True): cs_concat_frames, the one I_can shared
 
     There is no refine module in this pipeline.  The crops, the source's and the driving frames', come from chain.crop (cropper.py:144-152,
     196-204): `c = chain.crop(img[None], lmk)`, then `set_source(c["crops"][0], mask, c["M_c2o"][0], img, driving_id)`.  Outside: everything
-    FrameChain leaves outside, getid (the driving identity is passed in) and concat_frames."""
+    FrameChain leaves outside and getid (the driving identity is passed in)."""
 
     def __init__(self, swapper, kernel_size: int = 21, threshold: float = 0.9, iterations: int = 2, valid=tail.FACE_VALID):
         super().__init__(swapper, kernel_size, threshold, iterations, valid)      # SoftErosion(21, 0.9, 2): can_swap_pipeline_v2i.py:43; valid_list :82
         self._src = None                                              # source_state()
+        self._I_can = None                                            # set_source's I_can, the middle panel of concat=True; beside _src, not in it
 
     # ---- once per (source image, driving identity)
     def set_source(self, crop_u8, mask, M_c2o, img_ori, driving_id, logits=None):
@@ -260,7 +285,8 @@ class AnimateChain(_StagedChain):
         mask_ori = tail.prepare_paste_back(e, soft[0], M, (ori.shape[1], ori.shape[0]))      # :258
         self._src = {"f_swap_can_2": f_swap_can_2, "x_swap": x_swap, "kp_swap": raw_swap[0, :63].view(21, 3), "raw_pose": raw_pose,
                      "mask_ori": mask_ori, "img_ori": ori, "M_c2o": M}
-        return {"I_can": e.pack_u8(swap_can)[0], "swap_can": swap_can, "x_swap": x_swap, "x_s": x_s}      # :290 parse_output
+        self._I_can = e.pack_u8(swap_can)[0]                                         # :290 parse_output
+        return {"I_can": self._I_can, "swap_can": swap_can, "x_swap": x_swap, "x_s": x_s}
 
     def _check_stageable(self):
         if self._src is None:
@@ -292,6 +318,7 @@ class AnimateChain(_StagedChain):
         src["M_c2o"] = tail._m6(d["M_c2o"])[0].copy()
         self.drop_prefetches()
         self._src = src
+        self._I_can = None                                            # the state holds no picture of its source: concat=True needs I_can= from here on
 
     # ---- stage A: what the generator needs from a batch of driving crops.  The reference runs it as a pre-pass over the whole driving video
     # (prepare_videos + make_motion_template, can_swap_pipeline_v2i.py:235-238) and forms x_t_2 in the loop (:305)
@@ -311,10 +338,21 @@ class AnimateChain(_StagedChain):
         order; not on a latency-mode engine (split-K scratch shared by M and the generator)."""
         self._stage_ahead(crops_u8)
 
-    def __call__(self, crops_u8, out=None, keep=False):
+    def __call__(self, crops_u8, out=None, keep=False, concat=False, I_can=None, concat_out=None):
         """crops_u8 (B,512,512,3) or (B,256,256,3) u8: the cropper's crops of B driving frames
-        -> {"frames": (B,Ho,Wo,3) u8[, "crops_out" (B,512,512,3) u8, "x_t" (B,21,3), "I" (B,3,256,256) with keep=True]}"""
+        concat=True: also the frames of the pipeline's side-by-side video (:328, video.py:84-109), "concat" (B,512,1536,3) u8 (into concat_out):
+        driving crop | I_can | I_p, the one I_can (512,512,3) u8 shown in every frame: set_source's by default, I_can= otherwise (after
+        load_source_state, which carries no picture, it has to be given).
+        -> {"frames": (B,Ho,Wo,3) u8[, "concat"][, "crops_out" (B,512,512,3) u8, "x_t" (B,21,3), "I" (B,3,256,256) with keep=True]}"""
         e = self.e
+        if concat:
+            self._check_stageable()
+            ic = self._I_can if I_can is None else torch.as_tensor(I_can)
+            if ic is None:
+                raise RuntimeError("AnimateChain: concat=True after load_source_state needs I_can= (the state holds no picture of its source)")
+            ic = ic[None] if ic.dim() == 3 else ic
+            if ic.dtype != torch.uint8 or tuple(ic.shape) != (1, 512, 512, 3):
+                raise ValueError("I_can: expected ONE (512, 512, 3) uint8 image")
         slot, (I, x_t) = self._resolve(crops_u8)
         src = self._src
         B = I.shape[0]
@@ -323,6 +361,8 @@ class AnimateChain(_StagedChain):
         frames = tail.paste_back_shared(e, gen, src["M_c2o"], src["img_ori"], src["mask_ori"], out=out)  # :317-321
         self._release(slot)
         res = {"frames": frames}
+        if concat:
+            res["concat"] = self._concat(crops_u8, [(ic, 0, 1)], gen, concat_out)                       # :328
         if keep:
             res.update(crops_out=gen, x_t=x_t, I=I)
         return res

@@ -252,6 +252,7 @@ int launch_crop_batch(const unsigned char* frames, int Ho, int Wo, const double*
 int launch_face_masks(const float* logits, int B, int C, int h, int w, int scale, unsigned valid_bits, unsigned char* masks, unsigned char* labels,
                       hipStream_t st);
 int launch_parser_input(const unsigned char* crops, int B, int Hc, int Wc, int halve, const float* lut, float* pv, unsigned char* u8, hipStream_t st);
+int launch_concat_frames(const void* const* panels, const int* kinds, const int* shared, int B, int P, int S, unsigned char* out, hipStream_t st);
 
 // ---- motion extractor pieces (motion.hip)
 int launch_m_keypoints(const float* raw, float* x_t, float* x_can, float* rot, int N, hipStream_t st);

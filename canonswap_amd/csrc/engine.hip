@@ -22,7 +22,7 @@ void cs_set_error(const char* fmt, ...)
     va_end(ap);
 }
 extern "C" const char* cs_last_error(void) { return g_err; }
-// 4, unchanged: cs_resize_half_bilinear, cs_motion_keypoints_driven, cs_paste_back_shared (the v2i device-side frame) cs_crop_frames (the crop in front of both chains), cs_face_masks (the parser's logits -> 0/1 masks) and cs_parser_input (crops -> the parser's pixel_values) were added; new entry points
+// 4, unchanged: cs_resize_half_bilinear, cs_motion_keypoints_driven, cs_paste_back_shared (the v2i device-side frame) cs_crop_frames (the crop in front of both chains), cs_face_masks (the parser's logits -> 0/1 masks), cs_parser_input (crops -> the parser's pixel_values) and cs_concat_frames (the side-by-side video frame) were added; new entry points
 // alone change no struct, no existing entry point's meaning and no blob format, which is what the header bumps the version for.
 // 4 (round 6): cs_soft_erosion_frames, cs_paste_back_batch, cs_motion_keypoints.
 // 3 (round 4): cs_conv_desc grew (hilo, stat_out, xf_*, ep_general), cs_op_conv takes conv_halo / vol32 / conv_wide configurations only, the
@@ -1769,6 +1769,27 @@ extern "C" int cs_parser_input(cs_engine* e, int B, const uint8_t* crops, int Hc
     DevGuard guard(e->dev);
     hipStream_t st = (hipStream_t)stream;
     return e->run(1, st, [&] { return launch_parser_input(crops, B, Hc, Wc, halve, lut, pixel_values, resized_u8, st); }, "parser_input");
+}
+
+// ---- the side-by-side video frame (src/utils/video.py:84-109; can_swap_pipeline_e2e.py:290, can_swap_pipeline_v2i.py:328): everything is refused
+// before any launch
+extern "C" int cs_concat_frames(cs_engine* e, int B, int P, int S, const void* const* panels, const int* kinds, const int* shared, uint8_t* out,
+                                void* stream)
+{
+    if (!e || !out || !panels || !kinds || !shared) {
+        cs_set_error("cs_concat_frames: NULL %s", !e ? "engine" : !out ? "out" : !panels ? "panels" : !kinds ? "kinds" : "shared");
+        return -1;
+    }
+    if (B < 1) { cs_set_error("cs_concat_frames: B = %d (at least 1)", B); return -1; }
+    if (P < 1 || P > 4) { cs_set_error("cs_concat_frames: P = %d (1 to 4 panels)", P); return -1; }
+    if (S < 4 || S % 4 || S > 16384) { cs_set_error("cs_concat_frames: S = %d (a multiple of 4 from 4 to 16384)", S); return -1; }
+    for (int p = 0; p < P; ++p) {
+        if (kinds[p] < 0 || kinds[p] > 3) { cs_set_error("cs_concat_frames: kind %d of panel %d (0 to 3)", kinds[p], p); return -1; }
+        if (!panels[p]) { cs_set_error("cs_concat_frames: NULL panel %d", p); return -1; }
+    }
+    DevGuard guard(e->dev);
+    hipStream_t st = (hipStream_t)stream;
+    return e->run(1, st, [&] { return launch_concat_frames(panels, kinds, shared, B, P, S, out, st); }, "concat_frames");
 }
 
 extern "C" int cs_profile_begin(cs_engine* e)

@@ -6,6 +6,7 @@
 //   * the crop itself: cv2.warpAffine of the frame into the crop's frame (src/utils/crop.py:429-455, src/utils/cropper.py:196-209).
 //   * the face parser's input: cv2.resize to one half + SegformerImageProcessor (PIL resize x 2, rescale, normalize) of a crop
 //     (src/can_swap_pipeline_e2e.py:171, 180, src/can_swap_pipeline_v2i.py:73).
+//   * the side-by-side video frame: concat_frames (src/utils/video.py:84-109; src/can_swap_pipeline_e2e.py:290, src/can_swap_pipeline_v2i.py:328).
 // All of them are HBM-bound byte / float work: one thread per output pixel, coalesced along the row.  The OpenCV steps follow
 // OpenCV's published fixed-point algorithm (restated in oracle/cv_ref.py, which the tests compare against bit for bit).
 #include "common.h"
@@ -921,6 +922,167 @@ int launch_parser_input(const unsigned char* crops, int B, int Hc, int Wc, int h
         if (halve) hipLaunchKernelGGL(parser_input_kernel<true>, grid, block, 0, st, c, Hc, Wc, lut, p, u, tiles_x, wide_f, wide_u);
         else hipLaunchKernelGGL(parser_input_kernel<false>, grid, block, 0, st, c, Hc, Wc, lut, p, u, tiles_x, wide_f, wide_u);
         LAUNCH_CHECK("parser_input");
+    }
+    return 0;
+}
+
+// ---------------------------------------------------------------------------------------------- the side-by-side ("concat") frame
+// concat_frames of src/utils/video.py:84-109 (src/can_swap_pipeline_e2e.py:290: driving | rec_can | I_can | I_p; src/can_swap_pipeline_v2i.py:328:
+// driving | I_can | I_p) for B frames in one launch: P panels, each brought to S x S uint8, side by side in out (B, S, P S, 3).  Panel kinds:
+//   0  u8 HWC S x S: copied (cv2.resize to the size the image has is the identity);
+//   1  u8 HWC S/2 x S/2: cv2.resize(img, (S, S)), INTER_LINEAR, OpenCV's 8-bit path (11-bit coefficients: at exactly x2 the weights are 512 and
+//      1536 of 2048).  Horizontal pass into int32: H[2j] = 512 s[j-1] + 1536 s[j], H[2j+1] = 1536 s[j] + 512 s[j+1], a tap beyond either border
+//      replaced by the border sample (2048 s[0], 2048 s[w-1]).  Vertical pass: row 2i from rows (max(i-1, 0), i) with (b0, b1) = (512, 1536),
+//      row 2i+1 from rows (i, min(i+1, h-1)) with (1536, 512); dst = (((b0 (H0 >> 4)) >> 16) + ((b1 (H1 >> 4)) >> 16) + 2) >> 2, truncations and all.
+//   2  u8 HWC S x S: cv2.resize to one half first, (a + b + c + d + 2) >> 2 per 2 x 2 block (can_swap_pipeline_e2e.py:171: the pipeline's driving
+//      crop is the halved 512 crop; parser_input_kernel's HALVE), then kind 1, with no half-size image in memory;
+//   3  fp32 CHW 3 x S x S: parse_output (can_swap_e2e.py:314-322), pack_u8_kernel's expression: clip(x, 0, 1) * 255, clip(., 0, 255), truncate.
+// PARITY UNPINNED: kinds 1 and 2 restate OpenCV's published arithmetic (tests/concat_ref.py is the same restatement in numpy); no vectors of
+// cv2's own were at hand.
+// A thread owns four consecutive pixels of one panel row: 12 output bytes, three dword stores, consecutive threads consecutive addresses (the
+// output row runs through the panels, so thread t of a frame writes bytes 12 t ... 12 t + 11 of it).  At S = 512 a panel row is two waves: no
+// wave straddles two panels, the branch on the kind is uniform.  Kind 3 reads one float4 per channel plane, the uint8 kinds aligned dwords.
+// Purely bandwidth bound (e2e arrangement at B = 64: 0.65 GB read, 0.2 GB written); no LDS, no scratch.
+struct ConcatPanels {
+    const unsigned char* ptr[4];      // the panel's first image
+    long step[4];                     // bytes from one frame's image to the next; 0: one image shared by all frames
+    uintptr_t lo[4], hi[4];           // the aligned dwords that hold the first and the last byte of the panel's buffer: uint8 loads stay between them
+    int kind[4];
+    int vec[4];                       // kind 3: the planes are 16-byte aligned, float4 loads
+};
+
+// N bytes from address a as N / 4 dwords: aligned dword loads, funnel-shifted.  The dword addresses are clamped to [lo, hi], so a neighbour
+// column beyond the image's border - whose value the caller replaces by the border sample - never reads outside the panel's buffer.
+template <int N> __device__ __forceinline__ void load_bytes(uintptr_t a, uintptr_t lo, uintptr_t hi, unsigned (&d)[N / 4])
+{
+    const unsigned sh = 8u * (unsigned)(a & 3);
+    const uintptr_t q = a & ~(uintptr_t)3;
+    unsigned w[N / 4 + 1];
+#pragma unroll
+    for (int k = 0; k < N / 4; ++k) w[k] = *(const unsigned*)min(max(q + 4 * k, lo), hi);
+    w[N / 4] = sh ? *(const unsigned*)min(max(q + N, lo), hi) : 0u;
+#pragma unroll
+    for (int k = 0; k < N / 4; ++k) d[k] = sh ? (w[k] >> sh) | (w[k + 1] << (32u - sh)) : w[k];
+}
+
+__device__ __forceinline__ int byte_of(const unsigned* d, int k) { return (int)((d[k >> 2] >> (8 * (k & 3))) & 255u); }
+
+// (H >> 4) of the horizontal pass for the thread's four output pixels (x 3 channels, in output byte order) of half-size row r: source
+// columns 2g - 1 .. 2g + 2, the first / last replaced by its neighbour at the image's border.  HALVE: the half-size row is the 2 x 2 mean of
+// rows 2r, 2r + 1 of the S x S image.
+template <bool HALVE>
+__device__ __forceinline__ void concat_hrow(const unsigned char* img, int r, int g, int S, uintptr_t lo, uintptr_t hi, int (&hq)[12])
+{
+    int s[4][3];
+    if (HALVE) {
+        unsigned a[6], b[6];
+        const uintptr_t p = (uintptr_t)img + ((long)(2 * r) * S + 4 * g - 2) * 3;
+        load_bytes<24>(p, lo, hi, a);
+        load_bytes<24>(p + (long)S * 3, lo, hi, b);
+#pragma unroll
+        for (int k = 0; k < 4; ++k)
+#pragma unroll
+            for (int c = 0; c < 3; ++c) s[k][c] = (byte_of(a, 6 * k + c) + byte_of(a, 6 * k + 3 + c) + byte_of(b, 6 * k + c) + byte_of(b, 6 * k + 3 + c) + 2) >> 2;
+    } else {
+        unsigned a[3];
+        load_bytes<12>((uintptr_t)img + ((long)r * (S >> 1) + 2 * g - 1) * 3, lo, hi, a);
+#pragma unroll
+        for (int k = 0; k < 4; ++k)
+#pragma unroll
+            for (int c = 0; c < 3; ++c) s[k][c] = byte_of(a, 3 * k + c);
+    }
+    const bool first = g == 0, last = g == (S >> 2) - 1;
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+        const int s0 = first ? s[1][c] : s[0][c], s1 = s[1][c], s2 = s[2][c], s3 = last ? s[2][c] : s[3][c];
+        hq[c] = (512 * s0 + 1536 * s1) >> 4;
+        hq[3 + c] = (1536 * s1 + 512 * s2) >> 4;
+        hq[6 + c] = (512 * s1 + 1536 * s2) >> 4;
+        hq[9 + c] = (1536 * s2 + 512 * s3) >> 4;
+    }
+}
+
+__device__ __forceinline__ unsigned pack_byte(float v)      // pack_u8_kernel's expression (kernels.hip)
+{
+    v = fminf(fmaxf(v, 0.f), 1.f) * 255.f;
+    v = fminf(fmaxf(v, 0.f), 255.f);
+    return (unsigned)(uint8_t)v;
+}
+
+__global__ void __launch_bounds__(256) concat_frames_kernel(ConcatPanels pn, int P, int S, unsigned char* __restrict__ out, int wide_out)
+{
+    const int G = S >> 2, PG = P * G;                                   // groups of four pixels per panel row, per output row
+    const long per_frame = (long)S * PG;
+    const long t = (long)blockIdx.x * 256 + threadIdx.x;
+    if (t >= per_frame) return;
+    const long n = blockIdx.y;
+    const int y = (int)(t / PG), gr = (int)(t % PG), p = gr / G, g = gr % G;
+    const unsigned char* img = pn.ptr[0] + n * pn.step[0];
+    uintptr_t lo = pn.lo[0], hi = pn.hi[0];
+    int kind = pn.kind[0], vec = pn.vec[0];
+#pragma unroll
+    for (int q = 1; q < 4; ++q)
+        if (p == q) { img = pn.ptr[q] + n * pn.step[q]; lo = pn.lo[q]; hi = pn.hi[q]; kind = pn.kind[q]; vec = pn.vec[q]; }
+    unsigned o[3];
+    if (kind == 0) {
+        load_bytes<12>((uintptr_t)img + ((long)y * S + 4 * g) * 3, lo, hi, o);
+    } else if (kind == 3) {
+        const float* f = (const float*)img + (long)y * S + 4 * g;
+        const long plane = (long)S * S;
+        unsigned v[12];
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+            float4 x;
+            if (vec) x = *(const float4*)(f + c * plane);
+            else x = make_float4(f[c * plane], f[c * plane + 1], f[c * plane + 2], f[c * plane + 3]);
+            v[c] = pack_byte(x.x); v[3 + c] = pack_byte(x.y); v[6 + c] = pack_byte(x.z); v[9 + c] = pack_byte(x.w);
+        }
+#pragma unroll
+        for (int k = 0; k < 3; ++k) o[k] = v[4 * k] | v[4 * k + 1] << 8 | v[4 * k + 2] << 16 | v[4 * k + 3] << 24;
+    } else {
+        const int h = S >> 1, i = y >> 1, odd = y & 1;
+        const int r0 = odd ? i : max(i - 1, 0), r1 = odd ? min(i + 1, h - 1) : i, b0 = odd ? 1536 : 512, b1 = 2048 - b0;
+        int h0[12], h1[12];
+        if (kind == 2) { concat_hrow<true>(img, r0, g, S, lo, hi, h0); concat_hrow<true>(img, r1, g, S, lo, hi, h1); }
+        else { concat_hrow<false>(img, r0, g, S, lo, hi, h0); concat_hrow<false>(img, r1, g, S, lo, hi, h1); }
+        o[0] = o[1] = o[2] = 0u;
+#pragma unroll
+        for (int k = 0; k < 12; ++k) o[k >> 2] |= (unsigned)((((b0 * h0[k]) >> 16) + ((b1 * h1[k]) >> 16) + 2) >> 2) << (8 * (k & 3));
+    }
+    unsigned char* d = out + (n * per_frame + t) * 12;
+    if (wide_out) {
+        unsigned* dw = (unsigned*)d;
+        dw[0] = o[0]; dw[1] = o[1]; dw[2] = o[2];
+    } else {
+#pragma unroll
+        for (int k = 0; k < 12; ++k) d[k] = (unsigned char)byte_of(o, k);
+    }
+}
+
+// B >= 1, 1 <= P <= 4, S a multiple of 4 in [4, 16384], kinds in 0..3, no NULL pointer: the caller checks (cs_concat_frames).  Frames are
+// grid rows, 65535 of them per launch; every offset is 64-bit.  Buffers at any address: unaligned uint8 panels are read through the
+// funnel shift, an fp32 panel off 16 bytes or an out off 4 bytes takes element accesses with the same values.
+int launch_concat_frames(const void* const* panels, const int* kinds, const int* shared, int B, int P, int S, unsigned char* out, hipStream_t st)
+{
+    ConcatPanels pn = {};
+    const long px = (long)S * S;
+    long img[4] = {0, 0, 0, 0};
+    for (int p = 0; p < P; ++p) {
+        img[p] = kinds[p] == 1 ? px * 3 / 4 : kinds[p] == 3 ? px * 12 : px * 3;
+        const uintptr_t a = (uintptr_t)panels[p];
+        pn.step[p] = shared[p] ? 0 : img[p];
+        pn.lo[p] = a & ~(uintptr_t)3;
+        pn.hi[p] = (a + (uintptr_t)(shared[p] ? img[p] : (long)B * img[p]) - 1) & ~(uintptr_t)3;
+        pn.kind[p] = kinds[p];
+        pn.vec[p] = (a & 15) == 0;
+    }
+    const long per_frame = px / 4 * P;
+    const int wide_out = ((uintptr_t)out & 3) == 0;
+    for (int b0 = 0; b0 < B; b0 += 65535) {
+        for (int p = 0; p < P; ++p) pn.ptr[p] = (const unsigned char*)panels[p] + (long)b0 * pn.step[p];
+        const dim3 grid((unsigned)((per_frame + 255) / 256), (unsigned)(B - b0 < 65535 ? B - b0 : 65535)), block(256);
+        hipLaunchKernelGGL(concat_frames_kernel, grid, block, 0, st, pn, P, S, out + (long)b0 * per_frame * 12, wide_out);
+        LAUNCH_CHECK("concat_frames");
     }
     return 0;
 }

@@ -266,10 +266,12 @@ class Engine:
         return out
 
     def swap_frames(self, img, x_t, x_can, source_id=None, want_f32=True, want_u8=False, debug=False,
-                    out_f32=None, out_u8=None, slots=None):
+                    out_f32=None, out_u8=None, slots=None, out_rec=None, out_swap=None):
         """Whole loop body of can_swap_pipeline_e2e.py:242-263 for B frames, on device.
         slots: identity slot per frame (ints, set with set_identity) instead of `source_id` rows - no identity lookup at all
-        (multi-stream callers that placed their identities themselves)."""
+        (multi-stream callers that placed their identities themselves).
+        debug: also the two canonical-space decodes of :248-250 and :257-259, "rec_can" and "swap_can" (B,3,512,512) fp32; out_rec / out_swap:
+        the caller's buffers for them (either one asks for its decode, with or without debug)."""
         img = self._in(img, (3, 256, 256)); x_t = self._in(x_t, (21, 3)); x_can = self._in(x_can, (21, 3))
         self._same_batch(img, x_t, x_can)
         B = img.shape[0]
@@ -281,12 +283,12 @@ class Engine:
             slots = self.identity_slots(source_id, B) if source_id is not None else self._default_slots(B)
         out_f32 = self._out(out_f32, (B, 3, 512, 512), torch.float32) if (want_f32 or out_f32 is not None) else None
         out_u8 = self._out(out_u8, (B, 512, 512, 3), torch.uint8) if (want_u8 or out_u8 is not None) else None
-        rec = self._new(B, 3, 512, 512) if debug else None
-        swp = self._new(B, 3, 512, 512) if debug else None
+        rec = self._out(out_rec, (B, 3, 512, 512), torch.float32) if (debug or out_rec is not None) else None
+        swp = self._out(out_swap, (B, 3, 512, 512), torch.float32) if (debug or out_swap is not None) else None
         _lib.check(self.lib.cs_swap_frames_ids(self.h, self._slot_array(slots), B, _ptr(img), _ptr(x_t), _ptr(x_can), _ptr(out_f32),
                                                _ptr(out_u8), _ptr(rec), _ptr(swp), self._stream()), "cs_swap_frames_ids")
         res = {"out": out_f32, "out_u8": out_u8}
-        if debug:
+        if debug or rec is not None or swp is not None:
             res.update(rec_can=rec, swap_can=swp)
         return res
 

@@ -7,6 +7,8 @@ per-frame loop (src/can_swap_pipeline_e2e.py:223-283) no longer leaves the GPU b
                              (F.interpolate to 512 x 512, argmax, isin) of B frames in one launch, nothing up-sampled in memory
 * ``parser_input``           src/can_swap_pipeline_e2e.py:171 + :180, src/can_swap_pipeline_v2i.py:73: crops -> the face parser's pixel_values
                              (cv2.resize to one half, SegformerImageProcessor's PIL resize x 2, rescale, normalize, CHW) of B crops in one launch
+* ``concat_frames``          src/utils/video.py:84-109 (called at src/can_swap_pipeline_e2e.py:290, src/can_swap_pipeline_v2i.py:328): the side-by-side
+                             video frame, up to four panels resized / packed to S x S uint8 and stacked left to right, B frames in one launch
 * ``SoftErosion``            src/utils/crop.py:21-47            (the reference runs it with .cuda() too: pure torch)
 * ``prepare_paste_back``     src/utils/crop.py:515-521          (cv2.warpAffine of the float mask)
 * ``paste_back``             src/utils/crop.py:523-529          (cv2.warpAffine of the crop + blend)
@@ -151,6 +153,63 @@ def parser_input(e: Engine, crops_u8, halve=None, mean=PARSER_MEAN, std=PARSER_S
     with torch.cuda.device(e.device):
         _lib.check(e.lib.cs_parser_input(e.h, B, _ptr(t), H, W, int(halve), _ptr(lut), _ptr(pv), _ptr(u8), e._stream()), "cs_parser_input")
     return {"pixel_values": pv, "resized_u8": u8} if want_u8 else pv
+
+
+CONCAT_KINDS = (0, 1, 2, 3)      # cs_concat_frames: u8 S x S as it is; u8 S/2 x S/2, cv2.resize x 2; u8 S x S halved, then x 2; fp32 3 x S x S, parse_output
+
+
+def concat_frames(e: Engine, panels, kinds=None, shared=None, out=None):
+    """concat_frames of src/utils/video.py:84-109 (can_swap_pipeline_e2e.py:290: driving | rec_can | I_can | I_p; can_swap_pipeline_v2i.py:328:
+    driving | I_can | I_p) for B frames in one launch: panels, 1 to 4 images per frame, left to right -> (B, S, P * S, 3) uint8 on the device.
+    A panel is (n,H,W,3) / (H,W,3) uint8 or (n,3,H,W) / (3,H,W) fp32, host or device, square; its kind (CONCAT_KINDS; cs_concat_frames in
+    include/canonswap_hip.h) is by default 3 for fp32 (parse_output), and for uint8 0 where its side is S (a copy) and 1 where it is S / 2
+    (cv2.resize(img, (S, S)), INTER_LINEAR, OpenCV's 8-bit arithmetic), S being the largest side among the panels; kind 2 (S x S uint8: cv2.resize to
+    one half first, can_swap_pipeline_e2e.py:171, then kind 1) is the caller's to name in kinds=.  B is the largest n; a panel with n = 1 beside
+    others with more is shared by all frames (shared=: one flag per panel, to say so explicitly).  No engine scratch, no allocation but the
+    result: it may run on the caller's stream while a prefetch is in flight."""
+    ts = [torch.as_tensor(p) for p in panels]
+    P = len(ts)
+    if not 1 <= P <= 4:
+        raise ValueError(f"concat_frames: {P} panels (1 to 4)")
+    if kinds is not None and (len(kinds) != P or any(k not in CONCAT_KINDS for k in kinds)):
+        raise ValueError(f"concat_frames: kinds {tuple(kinds)}: one of {CONCAT_KINDS} per panel")
+    if shared is not None and len(shared) != P:
+        raise ValueError("concat_frames: shared holds one flag per panel")
+    sides = []
+    for i, t in enumerate(ts):
+        if t.dtype not in (torch.uint8, torch.float32) or t.dim() not in (3, 4):
+            raise ValueError(f"concat_frames: panel {i} is neither uint8 (n,H,W,3) nor fp32 (n,3,H,W)")
+        if t.dim() == 3:
+            t = ts[i] = t[None]
+        side, ch = (t.shape[1:3], t.shape[3]) if t.dtype == torch.uint8 else (t.shape[2:4], t.shape[1])
+        if ch != 3 or side[0] != side[1] or side[0] < 1 or t.shape[0] < 1:
+            raise ValueError(f"concat_frames: panel {i} has shape {tuple(t.shape)}, not B square three-channel images")
+        if kinds is not None and (kinds[i] == 3) != (t.dtype == torch.float32):
+            raise ValueError(f"concat_frames: panel {i} is {t.dtype}, its kind {kinds[i]}")
+        sides.append(int(side[0]))
+    if kinds is None:
+        S = max(sides)
+        kinds = [3 if t.dtype == torch.float32 else 0 if n == S else 1 for t, n in zip(ts, sides)]
+    else:
+        kinds = [int(k) for k in kinds]
+        S = sides[0] * (2 if kinds[0] == 1 else 1)
+    if any(n * (2 if k == 1 else 1) != S for n, k in zip(sides, kinds)):
+        raise ValueError(f"concat_frames: panels of sides {sides} and kinds {kinds} do not come to one size")
+    if S < 4 or S % 4 or S > 16384:
+        raise ValueError(f"concat_frames: panel size {S} (a multiple of 4 from 4 to 16384)")
+    B = max(t.shape[0] for t in ts)
+    if shared is None:
+        shared = [t.shape[0] == 1 and B > 1 for t in ts]
+    shared = [int(bool(f)) for f in shared]
+    if any(t.shape[0] != (1 if f else B) for t, f in zip(ts, shared)):
+        raise ValueError(f"concat_frames: panels hold {[t.shape[0] for t in ts]} images: B = {B}, or one where shared")
+    ts = [t.to(e.device).contiguous() for t in ts]
+    out = e._out(out, (B, S, P * S, 3), torch.uint8)
+    ptrs = (C.c_void_p * P)(*[t.data_ptr() for t in ts])
+    with torch.cuda.device(e.device):
+        _lib.check(e.lib.cs_concat_frames(e.h, B, P, S, ptrs, (C.c_int * P)(*kinds), (C.c_int * P)(*shared), _ptr(out), e._stream()),
+                   "cs_concat_frames")
+    return out
 
 
 class SoftErosion:

@@ -196,6 +196,26 @@ int cs_face_masks(cs_engine* e, int B, int C, const float* logits, int h, int w,
 int cs_parser_input(cs_engine* e, int B, const uint8_t* crops, int Hc, int Wc, int halve, const float* lut, float* pixel_values,
                     uint8_t* resized_u8, void* stream);
 
+/* ---- the side-by-side ("concat") video frame, behind both chains ---- */
+/* concat_frames of src/utils/video.py:84-109, the video both pipelines write unconditionally (can_swap_pipeline_e2e.py:290: driving crop | rec_can
+ * (:248-250) | I_can (:257-259) | I_p; can_swap_pipeline_v2i.py:328: driving crop | I_can | I_p), for B frames in one launch: P panels per frame,
+ * each brought to S x S uint8, left to right in out BxSx(P S)x3 u8 (np.hstack).  panels, kinds, shared: HOST arrays of P entries; panels[p]: DEVICE
+ * pointer to B images of the panel, or to ONE image shown in every frame where shared[p] != 0 (v2i's single I_can).  kinds[p]:
+ *   0  u8 HWC SxS: copied (cv2.resize to the size the image has is the identity);
+ *   1  u8 HWC (S/2)x(S/2): cv2.resize(img, (S, S)), default INTER_LINEAR, OpenCV's 8-bit arithmetic with 11-bit coefficients, at exactly x2
+ *      (weights 512 and 1536 of 2048).  Horizontal pass into int32: H[2j] = 512 s[j-1] + 1536 s[j], H[2j+1] = 1536 s[j] + 512 s[j+1], at the
+ *      borders H[0] = 2048 s[0], H[2w-1] = 2048 s[w-1].  Vertical pass: row 2i from rows (max(i-1, 0), i) with (b0, b1) = (512, 1536), row
+ *      2i+1 from rows (i, min(i+1, h-1)) with (1536, 512): dst = (((b0 (H0 >> 4)) >> 16) + ((b1 (H1 >> 4)) >> 16) + 2) >> 2;
+ *   2  u8 HWC SxS: cv2.resize to one half first, (a + b + c + d + 2) >> 2 per 2x2 block (can_swap_pipeline_e2e.py:171: the pipeline's driving
+ *      crop is the halved 512 crop, and the concat resizes that back up), then kind 1, without the half-size image in memory;
+ *   3  fp32 CHW 3xSxS: parse_output (can_swap_e2e.py:314-322; cs_pack_u8's arithmetic): clip(x, 0, 1) * 255, clip(., 0, 255), truncated.
+ * PARITY UNPINNED for kinds 1 and 2: the arithmetic is OpenCV's as published, not checked against vectors of cv2's own.
+ * Any B >= 1 (not bound to max_batch); asynchronous on the stream, no engine scratch, allocates nothing: it may run beside a prefetch on
+ * another stream.  Returns nonzero and sets cs_last_error() before any launch for a NULL e, out, array or panel pointer, B < 1, P outside
+ * 1..4, a kind outside 0..3, or S below 4, above 16384 or no multiple of 4 (a thread owns four pixels). */
+int cs_concat_frames(cs_engine* e, int B, int P, int S, const void* const* panels, const int* kinds, const int* shared, uint8_t* out,
+                     void* stream);
+
 /* ---- measurement: per-kernel-family HIP-event timing on the launch stream */
 int cs_profile_begin(cs_engine* e);
 /* ms[0] = convolution kernels (conv_halo / conv_igemm), ms[1] = all other kernels except ms[2] = the feature warp
