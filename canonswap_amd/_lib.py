@@ -11,7 +11,7 @@ import subprocess
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
-SOURCES = [os.path.join(CSRC, f) for f in ("conv_halo.hip", "conv_wide.hip", "conv_lat.hip", "vol32.hip", "vol32_fused.hip", "kernels.hip", "motion.hip", "imgops.hip", "engine.hip")]
+SOURCES = [os.path.join(CSRC, f) for f in ("conv_halo.hip", "conv_wide.hip", "conv_lat.hip", "vol32.hip", "vol32_fused.hip", "kernels.hip", "motion.hip", "imgops.hip", "identity.hip", "engine.hip")]
 # test-only cross-check kernel (the first-generation implicit-GEMM conv): its own library, never linked into the product
 TEST_SRC = os.path.join(os.path.dirname(HERE), "tests", "csrc", "test_igemm.hip")
 TEST_LIB_PATH = os.path.join(os.path.dirname(HERE), "tests", "libcanonswap_test.so")
@@ -30,6 +30,7 @@ ABI_SYMBOLS = [
     "cs_op_t_style", "cs_op_t_modulate", "cs_op_t_read", "cs_op_t_layer",
     "cs_op_m_stem", "cs_op_m_dwln", "cs_op_m_ln_s2d", "cs_op_m_grn", "cs_op_m_head", "cs_op_m_pointwise",
     "cs_op_dm_compress", "cs_op_dm_sparse", "cs_op_dm_softmax_warp", "cs_op_occ_finish", "cs_op_dm_read",
+    "cs_identity", "cs_identity_u8", "cs_op_identity_read", "cs_op_id_conv", "cs_op_id_maxpool", "cs_op_id_se_tail", "cs_op_id_embed",
 ]
 ABI_VERSION = 4          # CS_ABI_VERSION of include/canonswap_hip.h
 HIPCC_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wno-unused-value"]
@@ -433,6 +434,13 @@ def load():
     lib.cs_op_dm_softmax_warp.argtypes = [vp, vp, vp, vp, ci, vp, ci, vp, vp, vp, ci, ci, ci, ci, vp]
     lib.cs_op_occ_finish.argtypes = [vp, ci, cf, vp, ci, ci, ci, vp]
     lib.cs_op_dm_read.argtypes = [vp, ci, ci, vp, vp]
+    lib.cs_identity.argtypes = [vp, ci, vp, ci, ci, vp, vp, vp]
+    lib.cs_identity_u8.argtypes = [vp, ci, vp, ci, ci, vp, vp, vp, vp]
+    lib.cs_op_identity_read.argtypes = [vp, ci, ci, vp, vp]
+    lib.cs_op_id_conv.argtypes = [vp, ci, ci, ci, ci, ci, ci, ci, ci, vp, vp, ci, vp, vp, ci, vp]
+    lib.cs_op_id_maxpool.argtypes = [vp, vp, vp, vp, vp, ci, ci, ci, ci, vp]
+    lib.cs_op_id_se_tail.argtypes = [vp, C.c_long, C.c_long, C.c_long, ci, ci, ci, ci, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
+    lib.cs_op_id_embed.argtypes = [vp, vp, vp, vp, vp, vp, ci, vp]
     lib.cs_op_resblock3d.argtypes = [vp, vp, vp, vp, ci, ci, ci, vp, vp, vp, vp, vp, vp, ci, cf, vp]
     lib.cs_op_chan_stats_partial_floats.argtypes = [ci, C.c_long, ci]
     lib.cs_op_chan_stats_partial_floats.restype = C.c_long

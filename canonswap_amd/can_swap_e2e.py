@@ -5,10 +5,11 @@ Same constructor argument, attribute names, method names and tensor signatures a
 operation is executed by the gfx950 HIP engine (libcanonswap_hip.so) -- there is no PyTorch or CPU fallback.
 Stage attributes (``warping_module``, ``swap_module`` ...) are small callables bound to the C ABI.
 
-The motion extractor M runs on the engine too (``get_kp_info``).  The ArcFace identity network
-behind ``getid`` (can_swap_e2e.py:80-84,102-107: a pickled third-party module, ``pretrained_weights/arcface_checkpoint.tar``) is
-outside the generator path: ``getid`` keeps the reference's arithmetic (nearest resize to 112x112, network, L2 normalisation)
-around a network the caller injects (``id_net=`` or ``can_swapper.netArc = ...``) and raises if there is none.
+The motion extractor M runs on the engine too (``get_kp_info``), and so does the ArcFace identity network
+behind ``getid`` (can_swap_e2e.py:80-84,102-107: a pickled third-party module, ``pretrained_weights/arcface_checkpoint.tar``) when its
+state-dict is among the weights (``state_dicts["arcface"]``, or ``id_on_engine=True`` to move an injected / file-loaded module there).
+A torch module the caller injects (``id_net=`` or ``can_swapper.netArc = ...``) keeps precedence: ``getid`` then runs the reference's
+arithmetic (nearest resize to 112x112, network, L2 normalisation) around it; with neither a module nor the weights it raises.
 """
 from __future__ import annotations
 
@@ -18,7 +19,7 @@ import os
 import numpy as np
 import torch
 
-from . import tail
+from . import pack, tail
 from .engine import Engine
 
 
@@ -54,9 +55,11 @@ class can_swapper(object):
     """MI355X engine behind the reference's ``can_swapper`` interface."""
 
     def __init__(self, inference_cfg=None, state_dicts=None, max_batch: int = 8, id_net=None, latency_mode: bool = False,
-                 packed_blobs=None):
+                 packed_blobs=None, id_on_engine: bool = False):
         """packed_blobs: the result of pack.build_blobs() for the same state-dicts, when another process of this node already ran the
-        load-time weight transform (engine.load_blobs)."""
+        load-time weight transform (engine.load_blobs).
+        id_on_engine: run getid on the engine with the weights of id_net (or of the module loaded from arcface_checkpoint.tar): its
+        state_dict() joins the state-dicts as "arcface" and the torch module is dropped."""
         self.inference_cfg = inference_cfg
         self.device_id = getattr(inference_cfg, "device_id", 0)
         self.compile = False                      # torch.compile switch of the reference (:47,:74-77) has no meaning here
@@ -76,7 +79,23 @@ class can_swapper(object):
         arc = "pretrained_weights/arcface_checkpoint.tar"
         if self.netArc is None and os.path.exists(arc):
             self.netArc = torch.load(arc, map_location=torch.device("cpu"), weights_only=False).to(self.device).eval()
+        self.id_on_engine = False
+        if id_on_engine:
+            if self.netArc is None:
+                raise RuntimeError("id_on_engine=True needs id_net= or pretrained_weights/arcface_checkpoint.tar")
+            arc_sd = self.netArc.state_dict()
+            self.netArc = None
+            if packed_blobs is not None:            # the generator's blobs came packed: pack the identity network beside them
+                packed_blobs = dict(packed_blobs)
+                pack._pack_A(packed_blobs, pack._np_sd(arc_sd))
+            else:
+                if state_dicts is None and os.path.exists("pretrained_weights/combined_weights.pth"):
+                    state_dicts = torch.load("pretrained_weights/combined_weights.pth", map_location=torch.device("cpu"))
+                if state_dicts is None:
+                    raise RuntimeError("id_on_engine=True: no generator weights to load the identity network with")
+                state_dicts = dict(state_dicts, arcface=arc_sd)
         if packed_blobs is not None:
+            self.id_on_engine = any(k.startswith("A.") for k in packed_blobs)
             if any(k.startswith("M.") for k in packed_blobs):
                 self.motion_extractor = _Callable(self.engine.motion_extract)
             self.engine.load_blobs(packed_blobs)
@@ -96,6 +115,9 @@ class can_swapper(object):
         if "motion_extractor" in combined:
             keys.append("motion_extractor")
             self.motion_extractor = _Callable(self.engine.motion_extract)
+        if "arcface" in combined:
+            keys.append("arcface")
+        self.id_on_engine = "arcface" in combined
         self.engine.load_state_dicts({k: combined[k] for k in keys})
 
     # ---- small helpers kept for interface parity
@@ -108,7 +130,10 @@ class can_swapper(object):
                 setattr(self.inference_cfg, k, v)
 
     def getid(self, img):
-        """can_swap_e2e.py:102-107: F.interpolate(img, (112, 112)) [nearest] -> netArc -> L2-normalised (B, 512) identity."""
+        """can_swap_e2e.py:102-107: F.interpolate(img, (112, 112)) [nearest] -> netArc -> L2-normalised (B, 512) identity.  A torch module in
+        self.netArc runs as in the reference; without one the engine runs the network if it holds the "arcface" weights."""
+        if self.netArc is None and getattr(self, "id_on_engine", False):
+            return self.engine.identity(img)
         if self.netArc is None:
             raise RuntimeError("getid: no identity network (pass id_net= to can_swapper or set .netArc; the reference loads "
                                "pretrained_weights/arcface_checkpoint.tar, which is outside the generator path)")
@@ -117,6 +142,16 @@ class can_swapper(object):
             out = self.netArc(x)
             idv = out[0] if isinstance(out, (tuple, list)) else out
             return torch.nn.functional.normalize(idv, p=2, dim=1)
+
+    def getid_crops(self, crops_u8):
+        """ID_transform + getid (can_swap_pipeline_e2e.py:43-46,97-98) for aligned uint8 crops (B,H,W,3) or (H,W,3), host or device -> (B, 512)."""
+        if self.netArc is None and getattr(self, "id_on_engine", False):
+            return self.engine.identity_u8(crops_u8)
+        t = torch.as_tensor(crops_u8)
+        t = (t[None] if t.dim() == 3 else t).to(self.device)
+        lut = tail.id_lut_on(self.engine)                      # (3, 256): ToTensor + Normalize per byte value
+        x = torch.stack([lut[c][t[..., c].long()] for c in range(3)], dim=1)
+        return self.getid(x)
 
     def get_kp_info(self, x, **kwargs):
         """can_swap_e2e.py:174-199: implicit key-point information of Bx3x256x256 images in [0,1]."""

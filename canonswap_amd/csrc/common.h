@@ -262,3 +262,45 @@ int launch_m_dwln(const float* x, const float* wt, const float* b, const float* 
 int launch_m_ln_s2d(const float* x, const float* g, const float* be, half_t* y, int N, int H, int W, int C, hipStream_t st);
 int launch_m_grn(const float* h, const float* gamma, const float* beta, float* sumsq, float* scale, half_t* out, int N, int P, int C, hipStream_t st);
 int launch_m_head(const float* x, const float* g, const float* be, const float* hw, const float* hb, float* out, int N, int P, hipStream_t st);
+
+// ---- the ArcFace identity network behind getid (identity.hip; models/arcface_models.py:10-136)
+// One convolution of it: fp16 (or fp32, converted on load) contiguous [N][IH][IW][Cin] -> [N][OH][OW][Cout] (fp32 or fp16) = prelu(conv + bias),
+// K x K taps (1 or 3), any stride, zero padding; w fp16 [K * K][Cout][Cin] (pack.pack_id_conv); Cin % 32 == 0, Cout % 64 == 0; slope: device
+// pointer to the PReLU's shared slope, nullptr = no activation.
+struct IdConvCall {
+    const void* in; int in_f32;
+    int N, IH, IW, Cin, OH, OW, stride, pad, K;
+    const half_t* w; const float* bias; int Cout;
+    const float* slope;
+    void* out; int out_f32;
+};
+constexpr int IDNET_DEPTH[4] = {3, 4, 14, 3}, IDNET_C[4] = {64, 128, 256, 512}, IDNET_HW[4] = {55, 28, 14, 7};
+struct IdBlock {          // IRBlock: (s0, t0) = bn0; bn1 / bn2 folded into (w1, b1) / (w2, b2); wd: downsample conv + BN, or nullptr
+    const float *s0, *t0; const half_t *w1, *w2, *wd; const float *b1, *b2, *bd;
+    const float *se_w1, *se_b1, *se_w2, *se_b2;
+    int cin, cout, stride;
+};
+struct IdNet {
+    bool present = false;
+    int cap = 0, lastB = 0;          // images per pass (the workspace's size); images of the last pass
+    const half_t* stem_w = nullptr; const float* stem_b = nullptr;
+    const float* slopes = nullptr;   // [1 + 2 * 24]: stem, then (block PReLU, SE PReLU) per block
+    IdBlock blk[24];
+    const float *post_s = nullptr, *post_t = nullptr;      // the net's bn2, applied by the last block's tail
+    const half_t* fc_w = nullptr; const float* fc_b = nullptr;
+    half_t *in16 = nullptr, *a16 = nullptr, *h16 = nullptr;
+    float *stem32 = nullptr, *stem_x = nullptr, *xs[4][2] = {}, *o32 = nullptr, *ds32 = nullptr, *se = nullptr, *part = nullptr;
+    const float* layer_x[4] = {};    // where the last pass left layer1 .. layer4
+};
+int launch_id_input(const float* img, const unsigned char* u8, const float* lut, half_t* out, int B, int H, int W, hipStream_t st);
+int launch_id_conv(const IdConvCall& c, hipStream_t st);
+int launch_id_maxpool(const float* in, const float* s, const float* t, float* x, half_t* a, int B, int IH, int IW, int C, hipStream_t st);
+int launch_id_se(const float* out, long sN, long sH, long sW, int B, int H, int W, int C, const float* w1, const float* b1, const float* slope,
+                 const float* w2, const float* b2, float* se, hipStream_t st);
+int launch_id_tail(const float* out, long sN, long sH, long sW, const float* se, const float* res, const float* slope, const float* s, const float* t,
+                   float* x, half_t* a, int B, int H, int W, int C, hipStream_t st);
+int launch_id_embed(const half_t* a, const half_t* w, const float* bias, float* part, float* raw, float* idn, int B, hipStream_t st);
+int launch_id_to_nchw(const void* in, int is_f16, float* out, int N, int C, int P, hipStream_t st);
+size_t idnet_workspace_bytes(int cap);
+void idnet_bind_workspace(IdNet& n, void* ws, int cap);
+int idnet_forward(IdNet& n, int B, float* idn, float* raw, hipStream_t st);

@@ -24,6 +24,8 @@ void cs_set_error(const char* fmt, ...)
 extern "C" const char* cs_last_error(void) { return g_err; }
 // 4, unchanged: cs_resize_half_bilinear, cs_motion_keypoints_driven, cs_paste_back_shared (the v2i device-side frame) cs_crop_frames (the crop in front of both chains), cs_face_masks (the parser's logits -> 0/1 masks), cs_parser_input (crops -> the parser's pixel_values) and cs_concat_frames (the side-by-side video frame) were added; new entry points
 // alone change no struct, no existing entry point's meaning and no blob format, which is what the header bumps the version for.
+// 4, unchanged: cs_identity, cs_identity_u8 (getid on the engine), cs_op_identity_read and cs_op_id_conv / cs_op_id_maxpool / cs_op_id_se_tail /
+// cs_op_id_embed (its kernels alone) were added; the optional "A.*" blobs are new names, no existing blob changed.
 // 4 (round 6): cs_soft_erosion_frames, cs_paste_back_batch, cs_motion_keypoints.
 // 3 (round 4): cs_conv_desc grew (hilo, stat_out, xf_*, ep_general), cs_op_conv takes conv_halo / vol32 / conv_wide configurations only, the
 // packed weight blobs of F.down0 / down1 / second carry [W_hi | W_lo], W.occ49 exists; cs_conv_desc::pool_hw.  _lib.load() refuses any other value.
@@ -106,6 +108,8 @@ struct cs_engine {
     float *m_x = nullptr, *m_sumsq = nullptr, *m_scale = nullptr;
     half_t *m_y = nullptr, *m_h = nullptr;   // split-precision GEMM operands [hi | lo]
     float* m_h32 = nullptr;
+    // ArcFace identity network (optional: present when the "A.*" blobs were uploaded); its workspace holds min(max_batch, 8) images per pass
+    IdNet idn;
     // soft-erosion scratch (allocated on first use for the largest B*H*W seen)
     float *se_a = nullptr, *se_b = nullptr, *se_part = nullptr; size_t se_cap = 0, se_part_cap = 0;      // se_part: 64 maxima per sample
 
@@ -1256,6 +1260,47 @@ extern "C" int cs_finalize_weights(cs_engine* e)
         TRY(get_f32(e, "M.norm.g", 768, &e->m_norm_g)); TRY(get_f32(e, "M.norm.b", 768, &e->m_norm_b));
         TRY(get_f32(e, "M.head.w", 328 * 768, &e->m_head_w)); TRY(get_f32(e, "M.head.b", 328, &e->m_head_b));
     }
+    // ---- A (optional): the identity network behind getid (pack.py _pack_A)
+    e->idn.present = e->find("A.stem.w") != nullptr;
+    if (e->idn.present) {
+        IdNet& A = e->idn;
+        const void* p;
+        TRY(need(e, "A.stem.w", (size_t)9 * 64 * 32 * 2, &p)); A.stem_w = (const half_t*)p;
+        TRY(get_f32(e, "A.stem.b", 64, &A.stem_b));
+        TRY(get_f32(e, "A.slopes", 49, &A.slopes));
+        int bi = 0, cin = 64;
+        for (int l = 0; l < 4; ++l)
+            for (int k = 0; k < IDNET_DEPTH[l]; ++k, ++bi) {
+                IdBlock& K = A.blk[bi];
+                const int cout = IDNET_C[l];
+                K.cin = cin; K.cout = cout; K.stride = (l > 0 && k == 0) ? 2 : 1;
+                snprintf(n, sizeof n, "A.b%d", bi);
+                const std::string q(n);
+                TRY(get_f32(e, q + ".pre.s", cin, &K.s0)); TRY(get_f32(e, q + ".pre.t", cin, &K.t0));
+                TRY(need(e, q + ".c1.w", (size_t)9 * cin * cin * 2, &p)); K.w1 = (const half_t*)p;
+                TRY(get_f32(e, q + ".c1.b", cin, &K.b1));
+                TRY(need(e, q + ".c2.w", (size_t)9 * cout * cin * 2, &p)); K.w2 = (const half_t*)p;
+                TRY(get_f32(e, q + ".c2.b", cout, &K.b2));
+                K.wd = nullptr; K.bd = nullptr;
+                if (K.stride == 2) {
+                    TRY(need(e, q + ".ds.w", (size_t)cout * cin * 2, &p)); K.wd = (const half_t*)p;
+                    TRY(get_f32(e, q + ".ds.b", cout, &K.bd));
+                }
+                TRY(get_f32(e, q + ".se.w1", cout / 16 * cout, &K.se_w1)); TRY(get_f32(e, q + ".se.b1", cout / 16, &K.se_b1));
+                TRY(get_f32(e, q + ".se.w2", cout * (cout / 16), &K.se_w2)); TRY(get_f32(e, q + ".se.b2", cout, &K.se_b2));
+                cin = cout;
+            }
+        TRY(get_f32(e, "A.post.s", 512, &A.post_s)); TRY(get_f32(e, "A.post.t", 512, &A.post_t));
+        TRY(need(e, "A.fc.w", (size_t)49 * 512 * 512 * 2, &p)); A.fc_w = (const half_t*)p;
+        TRY(get_f32(e, "A.fc.b", 512, &A.fc_b));
+        if (!A.in16) {
+            const int cap = e->maxB < 8 ? e->maxB : 8;
+            char* ws = nullptr;
+            TRY(e->alloc(&ws, idnet_workspace_bytes(cap)));
+            idnet_bind_workspace(A, ws, cap);
+        }
+        A.lastB = 0;
+    }
     // ---- F
     TRY(get_f32(e, "F.first.w", 64 * 27, &e->first_w)); TRY(get_f32(e, "F.first.b", 64, &e->first_b));
     // packed as [W_hi | W_lo] over twice the input channels (run_F: wsplit_in)
@@ -1792,6 +1837,42 @@ extern "C" int cs_concat_frames(cs_engine* e, int B, int P, int S, const void* c
     return e->run(1, st, [&] { return launch_concat_frames(panels, kinds, shared, B, P, S, out, st); }, "concat_frames");
 }
 
+// ---- getid on the engine (can_swap_e2e.py:102-107): nearest resize to 112 x 112, the ArcFace network, L2 normalisation.  Everything is refused
+// before any launch; more than the workspace's images run as several passes.
+static int identity_impl(cs_engine* e, const char* who, int B, const float* img, const uint8_t* u8, const float* lut, int H, int W, float* id_out,
+                         float* raw_out, void* stream)
+{
+    if (!e) { cs_set_error("%s: NULL engine", who); return -1; }
+    if (!e->finalized) { cs_set_error("%s: cs_finalize_weights has not been called", who); return -1; }
+    if (!e->idn.present) { cs_set_error("%s: the engine holds no identity network (no 'A.*' blobs: pass the 'arcface' state-dict)", who); return -1; }
+    if (B < 1 || B > e->maxB) { cs_set_error("%s: batch %d outside [1, %d]", who, B, e->maxB); return -1; }
+    if (!img && !u8) { cs_set_error("%s: NULL input", who); return -1; }
+    if (u8 && !lut) { cs_set_error("%s: NULL lut", who); return -1; }
+    if (H < 1 || W < 1 || H > 16384 || W > 16384) { cs_set_error("%s: H = %d, W = %d (each from 1 to 16384)", who, H, W); return -1; }
+    if (!id_out && !raw_out) { cs_set_error("%s: both outputs are NULL", who); return -1; }
+    DevGuard guard(e->dev);
+    hipStream_t st = (hipStream_t)stream;
+    IdNet& A = e->idn;
+    for (int b0 = 0; b0 < B; b0 += A.cap) {
+        const int nb = B - b0 < A.cap ? B - b0 : A.cap;
+        const size_t ofs = (size_t)b0 * 3 * H * W;
+        TRY(e->run(1, st, [&] { return launch_id_input(img ? img + ofs : nullptr, u8 ? u8 + ofs : nullptr, lut, A.in16, nb, H, W, st); }, "id_input"));
+        TRY(e->run(1, st, [&] { return idnet_forward(A, nb, id_out ? id_out + (size_t)b0 * 512 : nullptr, raw_out ? raw_out + (size_t)b0 * 512 : nullptr, st); },
+                   "identity"));
+    }
+    return 0;
+}
+
+extern "C" int cs_identity(cs_engine* e, int B, const float* img, int H, int W, float* id_out, float* raw_out, void* stream)
+{
+    return identity_impl(e, "cs_identity", B, img, nullptr, nullptr, H, W, id_out, raw_out, stream);
+}
+
+extern "C" int cs_identity_u8(cs_engine* e, int B, const uint8_t* crops, int H, int W, const float* lut, float* id_out, float* raw_out, void* stream)
+{
+    return identity_impl(e, "cs_identity_u8", B, nullptr, crops, lut, H, W, id_out, raw_out, stream);
+}
+
 extern "C" int cs_profile_begin(cs_engine* e)
 {
     if (!e) { cs_set_error("null engine"); return -1; }
@@ -2056,4 +2137,53 @@ extern "C" int cs_op_dm_read(cs_engine* e, int which, int B, void* dst, void* st
     else if (which == CS_DM_LOGITS) { src = e->dm_logits; bytes = (size_t)B * DM_LOGIT_FLOATS * sizeof(float); }
     else { cs_set_error("cs_op_dm_read: no buffer %d", which); return -1; }
     return copy_dd(dst, src, bytes, (hipStream_t)stream);
+}
+
+// ---- operator level: the identity network's kernels (csrc/identity.hip) without an engine, and the activations the last cs_identity pass left
+extern "C" int cs_op_id_conv(const void* in, int in_f32, int N, int IH, int IW, int Cin, int K, int stride, int pad, const void* w, const float* bias,
+                             int Cout, const float* slope, void* out, int out_f32, void* stream)
+{
+    IdConvCall c{};
+    c.in = in; c.in_f32 = in_f32; c.N = N; c.IH = IH; c.IW = IW; c.Cin = Cin; c.K = K; c.stride = stride; c.pad = pad;
+    if (K < 1 || stride < 1 || IH + 2 * pad < K || IW + 2 * pad < K) { cs_set_error("cs_op_id_conv: bad arguments"); return -1; }
+    c.OH = (IH + 2 * pad - K) / stride + 1; c.OW = (IW + 2 * pad - K) / stride + 1;
+    c.w = (const half_t*)w; c.bias = bias; c.Cout = Cout; c.slope = slope; c.out = out; c.out_f32 = out_f32;
+    return launch_id_conv(c, (hipStream_t)stream);
+}
+
+extern "C" int cs_op_id_maxpool(const float* in, const float* s, const float* t, float* x, void* a16, int B, int IH, int IW, int C, void* stream)
+{
+    return launch_id_maxpool(in, s, t, x, (half_t*)a16, B, IH, IW, C, (hipStream_t)stream);
+}
+
+extern "C" int cs_op_id_se_tail(const float* out, long sN, long sH, long sW, int B, int H, int W, int C, const float* w1, const float* b1,
+                                const float* w2, const float* b2, const float* slopes, const float* res, const float* s, const float* t, float* se,
+                                float* x, void* a16, void* stream)
+{
+    if (!slopes) { cs_set_error("cs_op_id_se_tail: NULL slopes"); return -1; }
+    TRY(launch_id_se(out, sN, sH, sW, B, H, W, C, w1, b1, slopes + 1, w2, b2, se, (hipStream_t)stream));
+    return launch_id_tail(out, sN, sH, sW, se, res, slopes, s, t, x, (half_t*)a16, B, H, W, C, (hipStream_t)stream);
+}
+
+extern "C" int cs_op_id_embed(const void* a16, const void* w, const float* bias, float* part, float* raw, float* idn, int B, void* stream)
+{
+    return launch_id_embed((const half_t*)a16, (const half_t*)w, bias, part, raw, idn, B, (hipStream_t)stream);
+}
+
+extern "C" int cs_op_identity_read(cs_engine* e, int which, int B, float* dst, void* stream)
+{
+    if (!e || !e->idn.present) { cs_set_error("cs_op_identity_read: no engine, or no identity network in it"); return -1; }
+    const IdNet& A = e->idn;
+    if (!dst) { cs_set_error("cs_op_identity_read: null destination"); return -1; }
+    if (B < 1 || B > A.lastB) { cs_set_error("cs_op_identity_read: %d samples, the last pass held %d", B, A.lastB); return -1; }
+    DevGuard guard(e->dev);
+    hipStream_t st = (hipStream_t)stream;
+    if (which == CS_ID_STEM) return launch_id_to_nchw(A.stem_x, 0, dst, B, 64, 55 * 55, st);
+    if (which >= CS_ID_LAYER1 && which < CS_ID_LAYER1 + 4) {
+        const int l = which - CS_ID_LAYER1;
+        return launch_id_to_nchw(A.layer_x[l], 0, dst, B, IDNET_C[l], IDNET_HW[l] * IDNET_HW[l], st);
+    }
+    if (which == CS_ID_PREFC) return launch_id_to_nchw(A.a16, 1, dst, B, 512, 49, st);
+    cs_set_error("cs_op_identity_read: no activation %d", which);
+    return -1;
 }

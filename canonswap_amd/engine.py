@@ -335,6 +335,55 @@ class Engine:
                    "cs_motion_keypoints_driven")
         return x_t
 
+    # ---------------------------------------------------------------- identity network (getid)
+    def identity(self, img, normalize=True, want_raw=False, out=None):
+        """can_swapper.getid on the engine (can_swap_e2e.py:102-107): img (B,3,H,W) fp32, any H, W -> nearest resize to 112 x 112 -> the ArcFace
+        network -> (B,512), L2-normalised rows with normalize, the network's raw output without; want_raw: (normalised, raw).  Needs the
+        "arcface" state-dict among the loaded weights.  The result lives on the device and feeds set_identity / swap_frames as it is."""
+        if not isinstance(img, torch.Tensor) or img.dim() != 4 or img.shape[1] != 3 or min(img.shape) < 1:
+            raise ValueError("identity expects a (B, 3, H, W) tensor")
+        img = self._in(img)
+        return self._identity(img.shape[0], img, None, None, img.shape[2], img.shape[3], normalize, want_raw, out)
+
+    def identity_u8(self, crops_u8, lut=None, normalize=True, want_raw=False, out=None):
+        """identity() from aligned uint8 crops (B,H,W,3) or (H,W,3), host or device: ID_transform (ToTensor + Normalize,
+        can_swap_pipeline_e2e.py:43-46) as a (3,256) table, then getid; lut: another table (tail.id_lut builds them)."""
+        from . import tail
+        t = torch.as_tensor(crops_u8)
+        if t.dim() == 3:
+            t = t[None]
+        if t.dtype != torch.uint8 or t.dim() != 4 or t.shape[3] != 3 or min(t.shape) < 1:
+            raise ValueError("identity_u8 expects (B, H, W, 3) uint8 crops")
+        if t.shape[0] > self.max_batch:
+            raise ValueError(f"batch {t.shape[0]} outside [1, {self.max_batch}]")
+        t = t.to(self.device).contiguous()
+        if lut is None:
+            lut = tail.id_lut_on(self)
+        else:
+            lut = torch.as_tensor(lut, dtype=torch.float32).to(self.device).contiguous()
+            if tuple(lut.shape) != (3, 256):
+                raise ValueError("lut must be a (3, 256) table")
+        return self._identity(t.shape[0], None, t, lut, t.shape[1], t.shape[2], normalize, want_raw, out)
+
+    def _identity(self, B, img, u8, lut, H, W, normalize, want_raw, out):
+        idn = self._out(out, (B, 512), torch.float32) if normalize else None
+        raw = (self._out(None if normalize else out, (B, 512), torch.float32)) if (want_raw or not normalize) else None
+        with torch.cuda.device(self.device):
+            if u8 is None:
+                _lib.check(self.lib.cs_identity(self.h, B, _ptr(img), H, W, _ptr(idn), _ptr(raw), self._stream()), "cs_identity")
+            else:
+                _lib.check(self.lib.cs_identity_u8(self.h, B, _ptr(u8), H, W, _ptr(lut), _ptr(idn), _ptr(raw), self._stream()), "cs_identity_u8")
+        if normalize:
+            return (idn, raw) if want_raw else idn
+        return raw
+
+    def identity_read(self, which: int, B: int):
+        """cs_op_identity_read: activation `which` (0 stem, 1-4 layer1-4, 5 pre-fc) of the last identity pass as fp32 NCHW (tests)."""
+        shape = [(64, 55, 55), (64, 55, 55), (128, 28, 28), (256, 14, 14), (512, 7, 7), (512, 7, 7)][which]
+        dst = self._new(B, *shape)
+        _lib.check(self.lib.cs_op_identity_read(self.h, which, B, _ptr(dst), self._stream()), "cs_op_identity_read")
+        return dst
+
     # ---------------------------------------------------------------- measurement
     def profile_begin(self):
         _lib.check(self.lib.cs_profile_begin(self.h), "cs_profile_begin")

@@ -374,13 +374,82 @@ def _pack_M(out, sd):
     assert out["M.head.w"].shape == (328, 768)
 
 
+A_DEPTHS, A_DIMS = (3, 4, 14, 3), (64, 128, 256, 512)      # ResNet(IRBlock, [3, 4, 14, 3]) (arcface_models.py:66-83)
+
+
+def pack_id_conv(w):
+    """w: [Cout, Cin, KH, KW] -> fp16 [KH*KW, Cout, Cin padded to a multiple of 32] (csrc/identity.hip: a tap's [Cout][Cin] slice is what one
+    K-step's MFMA fragments read)."""
+    w = np.asarray(w, dtype=np.float64)
+    co, ci, kh, kw = w.shape
+    full = np.zeros((kh * kw, co, -(-ci // 32) * 32), np.float64)
+    full[:, :, :ci] = w.transpose(2, 3, 0, 1).reshape(kh * kw, co, ci)
+    return np.ascontiguousarray(full.astype(np.float16))
+
+
+def unpack_id_conv(packed, cin, kh, kw):
+    """Inverse of pack_id_conv (tests): -> fp32 [Cout, cin, kh, kw]."""
+    t, co, _ = packed.shape
+    assert t == kh * kw
+    return packed.astype(np.float32)[:, :, :cin].reshape(kh, kw, co, cin).transpose(2, 3, 0, 1)
+
+
+def id_blocks():
+    """(blob prefix, state-dict prefix, cin, cout, stride) of the 24 IRBlocks in execution order."""
+    res, cin, i = [], 64, 0
+    for l, (n, c) in enumerate(zip(A_DEPTHS, A_DIMS)):
+        for k in range(n):
+            res.append((f"A.b{i}", f"layer{l + 1}.{k}", cin, c, 2 if (l > 0 and k == 0) else 1))
+            cin, i = c, i + 1
+    return res
+
+
+def _pack_A(out, sd):
+    """The ArcFace identity network behind getid (models/arcface_models.py:10-136; keys of the pickled class, unchanged).  Folds, all in float64:
+      * the stem's bn1 into conv1 (3 input channels padded to 32), every block's bn1 into its conv1 and bn2 into its conv2, the downsample's
+        BatchNorm into its 1x1 conv: w * s[o] as fp16, the shift as an fp32 bias (no conv of this network has a bias of its own);
+      * bn0 stays an affine pair ".pre.s/.t": it sits in front of a ZERO-padded conv, so its shift must not reach the padding - the kernel that
+        writes a block's input applies it to the valid positions and the conv pads the result with zeros;
+      * the net's bn2 is the pair "A.post.s/.t", applied where the last block's output is written; bn3 is folded into fc's rows and bias;
+      * fc's 25088 columns go from the reference's NCHW flatten (c * 49 + h * 7 + w) to the engine's [h * 7 + w][out][c] slices;
+      * the 49 PReLU slopes (one shared slope each): "A.slopes" = [stem, (block, its SE) x 24]."""
+    s, t = bn_affine(sd, "bn1")
+    w, b = fold_conv_bn(sd["conv1.weight"], None, s, t)
+    out["A.stem.w"] = pack_id_conv(w)
+    out["A.stem.b"] = _f32(b)
+    slopes = [np.asarray(sd["prelu.weight"], np.float64).reshape(-1)]
+    for n, p, cin, cout, stride in id_blocks():
+        s, t = bn_affine(sd, p + ".bn0")
+        out[n + ".pre.s"], out[n + ".pre.t"] = _f32(s), _f32(t)
+        for c, bn in (("1", ".bn1"), ("2", ".bn2")):
+            w, b = fold_conv_bn(sd[f"{p}.conv{c}.weight"], None, *bn_affine(sd, p + bn))
+            out[f"{n}.c{c}.w"] = pack_id_conv(w)
+            out[f"{n}.c{c}.b"] = _f32(b)
+        if p + ".downsample.0.weight" in sd:
+            w, b = fold_conv_bn(sd[p + ".downsample.0.weight"], None, *bn_affine(sd, p + ".downsample.1"))
+            out[n + ".ds.w"] = pack_id_conv(w)
+            out[n + ".ds.b"] = _f32(b)
+        out[n + ".se.w1"], out[n + ".se.b1"] = _f32(sd[p + ".se.fc.0.weight"]), _f32(sd[p + ".se.fc.0.bias"])
+        out[n + ".se.w2"], out[n + ".se.b2"] = _f32(sd[p + ".se.fc.2.weight"]), _f32(sd[p + ".se.fc.2.bias"])
+        slopes += [np.asarray(sd[p + ".prelu.weight"], np.float64).reshape(-1), np.asarray(sd[p + ".se.fc.1.weight"], np.float64).reshape(-1)]
+    if any(len(v) != 1 for v in slopes):
+        raise ValueError("arcface: a PReLU with per-channel slopes (the engine takes nn.PReLU()'s one shared slope)")
+    out["A.slopes"] = _f32(np.concatenate(slopes))
+    s, t = bn_affine(sd, "bn2")
+    out["A.post.s"], out["A.post.t"] = _f32(s), _f32(t)
+    s3, t3 = bn_affine(sd, "bn3")
+    wf = sd["fc.weight"].astype(np.float64).reshape(512, 512, 49) * s3[:, None, None]       # [o][c][h * 7 + w]
+    out["A.fc.w"] = np.ascontiguousarray(wf.transpose(2, 0, 1).astype(np.float16))            # [h * 7 + w][o][c]
+    out["A.fc.b"] = _f32(sd["fc.bias"].astype(np.float64) * s3 + t3)
+
+
 def _np_sd(sd):
     return {k: (v.detach().cpu().numpy() if hasattr(v, "detach") else np.asarray(v)) for k, v in sd.items()}
 
 
 def build_blobs(state_dicts: dict) -> dict:
     """``state_dicts``: {'appearance_feature_extractor', 'warping_module', 'spade_generator', 'transfer',
-    'refine'[, 'motion_extractor']} -> {blob name: contiguous ndarray}; values may be torch tensors or numpy arrays."""
+    'refine'[, 'motion_extractor'][, 'arcface']} -> {blob name: contiguous ndarray}; values may be torch tensors or numpy arrays."""
     out: dict = {}
     _pack_F(out, _np_sd(state_dicts["appearance_feature_extractor"]))
     _pack_W(out, _np_sd(state_dicts["warping_module"]))
@@ -389,4 +458,6 @@ def build_blobs(state_dicts: dict) -> dict:
     _pack_G(out, _np_sd(state_dicts["spade_generator"]))
     if "motion_extractor" in state_dicts:                      # optional
         _pack_M(out, _np_sd(state_dicts["motion_extractor"]))
+    if "arcface" in state_dicts:                               # optional: getid on the engine (blobs "A.*")
+        _pack_A(out, _np_sd(state_dicts["arcface"]))
     return out

@@ -52,10 +52,10 @@ class _Builder:
         if bias:
             self.sd[f"{name}.bias"] = self._r(f"{name}.bias").uniform(-0.1, 0.1, size=(cout,)).astype(np.float32)
 
-    def bn(self, name, c):
+    def bn(self, name, c, mean=0.0):
         self.sd[f"{name}.weight"] = self._r(f"{name}.weight").uniform(0.8, 1.2, size=(c,)).astype(np.float32)
         self.sd[f"{name}.bias"] = self._r(f"{name}.bias").uniform(-0.1, 0.1, size=(c,)).astype(np.float32)
-        self.sd[f"{name}.running_mean"] = (0.1 * self._r(f"{name}.running_mean").standard_normal(c)).astype(np.float32)
+        self.sd[f"{name}.running_mean"] = (mean + 0.1 * self._r(f"{name}.running_mean").standard_normal(c)).astype(np.float32)
         self.sd[f"{name}.running_var"] = self._r(f"{name}.running_var").uniform(0.6, 1.4, size=(c,)).astype(np.float32)
         self.sd[f"{name}.num_batches_tracked"] = np.array(100, dtype=np.int64)
 
@@ -236,10 +236,42 @@ def _motion_extractor(seed):
 _BUILDERS["motion_extractor"] = _motion_extractor
 
 
+def _arcface(seed):
+    """ResNet(IRBlock, [3, 4, 14, 3], use_se=True) state-dict of the identity network behind getid (models/arcface_models.py:10-136): the 589 keys
+    of the pickled class in its own order.  conv3x3 is the upstream 3x3 / padding 1 / no-bias conv (the reference file calls it without defining
+    it).  PReLU slopes come from U(0.1, 0.4) rather than the initial 0.25; the SE linears are wide enough for the gates to spread over
+    about [0.25, 0.75]; conv2's gain keeps the 24-block residual chain tame; bn0's running mean sits at 0.5, so its shift is large enough for a
+    shift that leaks into the conv's zero padding to show (tests/test_identity_cpu.py, discrimination)."""
+    b = _Builder(seed, "A")
+
+    def prelu(name):
+        b.sd[f"{name}.weight"] = b._r(f"{name}.weight").uniform(0.1, 0.4, size=(1,)).astype(np.float32)
+
+    b.conv("conv1", 64, 3, 3, 3, bias=False); b.bn("bn1", 64); prelu("prelu")
+    cin = 64
+    for l, (n, c) in enumerate(zip((3, 4, 14, 3), (64, 128, 256, 512))):
+        for k in range(n):
+            p = f"layer{l + 1}.{k}"
+            b.bn(f"{p}.bn0", cin, mean=0.5)      # the stream behind a PReLU has a positive mean, and so has the statistic that tracked it
+            b.conv(f"{p}.conv1", cin, cin, 3, 3, bias=False); b.bn(f"{p}.bn1", cin); prelu(f"{p}.prelu")
+            b.conv(f"{p}.conv2", c, cin, 3, 3, bias=False, gain=0.5); b.bn(f"{p}.bn2", c)
+            if l > 0 and k == 0:
+                b.conv(f"{p}.downsample.0", c, cin, 1, 1, bias=False); b.bn(f"{p}.downsample.1", c)
+            b.linear(f"{p}.se.fc.0", c // 16, c, gain=3.0); prelu(f"{p}.se.fc.1"); b.linear(f"{p}.se.fc.2", c, c // 16, gain=2.0)
+            cin = c
+    b.bn("bn2", 512)
+    b.linear("fc", 512, 512 * 7 * 7)
+    b.bn("bn3", 512)
+    return b.sd
+
+
+_BUILDERS["arcface"] = _arcface
+
+
 def make_state_dicts(seed: int = 0, modules=MODULES, family: str = "uniform") -> dict:
     """Return ``{module_name: OrderedDict[str, np.ndarray]}`` laid out like the reference's
     ``combined_weights.pth`` (``src/can_swap_e2e.py:87-100``).  The motion extractor is built on
-    request: ``modules=MODULES + ("motion_extractor",)``.  family: "uniform" (default) or "heavy_tail"."""
+    request: ``modules=MODULES + ("motion_extractor",)``, and so is the identity network behind getid: ``"arcface"``.  family: "uniform" (default) or "heavy_tail"."""
     global FAMILY
     prev, FAMILY = FAMILY, family
     try:
@@ -342,6 +374,17 @@ def make_smooth_images(n: int, seed: int = 2000, size: int = 256) -> np.ndarray:
     img = rows[:, :, :, i0] * (1 - f) + rows[:, :, :, i0 + 1] * f
     img = img + 0.05 * r.standard_normal(img.shape).astype(np.float32)
     return np.clip(img, 0, 1).astype(np.float32)
+
+
+ID_MEAN, ID_STD = (0.485, 0.456, 0.406), (0.229, 0.224, 0.225)      # ID_transform's Normalize (can_swap_pipeline_e2e.py:43-46)
+
+
+def make_identity_inputs(n: int, seed: int = 3000, size: int = 112) -> np.ndarray:
+    """(n,3,size,size) fp32 inputs of getid: smooth images in [0,1] (make_smooth_images) after ID_transform's Normalize, i.e. values in about
+    [-2.2, 2.7]."""
+    img = make_smooth_images(n, seed=seed, size=size).astype(np.float64)
+    m, s = np.array(ID_MEAN).reshape(1, 3, 1, 1), np.array(ID_STD).reshape(1, 3, 1, 1)
+    return ((img - m) / s).astype(np.float32)
 
 
 def make_identity(seed: int = 7, n: int = 1) -> np.ndarray:

@@ -124,6 +124,33 @@ def _parser_lut_on(e: Engine, mean, std, rescale):
     return t
 
 
+ID_MEAN, ID_STD = (0.485, 0.456, 0.406), (0.229, 0.224, 0.225)      # ID_transform's Normalize (can_swap_pipeline_e2e.py:43-46, can_swap_pipeline_v2i.py:44-47)
+
+
+def id_lut(mean=ID_MEAN, std=ID_STD) -> np.ndarray:
+    """(3, 256) fp32: what ID_transform makes of byte v in channel c, by torchvision's own arithmetic: ToTensor = byte.float().div(255),
+    Normalize = (x - mean) / std with mean and std as float32 tensors (the kind of table parser_lut builds by the image processor's numpy
+    lines).  cs_identity_u8 looks this up."""
+    mean, std = [float(m) for m in mean], [float(s) for s in std]
+    if len(mean) != 3 or len(std) != 3 or any(s == 0 for s in std):
+        raise ValueError("id_lut: mean and std are three numbers each, std nonzero")
+    x = torch.arange(256, dtype=torch.uint8).to(torch.float32).div(255)
+    m, s = torch.tensor(mean, dtype=torch.float32), torch.tensor(std, dtype=torch.float32)
+    return np.ascontiguousarray(((x[None, :] - m[:, None]) / s[:, None]).numpy())
+
+
+def id_lut_on(e: Engine, mean=ID_MEAN, std=ID_STD):
+    """The table on the engine's device, uploaded once per engine and set of constants."""
+    key = (tuple(float(m) for m in mean), tuple(float(s) for s in std))
+    cache = e.__dict__.setdefault("_id_luts", {})
+    t = cache.get(key)
+    if t is None:
+        t = torch.from_numpy(id_lut(*key)).to(e.device)
+        torch.cuda.current_stream(e.device).synchronize()      # once: later calls may come from any stream
+        cache[key] = t
+    return t
+
+
 def parser_input(e: Engine, crops_u8, halve=None, mean=PARSER_MEAN, std=PARSER_STD, rescale=PARSER_RESCALE, out=None, want_u8=False, out_u8=None):
     """What both pipelines feed the face parser (can_swap_pipeline_e2e.py:171 + :180, can_swap_pipeline_v2i.py:73) for B crops in one launch:
     crops_u8 (B,H,W,3), or (H,W,3) for one crop, uint8, host or device -> pixel_values (B,3,Ho,Wo) fp32 on the device =

@@ -39,6 +39,19 @@ int cs_finalize_weights(cs_engine* e);
  * identities stay resident (concurrent streams, BASELINE configs[4]) and may be mixed inside one batch (cs_swap_ids). */
 int cs_set_identity(cs_engine* e, int slot, const float* id, void* stream);
 
+/* can_swapper.getid (can_swap_e2e.py:102-107; the network: models/arcface_models.py:66-136, ResNet(IRBlock, [3, 4, 14, 3], use_se=True)):
+ * img fp32 Bx3xHxW (any H, W >= 1; the pipeline passes ID_transform's values, can_swap_pipeline_e2e.py:43-46,97-98) -> F.interpolate(size=(112, 112)),
+ * nearest -> the network -> id_out Bx512 = F.normalize(raw, p=2, dim=1), raw_out Bx512 = the network's first output (its second, the pooled layer-3
+ * map, is never computed).  Either output may be NULL, not both.  B <= max_batch; needs the optional "A.*" blobs (pack.py: the "arcface"
+ * state-dict) and fails without them.  Deterministic, and a row's bits do not depend on the batch it is part of.  id_out can be handed to
+ * cs_set_identity on the same stream.  The calls use a workspace of their own (allocated by cs_finalize_weights when the blobs are there, for
+ * min(max_batch, 8) images per pass; larger batches run as several passes), not the generator's scratch: they may be enqueued beside any other
+ * entry point of the engine, but two identity calls on one engine must be ordered with each other. */
+int cs_identity(cs_engine* e, int B, const float* img, int H, int W, float* id_out, float* raw_out, void* stream);
+/* The same from aligned uint8 crops BxHxWx3 (can_swap_pipeline_e2e.py:97: ID_transform = ToTensor + Normalize, then getid): lut fp32 [3][256] on the
+ * device holds what the transform makes of byte v in channel c (canonswap_amd/tail.py id_lut); bit-equal to cs_identity on the table's values. */
+int cs_identity_u8(cs_engine* e, int B, const uint8_t* crops, int H, int W, const float* lut, float* id_out, float* raw_out, void* stream);
+
 /* Single-frame latency mode (BASELINE configs[1]): launches that cannot fill the 256 CUs at one or two frames per call take forms that
  * add an output element's products in another (fixed) order than the batched path - the 512-channel 3x3 convs split their K loop over twelve waves
  * of a workgroup (conv_lat.hip), the deep hourglass levels over workgroups (split-K), R's volume convs emit 2-row statistics blocks.  Deterministic,
@@ -347,6 +360,29 @@ int cs_op_occ_finish(const float* part, int taps, float bias, float* occ, int N,
  *   CS_DM_LOGITS:  fp32 [B][16][64][16][10][22]: the mask conv's compact-2 partials (cs_op_dm_softmax_warp) */
 enum { CS_DM_COMP = 0, CS_DM_L0 = 1, CS_DM_PRED = 7, CS_DM_LOGITS = 8 };
 int cs_op_dm_read(cs_engine* e, int which, int B, void* dst, void* stream);
+
+/* The identity network's kernels one at a time (csrc/identity.hip; weights as pack._pack_A lays them out; models/arcface_models.py:10-136).
+ * conv: in fp16 (in_f32: fp32, rounded to fp16 on load) contiguous [N][IH][IW][Cin] -> out fp32 / fp16 [N][OH][OW][Cout] = prelu(conv + bias), K x K
+ * taps (1 or 3), stride >= 1, zero padding pad < K, OH = (IH + 2 pad - K) / stride + 1; w fp16 [K * K][Cout][Cin] (pack.pack_id_conv); Cin % 32 == 0,
+ * Cout % 64 == 0; slope: device pointer to the PReLU's one slope, NULL = no activation; bias may be NULL */
+int cs_op_id_conv(const void* in, int in_f32, int N, int IH, int IW, int Cin, int K, int stride, int pad, const void* w, const float* bias,
+                  int Cout, const float* slope, void* out, int out_f32, void* stream);
+/* MaxPool2d(2, 2) (arcface_models.py:116): in fp32 [B][IH][IW][C] -> x fp32 [B][IH/2][IW/2][C], a16 fp16 = x s + t (the first block's bn0); C % 4 == 0 */
+int cs_op_id_maxpool(const float* in, const float* s, const float* t, float* x, void* a16, int B, int IH, int IW, int C, void* stream);
+/* SE gate + block tail (arcface_models.py:21-25,54-63): out fp32, position (h, w) of sample n at n sN + h sH + w sW (a stride-1 map read at its even
+ * positions: doubled sH / sW), channels contiguous; se [B][C] = sigmoid(W2 prelu(W1 mean_hw(out) + b1, slopes[1]) + b2) (w1 [C/16][C], w2 [C][C/16]);
+ * x fp32 [B][H][W][C] = prelu(out se + res, slopes[0]), res fp32 [B][H][W][C]; a16 fp16 = x s + t.  C = 64, 128, 256 or 512; strides multiples of 4. */
+int cs_op_id_se_tail(const float* out, long sN, long sH, long sW, int B, int H, int W, int C, const float* w1, const float* b1,
+                     const float* w2, const float* b2, const float* slopes, const float* res, const float* s, const float* t, float* se,
+                     float* x, void* a16, void* stream);
+/* bn2 -> flatten -> fc -> bn3 [-> F.normalize] (arcface_models.py:129-134; can_swap_e2e.py:106): a16 fp16 [B][49][512] = bn2(x) in (h, w, c) order,
+ * w fp16 [49][512][512] and bias [512] (the "A.fc" blobs), part: scratch of 49 x B x 512 floats -> raw [B][512], idn [B][512] (either may be NULL) */
+int cs_op_id_embed(const void* a16, const void* w, const float* bias, float* part, float* raw, float* idn, int B, void* stream);
+/* Copies to dst on `stream`, as fp32 NCHW at its valid extent, an activation the LAST pass of cs_identity / cs_identity_u8 left (B <= the images of
+ * that pass, at most min(max_batch, 8); arcface_models.py:116-129): CS_ID_STEM Bx64x55x55 (after the max-pool), CS_ID_LAYER1 + i: Bx64x55x55, Bx128x28x28, Bx256x14x14,
+ * Bx512x7x7 (i = 0 .. 3), CS_ID_PREFC Bx512x7x7 (bn2's output as the fc reads it, fp16 values) */
+enum { CS_ID_STEM = 0, CS_ID_LAYER1 = 1, CS_ID_PREFC = 5 };
+int cs_op_identity_read(cs_engine* e, int which, int B, float* dst, void* stream);
 
 #ifdef __cplusplus
 }
