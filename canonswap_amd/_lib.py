@@ -11,7 +11,7 @@ import subprocess
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
-SOURCES = [os.path.join(CSRC, f) for f in ("conv_halo.hip", "conv_wide.hip", "conv_lat.hip", "vol32.hip", "vol32_fused.hip", "kernels.hip", "motion.hip", "imgops.hip", "identity.hip", "engine.hip")]
+SOURCES = [os.path.join(CSRC, f) for f in ("conv_halo.hip", "conv_wide.hip", "conv_lat.hip", "vol32.hip", "vol32_fused.hip", "kernels.hip", "motion.hip", "imgops.hip", "identity.hip", "parser.hip", "engine.hip")]
 # test-only cross-check kernel (the first-generation implicit-GEMM conv): its own library, never linked into the product
 TEST_SRC = os.path.join(os.path.dirname(HERE), "tests", "csrc", "test_igemm.hip")
 TEST_LIB_PATH = os.path.join(os.path.dirname(HERE), "tests", "libcanonswap_test.so")
@@ -31,6 +31,8 @@ ABI_SYMBOLS = [
     "cs_op_m_stem", "cs_op_m_dwln", "cs_op_m_ln_s2d", "cs_op_m_grn", "cs_op_m_head", "cs_op_m_pointwise",
     "cs_op_dm_compress", "cs_op_dm_sparse", "cs_op_dm_softmax_warp", "cs_op_occ_finish", "cs_op_dm_read",
     "cs_identity", "cs_identity_u8", "cs_op_identity_read", "cs_op_id_conv", "cs_op_id_maxpool", "cs_op_id_se_tail", "cs_op_id_embed",
+    "cs_parser", "cs_op_parser_read", "cs_op_parser_input", "cs_op_parser_gemm", "cs_op_parser_layernorm", "cs_op_parser_attention", "cs_op_parser_dwgelu",
+    "cs_op_parser_upadd",
 ]
 ABI_VERSION = 4          # CS_ABI_VERSION of include/canonswap_hip.h
 HIPCC_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wno-unused-value"]
@@ -441,6 +443,14 @@ def load():
     lib.cs_op_id_maxpool.argtypes = [vp, vp, vp, vp, vp, ci, ci, ci, ci, vp]
     lib.cs_op_id_se_tail.argtypes = [vp, C.c_long, C.c_long, C.c_long, ci, ci, ci, ci, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
     lib.cs_op_id_embed.argtypes = [vp, vp, vp, vp, vp, vp, ci, vp]
+    lib.cs_parser.argtypes = [vp, ci, vp, ci, ci, vp, vp]
+    lib.cs_op_parser_read.argtypes = [vp, ci, ci, vp, vp]
+    lib.cs_op_parser_input.argtypes = [vp, vp, ci, ci, ci, vp]
+    lib.cs_op_parser_gemm.argtypes = [vp, vp, vp, ci, ci, ci, ci, vp, ci, ci, vp]
+    lib.cs_op_parser_layernorm.argtypes = [vp, vp, vp, cf, C.c_long, ci, vp, vp, vp]
+    lib.cs_op_parser_attention.argtypes = [vp, vp, vp, ci, ci, ci, ci, ci, vp]
+    lib.cs_op_parser_dwgelu.argtypes = [vp, vp, vp, vp, ci, ci, ci, ci, vp]
+    lib.cs_op_parser_upadd.argtypes = [vp, vp, vp, vp, vp, ci, ci, ci, ci, vp]
     lib.cs_op_resblock3d.argtypes = [vp, vp, vp, vp, ci, ci, ci, vp, vp, vp, vp, vp, vp, ci, cf, vp]
     lib.cs_op_chan_stats_partial_floats.argtypes = [ci, C.c_long, ci]
     lib.cs_op_chan_stats_partial_floats.restype = C.c_long

@@ -55,11 +55,14 @@ class can_swapper(object):
     """MI355X engine behind the reference's ``can_swapper`` interface."""
 
     def __init__(self, inference_cfg=None, state_dicts=None, max_batch: int = 8, id_net=None, latency_mode: bool = False,
-                 packed_blobs=None, id_on_engine: bool = False):
+                 packed_blobs=None, id_on_engine: bool = False, parser=None):
         """packed_blobs: the result of pack.build_blobs() for the same state-dicts, when another process of this node already ran the
         load-time weight transform (engine.load_blobs).
         id_on_engine: run getid on the engine with the weights of id_net (or of the module loaded from arcface_checkpoint.tar): its
-        state_dict() joins the state-dicts as "arcface" and the torch module is dropped."""
+        state_dict() joins the state-dicts as "arcface" and the torch module is dropped.
+        parser: the SegFormer face parser to run on the engine (parse, face_masks_from_crops, the chains' parse=True): an HF
+        SegformerForSemanticSegmentation module or a (state_dict, config) pair (config: an HF config or {"num_attention_heads": [...]}, may be
+        None); without it state_dicts["parser"] (and ["parser_config"]) are picked up when present.  The torch module is not kept."""
         self.inference_cfg = inference_cfg
         self.device_id = getattr(inference_cfg, "device_id", 0)
         self.compile = False                      # torch.compile switch of the reference (:47,:74-77) has no meaning here
@@ -94,6 +97,17 @@ class can_swapper(object):
                 if state_dicts is None:
                     raise RuntimeError("id_on_engine=True: no generator weights to load the identity network with")
                 state_dicts = dict(state_dicts, arcface=arc_sd)
+        if parser is not None:
+            psd, pcfg = parser if isinstance(parser, (tuple, list)) else (parser.state_dict(), getattr(parser, "config", None))
+            if packed_blobs is not None:
+                packed_blobs = dict(packed_blobs)
+                pack._pack_P(packed_blobs, pack._np_sd(psd), pcfg)
+            else:
+                if state_dicts is None and os.path.exists("pretrained_weights/combined_weights.pth"):
+                    state_dicts = torch.load("pretrained_weights/combined_weights.pth", map_location=torch.device("cpu"))
+                if state_dicts is None:
+                    raise RuntimeError("parser=: no generator weights to load the face parser with")
+                state_dicts = dict(state_dicts, parser=psd, parser_config=pcfg)
         if packed_blobs is not None:
             self.id_on_engine = any(k.startswith("A.") for k in packed_blobs)
             if any(k.startswith("M.") for k in packed_blobs):
@@ -118,6 +132,10 @@ class can_swapper(object):
         if "arcface" in combined:
             keys.append("arcface")
         self.id_on_engine = "arcface" in combined
+        if "parser" in combined:
+            keys.append("parser")
+            if combined.get("parser_config") is not None:
+                keys.append("parser_config")
         self.engine.load_state_dicts({k: combined[k] for k in keys})
 
     # ---- small helpers kept for interface parity
@@ -142,6 +160,17 @@ class can_swapper(object):
             out = self.netArc(x)
             idv = out[0] if isinstance(out, (tuple, list)) else out
             return torch.nn.functional.normalize(idv, p=2, dim=1)
+
+    def parse(self, pixel_values, out=None):
+        """The face parser on the engine (can_swap_pipeline_e2e.py:178-182: model(pixel_values).logits): (B,3,H,W) fp32 -> logits (B,L,H/4,W/4)."""
+        return self.engine.parser(pixel_values, out=out)
+
+    def face_masks_from_crops(self, crops_u8, valid=tail.FACE_VALID, **kw):
+        """crops (B,512,512,3) or (B,256,256,3) u8 -> (B,512,512) u8 0/1 face masks, all on the engine: parser_input -> parser -> face_masks
+        (can_swap_pipeline_e2e.py:171-190 without the torch module)."""
+        if not self.engine.has_parser:
+            raise RuntimeError("face_masks_from_crops: the engine holds no face parser (pass parser= or the 'parser' state-dict)")
+        return tail.face_masks(self.engine, self.engine.parser(tail.parser_input(self.engine, crops_u8)), valid, **kw)
 
     def getid_crops(self, crops_u8):
         """ID_transform + getid (can_swap_pipeline_e2e.py:43-46,97-98) for aligned uint8 crops (B,H,W,3) or (H,W,3), host or device -> (B, 512)."""

@@ -20,16 +20,16 @@ the generator).
     :248-250, :257-259, :290  rec_can, I_can, concat_frames (video.py:84-109)  chain(..., concat=True): the two debug decodes of
                               [three images per frame D2H, cv2.resize, hstack]  cs_swap_frames_ids + cs_concat_frames
 
-The loop of a caller:  c = chain.crop(frames, lmk);  logits = model(pixel_values=chain.parser_input(c["crops"])).logits, (B,19,128,128);
-frames_out = chain(c["crops"], None, c["M_c2o"], frames, source_id, logits=logits)["frames"]
-(or, with 0/1 masks the caller has made of them: chain(c["crops"], masks, c["M_c2o"], frames, source_id)).
+The loop of a caller:  c = chain.crop(frames, lmk);  frames_out = chain(c["crops"], None, c["M_c2o"], frames, source_id, parse=True)["frames"]
+with the face parser among the engine's weights (cs_parser_input + cs_parser + cs_face_masks in stage A, no torch module in the process).  A
+caller who runs the parser himself:  logits = model(pixel_values=chain.parser_input(c["crops"])).logits, (B,19,128,128);
+chain(c["crops"], None, c["M_c2o"], frames, source_id, logits=logits)  (or, with 0/1 masks made of them: chain(c["crops"], masks, ...)).
 
 AnimateChain below is the same for the second program, inference_v2i.py (src/can_swap_pipeline_v2i.py: one source image animated by a
 driving video, the driving identity swapped in); its table stands in the class's docstring.
 
-What stays outside (out of scope): face detection and the landmark network (they produce the landmarks), the SegFormer
-network (a third-party model: it turns pixel_values into the logits; its image processor is cs_parser_input, what the pipelines do with its logits
-is cs_face_masks), video decode / encode.
+What stays outside (out of scope): face detection and the landmark network (they produce the landmarks), video decode /
+encode.  The SegFormer face parser runs on the engine when its weights are loaded (parse=True: cs_parser between cs_parser_input and cs_face_masks).
 """
 from __future__ import annotations
 
@@ -89,9 +89,15 @@ class _StagedChain:
     def _check_stageable(self):
         """Raises where stage A cannot run yet (AnimateChain: no source)."""
 
-    @staticmethod
-    def _mask_or_logits(masks, logits, who):
-        """The parser's result comes as 0/1 masks or as logits (tail.face_masks makes the masks of them), never both, never neither."""
+    def _mask_or_logits(self, masks, logits, who, parse=False):
+        """The parser's result comes as 0/1 masks or as logits (tail.face_masks makes the masks of them), never both, never neither; or, with
+        parse=True, from the engine's own parser: then neither is passed, and the engine must hold the network (checked before anything is enqueued)."""
+        if parse:
+            if masks is not None or logits is not None:
+                raise ValueError(f"{who}: parse=True takes the place of masks and logits=; pass neither")
+            if not self.e.has_parser:
+                raise RuntimeError(f"{who}: parse=True, but the engine holds no face parser (pass parser= to can_swapper or the 'parser' state-dict)")
+            return
         if (masks is None) == (logits is None):
             raise ValueError(f"{who}: pass either masks or logits=" + (", not both" if masks is not None else " (got neither)"))
 
@@ -160,9 +166,12 @@ class FrameChain(_StagedChain):
     # ---- stage A: everything the generator needs from a batch of crops (input staging + motion extractor).  The reference runs it as a
     # pre-pass over the whole video (prepare_videos + make_motion_template, can_swap_pipeline_e2e.py:196-197) before the swapping loop
     # ... and the soft mask, which depends on the parser's labels only (:274); given the logits, the labels' mask first (:183-190)
-    def _stage_a(self, crops_u8, masks, logits, slot):
+    def _stage_a(self, crops_u8, masks, logits, parse, slot):
         t = torch.as_tensor(crops_u8)
         B = t.shape[0] if t.dim() == 4 else 1
+        if parse:                                                                                         # :171-182 on the engine
+            pv = tail.parser_input(self.e, t, out=self._get(("pv", slot), (B, 3, 512, 512), torch.float32))
+            logits = self.e.parser(pv, out=self._get(("logits", slot), (B, self.e.parser_cfg["L"], 128, 128), torch.float32))
         I = tail.prepare_crops(self.e, t, out=self._get(("I", slot), (B, 3, 256, 256), torch.float32))      # cropper.py:209 + can_swap_e2e.py:147-163
         x_t, x_can = self.keypoints(I, slot)                                                              # can_swap_pipeline_e2e.py:111-125, 243
         if logits is not None:
@@ -173,18 +182,19 @@ class FrameChain(_StagedChain):
                                         out=self._get(("soft", slot), (B,) + tuple(m.shape[-2:]), torch.float32))      # :274
         return I, x_t, x_can, soft
 
-    def prefetch(self, crops_u8, masks=None, logits=None):
-        """Stage A of the NEXT batch on a side stream (masks or logits= as in __call__), so that it runs beside the generator of the current one
+    def prefetch(self, crops_u8, masks=None, logits=None, parse=False):
+        """Stage A of the NEXT batch on a side stream (masks, logits= or parse=True as in __call__; the engine's parser then runs there too, beside the generator: its workspace is its own), so that it runs beside the generator of the current one
         (M and the staging are bandwidth / latency bound, the generator is matrix-pipe bound): call it before __call__ of the current batch; the next __call__ with
         the same crops tensor picks the result up (the soft masks of that batch included: they depend on the parser's labels only).  M's workspace is its own, the batch's inputs land in the other half of a double buffer.
         Staged batches may be run in any order.  Not on a latency-mode engine: there every small plain conv (M's and the generator's
         alike) runs split-K on the engine's one partial-sum buffer, which M on the side stream and the generator would share."""
-        self._mask_or_logits(masks, logits, "FrameChain.prefetch")
-        self._stage_ahead(crops_u8, masks, logits)
+        self._mask_or_logits(masks, logits, "FrameChain.prefetch", parse)
+        self._stage_ahead(crops_u8, masks, logits, parse)
 
     def __call__(self, crops_u8, masks, M_c2o, frames_ori, source_id=None, slots=None, out=None, keep=False, logits=None, concat=False,
-                 concat_out=None):
-        """crops_u8 (B,512,512,3) or (B,256,256,3) u8; masks (B,512,512) u8 0/1 or fp32 (the parser's `torch.isin(labels, valid)`), or None
+                 concat_out=None, parse=False):
+        """parse=True (masks None, no logits=): the engine's own face parser makes the logits of the crops in stage A (parser_input -> parser).
+        crops_u8 (B,512,512,3) or (B,256,256,3) u8; masks (B,512,512) u8 0/1 or fp32 (the parser's `torch.isin(labels, valid)`), or None
         with logits= (B,C,128,128), (B,C,256,256) or (B,C,512,512) fp32: the parser's logits, masked here (tail.face_masks with the chain's valid);
         M_c2o (B,2,3)/(B,3,3) host; frames_ori (B,Ho,Wo,3) u8; source_id (1,512)/(B,512) or identity slots.
         concat=True: also the frames of the pipeline's side-by-side video (:290, video.py:84-109), "concat" (B,512,2048,3) u8 (into concat_out):
@@ -193,8 +203,8 @@ class FrameChain(_StagedChain):
         -> {"frames": (B,Ho,Wo,3) u8[, "concat"][, "crops_out", "x_t", "x_can", "soft_mask" with keep=True, and "rec_can", "swap_can"
         (B,3,512,512) fp32 with keep and concat]}"""
         e = self.e
-        self._mask_or_logits(masks, logits, "FrameChain")
-        slot, (I, x_t, x_can, soft) = self._resolve(crops_u8, masks, logits)
+        self._mask_or_logits(masks, logits, "FrameChain", parse)
+        slot, (I, x_t, x_can, soft) = self._resolve(crops_u8, masks, logits, parse)
         B = I.shape[0]
         rec = self._get("rec_can", (B, 3, 512, 512), torch.float32) if concat else None
         swp = self._get("swap_can", (B, 3, 512, 512), torch.float32) if concat else None
@@ -238,7 +248,8 @@ class AnimateChain(_StagedChain):
 
     There is no refine module in this pipeline.  The crops, the source's and the driving frames', come from chain.crop (cropper.py:144-152,
     196-204): `c = chain.crop(img[None], lmk)`, then `set_source(c["crops"][0], mask, c["M_c2o"][0], img, driving_id)`.  Outside: everything
-    FrameChain leaves outside and getid (the driving identity is passed in)."""
+    FrameChain leaves outside and getid (the driving identity is passed in).  With the face parser among the engine's weights,
+    set_source(crop, None, M_c2o, img, driving_id, parse=True) runs it on the crop."""
 
     def __init__(self, swapper, kernel_size: int = 21, threshold: float = 0.9, iterations: int = 2, valid=tail.FACE_VALID):
         super().__init__(swapper, kernel_size, threshold, iterations, valid)      # SoftErosion(21, 0.9, 2): can_swap_pipeline_v2i.py:43; valid_list :82
@@ -246,10 +257,10 @@ class AnimateChain(_StagedChain):
         self._I_can = None                                            # set_source's I_can, the middle panel of concat=True; beside _src, not in it
 
     # ---- once per (source image, driving identity)
-    def set_source(self, crop_u8, mask, M_c2o, img_ori, driving_id, logits=None):
+    def set_source(self, crop_u8, mask, M_c2o, img_ori, driving_id, logits=None, parse=False):
         """crop_u8 (512,512,3) or (256,256,3) u8: the cropper's crop of the source image; mask (Hm,Wm) u8 0/1 or fp32: the parser's
         `torch.isin(labels, valid)` of that crop, or None with logits= (C,h,w) / (1,C,h,w): the parser's logits of that crop (:76-83 run
-        here); M_c2o 2x3 / 3x3 host, crop -> image; img_ori (Ho,Wo,3) u8; driving_id (1,512).
+        here), or None with parse=True: the engine's own face parser makes them of the crop (:73-76); M_c2o 2x3 / 3x3 host, crop -> image; img_ori (Ho,Wo,3) u8; driving_id (1,512).
         Everything on the device, on the caller's stream.  -> {"I_can" (512,512,3) u8, "swap_can" (1,3,512,512), "x_swap", "x_s" (1,21,3)}"""
         e = self.e
         self.drop_prefetches()                                                       # staged key-points were formed with the old kp_swap / pose
@@ -257,7 +268,10 @@ class AnimateChain(_StagedChain):
         if ori.dtype != torch.uint8 or ori.dim() != 3 or ori.shape[2] != 3:
             raise ValueError("img_ori: expected ONE HoxWox3 uint8 image")
         ori = ori.to(e.device).contiguous()
-        self._mask_or_logits(mask, logits, "AnimateChain.set_source")
+        self._mask_or_logits(mask, logits, "AnimateChain.set_source", parse)
+        if parse:
+            c1 = torch.as_tensor(crop_u8)
+            logits = e.parser(tail.parser_input(e, c1[None] if c1.dim() == 3 else c1))      # :73-76
         if logits is not None:
             lg = torch.as_tensor(logits)
             if lg.dim() not in (3, 4) or (lg.dim() == 4 and lg.shape[0] != 1):

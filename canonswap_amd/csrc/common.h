@@ -265,7 +265,7 @@ int launch_m_head(const float* x, const float* g, const float* be, const float* 
 
 // ---- the ArcFace identity network behind getid (identity.hip; models/arcface_models.py:10-136)
 // One convolution of it: fp16 (or fp32, converted on load) contiguous [N][IH][IW][Cin] -> [N][OH][OW][Cout] (fp32 or fp16) = prelu(conv + bias),
-// K x K taps (1 or 3), any stride, zero padding; w fp16 [K * K][Cout][Cin] (pack.pack_id_conv); Cin % 32 == 0, Cout % 64 == 0; slope: device
+// K x K taps (K from 1 to 8), any stride, zero padding; w fp16 [K * K][Cout][Cin] (pack.pack_id_conv); Cin % 32 == 0, Cout % 64 == 0; slope: device
 // pointer to the PReLU's shared slope, nullptr = no activation.
 struct IdConvCall {
     const void* in; int in_f32;
@@ -304,3 +304,45 @@ int launch_id_to_nchw(const void* in, int is_f16, float* out, int N, int C, int 
 size_t idnet_workspace_bytes(int cap);
 void idnet_bind_workspace(IdNet& n, void* ws, int cap);
 int idnet_forward(IdNet& n, int B, float* idn, float* raw, hipStream_t st);
+
+// ---- the SegFormer face parser (parser.hip)
+// One token GEMM: out[M][N] = a[M][K] w[N][K]^T + bias (fp16 operands, fp32 accumulation); K % 32 == 0, N % 64 == 0, any M.
+enum { P_GEMM_F16 = 0 /* fp16 [M][N] */, P_GEMM_RES = 1 /* out (fp32 [M][N], the residual stream) += result */, P_GEMM_F32 = 2 /* fp32 [M][N] */,
+       P_GEMM_NCHW = 3 /* fp32 [M / P][L][P]: the first L columns only (the classifier's real classes) */ };
+struct PGemmCall {
+    const half_t* a; const half_t* w; const float* bias; void* out;
+    int M, K, N, mode;
+    int P, L;          // P_GEMM_NCHW only
+};
+constexpr int P_MAX_DEPTH = 64, P_CHUNK = 8;
+struct PBlock {
+    const float *ln1g, *ln1b, *ln2g, *ln2b, *srlng, *srlnb, *qb, *kvb, *ob, *fc1b, *fc2b, *dww, *dwb, *srb;
+    const half_t *qw, *kvw, *ow, *fc1w, *fc2w, *srw;
+};
+struct PStage {
+    int depth, C, heads, sr;
+    const half_t *pew, *headw; const float *peb, *pelng, *pelnb, *lng, *lnb;
+    PBlock blk[P_MAX_DEPTH];
+};
+struct ParserNet {
+    bool present = false;
+    int cap = 0, lastB = 0, lastH = 0, lastW = 0;      // images per pass (the workspace's size); what the last pass held
+    int maxH = 512, maxW = 512;                          // the workspace's extent
+    int mlp = 4, D = 0, L = 0, Lpad = 0;
+    float eps = 1e-6f;
+    PStage st[4];
+    const float *headb = nullptr, *clsb = nullptr; const half_t* clsw = nullptr;
+    half_t *in16 = nullptr, *a16 = nullptr, *q16 = nullptr, *c16 = nullptr, *kvin16 = nullptr, *kv16 = nullptr, *h16 = nullptr, *g16 = nullptr,
+           *st16[4] = {}, *pre16 = nullptr;
+    float *x32 = nullptr, *s32 = nullptr, *sr32 = nullptr, *st32[4] = {}, *p32[4] = {};
+};
+int launch_p_input(const float* pv, half_t* out, int B, int H, int W, hipStream_t st);
+int launch_p_gemm(const PGemmCall& g, hipStream_t st);
+int launch_p_ln(const float* in, const float* g, const float* b, float eps, long M, int C, float* out32, half_t* out16, hipStream_t st);
+int launch_p_attn(const half_t* q, const half_t* kv, half_t* ctx, int B, int Nq, int Nk, int heads, int d, hipStream_t st);
+int launch_p_dwgelu(const half_t* in, const float* w, const float* bias, half_t* out, int B, int H, int W, int C, hipStream_t st);
+int launch_p_upadd(const float* p0, const float* p1, const float* p2, const float* p3, half_t* out, int B, int H, int W, int D, hipStream_t st);
+int launch_p_to_nchw(const float* in, float* out, int N, int C, long P, hipStream_t st);
+size_t parser_workspace_bytes(const ParserNet& n, int cap);
+void parser_bind_workspace(ParserNet& n, void* ws, int cap);
+int parser_forward(ParserNet& n, int B, int H, int W, float* logits, hipStream_t st);

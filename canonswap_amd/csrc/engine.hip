@@ -26,6 +26,8 @@ extern "C" const char* cs_last_error(void) { return g_err; }
 // alone change no struct, no existing entry point's meaning and no blob format, which is what the header bumps the version for.
 // 4, unchanged: cs_identity, cs_identity_u8 (getid on the engine), cs_op_identity_read and cs_op_id_conv / cs_op_id_maxpool / cs_op_id_se_tail /
 // cs_op_id_embed (its kernels alone) were added; the optional "A.*" blobs are new names, no existing blob changed.
+// 4, unchanged: cs_parser (the SegFormer face parser on the engine), cs_op_parser_read and cs_op_parser_input / cs_op_parser_gemm / cs_op_parser_layernorm /
+// cs_op_parser_attention / cs_op_parser_dwgelu / cs_op_parser_upadd (its kernels alone) were added; the optional "P.*" blobs are new names; cs_op_id_conv takes K up to 8.
 // 4 (round 6): cs_soft_erosion_frames, cs_paste_back_batch, cs_motion_keypoints.
 // 3 (round 4): cs_conv_desc grew (hilo, stat_out, xf_*, ep_general), cs_op_conv takes conv_halo / vol32 / conv_wide configurations only, the
 // packed weight blobs of F.down0 / down1 / second carry [W_hi | W_lo], W.occ49 exists; cs_conv_desc::pool_hw.  _lib.load() refuses any other value.
@@ -110,6 +112,8 @@ struct cs_engine {
     float* m_h32 = nullptr;
     // ArcFace identity network (optional: present when the "A.*" blobs were uploaded); its workspace holds min(max_batch, 8) images per pass
     IdNet idn;
+    // SegFormer face parser (optional: present when the "P.*" blobs were uploaded); its workspace holds min(max_batch, P_CHUNK) images of 512 x 512 per pass
+    ParserNet psr;
     // soft-erosion scratch (allocated on first use for the largest B*H*W seen)
     float *se_a = nullptr, *se_b = nullptr, *se_part = nullptr; size_t se_cap = 0, se_part_cap = 0;      // se_part: 64 maxima per sample
 
@@ -1301,6 +1305,63 @@ extern "C" int cs_finalize_weights(cs_engine* e)
         }
         A.lastB = 0;
     }
+    // ---- P (optional): the SegFormer face parser (pack.py _pack_P); "P.cfg" holds the geometry
+    e->psr.present = e->find("P.cfg") != nullptr;
+    if (e->psr.present) {
+        ParserNet& P = e->psr;
+        const void* p;
+        int cfg[20];
+        TRY(need(e, "P.cfg", sizeof cfg, &p));
+        CS_CHECK_HIP(hipMemcpy(cfg, p, sizeof cfg, hipMemcpyDeviceToHost));
+        P.mlp = cfg[16]; P.D = cfg[17]; P.L = cfg[18]; P.Lpad = (P.L + 63) / 64 * 64;
+        memcpy(&P.eps, &cfg[19], 4);
+        if (P.mlp < 1 || P.mlp > 8 || P.D < 64 || P.D % 64 || P.L < 1 || P.L > 4096 || !(P.eps >= 0.f)) { cs_set_error("weights: 'P.cfg' holds an unsupported decode head"); return -1; }
+        int cin = 32;
+        for (int s = 0; s < 4; ++s) {
+            PStage& S = P.st[s];
+            S.depth = cfg[s]; S.C = cfg[4 + s]; S.heads = cfg[8 + s]; S.sr = cfg[12 + s];
+            const int Cc = S.C, ksz = s ? 3 : 7;
+            if (S.depth < 1 || S.depth > P_MAX_DEPTH || Cc < 64 || Cc > 512 || Cc % 64 || S.heads < 1 || Cc % S.heads || (Cc / S.heads != 32 && Cc / S.heads != 64) ||
+                S.sr != (8 >> s)) {
+                cs_set_error("weights: 'P.cfg' stage %d (depth %d, width %d, heads %d, sr %d) is not supported", s, S.depth, Cc, S.heads, S.sr); return -1;
+            }
+            snprintf(n, sizeof n, "P.s%d", s);
+            const std::string q(n);
+            TRY(need(e, q + ".pe.w", (size_t)ksz * ksz * Cc * cin * 2, &p)); S.pew = (const half_t*)p;
+            TRY(get_f32(e, q + ".pe.b", Cc, &S.peb));
+            TRY(get_f32(e, q + ".peln.g", Cc, &S.pelng)); TRY(get_f32(e, q + ".peln.b", Cc, &S.pelnb));
+            TRY(get_f32(e, q + ".ln.g", Cc, &S.lng)); TRY(get_f32(e, q + ".ln.b", Cc, &S.lnb));
+            TRY(need(e, q + ".head.w", (size_t)P.D * Cc * 2, &p)); S.headw = (const half_t*)p;
+            for (int k = 0; k < S.depth; ++k) {
+                PBlock& K = S.blk[k];
+                snprintf(n, sizeof n, "P.s%d.b%d", s, k);
+                const std::string b(n);
+                const int Hd = P.mlp * Cc;
+                TRY(get_f32(e, b + ".ln1.g", Cc, &K.ln1g)); TRY(get_f32(e, b + ".ln1.b", Cc, &K.ln1b));
+                TRY(get_f32(e, b + ".ln2.g", Cc, &K.ln2g)); TRY(get_f32(e, b + ".ln2.b", Cc, &K.ln2b));
+                TRY(need(e, b + ".q.w", (size_t)Cc * Cc * 2, &p)); K.qw = (const half_t*)p; TRY(get_f32(e, b + ".q.b", Cc, &K.qb));
+                TRY(need(e, b + ".kv.w", (size_t)2 * Cc * Cc * 2, &p)); K.kvw = (const half_t*)p; TRY(get_f32(e, b + ".kv.b", 2 * Cc, &K.kvb));
+                TRY(need(e, b + ".o.w", (size_t)Cc * Cc * 2, &p)); K.ow = (const half_t*)p; TRY(get_f32(e, b + ".o.b", Cc, &K.ob));
+                TRY(need(e, b + ".fc1.w", (size_t)Hd * Cc * 2, &p)); K.fc1w = (const half_t*)p; TRY(get_f32(e, b + ".fc1.b", Hd, &K.fc1b));
+                TRY(need(e, b + ".fc2.w", (size_t)Hd * Cc * 2, &p)); K.fc2w = (const half_t*)p; TRY(get_f32(e, b + ".fc2.b", Cc, &K.fc2b));
+                TRY(get_f32(e, b + ".dw.w", 9 * Hd, &K.dww)); TRY(get_f32(e, b + ".dw.b", Hd, &K.dwb));
+                K.srw = nullptr; K.srb = K.srlng = K.srlnb = nullptr;
+                if (S.sr > 1) {
+                    TRY(need(e, b + ".sr.w", (size_t)S.sr * S.sr * Cc * Cc * 2, &p)); K.srw = (const half_t*)p; TRY(get_f32(e, b + ".sr.b", Cc, &K.srb));
+                    TRY(get_f32(e, b + ".srln.g", Cc, &K.srlng)); TRY(get_f32(e, b + ".srln.b", Cc, &K.srlnb));
+                }
+            }
+            cin = Cc;
+        }
+        TRY(get_f32(e, "P.head.b", P.D, &P.headb));
+        TRY(need(e, "P.cls.w", (size_t)P.Lpad * P.D * 2, &p)); P.clsw = (const half_t*)p;
+        TRY(get_f32(e, "P.cls.b", P.Lpad, &P.clsb));
+        const int cap = e->maxB < P_CHUNK ? e->maxB : P_CHUNK;
+        char* ws = nullptr;          // (a reload with another geometry gets a workspace of its own; the old one lives until cs_destroy)
+        TRY(e->alloc(&ws, parser_workspace_bytes(P, cap)));
+        parser_bind_workspace(P, ws, cap);
+        P.lastB = 0;
+    }
     // ---- F
     TRY(get_f32(e, "F.first.w", 64 * 27, &e->first_w)); TRY(get_f32(e, "F.first.b", 64, &e->first_b));
     // packed as [W_hi | W_lo] over twice the input channels (run_F: wsplit_in)
@@ -1873,6 +1934,29 @@ extern "C" int cs_identity_u8(cs_engine* e, int B, const uint8_t* crops, int H, 
     return identity_impl(e, "cs_identity_u8", B, nullptr, crops, lut, H, W, id_out, raw_out, stream);
 }
 
+// ---- the SegFormer face parser on the engine (can_swap_pipeline_e2e.py:178-182: model(pixel_values).logits): pixel_values fp32 NCHW -> logits fp32
+// [B][L][H / 4][W / 4].  Everything is refused before any launch; more than the workspace's images run as several passes.
+extern "C" int cs_parser(cs_engine* e, int B, const float* pixel_values, int H, int W, float* logits_out, void* stream)
+{
+    if (!e) { cs_set_error("cs_parser: NULL engine"); return -1; }
+    if (!e->finalized) { cs_set_error("cs_parser: cs_finalize_weights has not been called"); return -1; }
+    if (!e->psr.present) { cs_set_error("cs_parser: the engine holds no face parser (no 'P.*' blobs: pass the 'parser' state-dict)"); return -1; }
+    if (B < 1 || B > e->maxB) { cs_set_error("cs_parser: batch %d outside [1, %d]", B, e->maxB); return -1; }
+    if (!pixel_values || !logits_out) { cs_set_error("cs_parser: NULL pointer"); return -1; }
+    ParserNet& P = e->psr;
+    if (H < 32 || W < 32 || H % 32 || W % 32) { cs_set_error("cs_parser: H = %d, W = %d (each a multiple of 32)", H, W); return -1; }
+    if ((long)H * W > (long)P.maxH * P.maxW) { cs_set_error("cs_parser: %d x %d exceeds the workspace's %d x %d", H, W, P.maxH, P.maxW); return -1; }
+    if ((H / 32) * (W / 32) > 256) { cs_set_error("cs_parser: %d keys per stage (at most 256: inputs up to 512 x 512)", (H / 32) * (W / 32)); return -1; }
+    DevGuard guard(e->dev);
+    hipStream_t st = (hipStream_t)stream;
+    for (int b0 = 0; b0 < B; b0 += P.cap) {
+        const int nb = B - b0 < P.cap ? B - b0 : P.cap;
+        TRY(e->run(1, st, [&] { return launch_p_input(pixel_values + (size_t)b0 * 3 * H * W, P.in16, nb, H, W, st); }, "parser_input16"));
+        TRY(e->run(1, st, [&] { return parser_forward(P, nb, H, W, logits_out + (size_t)b0 * P.L * (H / 4) * (W / 4), st); }, "parser"));
+    }
+    return 0;
+}
+
 extern "C" int cs_profile_begin(cs_engine* e)
 {
     if (!e) { cs_set_error("null engine"); return -1; }
@@ -2185,5 +2269,54 @@ extern "C" int cs_op_identity_read(cs_engine* e, int which, int B, float* dst, v
     }
     if (which == CS_ID_PREFC) return launch_id_to_nchw(A.a16, 1, dst, B, 512, 49, st);
     cs_set_error("cs_op_identity_read: no activation %d", which);
+    return -1;
+}
+
+// ---- operator level: the face parser's kernels (csrc/parser.hip) without an engine, and the activations the last cs_parser pass left
+extern "C" int cs_op_parser_input(const float* pixel_values, void* out16, int B, int H, int W, void* stream)
+{
+    return launch_p_input(pixel_values, (half_t*)out16, B, H, W, (hipStream_t)stream);
+}
+
+extern "C" int cs_op_parser_gemm(const void* a16, const void* w16, const float* bias, int M, int K, int N, int mode, void* out, int P, int L, void* stream)
+{
+    PGemmCall g{(const half_t*)a16, (const half_t*)w16, bias, out, M, K, N, mode, P, L};
+    return launch_p_gemm(g, (hipStream_t)stream);
+}
+
+extern "C" int cs_op_parser_layernorm(const float* in, const float* g, const float* b, float eps, long M, int C, float* out32, void* out16, void* stream)
+{
+    return launch_p_ln(in, g, b, eps, M, C, out32, (half_t*)out16, (hipStream_t)stream);
+}
+
+extern "C" int cs_op_parser_attention(const void* q16, const void* kv16, void* ctx16, int B, int Nq, int Nk, int heads, int d, void* stream)
+{
+    return launch_p_attn((const half_t*)q16, (const half_t*)kv16, (half_t*)ctx16, B, Nq, Nk, heads, d, (hipStream_t)stream);
+}
+
+extern "C" int cs_op_parser_dwgelu(const void* in16, const float* w, const float* bias, void* out16, int B, int H, int W, int C, void* stream)
+{
+    return launch_p_dwgelu((const half_t*)in16, w, bias, (half_t*)out16, B, H, W, C, (hipStream_t)stream);
+}
+
+extern "C" int cs_op_parser_upadd(const float* p0, const float* p1, const float* p2, const float* p3, void* out16, int B, int H, int W, int D, void* stream)
+{
+    return launch_p_upadd(p0, p1, p2, p3, (half_t*)out16, B, H, W, D, (hipStream_t)stream);
+}
+
+extern "C" int cs_op_parser_read(cs_engine* e, int which, int B, float* dst, void* stream)
+{
+    if (!e || !e->psr.present) { cs_set_error("cs_op_parser_read: no engine, or no face parser in it"); return -1; }
+    const ParserNet& P = e->psr;
+    if (!dst) { cs_set_error("cs_op_parser_read: null destination"); return -1; }
+    if (B < 1 || B > P.lastB) { cs_set_error("cs_op_parser_read: %d samples, the last pass held %d", B, P.lastB); return -1; }
+    DevGuard guard(e->dev);
+    hipStream_t st = (hipStream_t)stream;
+    if (which >= CS_PARSER_STAGE0 && which < CS_PARSER_STAGE0 + 4) {
+        const int s = which - CS_PARSER_STAGE0;
+        return launch_p_to_nchw(P.st32[s], dst, B, P.st[s].C, (long)(P.lastH >> (s + 2)) * (P.lastW >> (s + 2)), st);
+    }
+    if (which == CS_PARSER_PRE) return launch_nhwc16_to_nchw(P.pre16, dst, B, P.D, (P.lastH / 4) * (P.lastW / 4), st);
+    cs_set_error("cs_op_parser_read: no activation %d", which);
     return -1;
 }

@@ -258,7 +258,7 @@ int launch_id_input(const float* img, const unsigned char* u8, const float* lut,
 int launch_id_conv(const IdConvCall& c, hipStream_t st)
 {
     if (!c.in || !c.w || !c.out || c.N < 1 || c.IH < 1 || c.IW < 1 || c.Cin < 32 || c.Cin % 32 || c.Cout < 64 || c.Cout % 64 ||
-        (c.K != 1 && c.K != 3) || c.stride < 1 || c.pad < 0 || c.pad >= c.K) { cs_set_error("id_conv: bad arguments"); return -1; }
+        c.K < 1 || c.K > 8 || c.stride < 1 || c.pad < 0 || c.pad >= c.K) { cs_set_error("id_conv: bad arguments"); return -1; }
     if (c.IH + 2 * c.pad < c.K || c.IW + 2 * c.pad < c.K) { cs_set_error("id_conv: input smaller than the kernel"); return -1; }
     if (c.OH != (c.IH + 2 * c.pad - c.K) / c.stride + 1 || c.OW != (c.IW + 2 * c.pad - c.K) / c.stride + 1) { cs_set_error("id_conv: output extent does not match"); return -1; }
     const long M = (long)c.N * c.OH * c.OW;

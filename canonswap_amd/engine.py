@@ -35,6 +35,7 @@ class Engine:
             _lib.check(self.lib.cs_set_latency_mode(h, 1), "cs_set_latency_mode")
         self._ids = []            # resident identities: [slot, device copy (512,), last tensor seen, its _version, use tick]
         self._tick = 0
+        self.parser_cfg = None    # geometry of the face parser the loaded blobs hold ("P.cfg"), or None
 
     def close(self):
         if getattr(self, "h", None):
@@ -60,6 +61,9 @@ class Engine:
             _lib.check(self.lib.cs_upload(self.h, name.encode(), arr.ctypes.data_as(C.c_void_p), arr.nbytes), f"cs_upload({name})")
         _lib.check(self.lib.cs_finalize_weights(self.h), "cs_finalize_weights")
         self._ids = []
+        if "P.cfg" in blobs:
+            c = [int(v) for v in np.asarray(blobs["P.cfg"]).reshape(-1)]
+            self.parser_cfg = {"depths": c[0:4], "widths": c[4:8], "heads": c[8:12], "sr": c[12:16], "mlp": c[16], "D": c[17], "L": c[18]}
 
     def _stream(self):
         return C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
@@ -382,6 +386,40 @@ class Engine:
         shape = [(64, 55, 55), (64, 55, 55), (128, 28, 28), (256, 14, 14), (512, 7, 7), (512, 7, 7)][which]
         dst = self._new(B, *shape)
         _lib.check(self.lib.cs_op_identity_read(self.h, which, B, _ptr(dst), self._stream()), "cs_op_identity_read")
+        return dst
+
+    # ---------------------------------------------------------------- face parser (SegFormer)
+    @property
+    def has_parser(self):
+        return self.parser_cfg is not None
+
+    def parser(self, pixel_values, out=None):
+        """The SegFormer face parser on the engine (can_swap_pipeline_e2e.py:178-182: model(pixel_values).logits): pixel_values (B,3,H,W) fp32, H and W
+        multiples of 32 up to 512 x 512 (what parser_input makes of the crops) -> logits (B,L,H/4,W/4) fp32 on the device, the tensor face_masks
+        takes.  Needs the "parser" state-dict among the loaded weights.  A workspace of its own: it may be enqueued beside the generator, but two
+        parser calls on one engine must be ordered with each other."""
+        if not self.has_parser:
+            raise RuntimeError("parser: the engine holds no face parser (pass the 'parser' state-dict with the weights)")
+        if not isinstance(pixel_values, torch.Tensor) or pixel_values.dim() != 4 or pixel_values.shape[1] != 3 or min(pixel_values.shape) < 1:
+            raise ValueError("parser expects a (B, 3, H, W) tensor")
+        pv = self._in(pixel_values)
+        B, _, H, W = pv.shape
+        if H % 32 or W % 32:
+            raise ValueError(f"parser: H = {H}, W = {W} (each a multiple of 32)")
+        logits = self._out(out, (B, self.parser_cfg["L"], H // 4, W // 4), torch.float32)
+        with torch.cuda.device(self.device):
+            _lib.check(self.lib.cs_parser(self.h, B, _ptr(pv), H, W, _ptr(logits), self._stream()), "cs_parser")
+        return logits
+
+    def parser_read(self, which: int, B: int, H: int, W: int):
+        """cs_op_parser_read: activation `which` (0-3: the encoder stages' outputs, 4: the decode head's map in front of the classifier) of the
+        last parser pass, whose input was H x W, as fp32 NCHW (tests)."""
+        if not self.has_parser:
+            raise RuntimeError("parser_read: the engine holds no face parser")
+        c = self.parser_cfg
+        shape = (c["D"], H // 4, W // 4) if which == 4 else (c["widths"][which], H >> (which + 2), W >> (which + 2))
+        dst = self._new(B, *shape)
+        _lib.check(self.lib.cs_op_parser_read(self.h, which, B, _ptr(dst), self._stream()), "cs_op_parser_read")
         return dst
 
     # ---------------------------------------------------------------- measurement

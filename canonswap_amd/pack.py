@@ -442,6 +442,172 @@ def _pack_A(out, sd):
     out["A.fc.w"] = np.ascontiguousarray(wf.transpose(2, 0, 1).astype(np.float16))            # [h * 7 + w][o][c]
     out["A.fc.b"] = _f32(sd["fc.bias"].astype(np.float64) * s3 + t3)
 
+# ---- the SegFormer face parser.  Keys are normalised to the transformers 5.x spelling; the published checkpoint
+# (jonathandinu/face-parsing) and transformers 4.x spell them as on the left (transformers/conversion_mapping.py, "SegformerModel" and
+# "SegformerForSemanticSegmentation").  Applied in this order, each to the whole key.
+P_RENAMES = (
+    (r"encoder\.patch_embeddings\.(\d+)\.", r"stages.\1.patch_embeddings."),
+    (r"encoder\.block\.(\d+)\.", r"stages.\1.blocks."),
+    (r"encoder\.layer_norm\.(\d+)", r"stages.\1.layer_norm"),
+    (r"attention\.self\.query", "attention.q_proj"),
+    (r"attention\.self\.key", "attention.k_proj"),
+    (r"attention\.self\.value", "attention.v_proj"),
+    (r"attention\.self\.sr", "attention.sequence_reduction.sequence_reduction"),
+    (r"attention\.self\.layer_norm", "attention.sequence_reduction.layer_norm"),
+    (r"attention\.output\.dense", "attention.o_proj"),
+    (r"mlp\.dense1", "mlp.fc1"),
+    (r"mlp\.dense2", "mlp.fc2"),
+    (r"layer_norm_1", "layernorm_before"),
+    (r"layer_norm_2", "layernorm_after"),
+    (r"decode_head\.linear_c", "decode_head.linear_projections"),
+)
+P_BN_EPS = 1e-5          # nn.BatchNorm2d's default: the decode head's batch_norm
+# Every LayerNorm of transformers' SegFormer is a plain nn.LayerNorm(hidden_size): eps = 1e-5.  The config's layer_norm_eps (1e-6) is not read by
+# the class, so it is not read here either; a caller who wants another value passes {"ln_eps": ...}.
+P_LN_EPS = 1e-5
+
+
+def parser_rename(sd):
+    """State-dict in either spelling -> the 5.x spelling (a dict of the same arrays)."""
+    import re
+    out = {}
+    for k, v in sd.items():
+        for a, b in P_RENAMES:
+            k = re.sub(a, b, k)
+        out[k] = v
+    return out
+
+
+def parser_config(sd, config=None):
+    """Geometry of a (renamed) SegFormer state-dict from its shapes; heads come from `config` (an HF config or a dict with
+    num_attention_heads; default C / 64), the LayerNorm eps is P_LN_EPS unless the config carries "ln_eps".  Refuses by name what the engine does not run."""
+    get = (lambda k, d: config.get(k, d)) if isinstance(config, dict) else (lambda k, d: getattr(config, k, d))
+    pe = "segformer.stages.%d.patch_embeddings.proj.weight"
+    if pe % 0 not in sd:
+        raise ValueError(f"parser: key '{pe % 0}' is missing")
+    if pe % 4 in sd or any(pe % s not in sd for s in range(4)):
+        raise ValueError("parser: the encoder must have 4 stages")
+    widths = [int(sd[pe % s].shape[0]) for s in range(4)]
+    depths, srs = [], []
+    for s in range(4):
+        n = 0
+        while f"segformer.stages.{s}.blocks.{n}.attention.q_proj.weight" in sd:
+            n += 1
+        if n < 1 or n > 64:
+            raise ValueError(f"parser: stage {s} has {n} blocks (1 to 64)")
+        depths.append(n)
+        k = f"segformer.stages.{s}.blocks.0.attention.sequence_reduction.sequence_reduction.weight"
+        srs.append(int(sd[k].shape[2]) if k in sd else 1)
+    heads = [int(h) for h in (get("num_attention_heads", None) or [max(c // 64, 1) for c in widths])]
+    eps = float(get("ln_eps", P_LN_EPS))
+    mlp = int(sd["segformer.stages.0.blocks.0.mlp.fc1.weight"].shape[0]) // widths[0]
+    D, L = int(sd["decode_head.linear_fuse.weight"].shape[0]), int(sd["decode_head.classifier.weight"].shape[0])
+    for s, (c, h, r) in enumerate(zip(widths, heads, srs)):
+        if c % 64 or c > 512:
+            raise ValueError(f"parser: stage {s} is {c} channels wide (a multiple of 64 up to 512)")
+        if c % h or c // h not in (32, 64):
+            raise ValueError(f"parser: stage {s} has head dimension {c / h:g} ({c} channels, {h} heads); 32 or 64 are supported")
+        if r != 8 >> s:
+            raise ValueError(f"parser: stage {s} has sequence-reduction ratio {r}; the engine runs {8 >> s} there (every stage sees (H/32)(W/32) keys)")
+        if tuple(sd[pe % s].shape[2:]) != ((7, 7) if s == 0 else (3, 3)):
+            raise ValueError(f"parser: stage {s} has a {tuple(sd[pe % s].shape[2:])} patch embedding (7 x 7 stride 4, then 3 x 3 stride 2)")
+    if D % 64:
+        raise ValueError(f"parser: decoder width {D} (a multiple of 64)")
+    return {"depths": depths, "widths": widths, "heads": heads, "sr": srs, "mlp": mlp, "D": D, "L": L, "eps": eps}
+
+
+def parser_keys(cfg):
+    """Every key of the 5.x state-dict for a geometry (num_batches_tracked aside)."""
+    keys = []
+    wb = lambda p: [p + ".weight", p + ".bias"]
+    for s in range(4):
+        q = f"segformer.stages.{s}"
+        keys += wb(q + ".patch_embeddings.proj") + wb(q + ".patch_embeddings.layer_norm") + wb(q + ".layer_norm")
+        for i in range(cfg["depths"][s]):
+            b = f"{q}.blocks.{i}"
+            for n in ("layernorm_before", "attention.q_proj", "attention.k_proj", "attention.v_proj", "attention.o_proj", "layernorm_after",
+                      "mlp.fc1", "mlp.dwconv.dwconv", "mlp.fc2"):
+                keys += wb(f"{b}.{n}")
+            if cfg["sr"][s] > 1:
+                keys += wb(b + ".attention.sequence_reduction.sequence_reduction") + wb(b + ".attention.sequence_reduction.layer_norm")
+        keys += wb(f"decode_head.linear_projections.{s}.proj")
+    keys += ["decode_head.linear_fuse.weight"] + wb("decode_head.batch_norm") + ["decode_head.batch_norm.running_mean", "decode_head.batch_norm.running_var"]
+    return keys + wb("decode_head.classifier")
+
+
+def parser_compose_head(sd, cfg):
+    """BN(linear_fuse(cat(up(linear_c[s](x_s))[::-1]))) = sum_s up(W'_s x_s) + b' (bilinear weights sum to 1, everything is linear): float64
+    ([W'_0 .. W'_3] each [D][C_s], b' [D]).  The concatenation is reversed: stage s reads columns (3 - s) D .. (4 - s) D of linear_fuse."""
+    f8 = lambda k: np.asarray(sd[k], np.float64)
+    D = cfg["D"]
+    p = "decode_head.batch_norm"
+    sc = f8(p + ".weight") / np.sqrt(f8(p + ".running_var") + P_BN_EPS)
+    sh = f8(p + ".bias") - f8(p + ".running_mean") * sc
+    fuse = f8("decode_head.linear_fuse.weight").reshape(D, 4 * D)
+    ws, b = [], sh.copy()
+    for s in range(4):
+        fs = fuse[:, (3 - s) * D:(4 - s) * D]
+        ws.append(sc[:, None] * (fs @ f8(f"decode_head.linear_projections.{s}.proj.weight")))
+        b += sc * (fs @ f8(f"decode_head.linear_projections.{s}.proj.bias"))
+    return ws, b
+
+
+def _pack_P(out, sd, config=None):
+    """The SegFormer face parser (transformers' SegformerForSemanticSegmentation), keys in either spelling.  All in float64:
+      * "P.cfg" int32 [20]: depths, widths, heads, sr ratios (4 each), MLP ratio, decoder width D, labels L, the LayerNorm eps as fp32 bits;
+      * the d^-1/2 scale of the attention folded into q_proj's weight and bias; k_proj and v_proj stacked into one [2 C][C] matrix;
+      * the patch-embedding and sequence-reduction convs in pack_id_conv's layout (the first one's 3 input channels padded to 32); the
+        depth-wise weights tap-major [9][4 C] fp32;
+      * the decode head composed (parser_compose_head): "P.s<s>.head.w" = W'_s, "P.head.b" = b'; the classifier padded to 64 rows of zeros."""
+    sd = parser_rename(sd)
+    sd = {k: v for k, v in sd.items() if not k.endswith("num_batches_tracked")}
+    cfg = parser_config(sd, config)
+    want = parser_keys(cfg)
+    for k in want:
+        if k not in sd:
+            raise ValueError(f"parser: key '{k}' is missing")
+    extra = sorted(set(sd) - set(want))
+    if extra:
+        raise ValueError(f"parser: unexpected key '{extra[0]}'")
+    f8 = lambda k: np.asarray(sd[k], np.float64)
+    h16 = lambda a: np.ascontiguousarray(np.asarray(a, np.float64).astype(np.float16))
+    out["P.cfg"] = np.array(cfg["depths"] + cfg["widths"] + cfg["heads"] + cfg["sr"] + [cfg["mlp"], cfg["D"], cfg["L"],
+                            int(np.array([cfg["eps"]], np.float32).view(np.int32)[0])], np.int32)
+    for s in range(4):
+        q, o = f"segformer.stages.{s}", f"P.s{s}"
+        C = cfg["widths"][s]
+        scale = float(C // cfg["heads"][s]) ** -0.5
+        out[o + ".pe.w"] = pack_id_conv(f8(q + ".patch_embeddings.proj.weight"))
+        out[o + ".pe.b"] = _f32(f8(q + ".patch_embeddings.proj.bias"))
+        out[o + ".peln.g"], out[o + ".peln.b"] = _f32(f8(q + ".patch_embeddings.layer_norm.weight")), _f32(f8(q + ".patch_embeddings.layer_norm.bias"))
+        out[o + ".ln.g"], out[o + ".ln.b"] = _f32(f8(q + ".layer_norm.weight")), _f32(f8(q + ".layer_norm.bias"))
+        for i in range(cfg["depths"][s]):
+            b, n = f"{q}.blocks.{i}", f"{o}.b{i}"
+            for dst, src in ((".ln1", ".layernorm_before"), (".ln2", ".layernorm_after")):
+                out[n + dst + ".g"], out[n + dst + ".b"] = _f32(f8(b + src + ".weight")), _f32(f8(b + src + ".bias"))
+            out[n + ".q.w"], out[n + ".q.b"] = h16(f8(b + ".attention.q_proj.weight") * scale), _f32(f8(b + ".attention.q_proj.bias") * scale)
+            out[n + ".kv.w"] = h16(np.concatenate([f8(b + ".attention.k_proj.weight"), f8(b + ".attention.v_proj.weight")], 0))
+            out[n + ".kv.b"] = _f32(np.concatenate([f8(b + ".attention.k_proj.bias"), f8(b + ".attention.v_proj.bias")], 0))
+            out[n + ".o.w"], out[n + ".o.b"] = h16(f8(b + ".attention.o_proj.weight")), _f32(f8(b + ".attention.o_proj.bias"))
+            if cfg["sr"][s] > 1:
+                r = b + ".attention.sequence_reduction"
+                out[n + ".sr.w"], out[n + ".sr.b"] = pack_id_conv(f8(r + ".sequence_reduction.weight")), _f32(f8(r + ".sequence_reduction.bias"))
+                out[n + ".srln.g"], out[n + ".srln.b"] = _f32(f8(r + ".layer_norm.weight")), _f32(f8(r + ".layer_norm.bias"))
+            out[n + ".fc1.w"], out[n + ".fc1.b"] = h16(f8(b + ".mlp.fc1.weight")), _f32(f8(b + ".mlp.fc1.bias"))
+            out[n + ".dw.w"] = _f32(f8(b + ".mlp.dwconv.dwconv.weight").reshape(-1, 9).T)
+            out[n + ".dw.b"] = _f32(f8(b + ".mlp.dwconv.dwconv.bias"))
+            out[n + ".fc2.w"], out[n + ".fc2.b"] = h16(f8(b + ".mlp.fc2.weight")), _f32(f8(b + ".mlp.fc2.bias"))
+    ws, bp = parser_compose_head(sd, cfg)
+    for s in range(4):
+        out[f"P.s{s}.head.w"] = h16(ws[s])
+    out["P.head.b"] = _f32(bp)
+    D, L = cfg["D"], cfg["L"]
+    Lp = -(-L // 64) * 64
+    cw, cb = np.zeros((Lp, D), np.float64), np.zeros(Lp, np.float64)
+    cw[:L], cb[:L] = f8("decode_head.classifier.weight").reshape(L, D), f8("decode_head.classifier.bias")
+    out["P.cls.w"], out["P.cls.b"] = h16(cw), _f32(cb)
+    return cfg
+
 
 def _np_sd(sd):
     return {k: (v.detach().cpu().numpy() if hasattr(v, "detach") else np.asarray(v)) for k, v in sd.items()}
@@ -449,7 +615,7 @@ def _np_sd(sd):
 
 def build_blobs(state_dicts: dict) -> dict:
     """``state_dicts``: {'appearance_feature_extractor', 'warping_module', 'spade_generator', 'transfer',
-    'refine'[, 'motion_extractor'][, 'arcface']} -> {blob name: contiguous ndarray}; values may be torch tensors or numpy arrays."""
+    'refine'[, 'motion_extractor'][, 'arcface'][, 'parser'][, 'parser_config']} -> {blob name: contiguous ndarray}; values may be torch tensors or numpy arrays."""
     out: dict = {}
     _pack_F(out, _np_sd(state_dicts["appearance_feature_extractor"]))
     _pack_W(out, _np_sd(state_dicts["warping_module"]))
@@ -460,4 +626,6 @@ def build_blobs(state_dicts: dict) -> dict:
         _pack_M(out, _np_sd(state_dicts["motion_extractor"]))
     if "arcface" in state_dicts:                               # optional: getid on the engine (blobs "A.*")
         _pack_A(out, _np_sd(state_dicts["arcface"]))
+    if "parser" in state_dicts:                                # optional: the SegFormer face parser on the engine (blobs "P.*")
+        _pack_P(out, _np_sd(state_dicts["parser"]), state_dicts.get("parser_config"))
     return out

@@ -268,6 +268,72 @@ def _arcface(seed):
 _BUILDERS["arcface"] = _arcface
 
 
+MIT_B5 = {"depths": (3, 6, 40, 3), "widths": (64, 128, 320, 512), "heads": (1, 2, 5, 8), "sr": (8, 4, 2, 1), "mlp": 4, "D": 768, "L": 19}
+PARSER_A = dict(MIT_B5, depths=(1, 1, 2, 1))          # the tests' geometry: the real widths and heads, few blocks
+PARSER_B = dict(PARSER_A, D=256)
+
+
+def _segformer(seed, cfg=None):
+    """SegformerForSemanticSegmentation state-dict (the face parser) in the transformers 4.x spelling of the published
+    checkpoint; cfg: geometry as MIT_B5 (the default).  Heads are not in the weights: pass {"num_attention_heads": cfg["heads"]} as the config.
+    Gains: q and k at 1.2 give scores of standard deviation about 1.4 (rows neither uniform nor one-hot); o_proj and fc2 at 0.3 keep the
+    pre-norm residual chain tame over 52 blocks; the classifier at 2 spreads the logits so that label margins are usable."""
+    cfg = cfg or MIT_B5
+    b = _Builder(seed, "P")
+
+    def ln(name, c):
+        b.gn(name, c)
+
+    cin = 3
+    for s, (n, c, r) in enumerate(zip(cfg["depths"], cfg["widths"], cfg["sr"])):
+        k = 7 if s == 0 else 3
+        b.conv(f"segformer.encoder.patch_embeddings.{s}.proj", c, cin, k, k)
+        ln(f"segformer.encoder.patch_embeddings.{s}.layer_norm", c)
+        for i in range(n):
+            p = f"segformer.encoder.block.{s}.{i}"
+            ln(p + ".layer_norm_1", c)
+            b.conv(p + ".attention.self.query", c, c, gain=1.2)
+            b.conv(p + ".attention.self.key", c, c, gain=1.2)
+            b.conv(p + ".attention.self.value", c, c)
+            if r > 1:
+                b.conv(p + ".attention.self.sr", c, c, r, r)
+                ln(p + ".attention.self.layer_norm", c)
+            b.conv(p + ".attention.output.dense", c, c, gain=0.3)
+            ln(p + ".layer_norm_2", c)
+            b.conv(p + ".mlp.dense1", cfg["mlp"] * c, c)
+            b.conv(p + ".mlp.dwconv.dwconv", cfg["mlp"] * c, 1, 3, 3)
+            b.conv(p + ".mlp.dense2", c, cfg["mlp"] * c, gain=0.3)
+        ln(f"segformer.encoder.layer_norm.{s}", c)
+        cin = c
+    D = cfg["D"]
+    for s, c in enumerate(cfg["widths"]):
+        b.conv(f"decode_head.linear_c.{s}.proj", D, c)
+    b.conv("decode_head.linear_fuse", D, 4 * D, 1, 1, bias=False)
+    b.bn("decode_head.batch_norm", D)
+    b.conv("decode_head.classifier", cfg["L"], D, 1, 1, gain=2.0)
+    return b.sd
+
+
+_BUILDERS["parser"] = _segformer
+
+
+def parser_pixel_values(img_u8) -> np.ndarray:
+    """(n,3,H,W) uint8 -> fp32 pixel_values: the image processor's rescale (1 / 255) and Normalize (ID_MEAN / ID_STD), computed in float64."""
+    m, s = np.array(ID_MEAN).reshape(1, 3, 1, 1), np.array(ID_STD).reshape(1, 3, 1, 1)
+    return np.ascontiguousarray(((np.asarray(img_u8, np.float64) / 255.0 - m) / s).astype(np.float32))
+
+
+def make_parser_images(n: int, seed: int = 4000, H: int = 512, W: int = 512) -> np.ndarray:
+    """(n,3,H,W) uint8: smooth synthetic images (make_smooth_images), the face parser's input before its image processor."""
+    img = make_smooth_images(n, seed=seed, size=max(H, W))[:, :, :H, :W]
+    return np.ascontiguousarray(np.round(img * 255.0).astype(np.uint8))
+
+
+def make_parser_inputs(n: int, seed: int = 4000, H: int = 512, W: int = 512) -> np.ndarray:
+    """(n,3,H,W) fp32 pixel_values of make_parser_images: values in about [-2.2, 2.7]."""
+    return parser_pixel_values(make_parser_images(n, seed, H, W))
+
+
 def make_state_dicts(seed: int = 0, modules=MODULES, family: str = "uniform") -> dict:
     """Return ``{module_name: OrderedDict[str, np.ndarray]}`` laid out like the reference's
     ``combined_weights.pth`` (``src/can_swap_e2e.py:87-100``).  The motion extractor is built on

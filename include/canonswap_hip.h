@@ -52,6 +52,14 @@ int cs_identity(cs_engine* e, int B, const float* img, int H, int W, float* id_o
  * device holds what the transform makes of byte v in channel c (canonswap_amd/tail.py id_lut); bit-equal to cs_identity on the table's values. */
 int cs_identity_u8(cs_engine* e, int B, const uint8_t* crops, int H, int W, const float* lut, float* id_out, float* raw_out, void* stream);
 
+/* The SegFormer face parser on the engine (can_swap_pipeline_e2e.py:178-182, can_swap_pipeline_v2i.py:73-76: model(pixel_values).logits): needs the
+ * optional "P.*" blobs (pack.py _pack_P, from the "parser" state-dict).  pixel_values fp32 Bx3xHxW on the device (what cs_parser_input writes), H and W
+ * multiples of 32 up to 512 x 512 -> logits_out fp32 BxLx(H/4)x(W/4), the tensor cs_face_masks takes.  Everything is checked before any launch.  The
+ * call uses a workspace of its own (allocated by cs_finalize_weights when the blobs are there, for min(max_batch, 8) images of 512 x 512 per pass;
+ * larger batches run as several passes), not the generator's scratch: it may be enqueued beside any other entry point of the engine, but two parser
+ * calls on one engine must be ordered with each other. */
+int cs_parser(cs_engine* e, int B, const float* pixel_values, int H, int W, float* logits_out, void* stream);
+
 /* Single-frame latency mode (BASELINE configs[1]): launches that cannot fill the 256 CUs at one or two frames per call take forms that
  * add an output element's products in another (fixed) order than the batched path - the 512-channel 3x3 convs split their K loop over twelve waves
  * of a workgroup (conv_lat.hip), the deep hourglass levels over workgroups (split-K), R's volume convs emit 2-row statistics blocks.  Deterministic,
@@ -363,7 +371,7 @@ int cs_op_dm_read(cs_engine* e, int which, int B, void* dst, void* stream);
 
 /* The identity network's kernels one at a time (csrc/identity.hip; weights as pack._pack_A lays them out; models/arcface_models.py:10-136).
  * conv: in fp16 (in_f32: fp32, rounded to fp16 on load) contiguous [N][IH][IW][Cin] -> out fp32 / fp16 [N][OH][OW][Cout] = prelu(conv + bias), K x K
- * taps (1 or 3), stride >= 1, zero padding pad < K, OH = (IH + 2 pad - K) / stride + 1; w fp16 [K * K][Cout][Cin] (pack.pack_id_conv); Cin % 32 == 0,
+ * taps (K from 1 to 8), stride >= 1, zero padding pad < K, OH = (IH + 2 pad - K) / stride + 1; w fp16 [K * K][Cout][Cin] (pack.pack_id_conv); Cin % 32 == 0,
  * Cout % 64 == 0; slope: device pointer to the PReLU's one slope, NULL = no activation; bias may be NULL */
 int cs_op_id_conv(const void* in, int in_f32, int N, int IH, int IW, int Cin, int K, int stride, int pad, const void* w, const float* bias,
                   int Cout, const float* slope, void* out, int out_f32, void* stream);
@@ -383,6 +391,28 @@ int cs_op_id_embed(const void* a16, const void* w, const float* bias, float* par
  * Bx512x7x7 (i = 0 .. 3), CS_ID_PREFC Bx512x7x7 (bn2's output as the fc reads it, fp16 values) */
 enum { CS_ID_STEM = 0, CS_ID_LAYER1 = 1, CS_ID_PREFC = 5 };
 int cs_op_identity_read(cs_engine* e, int which, int B, float* dst, void* stream);
+
+/* ---- operator level: the face parser's kernels alone (csrc/parser.hip; all tensors contiguous, channels-last, on the device).
+ * input: pixel_values fp32 [B][3][H][W] -> fp16 [B][H][W][32] (3 real + 29 zero channels) */
+int cs_op_parser_input(const float* pixel_values, void* out16, int B, int H, int W, void* stream);
+/* token GEMM: a16 fp16 [M][K] x w16 fp16 [N][K]^T + bias (may be NULL), fp32 accumulation; K % 32 == 0, N % 64 == 0, any M >= 1.  mode 0: out fp16
+ * [M][N]; 1: out fp32 [M][N] += result (the residual stream, in place); 2: out fp32 [M][N]; 3: out fp32 [M / P][L][P], the first L columns only */
+int cs_op_parser_gemm(const void* a16, const void* w16, const float* bias, int M, int K, int N, int mode, void* out, int P, int L, void* stream);
+/* LayerNorm over C channels (a multiple of 64 up to 512) of M tokens: in fp32 [M][C] -> out32 fp32 and / or out16 fp16 (either may be NULL) */
+int cs_op_parser_layernorm(const float* in, const float* g, const float* b, float eps, long M, int C, float* out32, void* out16, void* stream);
+/* attention: q16 fp16 [B][Nq][heads d] (scale folded in), kv16 fp16 [B][Nk][2 heads d] (keys | values) -> ctx16 fp16 [B][Nq][heads d] =
+ * softmax(q k^T) v per head (contiguous channel slices); d = 32 or 64, Nk <= 256 (more is refused) */
+int cs_op_parser_attention(const void* q16, const void* kv16, void* ctx16, int B, int Nq, int Nk, int heads, int d, void* stream);
+/* GELU(depth-wise 3 x 3 conv + bias), zero padding 1: in16 fp16 [B][H][W][C] -> out16; w fp32 [9][C] tap-major, bias fp32 [C]; C % 8 == 0 */
+int cs_op_parser_dwgelu(const void* in16, const float* w, const float* bias, void* out16, int B, int H, int W, int C, void* stream);
+/* decode head: out16 fp16 [B][H][W][D] = relu(p0 + up2(p1) + up4(p2) + up8(p3)), bilinear with align_corners = False; p_s fp32 [B][H >> s][W >> s][D];
+ * H, W multiples of 8, D % 4 == 0 */
+int cs_op_parser_upadd(const float* p0, const float* p1, const float* p2, const float* p3, void* out16, int B, int H, int W, int D, void* stream);
+/* Copies to dst on `stream`, as fp32 NCHW, an activation the LAST pass of cs_parser left (B <= the images of that pass): CS_PARSER_STAGE0 + s: the
+ * output of encoder stage s after its final LayerNorm, BxC_sx(H >> (s + 2))x(W >> (s + 2)); CS_PARSER_PRE: the decode head's map in front of the
+ * classifier, BxDx(H/4)x(W/4) (fp16 values) */
+enum { CS_PARSER_STAGE0 = 0, CS_PARSER_PRE = 4 };
+int cs_op_parser_read(cs_engine* e, int which, int B, float* dst, void* stream);
 
 #ifdef __cplusplus
 }
