@@ -25,7 +25,7 @@ ABI_SYMBOLS = [
     "cs_extract_feature_3d", "cs_warp", "cs_warp_out", "cs_swap", "cs_swap_ids", "cs_swap_frames_ids", "cs_refine", "cs_warp_forward", "cs_spade_decode",
     "cs_pack_u8", "cs_unpack_u8", "cs_soft_erosion", "cs_prepare_crops", "cs_warp_affine_u8", "cs_warp_affine_f32", "cs_paste_back",
     "cs_motion_extract", "cs_motion_keypoints", "cs_soft_erosion_frames", "cs_paste_back_batch", "cs_swap_frames", "cs_animate_frames", 
-    "cs_resize_half_bilinear", "cs_motion_keypoints_driven", "cs_paste_back_shared", "cs_crop_frames", "cs_face_masks", "cs_parser_input", "cs_concat_frames", "cs_profile_begin", "cs_profile_end", "cs_profile_exec_flops", "cs_op_conv", "cs_op_grid_sample3d",
+    "cs_resize_half_bilinear", "cs_motion_keypoints_driven", "cs_paste_back_shared", "cs_crop_frames", "cs_crop_faces", "cs_paste_back_faces", "cs_face_masks", "cs_parser_input", "cs_concat_frames", "cs_profile_begin", "cs_profile_end", "cs_profile_exec_flops", "cs_op_conv", "cs_op_grid_sample3d",
     "cs_op_chan_stats", "cs_op_chan_stats_partial_floats", "cs_op_pair_ragged", "cs_op_resblock3d", "cs_op_t_mask",
     "cs_op_t_style", "cs_op_t_modulate", "cs_op_t_read", "cs_op_t_layer",
     "cs_op_m_stem", "cs_op_m_dwln", "cs_op_m_ln_s2d", "cs_op_m_grn", "cs_op_m_head", "cs_op_m_pointwise",
@@ -409,6 +409,8 @@ def load():
     lib.cs_motion_keypoints_driven.argtypes = [vp, ci, vp, vp, vp, vp, vp]
     lib.cs_paste_back_shared.argtypes = [vp, ci, vp, ci, ci, vp, d6, vp, vp, ci, ci, vp]
     lib.cs_crop_frames.argtypes = [vp, ci, vp, ci, ci, C.POINTER(C.c_double), ci, vp, vp, vp]
+    lib.cs_crop_faces.argtypes = [vp, ci, ci, vp, ci, ci, C.POINTER(ci), d6, ci, vp, vp, vp]
+    lib.cs_paste_back_faces.argtypes = [vp, ci, ci, vp, vp, ci, ci, C.POINTER(ci), d6, vp, vp, ci, ci, vp]
     lib.cs_face_masks.argtypes = [vp, ci, ci, vp, ci, ci, ci, C.c_uint32, vp, vp, vp]
     lib.cs_parser_input.argtypes = [vp, ci, vp, ci, ci, ci, vp, vp, vp, vp]
     lib.cs_concat_frames.argtypes = [vp, ci, ci, ci, C.POINTER(vp), C.POINTER(ci), C.POINTER(ci), vp, vp]

@@ -282,6 +282,12 @@ class can_swapper(object):
     def crop_frames(self, frames, lmk, **kw):                                           # crop.py:429-455 of B frames (cropper.py:196-204)
         return tail.crop_frames(self.engine, frames, lmk, **kw)
 
+    def crop_faces(self, frames, lmk, frame_index, **kw):                               # the same for B faces in F frames: face b from frames[frame_index[b]]
+        return tail.crop_faces(self.engine, frames, lmk, frame_index, **kw)
+
+    def paste_back_faces(self, crops, masks_crop, M_c2o, frame_index, imgs_ori, out=None):      # crop.py:515-529 once per face of a frame, in order
+        return tail.paste_back_faces(self.engine, crops, masks_crop, M_c2o, frame_index, imgs_ori, out=out)
+
     # ---- stages
     def extract_feature_3d(self, x: torch.Tensor) -> torch.Tensor:                      # (:165-172)
         return self.engine.extract_feature_3d(x)

@@ -17,6 +17,8 @@ the generator).
                               [19.9 MB of up-sampled logits per frame]          are; with masks: the caller has run these lines)
     :274      soft_mask(masks[i]) [D2H]                                        cs_soft_erosion_frames
     :279-282  prepare_paste_back + paste_back (two cv2.warpAffine) [host]      cs_paste_back_batch
+    (one face per frame; face_detect_crop_multi.py:63-99 finds them all)       chain.crop(frames, lmk, frame_index=) / chain(..., frame_index=):
+                                                                               cs_crop_faces, cs_paste_back_faces - B faces in F frames
     :248-250, :257-259, :290  rec_can, I_can, concat_frames (video.py:84-109)  chain(..., concat=True): the two debug decodes of
                               [three images per frame D2H, cv2.resize, hstack]  cs_swap_frames_ids + cs_concat_frames
 
@@ -24,6 +26,10 @@ The loop of a caller:  c = chain.crop(frames, lmk);  frames_out = chain(c["crops
 with the face parser among the engine's weights (cs_parser_input + cs_parser + cs_face_masks in stage A, no torch module in the process).  A
 caller who runs the parser himself:  logits = model(pixel_values=chain.parser_input(c["crops"])).logits, (B,19,128,128);
 chain(c["crops"], None, c["M_c2o"], frames, source_id, logits=logits)  (or, with 0/1 masks made of them: chain(c["crops"], masks, ...)).
+
+Several faces per frame, or none (frame_index: the frame of each face, non-decreasing; DESIGN 8.9):  c = chain.crop(frames, lmk, frame_index=fi);
+frames_out = chain(c["crops"], None, c["M_c2o"], frames, slots=slot_of_face, parse=True, frame_index=fi)["frames"] - F frames in, F frames out,
+every face of a frame pasted in order in one pass, a frame without a face returned as it came.
 
 AnimateChain below is the same for the second program, inference_v2i.py (src/can_swap_pipeline_v2i.py: one source image animated by a
 driving video, the driving identity swapped in); its table stands in the class's docstring.
@@ -62,12 +68,16 @@ class _StagedChain:
             self._buf[key] = t
         return t
 
-    def crop(self, frames_ori, lmk, **cfg):
+    def crop(self, frames_ori, lmk, frame_index=None, **cfg):
         """The cropper's step in front of the chain (cropper.py:196-204, crop.py:429-455): frames_ori (B,Ho,Wo,3) u8 on the device, lmk (B,N,2)
         tracked landmarks (host) -> {"crops" (B,512,512,3) u8 on the device, "M_c2o", "M_o2c" (B,3,3) host, "lmk_crop"}: tail.crop_frames with
         CropConfig's defaults (cfg: dsize, scale, vy_ratio, flag_do_rot, out, want_I).  A new crops tensor per call, so a batch may be cropped
-        and prefetched while the one before it runs; stage A reads the crops as it would a caller's."""
-        return tail.crop_frames(self.e, frames_ori, lmk, **cfg)
+        and prefetched while the one before it runs; stage A reads the crops as it would a caller's.
+        frame_index (B host ints, non-decreasing, in [0, F)): B faces in F frames, frames_ori (F,Ho,Wo,3), face b cut from frame frame_index[b]
+        (tail.crop_faces); the dict is per face."""
+        if frame_index is None:
+            return tail.crop_frames(self.e, frames_ori, lmk, **cfg)
+        return tail.crop_faces(self.e, frames_ori, lmk, frame_index, **cfg)
 
     def parser_input(self, crops_u8, **kw):
         """What the caller's face parsing network takes (can_swap_pipeline_e2e.py:171 + :180, can_swap_pipeline_v2i.py:73): crops_u8 (B,512,512,3) or
@@ -192,7 +202,7 @@ class FrameChain(_StagedChain):
         self._stage_ahead(crops_u8, masks, logits, parse)
 
     def __call__(self, crops_u8, masks, M_c2o, frames_ori, source_id=None, slots=None, out=None, keep=False, logits=None, concat=False,
-                 concat_out=None, parse=False):
+                 concat_out=None, parse=False, frame_index=None):
         """parse=True (masks None, no logits=): the engine's own face parser makes the logits of the crops in stage A (parser_input -> parser).
         crops_u8 (B,512,512,3) or (B,256,256,3) u8; masks (B,512,512) u8 0/1 or fp32 (the parser's `torch.isin(labels, valid)`), or None
         with logits= (B,C,128,128), (B,C,256,256) or (B,C,512,512) fp32: the parser's logits, masked here (tail.face_masks with the chain's valid);
@@ -201,16 +211,27 @@ class FrameChain(_StagedChain):
         driving crop | rec_can (:248-250) | I_can (:257-259) | I_p.  The generator then runs its two debug decodes, into chain-owned buffers; without
         concat it runs neither.
         -> {"frames": (B,Ho,Wo,3) u8[, "concat"][, "crops_out", "x_t", "x_can", "soft_mask" with keep=True, and "rec_can", "swap_can"
-        (B,3,512,512) fp32 with keep and concat]}"""
+        (B,3,512,512) fp32 with keep and concat]}
+        frame_index (B host ints, non-decreasing, in [0, F)): B faces in F frames.  Everything above stays per face (B up to the engine's
+        max_batch; crops, masks / logits, M_c2o, source_id / slots, "concat", the kept stages); frames_ori, out and "frames" are (F,Ho,Wo,3): face b
+        is pasted into frame frame_index[b], the faces of a frame in their order (tail.paste_back_faces), a frame without a face comes back as
+        it is.  B = 0 (crops (0,512,512,3), F >= 1): no generator runs, "frames" is frames_ori (copied into out, if given)."""
         e = self.e
+        if frame_index is not None and torch.as_tensor(crops_u8).shape[0] == 0:
+            return self._no_faces(frames_ori, frame_index, out)
         self._mask_or_logits(masks, logits, "FrameChain", parse)
+        if frame_index is not None:                                   # before anything is enqueued: the error names the argument
+            frame_index = tail.frame_index_of(frame_index, len(crops_u8), len(frames_ori))
         slot, (I, x_t, x_can, soft) = self._resolve(crops_u8, masks, logits, parse)
         B = I.shape[0]
         rec = self._get("rec_can", (B, 3, 512, 512), torch.float32) if concat else None
         swp = self._get("swap_can", (B, 3, 512, 512), torch.float32) if concat else None
         gen = e.swap_frames(I, x_t, x_can, source_id, want_f32=False, want_u8=True, slots=slots,
                             out_u8=self._get("gen", (B, 512, 512, 3), torch.uint8), out_rec=rec, out_swap=swp)["out_u8"]   # :242-267
-        frames = tail.paste_back_batch(e, gen, soft, M_c2o, frames_ori, out=out)                # :279-282
+        if frame_index is None:
+            frames = tail.paste_back_batch(e, gen, soft, M_c2o, frames_ori, out=out)            # :279-282
+        else:
+            frames = tail.paste_back_faces(e, gen, soft, M_c2o, frame_index, frames_ori, out=out)      # :279-282 once per face of a frame
         self._release(slot)
         res = {"frames": frames}
         if concat:
@@ -220,6 +241,19 @@ class FrameChain(_StagedChain):
             if concat:
                 res.update(rec_can=rec, swap_can=swp)
         return res
+
+
+    def _no_faces(self, frames_ori, frame_index, out):
+        """A batch of frames in which nobody was found: nothing to generate.  The frames come back as they are, copied into `out` if given
+        (cs_paste_back_faces with B = 0)."""
+        fr = torch.as_tensor(frames_ori)
+        if fr.dtype != torch.uint8 or fr.dim() != 4 or fr.shape[3] != 3 or fr.shape[0] < 1:
+            raise ValueError("expected FxHoxWox3 uint8 original frames, F >= 1")
+        tail.frame_index_of(frame_index, 0, fr.shape[0])
+        if out is None:
+            return {"frames": fr.to(self.e.device)}
+        none = torch.empty((0, 512, 512, 3), dtype=torch.uint8, device=self.e.device)
+        return {"frames": tail.paste_back_faces(self.e, none, none[..., 0].float(), None, frame_index, fr, out=out)}
 
 
 class AnimateChain(_StagedChain):

@@ -248,7 +248,10 @@ int launch_warp_f32(const float* src, int Hs, int Ws, const double M[6], float* 
 int launch_resize_half(const float* in, float* out, long planes, int H, int W, hipStream_t st);
 int launch_paste_shared(const unsigned char* crops, int Hc, int Wc, const float* mask_ori, const double M[6], const unsigned char* ori,
                         unsigned char* outs, int B, int Ho, int Wo, hipStream_t st);
-int launch_crop_batch(const unsigned char* frames, int Ho, int Wo, const double* M, int dsize, unsigned char* crops, float* I, int B, hipStream_t st);
+int launch_crop_batch(const unsigned char* frames, int Ho, int Wo, const double* M, const int* frame_index, int dsize, unsigned char* crops, float* I,
+                      int B, hipStream_t st);
+int launch_paste_faces(const unsigned char* crops, const float* masks, int Hc, int Wc, const double* M, const int* frame_index,
+                       const unsigned char* oris, unsigned char* outs, int B, int F, int Ho, int Wo, hipStream_t st);
 int launch_face_masks(const float* logits, int B, int C, int h, int w, int scale, unsigned valid_bits, unsigned char* masks, unsigned char* labels,
                       hipStream_t st);
 int launch_parser_input(const unsigned char* crops, int B, int Hc, int Wc, int halve, const float* lut, float* pv, unsigned char* u8, hipStream_t st);

@@ -28,6 +28,7 @@ extern "C" const char* cs_last_error(void) { return g_err; }
 // cs_op_id_embed (its kernels alone) were added; the optional "A.*" blobs are new names, no existing blob changed.
 // 4, unchanged: cs_parser (the SegFormer face parser on the engine), cs_op_parser_read and cs_op_parser_input / cs_op_parser_gemm / cs_op_parser_layernorm /
 // cs_op_parser_attention / cs_op_parser_dwgelu / cs_op_parser_upadd (its kernels alone) were added; the optional "P.*" blobs are new names; cs_op_id_conv takes K up to 8.
+// 4, unchanged: cs_crop_faces and cs_paste_back_faces (several faces per frame: the crop and the ordered paste-back under a frame index) were added.
 // 4 (round 6): cs_soft_erosion_frames, cs_paste_back_batch, cs_motion_keypoints.
 // 3 (round 4): cs_conv_desc grew (hilo, stat_out, xf_*, ep_general), cs_op_conv takes conv_halo / vol32 / conv_wide configurations only, the
 // packed weight blobs of F.down0 / down1 / second carry [W_hi | W_lo], W.occ49 exists; cs_conv_desc::pool_hw.  _lib.load() refuses any other value.
@@ -1844,7 +1845,55 @@ extern "C" int cs_crop_frames(cs_engine* e, int B, const uint8_t* frames, int Ho
     if (I_out && dsize != 256 && dsize != 512) { cs_set_error("cs_crop_frames: I_out goes with dsize 256 or 512 (got %d)", dsize); return -1; }
     DevGuard guard(e->dev);
     hipStream_t st = (hipStream_t)stream;
-    return e->run(1, st, [&] { return launch_crop_batch(frames, Ho, Wo, M_o2c, dsize, crops, I_out, B, st); }, "crop_frames");
+    return e->run(1, st, [&] { return launch_crop_batch(frames, Ho, Wo, M_o2c, nullptr, dsize, crops, I_out, B, st); }, "crop_frames");
+}
+
+// ---- several faces per frame: face b is cut from, and pasted into, frame frame_index[b]
+// frame_index: B host ints, non-decreasing, in [0, F).  Sets the error and returns nonzero otherwise; nothing has been launched then.
+static int check_frame_index(const char* who, const int* frame_index, int B, int F)
+{
+    for (int b = 0; b < B; ++b) {
+        if (frame_index[b] < 0 || frame_index[b] >= F) {
+            cs_set_error("%s: frame_index[%d] = %d outside [0, %d)", who, b, frame_index[b], F);
+            return -1;
+        }
+        if (b && frame_index[b] < frame_index[b - 1]) {
+            cs_set_error("%s: frame_index decreases at %d (%d after %d): the faces of a frame are contiguous, frames in order", who, b, frame_index[b],
+                         frame_index[b - 1]);
+            return -1;
+        }
+    }
+    return 0;
+}
+
+extern "C" int cs_crop_faces(cs_engine* e, int B, int F, const uint8_t* frames, int Ho, int Wo, const int* frame_index, const double* M_o2c,
+                             int dsize, uint8_t* crops, float* I_out, void* stream)
+{
+    if (!e || !frames || !frame_index || !M_o2c || !crops || B < 1 || F < 1 || Ho < 1 || Wo < 1) {
+        cs_set_error("cs_crop_faces: bad arguments (B = %d faces, F = %d frames)", B, F);
+        return -1;
+    }
+    if (dsize < 4 || dsize % 4 || dsize > 16384) { cs_set_error("cs_crop_faces: dsize %d (a multiple of 4 from 4 to 16384)", dsize); return -1; }
+    if (I_out && dsize != 256 && dsize != 512) { cs_set_error("cs_crop_faces: I_out goes with dsize 256 or 512 (got %d)", dsize); return -1; }
+    if (check_frame_index("cs_crop_faces", frame_index, B, F)) return -1;
+    DevGuard guard(e->dev);
+    hipStream_t st = (hipStream_t)stream;
+    return e->run(1, st, [&] { return launch_crop_batch(frames, Ho, Wo, M_o2c, frame_index, dsize, crops, I_out, B, st); }, "crop_faces");
+}
+
+extern "C" int cs_paste_back_faces(cs_engine* e, int B, int F, const uint8_t* crops, const float* masks_crop, int Hc, int Wc, const int* frame_index,
+                                   const double* M_c2o, const uint8_t* imgs_ori, uint8_t* out, int Ho, int Wo, void* stream)
+{
+    // B == 0: no face at all, the frames are copied; crops, masks, index and matrices are then not read and may be NULL
+    if (!e || !imgs_ori || !out || B < 0 || F < 1 || Ho < 1 || Wo < 1 || (B > 0 && (!crops || !masks_crop || !frame_index || !M_c2o || Hc < 1 || Wc < 1))) {
+        cs_set_error("cs_paste_back_faces: bad arguments (B = %d faces, F = %d frames)", B, F);
+        return -1;
+    }
+    if (check_frame_index("cs_paste_back_faces", frame_index, B, F)) return -1;
+    DevGuard guard(e->dev);
+    hipStream_t st = (hipStream_t)stream;
+    return e->run(1, st, [&] { return launch_paste_faces(crops, masks_crop, Hc, Wc, M_c2o, frame_index, imgs_ori, out, B, F, Ho, Wo, st); },
+                  "paste_back_faces");
 }
 
 // ---- the face mask from the parser's logits (can_swap_pipeline_e2e.py:183-190, can_swap_pipeline_v2i.py:76-83)

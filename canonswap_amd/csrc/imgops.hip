@@ -295,8 +295,9 @@ __device__ __forceinline__ unsigned blend_u8(float m, int res, float rest)
 // crop frame here (mask_crop) or given in the destination frame (mask_ori)
 __global__ void __launch_bounds__(256) paste_kernel(const unsigned char* __restrict__ crop, const float* __restrict__ mask_crop,
                                                     const float* __restrict__ mask_ori, int Hc, int Wc, AffineInv A,
-                                                    const unsigned char* __restrict__ ori, unsigned char* __restrict__ out, int Ho, int Wo)
+                                                    const unsigned char* ori, unsigned char* out, int Ho, int Wo)
 {
+    // ori and out may be ONE buffer (launch_paste_faces' fallback pastes face after face into the frame): a thread reads and writes its own pixel only
     const long i = (long)blockIdx.x * 256 + threadIdx.x;
     if (i >= (long)Ho * Wo) return;
     const int y = (int)(i / Wo), x = (int)(i % Wo);
@@ -320,6 +321,22 @@ __global__ void __launch_bounds__(256) paste_kernel(const unsigned char* __restr
 // paste_kernel with mask_crop (tests/test_gpu_chain.py holds the two bit-equal).
 struct AffineBatch { AffineInv a[64]; };      // 3 KB of kernel arguments: no device-side staging buffer, nothing to race with
 
+// one face into a thread's four pixels (xb .. xb + 3, y), px their 12 bytes: the pixel is truncated to 8 bits, as paste_back's astype(np.uint8)
+__device__ __forceinline__ void paste_px4(const unsigned char* __restrict__ crop, const float* __restrict__ mask_crop, int Hc, int Wc,
+                                          const AffineInv& A, int xb, int y, unsigned char* px)
+{
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        const Tap t = tap_at(A, xb + k, y, Hc, Wc);
+        if (t.outside) continue;                                           // the original pixel
+        const float m = tap_f32(mask_crop, Wc, t);
+        int res[3];
+        tap_u8x3(crop, Wc, t, res);
+#pragma unroll
+        for (int c = 0; c < 3; ++c) px[k * 3 + c] = blend_u8(m, res[c], (1.f - m) * (float)px[k * 3 + c]);
+    }
+}
+
 __global__ void __launch_bounds__(256) paste_batch_kernel(const unsigned char* __restrict__ crops, const float* __restrict__ masks, int Hc, int Wc,
                                                           AffineBatch AB, const unsigned char* __restrict__ oris,
                                                           unsigned char* __restrict__ outs, int Ho, int Wo)
@@ -336,15 +353,46 @@ __global__ void __launch_bounds__(256) paste_batch_kernel(const unsigned char* _
     unsigned wv[3] = {ori[0], ori[1], ori[2]};
     unsigned char* px = (unsigned char*)wv;
     const int y = (int)((q * 4) / Wo), xb = (int)((q * 4) % Wo);
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-        const Tap t = tap_at(A, xb + k, y, Hc, Wc);
-        if (t.outside) continue;                                           // the original pixel
-        const float m = tap_f32(mask_crop, Wc, t);
-        int res[3];
-        tap_u8x3(crop, Wc, t, res);
-#pragma unroll
-        for (int c = 0; c < 3; ++c) px[k * 3 + c] = blend_u8(m, res[c], (1.f - m) * (float)px[k * 3 + c]);
+    paste_px4(crop, mask_crop, Hc, Wc, A, xb, y, px);
+    out[0] = wv[0]; out[1] = wv[1]; out[2] = wv[2];
+}
+
+// ---- several faces per frame: prepare_paste_back + paste_back (crop.py:515-529) applied once per face of a frame, in the faces' order, each on
+// the result of the one before, in ONE pass over the frame.  blockIdx.y = frame of the launch; a thread owns the four pixels of
+// paste_batch_kernel, loads their three dwords once, walks its frame's faces (paste_px4 per face: paste_batch_kernel's arithmetic, the pixel
+// truncated to 8 bits after every face, as sequential paste_back calls leave it) and stores the three dwords once: the frames between two faces
+// never exist in memory.  A frame without a face is copied (in place: left alone).  Matrices, boxes and face ranges are kernel arguments:
+// FACES_PER_LAUNCH = 48 faces and at most as many frames per launch, 48 x (48 B matrix + 16 B box) + 49 x 4 B ranges = 3272 B beside ~70 B of
+// scalars, under HIP's 4 KB argument block with the room AffineBatch leaves (64 matrices alone are 3 KB; with box and range 64 faces would be 4356 B).
+// box: a conservative integer rectangle (x0, y0, x1, y1, inclusive, clipped to the frame; x0 > x1: empty) that holds every pixel of the frame
+// for which !tap_at(...).outside, so a group of four pixels outside it skips the face before any double-precision coordinate is formed - most of
+// a 1080p frame, for every face.  It prunes only: inside it every pixel still decides by tap_at (face_box below for why it cannot cut a pixel).
+// oris / outs may be ONE buffer, and a launch may continue a frame that an earlier launch began (resume: frame 0 of this launch is read from
+// outs): a thread reads and writes its own twelve bytes only, so neither is a race.  crops and masks must not overlap outs.
+constexpr int FACES_PER_LAUNCH = 48;
+struct FaceBatch {
+    AffineInv a[FACES_PER_LAUNCH];
+    int box[FACES_PER_LAUNCH][4];
+    int first[FACES_PER_LAUNCH + 1];      // frame j of the launch owns the launch's faces first[j] .. first[j + 1] - 1
+};
+static_assert(sizeof(FaceBatch) <= 3328, "FaceBatch and the scalars beside it must fit HIP's 4 KB of kernel arguments");
+
+__global__ void __launch_bounds__(256) paste_faces_kernel(const unsigned char* __restrict__ crops, const float* __restrict__ masks, int Hc, int Wc,
+                                                          FaceBatch FB, const unsigned char* oris, unsigned char* outs, int Ho, int Wo, int resume)
+{
+    const int j = blockIdx.y;
+    const long q = (long)blockIdx.x * 256 + threadIdx.x;          // group of four pixels
+    const long P = (long)Ho * Wo;
+    if (q * 4 >= P) return;
+    const int i0 = FB.first[j], i1 = FB.first[j + 1];
+    const unsigned* in = (const unsigned*)((j == 0 && resume ? outs : oris) + (long)j * P * 3) + q * 3;
+    unsigned* out = (unsigned*)(outs + (long)j * P * 3) + q * 3;
+    if (i0 == i1 && in == out) return;                             // in place, no face: nothing to do
+    unsigned wv[3] = {in[0], in[1], in[2]};
+    const int y = (int)((q * 4) / Wo), xb = (int)((q * 4) % Wo);
+    for (int i = i0; i < i1; ++i) {
+        if (y < FB.box[i][1] || y > FB.box[i][3] || xb + 3 < FB.box[i][0] || xb > FB.box[i][2]) continue;
+        paste_px4(crops + (long)i * Hc * Wc * 3, masks + (long)i * Hc * Wc, Hc, Wc, FB.a[i], xb, y, (unsigned char*)wv);
     }
     out[0] = wv[0]; out[1] = wv[1]; out[2] = wv[2];
 }
@@ -588,6 +636,89 @@ int launch_paste_batch(const unsigned char* crops, const float* masks, int Hc, i
     });
 }
 
+// The box of paste_faces_kernel for one face, A its frame -> crop map.  A pixel (x, y) reads the crop (!outside) only if -1 <= sx <= Wc - 1 and
+// -1 <= sy <= Hc - 1, where sx = floor(u + 1/64 + e), u = A0 x + A1 y + A2 and |e| <= 1/1024 + the doubles' rounding (affine_coords: two rint at
+// 10 bits, + 16, >> 10), so u lies in [-1.017, Wc - 0.014], v likewise: inside R = [-1.0625, Wc + 0.0625] x [-1.0625, Hc + 0.0625] with 0.045 to
+// spare.  The pixels with (u, v) in R are the parallelogram A^-1 R; an affine map takes R's hull to the hull of its four corners, so the box
+// of the four corners A^-1 c, widened by one pixel on every side, holds them all, given that A^-1 c is off by less than that pixel: with the
+// guards below (entries up to 1e6, linear part at least 1e-3 and of condition (max |a|)^2 / |det| up to 1e4) the doubles' error in a corner that
+// lies within 1e5 pixels of the frame is below 1e-2 pixel.  Any other matrix (singular, not finite, a crop above the 32767 at which
+// affine_coords saturates) gets the whole frame: the box then prunes nothing, and the result is the same.
+static void face_box(const AffineInv& A, int Hc, int Wc, int Ho, int Wo, int (&box)[4])
+{
+    box[0] = 0; box[1] = 0; box[2] = Wo - 1; box[3] = Ho - 1;
+    const double* m = A.m;
+    double big = 0, lin = 0;
+    for (int i = 0; i < 6; ++i) big = fmax(big, fabs(m[i]));
+    for (int i : {0, 1, 3, 4}) lin = fmax(lin, fabs(m[i]));
+    const double D = m[0] * m[4] - m[1] * m[3];
+    if (!(big <= 1e6) || !(lin >= 1e-3) || !(fabs(D) * 1e4 >= lin * lin) || Hc > 32767 || Wc > 32767) return;
+    const double us[2] = {-1.0625, (double)Wc + 0.0625}, vs[2] = {-1.0625, (double)Hc + 0.0625};
+    double lo[2] = {HUGE_VAL, HUGE_VAL}, hi[2] = {-HUGE_VAL, -HUGE_VAL};
+    for (int c = 0; c < 4; ++c) {
+        const double du = us[c & 1] - m[2], dv = vs[c >> 1] - m[5];
+        const double p[2] = {(m[4] * du - m[1] * dv) / D, (m[0] * dv - m[3] * du) / D};
+        for (int k = 0; k < 2; ++k) { lo[k] = fmin(lo[k], p[k]); hi[k] = fmax(hi[k], p[k]); }
+    }
+    const double top[2] = {(double)Wo - 1, (double)Ho - 1};
+    for (int k = 0; k < 2; ++k) {
+        const double a = fmax(floor(lo[k]) - 1, 0.), b = fmin(ceil(hi[k]) + 1, top[k]);
+        if (!(a <= b)) { box[0] = box[1] = 1; box[2] = box[3] = 0; return; }      // the face does not reach the frame
+        box[k] = (int)a; box[k + 2] = (int)b;
+    }
+}
+
+// B faces into F frames, face b into frame frame_index[b] (non-decreasing, in [0, F): the caller checks), in the faces' order.  A launch takes up
+// to FACES_PER_LAUNCH faces and as many frames; a frame whose faces do not fit is finished by the next launch, which reads what this one wrote
+// (stream order).  outs == oris pastes in place.  Odd widths / unaligned buffers: the single-frame kernel per face, in order, the first face of a
+// frame from oris into outs, the others in place (the same arithmetic); there a frame without a face is copied by the runtime.
+int launch_paste_faces(const unsigned char* crops, const float* masks, int Hc, int Wc, const double* M, const int* frame_index,
+                       const unsigned char* oris, unsigned char* outs, int B, int F, int Ho, int Wo, hipStream_t st)
+{
+    const long P = (long)Ho * Wo, C = (long)Hc * Wc;
+    if (Wo % 4 != 0 || ((uintptr_t)oris & 3) != 0 || ((uintptr_t)outs & 3) != 0) {
+        int b = 0;
+        for (int f = 0; f < F; ++f) {
+            const unsigned char* from = oris + (long)f * P * 3;
+            unsigned char* to = outs + (long)f * P * 3;
+            if ((b == B || frame_index[b] != f) && from != to) {
+                hipError_t r = hipMemcpyAsync(to, from, (size_t)P * 3, hipMemcpyDeviceToDevice, st);
+                if (r != hipSuccess) { cs_set_error("paste_faces copy: %s", hipGetErrorString(r)); return -1; }
+            }
+            for (; b < B && frame_index[b] == f; ++b, from = to)
+                if (launch_paste(crops + b * C * 3, masks + b * C, nullptr, Hc, Wc, M + (long)b * 6, from, to, Ho, Wo, st)) return -1;
+        }
+        return 0;
+    }
+    constexpr int N = FACES_PER_LAUNCH;
+    int b = 0, f = 0, resume = 0;
+    while (f < F) {
+        FaceBatch FB = {};
+        const int b0 = b, f0 = f;
+        int nb = 0, nf = 0, split = 0;
+        while (nf < N && f0 + nf < F && !split) {
+            int cnt = 0;                                              // faces of this frame not pasted yet
+            while (b + cnt < B && frame_index[b + cnt] == f0 + nf) ++cnt;
+            if (cnt && nb == N) break;                                // the launch is full: the frame goes to the next one as a whole
+            const int take = cnt < N - nb ? cnt : N - nb;
+            for (int i = 0; i < take; ++i, ++nb, ++b) {
+                FB.a[nb] = invert_affine(M + (long)b * 6);
+                face_box(FB.a[nb], Hc, Wc, Ho, Wo, FB.box[nb]);
+            }
+            FB.first[++nf] = nb;
+            split = take < cnt;
+        }
+        if (nb || oris != outs) {
+            hipLaunchKernelGGL(paste_faces_kernel, dim3((unsigned)((P / 4 + 255) / 256), nf), dim3(256), 0, st, crops + b0 * C * 3, masks + b0 * C, Hc,
+                               Wc, FB, oris + (long)f0 * P * 3, outs + (long)f0 * P * 3, Ho, Wo, resume);
+            LAUNCH_CHECK("paste_faces");
+        }
+        f = f0 + nf - split;                                          // a split frame is frame 0 of the next launch, read from outs
+        resume = split;
+    }
+    return 0;
+}
+
 // ---------------------------------------------------------------------------------------------- the crop itself
 // crop_image's image step (src/utils/crop.py:429-455 as src/utils/cropper.py:196-209 calls it per frame): cv2.warpAffine(frame, M_o2c[:2],
 // (dsize, dsize), INTER_LINEAR), BORDER_CONSTANT 0, for B frames in one launch; blockIdx.y = frame, the matrices are kernel arguments as in
@@ -604,9 +735,11 @@ __device__ __forceinline__ void crop_pixel(const unsigned char* __restrict__ fra
     if (!t.outside) tap_u8x3(frame, Wo, t, res);
 }
 
+struct CropSource { int frame[64]; };         // crop n of a launch is cut from frame[n] of `frames` (several faces of one frame: the same entry)
+
 template <int STAGE>
-__global__ void __launch_bounds__(256) crop_batch_kernel(const unsigned char* __restrict__ frames, int Ho, int Wo, AffineBatch AB, int dsize,
-                                                         unsigned char* __restrict__ crops, float* __restrict__ I)
+__global__ void __launch_bounds__(256) crop_batch_kernel(const unsigned char* __restrict__ frames, int Ho, int Wo, AffineBatch AB, CropSource CS,
+                                                         int dsize, unsigned char* __restrict__ crops, float* __restrict__ I)
 {
     constexpr int ROWS = STAGE ? 2 : 1;
     const int n = blockIdx.y;
@@ -615,7 +748,7 @@ __global__ void __launch_bounds__(256) crop_batch_kernel(const unsigned char* __
     if (g >= gw * (dsize / ROWS)) return;
     const int yb = (g / gw) * ROWS, xb = (g % gw) * 4;
     const AffineInv& A = AB.a[n];
-    const unsigned char* frame = frames + (long)n * Ho * Wo * 3;
+    const unsigned char* frame = frames + (long)CS.frame[n] * Ho * Wo * 3;
     int v[ROWS][4][3];
 #pragma unroll
     for (int r = 0; r < ROWS; ++r)
@@ -648,25 +781,29 @@ __global__ void __launch_bounds__(256) crop_batch_kernel(const unsigned char* __
 }
 
 // dsize: a multiple of 4 (the caller checks); I != nullptr: dsize 256 or 512.  B is chunked by the 64 matrices of a launch, so it is not bound
-// by anything.  Buffers that do not allow the wide stores (a crop buffer off a 4-byte, an I off a 16-byte boundary): the single-frame kernel per
-// frame and prepare_crops_kernel behind it - the same arithmetic.
-int launch_crop_batch(const unsigned char* frames, int Ho, int Wo, const double* M, int dsize, unsigned char* crops, float* I, int B, hipStream_t st)
+// by anything.  frame_index: crop b is cut from frame frame_index[b] (cs_crop_faces); nullptr: from frame b (cs_crop_frames).  Buffers that do
+// not allow the wide stores (a crop buffer off a 4-byte, an I off a 16-byte boundary): the single-frame kernel per
+// crop and prepare_crops_kernel behind it - the same arithmetic.
+int launch_crop_batch(const unsigned char* frames, int Ho, int Wo, const double* M, const int* frame_index, int dsize, unsigned char* crops, float* I,
+                      int B, hipStream_t st)
 {
     const long P = (long)Ho * Wo * 3, C = (long)dsize * dsize * 3;
     if (((uintptr_t)crops & 3) != 0 || ((uintptr_t)I & 15) != 0) {
         for (int i = 0; i < B; ++i)
-            if (launch_paste(frames + i * P, nullptr, nullptr, Ho, Wo, M + (long)i * 6, nullptr, crops + i * C, dsize, dsize, st)) return -1;
+            if (launch_paste(frames + (frame_index ? frame_index[i] : i) * P, nullptr, nullptr, Ho, Wo, M + (long)i * 6, nullptr, crops + i * C, dsize,
+                             dsize, st)) return -1;
         return I ? launch_prepare_crops(crops, I, B, dsize, dsize, dsize / 256, st) : 0;
     }
     const int stage = I ? dsize / 256 : 0, rows = stage ? 2 : 1;
     const dim3 grid((unsigned)(((long)(dsize / 4) * (dsize / rows) + 255) / 256));
     return for_affine_batches(M, B, [&](int b0, int nb, const AffineBatch& AB) {
-        const unsigned char* f = frames + b0 * P;
+        CropSource CS;
+        for (int i = 0; i < 64; ++i) CS.frame[i] = i < nb ? (frame_index ? frame_index[b0 + i] : b0 + i) : 0;
         unsigned char* c = crops + b0 * C;
         float* Ib = I ? I + (long)b0 * 3 * 256 * 256 : nullptr;
-        if (stage == 2) hipLaunchKernelGGL(crop_batch_kernel<2>, dim3(grid.x, nb), dim3(256), 0, st, f, Ho, Wo, AB, dsize, c, Ib);
-        else if (stage == 1) hipLaunchKernelGGL(crop_batch_kernel<1>, dim3(grid.x, nb), dim3(256), 0, st, f, Ho, Wo, AB, dsize, c, Ib);
-        else hipLaunchKernelGGL(crop_batch_kernel<0>, dim3(grid.x, nb), dim3(256), 0, st, f, Ho, Wo, AB, dsize, c, Ib);
+        if (stage == 2) hipLaunchKernelGGL(crop_batch_kernel<2>, dim3(grid.x, nb), dim3(256), 0, st, frames, Ho, Wo, AB, CS, dsize, c, Ib);
+        else if (stage == 1) hipLaunchKernelGGL(crop_batch_kernel<1>, dim3(grid.x, nb), dim3(256), 0, st, frames, Ho, Wo, AB, CS, dsize, c, Ib);
+        else hipLaunchKernelGGL(crop_batch_kernel<0>, dim3(grid.x, nb), dim3(256), 0, st, frames, Ho, Wo, AB, CS, dsize, c, Ib);
         LAUNCH_CHECK("crop_batch");
         return 0;
     });

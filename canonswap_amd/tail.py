@@ -16,6 +16,8 @@ per-frame loop (src/can_swap_pipeline_e2e.py:223-283) no longer leaves the GPU b
 * ``paste_back_shared``      paste_back of B frames into one image under one mask (can_swap_pipeline_v2i.py:317-321)
 * ``crop_frames``            src/utils/crop.py:429-455 per frame (cropper.py:196-209): landmark geometry on the host (crop.py of this
                              package), cv2.warpAffine of B frames in one launch; ``crop_frames_M``: the same with the caller's matrices
+* ``crop_faces``, ``paste_back_faces``   several faces per frame: face b is cut from, and pasted into, frame frame_index[b]; the paste is
+                             paste_back once per face of a frame, in order, in one pass over the frame (``crop_faces_M``: the caller's matrices)
 * ``prepare_crops``          src/utils/cropper.py:209 + src/can_swap_e2e.py:126-163 (INTER_AREA 512 -> 256, /255, HWC -> CHW)
 * ``FrameStreamer``          streamed upload of the uint8 crops instead of the whole-video residency of prepare_videos
 
@@ -435,6 +437,88 @@ def crop_frames(e: Engine, frames, lmk, dsize=512, scale=2.3, vy_ratio=-0.125, f
     res = crop_frames_M(e, frames, M_o2c, dsize, out=out, want_I=want_I, out_I=out_I)
     res.update(M_o2c=M_o2c, M_c2o=M_c2o, lmk_crop=lmk_crop)
     return res
+
+
+def frame_index_of(frame_index, B, F, who="frame_index"):
+    """The frame of each face -> B contiguous int32 on the host: B integers, non-decreasing (the faces of a frame are contiguous, in paste
+    order), each in [0, F).  Raises ValueError naming the argument otherwise."""
+    a = np.asarray(frame_index.cpu() if isinstance(frame_index, torch.Tensor) else frame_index)
+    if a.ndim != 1 or a.shape[0] != B:
+        raise ValueError(f"{who}: expected {B} frame numbers, one per face, got shape {tuple(a.shape)}")
+    if B and a.dtype.kind not in "iu":
+        raise ValueError(f"{who}: expected integers, got {a.dtype}")
+    a = a.astype(np.int64)
+    if B and (a.min() < 0 or a.max() >= F):
+        raise ValueError(f"{who}: frame numbers must lie in [0, {F}), got {int(a.min())} .. {int(a.max())}")
+    if B > 1 and (np.diff(a) < 0).any():
+        raise ValueError(f"{who}: must not decrease (decreases at face {int(np.argmax(np.diff(a) < 0)) + 1}): the faces of a frame are contiguous")
+    return np.ascontiguousarray(a, dtype=np.int32)
+
+
+def _index_ptr(idx):
+    return idx.ctypes.data_as(C.POINTER(C.c_int))
+
+
+def crop_faces_M(e: Engine, frames, M_o2c, frame_index, dsize, out=None, want_I=False, out_I=None):
+    """crop_frames_M for B faces in F frames: frames (F,Ho,Wo,3) u8, M_o2c (B,2,3) or (B,3,3) host matrices, frame_index B host ints (non-decreasing,
+    in [0, F); a frame may own several faces or none) -> {"crops": (B,dsize,dsize,3) u8, crops[b] = cv2.warpAffine(frames[frame_index[b]], M_o2c[b][:2],
+    (dsize, dsize), INTER_LINEAR)[, "I": (B,3,256,256) fp32 = prepare_crops(crops)]}: the bits of crop_frames_M on frames[frame_index], no frame
+    gathered.  B >= 1."""
+    fr = torch.as_tensor(frames)
+    if fr.dtype != torch.uint8 or fr.dim() != 4 or fr.shape[3] != 3 or fr.shape[0] < 1:
+        raise ValueError("expected FxHoxWox3 uint8 frames")
+    fr = fr.to(e.device).contiguous()
+    F, dsize = fr.shape[0], int(dsize)
+    B = int(np.shape(M_o2c)[0]) if np.ndim(M_o2c) == 3 else -1
+    if B < 1 or tuple(np.shape(M_o2c)) not in ((B, 2, 3), (B, 3, 3)):
+        raise ValueError(f"M_o2c must be (B,2,3) or (B,3,3), B >= 1 faces, got {tuple(np.shape(M_o2c))}")
+    idx = frame_index_of(frame_index, B, F)
+    mm, mp = _m6(M_o2c, B)
+    want_I = want_I or out_I is not None
+    crops = e._out(out, (B, dsize, dsize, 3), torch.uint8)
+    I = e._out(out_I, (B, 3, 256, 256), torch.float32) if want_I else None
+    with torch.cuda.device(e.device):
+        _lib.check(e.lib.cs_crop_faces(e.h, B, F, _ptr(fr), fr.shape[1], fr.shape[2], _index_ptr(idx), mp, dsize, _ptr(crops), _ptr(I), e._stream()),
+                   "cs_crop_faces")
+    return {"crops": crops, "I": I} if want_I else {"crops": crops}
+
+
+def crop_faces(e: Engine, frames, lmk, frame_index, dsize=512, scale=2.3, vy_ratio=-0.125, flag_do_rot=True, out=None, want_I=False, out_I=None):
+    """crop_frames for B faces in F frames: frames (F,Ho,Wo,3) u8, lmk (B,N,2) landmarks of the B faces in their frames (host), frame_index as in
+    crop_faces_M -> crop_frames' dict, per face: {"crops" (B,dsize,dsize,3) u8, "M_o2c", "M_c2o" (B,3,3), "lmk_crop" (B,N,2)[, "I"]}."""
+    M_o2c, M_c2o, lmk_crop = crop_geometry.crop_matrices(lmk, dsize=dsize, scale=scale, vy_ratio=vy_ratio, flag_do_rot=flag_do_rot)
+    frame_index_of(frame_index, M_o2c.shape[0], np.shape(frames)[0])      # one frame number per landmark set: the error names frame_index
+    res = crop_faces_M(e, frames, M_o2c, frame_index, dsize, out=out, want_I=want_I, out_I=out_I)
+    res.update(M_o2c=M_o2c, M_c2o=M_c2o, lmk_crop=lmk_crop)
+    return res
+
+
+def paste_back_faces(e: Engine, crops, masks_crop, M_c2o, frame_index, imgs_ori, out=None):
+    """prepare_paste_back + paste_back (crop.py:515-529) of B faces into F frames, face b into frame frame_index[b], the faces of a frame in their
+    order and each on the result of the one before, in one pass over every frame: crops (B,Hc,Wc,3) u8, masks_crop (B,Hc,Wc) fp32 soft masks in the
+    crop frame, M_c2o (B,2,3) or (B,3,3) host, frame_index B host ints (non-decreasing, in [0, F)), imgs_ori (F,Ho,Wo,3) u8 -> (F,Ho,Wo,3) u8; a frame
+    without a face is copied.  out may be the imgs_ori tensor itself (in place).  B = 0 (crops (0,Hc,Wc,3)) copies the frames.  Bit-equal to
+    paste_back_fused face by face, and with frame_index = arange(B) to paste_back_batch."""
+    crops, ori = torch.as_tensor(crops), torch.as_tensor(imgs_ori)
+    if crops.dtype != torch.uint8 or crops.dim() != 4 or crops.shape[3] != 3 or ori.dtype != torch.uint8 or ori.dim() != 4 or ori.shape[3] != 3:
+        raise ValueError("expected BxHcxWcx3 uint8 crops and FxHoxWox3 uint8 original frames")
+    if ori.shape[0] < 1:
+        raise ValueError("imgs_ori must hold at least one frame")
+    crops, ori = crops.to(e.device).contiguous(), ori.to(e.device).contiguous()
+    B, F = crops.shape[0], ori.shape[0]
+    mc = torch.as_tensor(masks_crop).to(e.device).float().contiguous()
+    if tuple(mc.shape) != tuple(crops.shape[:3]):
+        raise ValueError("masks_crop must be (B, Hc, Wc), one mask per face")
+    idx = frame_index_of(frame_index, B, F)
+    if B and tuple(np.shape(M_c2o)) not in ((B, 2, 3), (B, 3, 3)):
+        raise ValueError(f"M_c2o must be (B,2,3) or (B,3,3) for the {B} faces, got {tuple(np.shape(M_c2o))}")
+    mm, mp = _m6(M_c2o, B) if B else (None, None)
+    out = e._out(out, ori.shape, torch.uint8)
+    with torch.cuda.device(e.device):
+        _lib.check(e.lib.cs_paste_back_faces(e.h, B, F, _ptr(crops) if B else None, _ptr(mc) if B else None, crops.shape[1], crops.shape[2],
+                                             _index_ptr(idx) if B else None, mp, _ptr(ori), _ptr(out), ori.shape[1], ori.shape[2], e._stream()),
+                   "cs_paste_back_faces")
+    return out
 
 
 class FrameStreamer:

@@ -182,6 +182,30 @@ int cs_paste_back_shared(cs_engine* e, int B, const uint8_t* crops, int Hc, int 
 int cs_crop_frames(cs_engine* e, int B, const uint8_t* frames, int Ho, int Wo, const double* M_o2c, int dsize, uint8_t* crops, float* I_out,
                    void* stream);
 
+/* ---- several faces per frame: the crop and the paste-back under a frame index ---- */
+/* B faces in F frames.  frame_index: HOST, B ints, non-decreasing, each in [0, F): face b is cut from, and pasted into, frame frame_index[b]; the
+ * faces of one frame are contiguous and their order is the paste order; a frame may own no face (F > B is fine).  The reference ships the
+ * detector wrapper that returns every face of a frame (insightface_func/face_detect_crop_multi.py:63-99); its pipelines run the steps below once
+ * per frame with one face.
+ * cs_crop_faces = cs_crop_frames with the source frame named per crop (src/utils/crop.py:429-455 per face): crops[b] = cv2.warpAffine(
+ * frames[frame_index[b]], M_o2c[b], (dsize, dsize), INTER_LINEAR), bit-equal to cs_crop_frames on the gathered frames and to cs_warp_affine_u8;
+ * frames FxHoxWox3 u8, M_o2c HOST B x 6 doubles, crops B x dsize x dsize x 3 u8, I_out NULL or Bx3x256x256 fp32 (= cs_prepare_crops of the crops;
+ * dsize 256 or 512 only); dsize a multiple of 4 from 4 to 16384.  B >= 1.
+ * cs_paste_back_faces = prepare_paste_back + paste_back (src/utils/crop.py:515-529) applied once per face, in order, each on the result of the
+ * one before: out = imgs_ori; for b: out[f] = paste_back(crops[b], M_c2o[b], out[f], prepare_paste_back(masks_crop[b], M_c2o[b])), f =
+ * frame_index[b] - bit-equal to that sequence of cs_paste_back calls (the frame is truncated to 8 bits after every face), and for frame_index =
+ * 0 .. B-1 to cs_paste_back_batch - in one pass over every frame: the frames between two faces never exist in memory.  crops BxHcxWcx3 u8, masks_crop
+ * BxHcxWc fp32, M_c2o HOST B x 6 doubles, imgs_ori / out FxHoxWox3 u8.  A frame without a face is copied.  out may BE imgs_ori (in place: a frame
+ * without a face is then not touched); any other overlap of out with an input is not allowed.  B == 0 with F >= 1 copies the frames (crops,
+ * masks_crop, frame_index and M_c2o are then not read).  One launch takes 48 faces and as many frames; neither B nor F is bound to that or to
+ * max_batch (more are further launches on the stream, a frame's faces may span two of them).
+ * Both return nonzero with cs_last_error() set, before anything is launched, for a NULL pointer, F < 1, B < 1 (cs_paste_back_faces: B < 0), an
+ * index outside [0, F), a decreasing index, and cs_crop_frames' rules for dsize and I_out. */
+int cs_crop_faces(cs_engine* e, int B, int F, const uint8_t* frames, int Ho, int Wo, const int* frame_index, const double* M_o2c,
+                  int dsize, uint8_t* crops, float* I_out, void* stream);
+int cs_paste_back_faces(cs_engine* e, int B, int F, const uint8_t* crops, const float* masks_crop, int Hc, int Wc, const int* frame_index,
+                        const double* M_c2o, const uint8_t* imgs_ori, uint8_t* out, int Ho, int Wo, void* stream);
+
 /* ---- the face mask from the parser's logits, in front of cs_soft_erosion_frames ---- */
 /* What both pipelines do between SegFormer and SoftErosion (can_swap_pipeline_e2e.py:183-190 per frame, can_swap_pipeline_v2i.py:76-83 per
  * source image) for B frames in one launch, without materialising the up-sampled logits:
