@@ -11,7 +11,7 @@ import subprocess
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
-SOURCES = [os.path.join(CSRC, f) for f in ("conv_halo.hip", "conv_wide.hip", "conv_lat.hip", "vol32.hip", "vol32_fused.hip", "kernels.hip", "motion.hip", "imgops.hip", "identity.hip", "parser.hip", "engine.hip")]
+SOURCES = [os.path.join(CSRC, f) for f in ("conv_halo.hip", "conv_wide.hip", "conv_lat.hip", "vol32.hip", "vol32_fused.hip", "kernels.hip", "motion.hip", "imgops.hip", "detect.hip", "identity.hip", "parser.hip", "engine.hip")]
 # test-only cross-check kernel (the first-generation implicit-GEMM conv): its own library, never linked into the product
 TEST_SRC = os.path.join(os.path.dirname(HERE), "tests", "csrc", "test_igemm.hip")
 TEST_LIB_PATH = os.path.join(os.path.dirname(HERE), "tests", "libcanonswap_test.so")
@@ -25,7 +25,7 @@ ABI_SYMBOLS = [
     "cs_extract_feature_3d", "cs_warp", "cs_warp_out", "cs_swap", "cs_swap_ids", "cs_swap_frames_ids", "cs_refine", "cs_warp_forward", "cs_spade_decode",
     "cs_pack_u8", "cs_unpack_u8", "cs_soft_erosion", "cs_prepare_crops", "cs_warp_affine_u8", "cs_warp_affine_f32", "cs_paste_back",
     "cs_motion_extract", "cs_motion_keypoints", "cs_soft_erosion_frames", "cs_paste_back_batch", "cs_swap_frames", "cs_animate_frames", 
-    "cs_resize_half_bilinear", "cs_motion_keypoints_driven", "cs_paste_back_shared", "cs_crop_frames", "cs_crop_faces", "cs_paste_back_faces", "cs_face_masks", "cs_parser_input", "cs_concat_frames", "cs_profile_begin", "cs_profile_end", "cs_profile_exec_flops", "cs_op_conv", "cs_op_grid_sample3d",
+    "cs_resize_half_bilinear", "cs_motion_keypoints_driven", "cs_paste_back_shared", "cs_crop_frames", "cs_crop_faces", "cs_paste_back_faces", "cs_face_masks", "cs_parser_input", "cs_concat_frames", "cs_det_input", "cs_det_decode", "cs_profile_begin", "cs_profile_end", "cs_profile_exec_flops", "cs_op_conv", "cs_op_grid_sample3d",
     "cs_op_chan_stats", "cs_op_chan_stats_partial_floats", "cs_op_pair_ragged", "cs_op_resblock3d", "cs_op_t_mask",
     "cs_op_t_style", "cs_op_t_modulate", "cs_op_t_read", "cs_op_t_layer",
     "cs_op_m_stem", "cs_op_m_dwln", "cs_op_m_ln_s2d", "cs_op_m_grn", "cs_op_m_head", "cs_op_m_pointwise",
@@ -353,6 +353,8 @@ class ConvDesc(C.Structure):
 
 
 MAX_IDENTITY_SLOTS = 8      # CS_MAX_IDENTITY_SLOTS (include/canonswap_hip.h)
+DET_MAX_CAND = 1024         # CS_DET_MAX_CAND: candidates per frame cs_det_decode takes
+DET_MAX_FACES = 256         # CS_DET_MAX_FACES: the largest max_faces of cs_det_decode
 _lib = None
 
 
@@ -414,6 +416,8 @@ def load():
     lib.cs_face_masks.argtypes = [vp, ci, ci, vp, ci, ci, ci, C.c_uint32, vp, vp, vp]
     lib.cs_parser_input.argtypes = [vp, ci, vp, ci, ci, ci, vp, vp, vp, vp]
     lib.cs_concat_frames.argtypes = [vp, ci, ci, ci, C.POINTER(vp), C.POINTER(ci), C.POINTER(ci), vp, vp]
+    lib.cs_det_input.argtypes = [vp, ci, vp, ci, ci, ci, ci, ci, vp, vp, vp]
+    lib.cs_det_decode.argtypes = [vp, ci, ci, C.POINTER(ci), ci, C.POINTER(vp), ci, ci, cf, cf, cf, ci, ci, ci, ci, ci, vp, vp, vp, vp]
     lib.cs_swap_frames.argtypes = [vp, ci, ci, vp, vp, vp, vp, vp, vp, vp, vp]
     lib.cs_profile_begin.argtypes = [vp]
     lib.cs_profile_end.argtypes = [vp, C.POINTER(C.c_double), C.POINTER(C.c_long), C.POINTER(C.c_double)]

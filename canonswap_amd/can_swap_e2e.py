@@ -19,7 +19,7 @@ import os
 import numpy as np
 import torch
 
-from . import pack, tail
+from . import detect, pack, tail
 from .engine import Engine
 
 
@@ -182,6 +182,20 @@ class can_swapper(object):
         x = torch.stack([lut[c][t[..., c].long()] for c in range(3)], dim=1)
         return self.getid(x)
 
+    def getid_faces(self, frames, kps, frame_index=None, mode="None"):
+        """get_source_id / get_driving_id without the host (can_swap_pipeline_e2e.py:93-98, can_swap_pipeline_v2i.py:113-118, 136-145): frames (F,Ho,Wo,3)
+        u8, kps (B,5,2) the detector's five points of B faces (host), frame_index (B host ints; None: face b in frame b) -> (B, 512) identities on the
+        device, the tensor set_identity / source_id take.  Per face align.estimate_norm(kps, 112, mode) (face_align_ffhqandnewarc.py:55-78), then
+        cv2.warpAffine(frame, M, (112, 112), borderValue=0) of all faces in one launch (tail.crop_faces_M), then getid_crops.  getid_crops reads the
+        crop's channels in the frame's own order (ID_transform is applied to what it is handed): frames in the order the identity network was
+        trained with, RGB in both pipelines (:96 converts before the transform)."""
+        from . import align
+        M, _ = align.norm_matrices(kps, 112, mode)
+        if frame_index is None:
+            frame_index = np.arange(M.shape[0], dtype=np.int32)
+        crops = tail.crop_faces_M(self.engine, frames, M, frame_index, 112)["crops"]
+        return self.getid_crops(crops)
+
     def get_kp_info(self, x, **kwargs):
         """can_swap_e2e.py:174-199: implicit key-point information of Bx3x256x256 images in [0,1]."""
         if self.motion_extractor is None:
@@ -278,6 +292,12 @@ class can_swapper(object):
 
     def concat_frames(self, panels, **kw):                                              # video.py:84-109: the side-by-side frames, panels left to right
         return tail.concat_frames(self.engine, panels, **kw)
+
+    def det_input(self, frames, **kw):                                                  # scrfd.py:224-235 + :154: frames -> the detector's blob
+        return detect.det_input(self.engine, frames, **kw)
+
+    def det_decode(self, outs, det_size, det_scale, frame_hw, **kw):                    # scrfd.py:160-218 + :239-303: the detector's outputs -> faces
+        return detect.det_decode(self.engine, outs, det_size, det_scale, frame_hw, **kw)
 
     def crop_frames(self, frames, lmk, **kw):                                           # crop.py:429-455 of B frames (cropper.py:196-204)
         return tail.crop_frames(self.engine, frames, lmk, **kw)

@@ -257,6 +257,13 @@ int launch_face_masks(const float* logits, int B, int C, int h, int w, int scale
 int launch_parser_input(const unsigned char* crops, int B, int Hc, int Wc, int halve, const float* lut, float* pv, unsigned char* u8, hipStream_t st);
 int launch_concat_frames(const void* const* panels, const int* kinds, const int* shared, int B, int P, int S, unsigned char* out, hipStream_t st);
 
+// ---- the face detector's input and decode (detect.hip)
+void det_letterbox(int Ho, int Wo, int Hd, int Wd, int* nh, int* nw);
+int launch_det_input(const unsigned char* frames, int F, int Ho, int Wo, int Hd, int Wd, int swap_rb, const float* lut, float* blob, hipStream_t st);
+int launch_det_decode(int F, int n_levels, const int* strides, int num_anchors, const void* const* outs, int Hd, int Wd, float det_scale,
+                      float det_thresh, float nms_thresh, int max_num, int metric_max, int Ho, int Wo, int max_faces, float* det, float* kps,
+                      int* count, hipStream_t st);
+
 // ---- motion extractor pieces (motion.hip)
 int launch_m_keypoints(const float* raw, float* x_t, float* x_can, float* rot, int N, hipStream_t st);
 int launch_m_keypoints_driven(const float* raw_driving, const float* raw_pose, const float* kp, float* x_t, int N, hipStream_t st);

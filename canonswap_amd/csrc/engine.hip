@@ -29,6 +29,7 @@ extern "C" const char* cs_last_error(void) { return g_err; }
 // 4, unchanged: cs_parser (the SegFormer face parser on the engine), cs_op_parser_read and cs_op_parser_input / cs_op_parser_gemm / cs_op_parser_layernorm /
 // cs_op_parser_attention / cs_op_parser_dwgelu / cs_op_parser_upadd (its kernels alone) were added; the optional "P.*" blobs are new names; cs_op_id_conv takes K up to 8.
 // 4, unchanged: cs_crop_faces and cs_paste_back_faces (several faces per frame: the crop and the ordered paste-back under a frame index) were added.
+// 4, unchanged: cs_det_input and cs_det_decode (the face detector's letterbox + blob and its decode + NMS, around the caller's network) were added.
 // 4 (round 6): cs_soft_erosion_frames, cs_paste_back_batch, cs_motion_keypoints.
 // 3 (round 4): cs_conv_desc grew (hilo, stat_out, xf_*, ep_general), cs_op_conv takes conv_halo / vol32 / conv_wide configurations only, the
 // packed weight blobs of F.down0 / down1 / second carry [W_hi | W_lo], W.occ49 exists; cs_conv_desc::pool_hw.  _lib.load() refuses any other value.
@@ -1945,6 +1946,60 @@ extern "C" int cs_concat_frames(cs_engine* e, int B, int P, int S, const void* c
     DevGuard guard(e->dev);
     hipStream_t st = (hipStream_t)stream;
     return e->run(1, st, [&] { return launch_concat_frames(panels, kinds, shared, B, P, S, out, st); }, "concat_frames");
+}
+
+// ---- the face detector's input (scrfd.py:224-235, :154) and decode (scrfd.py:160-218, :239-303): everything is refused before any launch
+extern "C" int cs_det_input(cs_engine* e, int F, const uint8_t* frames, int Ho, int Wo, int Hd, int Wd, int swap_rb, const float* lut, float* blob,
+                            void* stream)
+{
+    if (!e || !frames || !lut || !blob) {
+        cs_set_error("cs_det_input: NULL %s", !e ? "engine" : !frames ? "frames" : !lut ? "lut" : "blob");
+        return -1;
+    }
+    if (F < 1 || Ho < 1 || Wo < 1) { cs_set_error("cs_det_input: F = %d, Ho = %d, Wo = %d (each at least 1)", F, Ho, Wo); return -1; }
+    if (Hd < 1 || Wd < 1 || Hd > 16384 || Wd > 16384) { cs_set_error("cs_det_input: det size %dx%d (Hd x Wd) outside [1, 16384] a side", Hd, Wd); return -1; }
+    int nh, nw;
+    det_letterbox(Ho, Wo, Hd, Wd, &nh, &nw);
+    if (nh < 1 || nw < 1) { cs_set_error("cs_det_input: a %dx%d frame resizes to %dx%d inside %dx%d (empty)", Ho, Wo, nh, nw, Hd, Wd); return -1; }
+    DevGuard guard(e->dev);
+    hipStream_t st = (hipStream_t)stream;
+    return e->run(1, st, [&] { return launch_det_input(frames, F, Ho, Wo, Hd, Wd, swap_rb != 0, lut, blob, st); }, "det_input");
+}
+
+extern "C" int cs_det_decode(cs_engine* e, int F, int n_levels, const int* strides, int num_anchors, const void* const* outs, int Hd, int Wd,
+                             float det_scale, float det_thresh, float nms_thresh, int max_num, int metric_max, int Ho, int Wo, int max_faces,
+                             float* det, float* kps, int* count, void* stream)
+{
+    if (!e || !strides || !outs || !det || !count) {
+        cs_set_error("cs_det_decode: NULL %s", !e ? "engine" : !strides ? "strides" : !outs ? "outs" : !det ? "det" : "count");
+        return -1;
+    }
+    static const int S5[5] = {8, 16, 32, 64, 128};
+    bool layout = (n_levels == 3 && num_anchors == 2) || (n_levels == 5 && num_anchors == 1);
+    for (int l = 0; layout && l < n_levels; ++l) layout = strides[l] == S5[l];
+    if (!layout) {
+        cs_set_error("cs_det_decode: layout of %d levels with %d anchors is not 3 levels (8, 16, 32) x 2 or 5 levels (8 .. 128) x 1", n_levels, num_anchors);
+        return -1;
+    }
+    if (F < 1 || Ho < 1 || Wo < 1) { cs_set_error("cs_det_decode: F = %d, Ho = %d, Wo = %d (each at least 1)", F, Ho, Wo); return -1; }
+    if (Hd < 1 || Wd < 1 || Hd > 16384 || Wd > 16384) { cs_set_error("cs_det_decode: det size %dx%d (Hd x Wd) outside [1, 16384] a side", Hd, Wd); return -1; }
+    if (max_faces < 1 || max_faces > CS_DET_MAX_FACES) { cs_set_error("cs_det_decode: max_faces %d outside [1, %d]", max_faces, CS_DET_MAX_FACES); return -1; }
+    if (max_num < 0 || max_num > max_faces) { cs_set_error("cs_det_decode: max_num %d outside [0, max_faces = %d]", max_num, max_faces); return -1; }
+    if (!(det_scale > 0.f) || det_scale > 3.0e38f) { cs_set_error("cs_det_decode: det_scale %g is not a positive finite number", (double)det_scale); return -1; }
+    if (det_thresh != det_thresh || nms_thresh != nms_thresh) { cs_set_error("cs_det_decode: a threshold is NaN"); return -1; }
+    int nk = 0;
+    for (int l = 0; l < n_levels; ++l) {
+        if (!outs[l] || !outs[n_levels + l]) { cs_set_error("cs_det_decode: NULL %s pointer of level %d", !outs[l] ? "score" : "bbox", l); return -1; }
+        nk += outs[2 * n_levels + l] != nullptr;
+    }
+    if (nk != 0 && nk != n_levels) { cs_set_error("cs_det_decode: %d of %d kps pointers are NULL (all or none)", n_levels - nk, n_levels); return -1; }
+    if (kps && !nk) { cs_set_error("cs_det_decode: kps output given without kps pointers in outs"); return -1; }
+    DevGuard guard(e->dev);
+    hipStream_t st = (hipStream_t)stream;
+    return e->run(1, st, [&] {
+        return launch_det_decode(F, n_levels, strides, num_anchors, outs, Hd, Wd, det_scale, det_thresh, nms_thresh, max_num, metric_max != 0, Ho, Wo,
+                                 max_faces, det, kps, count, st);
+    }, "det_decode");
 }
 
 // ---- getid on the engine (can_swap_e2e.py:102-107): nearest resize to 112 x 112, the ArcFace network, L2 normalisation.  Everything is refused

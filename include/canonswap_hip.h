@@ -261,6 +261,68 @@ int cs_parser_input(cs_engine* e, int B, const uint8_t* crops, int Hc, int Wc, i
 int cs_concat_frames(cs_engine* e, int B, int P, int S, const void* const* panels, const int* kinds, const int* shared, uint8_t* out,
                      void* stream);
 
+/* ---- the face detector's input and decode: what stands around the caller's SCRFD network ---- */
+/* The detector network (SCRFD, src/utils/dependencies/insightface/model_zoo/scrfd.py; the pipelines reach it through Face_detect_crop.get,
+ * insightface_func/face_detect_crop_single.py:63-82 and _multi.py:63-100, at can_swap_pipeline_e2e.py:93-98 and can_swap_pipeline_v2i.py:113-118,
+ * 136-145) stays the caller's; cs_det_input is everything in front of it, cs_det_decode everything behind it, so a frame never leaves the device.
+ * cs_det_input = SCRFD.detect's letterbox (scrfd.py:224-235) and forward's blobFromImage (scrfd.py:154) for F frames in one launch, no
+ * intermediate in memory.  frames FxHoxWox3 u8, blob Fx3xHdxWd fp32 (NCHW), (Wd, Hd) = the detector's input_size.
+ *   1. the resized size exactly as :224-231, truncating int() included: im_ratio = Ho / Wo, model_ratio = Hd / Wd (doubles);
+ *      im_ratio > model_ratio ? (nh = Hd, nw = int(nh / im_ratio)) : (nw = Wd, nh = int(nw * im_ratio)); det_scale = double(nh) / Ho is the
+ *      caller's to keep (canonswap_amd/detect.py det_geometry) for cs_det_decode.
+ *   2. cv2.resize(frame, (nw, nh)), default INTER_LINEAR, OpenCV's 8-bit arithmetic at a general ratio.  One axis src -> dst:
+ *        scale = 1.0 / (double(dst) / src); f = float((d + 0.5) * scale - 0.5); s = floor(f); f -= s;
+ *        coefficients short(round_half_even((1 - f) * 2048)) for tap s and short(round_half_even(f * 2048)) for tap s + 1, in fp32.
+ *      Columns: s < 0 gives s = 0, f = 0; s >= src - 1 gives s = src - 1, f = 0.  Rows: the row numbers s and s + 1 are clamped to
+ *      [0, src - 1] and the weights kept, as resize.cpp does it and as cs_concat_frames kind 1 states it at x2.  Horizontal pass into int32,
+ *      vertical pass dst = (((b0 * (H0 >> 4)) >> 16) + ((b1 * (H1 >> 4)) >> 16) + 2) >> 2.  At exactly one half on BOTH axes OpenCV takes the
+ *      2 x 2 mean, (a + b + c + d + 2) >> 2; equal sizes copy.  At x2 and x1/2 the bits are those of cs_concat_frames kind 1 and of
+ *      cs_parser_input step 1.
+ *   3. rows and columns outside the resized image hold lut[c][0]: np.zeros goes through the blob arithmetic too.
+ *   4. blobFromImage(det_img, 1 / std, size, (mean,) * 3, swapRB=True) = (float(u8) - mean) * scalefactor, channels first, as a table look-up:
+ *      lut: DEVICE, 3 x 256 fp32, lut[c][v] for OUTPUT plane c, built on the host (canonswap_amd/detect.py det_lut; mean 127.5, std 128.0:
+ *      scrfd.py:107-108).  The device computes nothing in float.  swap_rb != 0: output plane c holds source channel 2 - c.  swap_rb = 1 is what
+ *      BOTH of the reference's calls do: forward passes swapRB=True whatever it is handed, BGR frames of cv2.imread at
+ *      can_swap_pipeline_e2e.py:93 and RGB crops at can_swap_pipeline_v2i.py:230 alike - the quirk is mirrored, not mended; swap_rb = 0 is for
+ *      callers who want the planes in the frame's own channel order.
+ * PARITY UNPINNED for step 2: the arithmetic is OpenCV's as published, not checked against vectors of cv2's own.
+ * Any F >= 1 (not bound to max_batch), any Ho, Wo >= 1, 1 <= Hd, Wd <= 16384; asynchronous on the stream, no engine scratch, allocates nothing;
+ * a frame's bits do not depend on its batch.  Returns nonzero and sets cs_last_error() before any launch for a NULL e, frames, lut or blob, F,
+ * Ho or Wo below 1, Hd or Wd outside [1, 16384], or a resized size that truncates to 0 (cv2.resize raises there). */
+int cs_det_input(cs_engine* e, int F, const uint8_t* frames, int Ho, int Wo, int Hd, int Wd, int swap_rb, const float* lut, float* blob,
+                 void* stream);
+/* cs_det_decode = SCRFD.forward's decode (scrfd.py:160-218) and detect's sort, NMS and max_num pick (scrfd.py:239-273 with :275-303) for F
+ * frames in one launch.  outs: HOST array of 3 * n_levels DEVICE pointers in the reference's output order - scores per level, then bbox per
+ * level, then kps per level (net_outs[idx], [idx + fmc], [idx + 2 fmc]) - each F x A_l x {1, 4, 10} fp32 contiguous, A_l = (Hd / s_l) * (Wd / s_l) *
+ * num_anchors; the kps pointers may ALL be NULL (a model without key points; kps must be NULL then).  strides: HOST, n_levels ints.  Supported
+ * layouts (scrfd.py:114-131): 3 levels (8, 16, 32) with 2 anchors, 5 levels (8, 16, 32, 64, 128) with 1 anchor.  Outputs on the device: det F x
+ * max_faces x 5 (x1, y1, x2, y2, score), kps F x max_faces x 5 x 2 or NULL, count F int32.  Per frame:
+ *   1. candidates: the anchors with score >= det_thresh, levels in order, anchors in order (np.where, vstack);
+ *   2. anchor centre ((cell % width) * stride, (cell / width) * stride) as fp32, cell = a / num_anchors, width = Wd / stride;
+ *   3. pred * stride in fp32, centre - / + distance (distance2bbox, distance2kps), then division by float32(det_scale);
+ *   4. descending score over the concatenation of the levels (:241) and again inside nms (:284);
+ *   5. greedy NMS: areas (x2 - x1 + 1) * (y2 - y1 + 1), ovr = inter / (area_i + area_j - inter), a box survives on ovr <= nms_thresh;
+ *   6. max_num > 0 and more than max_num survivors: the max_num largest by area - 2 * offset^2 (metric_max != 0: by area) come first, in that
+ *      order; area here without the + 1, offset from the image centre (Wo / 2, Ho / 2), integer division.
+ * All of it fp32 with every product, sum and quotient rounded on its own (numpy's arithmetic: the kernel is compiled with fp contraction off,
+ * its division is correctly rounded): the result is bit-equal to the numpy lines.  Where the reference's argsort()[::-1] leaves the order of
+ * equal keys open, the contract is a STABLE argsort reversed, at each of the three places: of two equal scores the candidate later in the
+ * concatenated list comes first in :241's order; nms' own sort (:284) reverses that once more, so NMS visits - and the result lists - equal
+ * scores in anchor order; of two equal max_num values the later survivor comes first.  Inputs are assumed finite.
+ * One workgroup per frame; the candidates are compacted in anchor order by a prefix scan over wave ballots, not with atomics; sort and NMS
+ * run in LDS: a frame's result depends neither on scheduling nor on its batch.  Caps, which are conditions and not errors of the call: a
+ * frame with more than CS_DET_MAX_CAND candidates reports count = -1; a frame with more than max_faces NMS survivors and max_num == 0 reports
+ * count = -2; nothing else of such a frame is defined.  A frame without a candidate reports 0.  Slots beyond count are not written.
+ * Any F >= 1 (not bound to max_batch); asynchronous on the stream, no engine scratch, allocates nothing.  Returns nonzero and sets
+ * cs_last_error() before any launch for a NULL e, outs, strides, det, count, score or bbox pointer, kps pointers partly NULL, kps given without
+ * kps pointers, an unsupported layout, F < 1, Hd or Wd outside [1, 16384], Ho or Wo below 1, max_faces outside [1, CS_DET_MAX_FACES], max_num
+ * below 0 or above max_faces, det_scale not a positive finite number, or a threshold that is NaN. */
+#define CS_DET_MAX_CAND 1024
+#define CS_DET_MAX_FACES 256
+int cs_det_decode(cs_engine* e, int F, int n_levels, const int* strides, int num_anchors, const void* const* outs, int Hd, int Wd,
+                  float det_scale, float det_thresh, float nms_thresh, int max_num, int metric_max, int Ho, int Wo, int max_faces, float* det,
+                  float* kps, int* count, void* stream);
+
 /* ---- measurement: per-kernel-family HIP-event timing on the launch stream */
 int cs_profile_begin(cs_engine* e);
 /* ms[0] = convolution kernels (conv_halo / conv_igemm), ms[1] = all other kernels except ms[2] = the feature warp

@@ -1,0 +1,377 @@
+"""The face detector's input and decode on the device (cs_det_input, cs_det_decode; detect.det_input / det_decode / FaceDetector; can_swapper's
+delegates and getid_faces).  Integer arithmetic, table look-ups and fp32 operations rounded one by one, so every comparison is bit for bit
+against tests/detect_ref.py (test_detect_cpu.py holds that to the reference's own detect() and to the x2 / x1/2 restatements).  The shapes are
+the smallest at which the kernels can still go wrong: both letterbox branches at a non-integer ratio, an up-scale, the x2, x1/2 and copy paths,
+a det_size that is not square; 168 anchors for the decode's cases, 341 for the five-level layout, and the 16 800 of a 640 x 640 input where the
+compaction runs over many waves, the sort is longer than the workgroup and the caps are met exactly."""
+import ctypes as C
+
+import numpy as np
+import pytest
+import torch
+
+import detect_ref as DR
+
+pytestmark = pytest.mark.gpu
+D64 = (64, 64)
+
+
+def _bits(a):
+    return np.ascontiguousarray(a, dtype=np.float32).view(np.uint32)
+
+
+def _dev(arrays):
+    return [torch.from_numpy(np.array(a)).cuda() for a in arrays]      # a copy: the shared cases are read-only
+
+
+@pytest.fixture(scope="module")
+def swapper():
+    from canonswap_amd import synth
+    from canonswap_amd.can_swap_e2e import can_swapper
+    sds = synth.to_torch(synth.make_state_dicts(0, modules=synth.MODULES + ("motion_extractor",)))
+    sds["arcface"] = synth.to_torch({"a": synth._arcface(0)})["a"]
+    return can_swapper(None, state_dicts=sds, max_batch=4)
+
+
+@pytest.fixture(scope="module")
+def engine(swapper):
+    return swapper.engine
+
+
+# ------------------------------------------------------------------------------------------------ cs_det_input
+INPUT_CASES = {
+    "landscape": (3, 45, 80, D64), "portrait": (3, 80, 45, D64), "wide_det": (1, 50, 70, (96, 64)), "upscale": (1, 20, 30, D64),
+    "x2": (3, 32, 32, D64), "half": (1, 128, 128, D64), "copy": (1, 64, 64, D64), "one_pixel": (1, 1, 1, D64), "odd": (1, 37, 53, (40, 24)),
+}
+
+
+@pytest.mark.parametrize("name", sorted(INPUT_CASES))
+@pytest.mark.parametrize("swap_rb", [True, False])
+def test_det_input_equals_the_restatement(engine, name, swap_rb):
+    from canonswap_amd import detect
+    F, Ho, Wo, size = INPUT_CASES[name]
+    frames = DR.frames_u8(F, Ho, Wo, 1)
+    want = DR.letterbox_blob(frames, size, swap_rb)
+    got = detect.det_input(engine, torch.from_numpy(frames).cuda(), size, swap_rb=swap_rb)
+    assert got.dtype == torch.float32 and tuple(got.shape) == (F, 3, size[1], size[0])
+    g = got.cpu().numpy()
+    assert np.array_equal(_bits(g), _bits(want)), int((_bits(g) != _bits(want)).sum())
+    one = detect.det_input(engine, frames[F - 1], size, swap_rb=swap_rb)               # a host frame alone: its bits do not depend on the batch
+    assert tuple(one.shape) == (1, 3, size[1], size[0]) and torch.equal(one[0], got[F - 1])
+
+
+def test_det_input_x2_and_half_are_the_bits_of_concat_and_parser_input(engine):
+    import concat_ref
+    import parser_input_ref as PR
+    from canonswap_amd import detect, tail
+    lut = DR.table()
+    x = DR.frames_u8(2, 32, 32, 2)
+    up = detect.det_input(engine, x, D64, swap_rb=False).cpu().numpy()
+    assert np.array_equal(_bits(up), _bits(np.stack([lut[c][concat_ref.resize_x2_cv(x)[..., c]] for c in range(3)], axis=1)))
+    panel = tail.concat_frames(engine, [x], kinds=[1]).cpu().numpy()                    # cs_concat_frames kind 1 itself
+    assert np.array_equal(_bits(up), _bits(np.stack([lut[c][panel[..., c]] for c in range(3)], axis=1)))
+    big = DR.frames_u8(2, 128, 128, 3)
+    down = detect.det_input(engine, big, D64, swap_rb=False).cpu().numpy()
+    assert np.array_equal(_bits(down), _bits(np.stack([lut[c][PR.halve_u8(big)[..., c]] for c in range(3)], axis=1)))
+
+
+def test_det_input_other_constants_out_buffer_and_delegate(engine, swapper):
+    from canonswap_amd import detect
+    frames = DR.frames_u8(2, 45, 80, 4)
+    mean, std = (104.0, 117.0, 123.0), 57.0
+    want = DR.letterbox_blob(frames, D64, True, DR.table(mean, std))
+    out = torch.full((2, 3, 64, 64), 7.0, device="cuda")
+    got = swapper.det_input(frames, det_size=D64, mean=mean, std=std, out=out)
+    assert got is out and np.array_equal(_bits(out.cpu().numpy()), _bits(want))
+    assert not np.array_equal(want, DR.letterbox_blob(frames, D64))
+    for bad in (out[:1], out.double(), out.cpu(), out.permute(0, 1, 3, 2)):
+        with pytest.raises(ValueError):
+            detect.det_input(engine, frames, D64, out=bad)
+
+
+def test_det_input_at_1080p(engine):
+    from canonswap_amd import detect
+    frames = DR.frames_u8(2, 1080, 1920, 5)
+    want = DR.letterbox_blob(frames, (640, 640))
+    got = detect.det_input(engine, torch.from_numpy(frames).cuda(), (640, 640)).cpu().numpy()
+    assert got.shape == (2, 3, 640, 640) and np.array_equal(_bits(got), _bits(want))
+    assert (got[:, :, 360:] == np.float32(-127.5 / 128)).all()
+
+
+def test_det_input_refuses_bad_arguments_before_any_launch(engine):
+    lib, e = engine.lib, engine
+    frames = torch.zeros((1, 8, 8, 3), dtype=torch.uint8, device="cuda")
+    lut = torch.from_numpy(DR.table()).cuda()
+    blob = torch.full((1, 3, 16, 16), 3.0, device="cuda")
+    p = lambda t: C.c_void_p(0 if t is None else t.data_ptr())
+    good = dict(F=1, frames=frames, Ho=8, Wo=8, Hd=16, Wd=16, lut=lut, blob=blob)
+    for kw, word in (({"F": 0}, "F = 0"), ({"frames": None}, "frames"), ({"lut": None}, "lut"), ({"blob": None}, "blob"), ({"Ho": 0}, "Ho = 0"),
+                     ({"Hd": 16385}, "16384"), ({"Wd": 0}, "16384"), ({"Ho": 1, "Wo": 8000}, "empty")):
+        a = dict(good, **kw)
+        rc = lib.cs_det_input(e.h, a["F"], p(a["frames"]), a["Ho"], a["Wo"], a["Hd"], a["Wd"], 1, p(a["lut"]), p(a["blob"]), e._stream())
+        err = lib.cs_last_error().decode()
+        assert rc != 0 and "cs_det_input" in err and word in err, (kw, err)
+    torch.cuda.synchronize()
+    assert (blob == 3.0).all()
+
+
+# ------------------------------------------------------------------------------------------------ cs_det_decode at 64 x 64: 168 anchors
+def _decode(engine, per_frame, det_size=D64, frame_hw=DR.FRAME_64, **kw):
+    """per_frame: the frames' network outputs -> (got, want), each (dets, kpss, frame_index)."""
+    from canonswap_amd import detect
+    outs = DR.stack_frames(per_frame)
+    scale = DR.geometry(frame_hw[0], frame_hw[1], det_size)[2]
+    want = DR.decode_frames(outs, det_size, scale, frame_hw, **kw)
+    got = detect.det_decode(engine, _dev(outs), det_size, scale, frame_hw, **kw)
+    return got, want
+
+
+def _same(got, want):
+    assert len(got[0]) == len(want[0])
+    for f, (g, w) in enumerate(zip(got[0], want[0])):
+        assert g.dtype == np.float32 and g.shape == w.shape and np.array_equal(_bits(g), _bits(w)), (f, g, w)
+    assert (got[1] is None) == (want[1] is None)
+    if want[1] is not None:
+        for f, (g, w) in enumerate(zip(got[1], want[1])):
+            assert g.shape == w.shape == (len(want[0][f]), 5, 2) and np.array_equal(_bits(g), _bits(w)), f
+    assert got[2].dtype == np.int32 and np.array_equal(got[2], want[2])
+
+
+def _one_candidate(score=0.7):
+    outs = [o.copy() for o in DR.scene_64([], 20)]
+    outs[1][5, 0] = score                                                                # one anchor of the 16-pixel level
+    return outs
+
+
+def test_no_candidate_one_candidate_and_a_score_exactly_at_the_threshold(engine):
+    got, want = _decode(engine, [DR.scene_64([], 20)])
+    _same(got, want)
+    assert got[0][0].shape == (0, 5) and got[1][0].shape == (0, 5, 2) and len(got[2]) == 0
+    got, want = _decode(engine, [_one_candidate()])
+    _same(got, want)
+    assert got[0][0].shape == (1, 5) and got[0][0][0, 4] == np.float32(0.7)
+    at = _one_candidate(np.float32(0.5))
+    below = _one_candidate(np.nextafter(np.float32(0.5), np.float32(0)))
+    got, want = _decode(engine, [at, below])
+    _same(got, want)
+    assert [len(d) for d in got[0]] == [1, 0]                                            # >= det_thresh: kept at the threshold, dropped one ulp below
+
+
+@pytest.mark.parametrize("faces,seed,n", [(DR.TWO, 1, 2), (DR.OVERLAP, 2, 1), (DR.CHAIN, 3, 2), (DR.PICK3, 6, 3)], ids=["two", "overlap", "chain", "pick3"])
+def test_clusters_are_thinned_as_the_restatement_thins_them(engine, faces, seed, n):
+    got, want = _decode(engine, [DR.scene_64(faces, seed)])
+    _same(got, want)
+    assert len(got[0][0]) == n
+    got, want = _decode(engine, [DR.scene_64(faces, seed)], det_thresh=0.6, nms_thresh=0.2)
+    _same(got, want)
+
+
+def test_three_frames_with_the_empty_one_in_the_middle_and_batch_independence(engine):
+    frames = [DR.scene_64(DR.TWO, 1), DR.scene_64([], 4), DR.scene_64(DR.CHAIN, 3)]
+    got, want = _decode(engine, frames)
+    _same(got, want)
+    assert [len(d) for d in got[0]] == [2, 0, 2] and list(got[2]) == [0, 0, 2, 2]
+    alone, _ = _decode(engine, [frames[2]])
+    assert np.array_equal(_bits(alone[0][0]), _bits(got[0][2])) and np.array_equal(_bits(alone[1][0]), _bits(got[1][2]))
+
+
+def test_a_model_without_key_points(engine):
+    got, want = _decode(engine, [DR.scene_64(DR.TWO, 5, use_kps=False), DR.scene_64(DR.OVERLAP, 2, use_kps=False)])
+    _same(got, want)
+    assert got[1] is None and [len(d) for d in got[0]] == [2, 1]
+
+
+@pytest.mark.parametrize("metric", ["default", "max"])
+@pytest.mark.parametrize("max_num", [1, 2, 3])
+def test_max_num_under_both_metrics(engine, max_num, metric):
+    got, want = _decode(engine, [DR.scene_64(DR.PICK3, 6), DR.scene_64(DR.TWO, 1)], max_num=max_num, metric=metric)
+    _same(got, want)
+    assert [len(d) for d in got[0]] == [min(max_num, 3), min(max_num, 2)]
+    if max_num == 1:
+        c = DR.golden_case("pick1max" if metric == "max" else "pick1")
+        assert np.array_equal(_bits(got[0][0]), _bits(c["det"]))                        # what the reference's own detect() picked
+
+
+def test_tie_contract_two_disjoint_boxes_of_equal_score(engine):
+    outs = [o.copy() for o in DR.scene_64(DR.TWO, 12, single=True)]
+    top = max(float(s.max()) for s in outs[:3])
+    for s in outs[:3]:
+        s[s >= np.float32(0.5)] = np.float32(top)
+    got, want = _decode(engine, [outs])
+    _same(got, want)
+    d = got[0][0]
+    assert d.shape == (2, 5) and d[0, 4] == d[1, 4] and d[0, 0] < d[1, 0]                # equal scores come out in anchor order
+    got, want = _decode(engine, [outs], max_num=1, metric="max")                         # and equal values pick as the restatement picks
+    _same(got, want)
+
+
+def test_five_levels_one_anchor(engine):
+    frames = [DR.synth_outputs((128, 128), 5, DR.FIVE, 7), DR.synth_outputs((128, 128), 5, DR.FIVE[:1], 8, use_kps=True)]
+    got, want = _decode(engine, frames, det_size=(128, 128), frame_hw=(150, 200))
+    _same(got, want)
+    assert [len(d) for d in got[0]] == [2, 1]
+    got, want = _decode(engine, frames, det_size=(128, 128), frame_hw=(150, 200), max_num=1, metric="max")
+    _same(got, want)
+    nokps = [DR.synth_outputs((128, 128), 5, DR.FIVE, 7, use_kps=False)]
+    _same(*_decode(engine, nokps, det_size=(128, 128), frame_hw=(150, 200)))
+
+
+# ------------------------------------------------------------------------------------------------ cs_det_decode at 640 x 640: 16 800 anchors
+FACES_640 = [((40, 60, 100, 130), 0.95), ((300, 90, 350, 140), 0.9), ((420, 300, 500, 380), 0.85), ((100, 400, 140, 440), 0.8), ((330, 110, 370, 160), 0.7)]
+
+
+def test_640_a_few_hundred_candidates_over_all_strides(engine):
+    frames = [DR.synth_outputs((640, 640), 3, FACES_640, 31), DR.synth_outputs((640, 640), 3, FACES_640[2:], 32)]
+    n = [sum(int((s >= np.float32(0.5)).sum()) for s in f[:3]) for f in frames]
+    per_level = [int((s >= np.float32(0.5)).sum()) for s in frames[0][:3]]
+    print("candidates per frame:", n, "per level:", per_level)
+    assert min(per_level) > 0 and 300 < n[0] <= 1024 and n[1] > 64
+    got, want = _decode(engine, frames, det_size=(640, 640), frame_hw=(1080, 1920))
+    _same(got, want)
+    assert len(got[0][0]) >= 4
+    _same(*_decode(engine, frames, det_size=(640, 640), frame_hw=(1080, 1920), max_num=2))
+
+
+def _disjoint_640(k, seed):
+    """k candidates on the 8-pixel level, one per cell (anchor 0), each a box of 3 pixels: no two overlap.  Scattered over the level, distinct scores."""
+    r = np.random.Generator(np.random.PCG64([5400, k, seed]))
+    outs = [o.copy() for o in DR.synth_outputs((640, 640), 3, [], seed)]
+    cells = np.sort(r.choice(6400, size=k, replace=False))
+    outs[0][2 * cells, 0] = (0.5 + 0.4 * r.permutation(k) / k).astype(np.float32)
+    outs[3][2 * cells] = np.float32(0.2)
+    return outs
+
+
+def test_640_the_candidate_cap_is_met_exactly(engine):
+    from canonswap_amd import _lib, detect
+    cap = _lib.DET_MAX_CAND
+    full, over = _disjoint_640(cap, 1), _disjoint_640(cap + 1, 2)
+    got, want = _decode(engine, [full], det_size=(640, 640), frame_hw=(640, 640), max_num=5)
+    _same(got, want)                                                                     # exactly the cap: accepted, sorted and thinned
+    assert len(got[0][0]) == 5
+    outs = _dev(DR.stack_frames([full, over]))
+    with pytest.raises(ValueError, match="frame 1 .*candidates"):
+        detect.det_decode(engine, outs, (640, 640), 1.0, (640, 640), max_num=5)
+    *_, raw = detect.det_decode(engine, _dev(DR.stack_frames([full])), (640, 640), 1.0, (640, 640), max_num=5, want_device=True)
+    assert raw["count"].tolist() == [5]
+    count = torch.zeros(2, dtype=torch.int32, device="cuda")                             # through the C ABI: -1 for the frame over the cap only
+    det = torch.zeros((2, 8, 5), device="cuda")
+    ptrs = (C.c_void_p * 9)(*[t.data_ptr() for t in outs])
+    rc = engine.lib.cs_det_decode(engine.h, 2, 3, (C.c_int * 3)(8, 16, 32), 2, ptrs, 640, 640, 1.0, 0.5, 0.4, 5, 0, 640, 640, 8, C.c_void_p(det.data_ptr()),
+                                  None, C.c_void_p(count.data_ptr()), engine._stream())
+    assert rc == 0 and count.tolist() == [5, -1]
+
+
+def test_640_the_survivor_cap_is_met_exactly(engine):
+    from canonswap_amd import detect
+    full, over = _disjoint_640(256, 3), _disjoint_640(257, 4)
+    outs = DR.stack_frames([full])
+    want = DR.decode_frames(outs, (640, 640), 1.0, (640, 640))
+    got = detect.det_decode(engine, _dev(outs), (640, 640), 1.0, (640, 640), max_faces=256)
+    _same(got, want)
+    assert len(got[0][0]) == 256
+    with pytest.raises(ValueError, match="frame 1 .*max_faces = 256"):
+        detect.det_decode(engine, _dev(DR.stack_frames([full, over])), (640, 640), 1.0, (640, 640), max_faces=256)
+    got = detect.det_decode(engine, _dev(DR.stack_frames([over])), (640, 640), 1.0, (640, 640), max_faces=256, max_num=256)      # with max_num: a pick, no cap
+    _same(got, DR.decode_frames(DR.stack_frames([over]), (640, 640), 1.0, (640, 640), max_num=256))
+
+
+def test_det_decode_refuses_bad_arguments_before_any_launch(engine):
+    lib, e = engine.lib, engine
+    outs = _dev(DR.stack_frames([DR.scene_64(DR.TWO, 1)]))
+    det = torch.full((1, 4, 5), 3.0, device="cuda")
+    kps = torch.full((1, 4, 5, 2), 3.0, device="cuda")
+    count = torch.full((1,), 77, dtype=torch.int32, device="cuda")
+    p = lambda t: C.c_void_p(0 if t is None else t.data_ptr())
+    good = dict(F=1, n=3, strides=(8, 16, 32), na=2, ptrs=[t.data_ptr() for t in outs], Hd=64, Wd=64, scale=0.64, thr=0.5, nms=0.4, max_num=0,
+                Ho=100, Wo=100, max_faces=4, det=det, kps=kps, count=count)
+
+    def call(**kw):
+        a = dict(good, **kw)
+        ptrs = (C.c_void_p * len(a["ptrs"]))(*a["ptrs"])
+        return lib.cs_det_decode(e.h, a["F"], a["n"], (C.c_int * len(a["strides"]))(*a["strides"]), a["na"], ptrs, a["Hd"], a["Wd"], a["scale"], a["thr"],
+                                 a["nms"], a["max_num"], 0, a["Ho"], a["Wo"], a["max_faces"], p(a["det"]), p(a["kps"]), p(a["count"]), e._stream())
+    no_kps = good["ptrs"][:6] + [None] * 3
+    part = good["ptrs"][:8] + [None]
+    for kw, word in (({"F": 0}, "F = 0"), ({"na": 1}, "layout"), ({"strides": (8, 16, 64)}, "layout"), ({"n": 4, "strides": (8, 16, 32, 64)}, "layout"),
+                     ({"det": None}, "det"), ({"count": None}, "count"), ({"max_faces": 0}, "max_faces"), ({"max_faces": 257}, "max_faces"),
+                     ({"max_num": 5}, "max_num"), ({"max_num": -1}, "max_num"), ({"scale": 0.0}, "det_scale"), ({"scale": float("inf")}, "det_scale"),
+                     ({"thr": float("nan")}, "NaN"), ({"Hd": 0}, "16384"), ({"Wo": 0}, "Wo = 0"), ({"ptrs": [None] + good["ptrs"][1:]}, "score"),
+                     ({"ptrs": part}, "kps pointers"), ({"ptrs": no_kps}, "without kps")):
+        rc = call(**kw)
+        err = lib.cs_last_error().decode()
+        assert rc != 0 and "cs_det_decode" in err and word in err, (kw, err)
+    torch.cuda.synchronize()
+    assert (det == 3.0).all() and (kps == 3.0).all() and count.tolist() == [77]
+    assert call() == 0 and call(ptrs=no_kps, kps=None) == 0                              # and the accepted calls still run
+    torch.cuda.synchronize()
+    assert count.tolist() == [2]
+
+
+# ------------------------------------------------------------------------------------------------ across layers
+@pytest.mark.parametrize("name", sorted(DR.GOLDEN_SCENES))
+def test_golden_scenes_through_the_c_abi(engine, swapper, name):
+    fx, c = DR.fixture(), DR.golden_case(name)
+    outs = _dev([o[None] for o in c["outs"]])
+    dets, kpss, fi = swapper.det_decode(outs, c["det_size"], c["det_scale"], c["frame_hw"], max_num=c["max_num"], metric=c["metric"])
+    assert np.array_equal(_bits(dets[0]), _bits(fx[f"{name}/det"])) and dets[0].shape == fx[f"{name}/det"].shape
+    if c["kps"] is None:
+        assert kpss is None
+    else:
+        assert np.array_equal(_bits(kpss[0]), _bits(fx[f"{name}/kps"]))
+    assert len(fi) == len(dets[0])
+
+
+def _video():
+    """F = 3 frames of 100 x 100 with faces in frames 0 and 2, and the stub network that returns their synthetic outputs."""
+    frames = DR.frames_u8(3, 100, 100, 40)
+    per_frame = [DR.scene_64(DR.TWO, 1), DR.scene_64([], 4), DR.scene_64(DR.PICK3, 6)]
+    outs = DR.stack_frames(per_frame)
+    seen = {}
+
+    def net(blob):
+        seen["blob"] = blob
+        return _dev(outs)
+    return frames, outs, net, seen
+
+
+def test_face_detector_feeds_the_chains_crop(swapper):
+    from canonswap_amd import detect, tail
+    from canonswap_amd.chain import FrameChain
+    frames, outs, net, seen = _video()
+    scale = DR.det_scale_64()
+    dets, kpss, fi = DR.decode_frames(outs, D64, scale, DR.FRAME_64)
+    fr = torch.from_numpy(frames).cuda()
+    detector = detect.FaceDetector(swapper, net, det_size=D64)
+    res = detector.detect(fr)
+    assert np.array_equal(_bits(seen["blob"].cpu().numpy()), _bits(DR.letterbox_blob(frames, D64)))      # the network saw the reference's blob
+    _same((res["dets"], res["kpss"], res["frame_index"]), (dets, kpss, fi))
+    assert list(res["frame_index"]) == [0, 0, 2, 2, 2] and res["kps"].shape == (5, 5, 2) and res["kps"].dtype == np.float32
+    chain = FrameChain(swapper)
+    c = chain.crop(fr, res["kps"], frame_index=res["frame_index"], dsize=64)
+    want = tail.crop_faces(swapper.engine, fr, np.concatenate(kpss), fi, dsize=64)
+    assert c["crops"].shape == (5, 64, 64, 3) and torch.equal(c["crops"], want["crops"]) and np.array_equal(c["M_c2o"], want["M_c2o"])
+    best = detector.detect(fr, best=True)                                                # face_detect_crop_single.py:71-80
+    assert list(best["frame_index"]) == [0, 2] and [len(d) for d in best["dets"]] == [1, 0, 1]
+    assert np.array_equal(best["dets"][2][0], dets[2][int(np.argmax(dets[2][:, 4]))])
+    one = detector.detect(fr, max_num=1, metric="max")
+    _same((one["dets"], one["kpss"], one["frame_index"]), DR.decode_frames(outs, D64, scale, DR.FRAME_64, max_num=1, metric="max"))
+
+
+def test_get_and_getid_faces_are_the_aligned_crops_and_their_identities(swapper):
+    from canonswap_amd import align, detect, tail
+    frames, outs, net, _ = _video()
+    fr = torch.from_numpy(frames).cuda()
+    detector = detect.FaceDetector(swapper, net, det_size=D64)
+    res = detector.get(fr, 112)
+    kps, fi = res["kps"], res["frame_index"]
+    M = np.stack([align.estimate_norm(k, 112, "None")[0] for k in kps])
+    assert np.array_equal(res["M"], M) and res["M"].dtype == np.float64
+    cut = tail.crop_faces_M(swapper.engine, fr, M, fi, 112)["crops"]
+    assert res["crops"].shape == (5, 112, 112, 3) and torch.equal(res["crops"], cut)
+    assert detect.FaceDetector(swapper, lambda blob: _dev(DR.stack_frames([DR.scene_64([], 4)] * 3)), det_size=D64).get(fr, 112) is None
+    ids = swapper.getid_faces(fr, kps[:4], fi[:4])                                       # max_batch is 4
+    assert ids.shape == (4, 512) and ids.is_cuda and torch.equal(ids, swapper.getid_crops(cut[:4]))
+    assert not torch.equal(ids[0], ids[2])
+    own = swapper.getid_faces(fr[[0, 0, 2]], kps[:3])                                    # frame_index=None: face b in frame b
+    assert torch.equal(own, ids[:3])
