@@ -30,6 +30,7 @@ ABI_SYMBOLS = [
     "cs_op_t_style", "cs_op_t_modulate", "cs_op_t_read", "cs_op_t_layer",
     "cs_op_m_stem", "cs_op_m_dwln", "cs_op_m_ln_s2d", "cs_op_m_grn", "cs_op_m_head", "cs_op_m_pointwise",
     "cs_op_dm_compress", "cs_op_dm_sparse", "cs_op_dm_softmax_warp", "cs_op_occ_finish", "cs_op_dm_read",
+    "cs_op_g_read", "cs_op_g_fill", "cs_op_g_stop",
     "cs_identity", "cs_identity_u8", "cs_op_identity_read", "cs_op_id_conv", "cs_op_id_maxpool", "cs_op_id_se_tail", "cs_op_id_embed",
     "cs_parser", "cs_op_parser_read", "cs_op_parser_input", "cs_op_parser_gemm", "cs_op_parser_layernorm", "cs_op_parser_attention", "cs_op_parser_dwgelu",
     "cs_op_parser_upadd",
@@ -442,6 +443,10 @@ def load():
     lib.cs_op_dm_softmax_warp.argtypes = [vp, vp, vp, vp, ci, vp, ci, vp, vp, vp, ci, ci, ci, ci, vp]
     lib.cs_op_occ_finish.argtypes = [vp, ci, cf, vp, ci, ci, ci, vp]
     lib.cs_op_dm_read.argtypes = [vp, ci, ci, vp, vp]
+    if hasattr(lib, "cs_op_g_read"):      # (tests only; an A/B build of an older tree - CANONSWAP_LIB, tools/cmp_libs.py - has none of the three)
+        lib.cs_op_g_read.argtypes = [vp, ci, ci, vp, vp]
+        lib.cs_op_g_fill.argtypes = [vp, ci, vp]
+        lib.cs_op_g_stop.argtypes = [vp, ci]
     lib.cs_identity.argtypes = [vp, ci, vp, ci, ci, vp, vp, vp]
     lib.cs_identity_u8.argtypes = [vp, ci, vp, ci, ci, vp, vp, vp, vp]
     lib.cs_op_identity_read.argtypes = [vp, ci, ci, vp, vp]

@@ -133,6 +133,7 @@ struct cs_engine {
     half_t *g_x[2], *g_h64, *g_dx64, *g_a64, *g_a128, *g_a256, *g_h128, *g_xs128, *g_dx128, *g_h1_128, *g_o128;
     half_t *g_h256, *g_xs256, *g_dx256, *g_h1_256, *g_o256;
     half_t* g_bs;         // the beta term of a learned shortcut (conv_s o mlp_beta of norm_s)
+    int g_stop = 0;       // tests (cs_op_g_stop): launches the next cs_spade_decode still runs before it returns; 0: all, -1: it stopped
     float *img_a, *img_b;
 
     // ---- profiling
@@ -151,13 +152,20 @@ struct cs_engine {
     }
     template <class F> int run(int fam, hipStream_t st, F f, const char* label = "", double fl = 0)
     {
-        if (!prof) return f();
+        if (!prof) return stop_after(f());
         hipEvent_t a = ev(), b = ev();
         hipEventRecord(a, st);
         int r = f();
         hipEventRecord(b, st);
         recs.push_back({fam, a, b, label, fl, -1});
-        return r;
+        return stop_after(r);
+    }
+    // the launch that uses up g_stop ends the call like a failed one (TRY unwinds); cs_spade_decode sees g_stop < 0 and reports success
+    int stop_after(int r)
+    {
+        if (r != 0 || g_stop <= 0 || --g_stop > 0) return r;
+        g_stop = -1;
+        return -1;
     }
     template <class T> int alloc(T** p, size_t n)
     {
@@ -1625,8 +1633,11 @@ extern "C" int cs_spade_decode(cs_engine* e, int B, const float* seg, float* img
 {
     ENTER(e, B);
     hipStream_t st = (hipStream_t)stream;
-    TRY(e->run(1, st, [&] { return launch_nchw_to_nhwc16(seg, e->seg16, B, 256, 4096, st); }, "nchw_to_nhwc16"));
-    return run_G(e, B, e->seg16, img_out, st);
+    int r = e->run(1, st, [&] { return launch_nchw_to_nhwc16(seg, e->seg16, B, 256, 4096, st); }, "nchw_to_nhwc16");
+    if (r == 0) r = run_G(e, B, e->seg16, img_out, st);
+    if (e->g_stop < 0) r = 0;      // cs_op_g_stop: stopped where the test asked
+    e->g_stop = 0;
+    return r;
 }
 
 extern "C" int cs_motion_extract(cs_engine* e, int B, const float* img, float* out, void* stream)
@@ -2325,6 +2336,67 @@ extern "C" int cs_op_dm_read(cs_engine* e, int which, int B, void* dst, void* st
     else if (which == CS_DM_LOGITS) { src = e->dm_logits; bytes = (size_t)B * DM_LOGIT_FLOATS * sizeof(float); }
     else { cs_set_error("cs_op_dm_read: no buffer %d", which); return -1; }
     return copy_dd(dst, src, bytes, (hipStream_t)stream);
+}
+
+// ---- operator level: G's workspace as the last cs_spade_decode left it (cs_op_g_read), a sentinel over all of it (cs_op_g_fill) and a stop after
+// the n-th launch of the next cs_spade_decode (cs_op_g_stop): the tests check every step of run_G on the engine's own input to it
+namespace {
+struct GBuf { void* p; size_t elems; };      // elements per sample
+GBuf g_buf(cs_engine* e, int which)
+{
+    switch (which) {
+    case CS_G_X0: return {e->g_x[0], (size_t)4096 * 512};
+    case CS_G_X1: return {e->g_x[1], (size_t)4096 * 512};
+    case CS_G_A64: return {e->g_a64, (size_t)4096 * 1536};
+    case CS_G_A128: return {e->g_a128, (size_t)16384 * 384};
+    case CS_G_A256: return {e->g_a256, (size_t)65536 * 384};
+    case CS_G_H64: return {e->g_h64, (size_t)4096 * 512};
+    case CS_G_DX64: return {e->g_dx64, (size_t)4096 * 512};
+    case CS_G_H128: return {e->g_h128, (size_t)16384 * 512};
+    case CS_G_XS128: return {e->g_xs128, (size_t)16384 * 256};
+    case CS_G_DX128: return {e->g_dx128, (size_t)16384 * 256};
+    case CS_G_H1_128: return {e->g_h1_128, (size_t)16384 * 256};
+    case CS_G_O128: return {e->g_o128, (size_t)16384 * 256};
+    case CS_G_BS: return {e->g_bs, (size_t)65536 * 64};
+    case CS_G_H256: return {e->g_h256, (size_t)65536 * 256};
+    case CS_G_XS256: return {e->g_xs256, (size_t)65536 * 64};
+    case CS_G_DX256: return {e->g_dx256, (size_t)65536 * 64};
+    case CS_G_H1_256: return {e->g_h1_256, (size_t)65536 * 64};
+    case CS_G_O256: return {e->g_o256, (size_t)65536 * 64};
+    }
+    return {nullptr, 0};
+}
+}  // namespace
+
+extern "C" int cs_op_g_read(cs_engine* e, int which, int B, void* dst, void* stream)
+{
+    ENTER(e, B);
+    if (!dst) { cs_set_error("cs_op_g_read: null destination"); return -1; }
+    if (which == CS_G_STATS) {      // the slot stats_slot() handed out last
+        const float* slot = e->stats_pool + ((e->stats_next + e->stats_slots - 1) % e->stats_slots) * e->stats_slot_floats;
+        return copy_dd(dst, slot, (size_t)B * 512 * 2 * sizeof(float), (hipStream_t)stream);
+    }
+    const GBuf b = g_buf(e, which);
+    if (!b.p) { cs_set_error("cs_op_g_read: no buffer %d", which); return -1; }
+    return copy_dd(dst, b.p, (size_t)B * b.elems * sizeof(half_t), (hipStream_t)stream);
+}
+
+extern "C" int cs_op_g_fill(cs_engine* e, int B, void* stream)
+{
+    ENTER(e, B);
+    for (int which = CS_G_X0; which <= CS_G_O256; ++which) {
+        const GBuf b = g_buf(e, which);
+        CS_CHECK_HIP(hipMemsetD16Async((hipDeviceptr_t)b.p, CS_G_SENTINEL, (size_t)B * b.elems, (hipStream_t)stream));
+    }
+    CS_CHECK_HIP(hipMemsetD16Async((hipDeviceptr_t)e->stats_pool, CS_G_SENTINEL, e->stats_slots * e->stats_slot_floats * 2, (hipStream_t)stream));
+    return 0;
+}
+
+extern "C" int cs_op_g_stop(cs_engine* e, int n)
+{
+    if (!e || n < 0) { cs_set_error("cs_op_g_stop: bad arguments"); return -1; }
+    e->g_stop = n;
+    return 0;
 }
 
 // ---- operator level: the identity network's kernels (csrc/identity.hip) without an engine, and the activations the last cs_identity pass left

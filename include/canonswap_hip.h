@@ -455,6 +455,33 @@ int cs_op_occ_finish(const float* part, int taps, float bias, float* occ, int N,
 enum { CS_DM_COMP = 0, CS_DM_L0 = 1, CS_DM_PRED = 7, CS_DM_LOGITS = 8 };
 int cs_op_dm_read(cs_engine* e, int which, int B, void* dst, void* stream);
 
+/* The SPADE decoder's workspace, for tests that check G launch by launch on the engine's own tensors.
+ * cs_op_g_read copies one buffer, as the last cs_spade_decode left it, to dst on `stream`; B: samples to copy (<= max_batch).  All fp16, channels last:
+ *   CS_G_X0, CS_G_X1:  [B][64][64][512]    x of the middle blocks: fc writes X0, block b reads X(b & 1) and writes X(~b & 1); up_0 reads X0
+ *   CS_G_A64:          [B][64][64][1536]   relu(mlp_shared) of G_middle_b.norm_k in channels [(2 b + k) 128, +128)
+ *   CS_G_A128 / A256:  [B][S][S][384]      relu(mlp_shared) of up_0 / up_1 (S = 128 / 256): norm_0 in [0, 128), norm_1 in [128, 256), norm_s in [256, 384)
+ *   CS_G_H64:          [B][64][64][512]    lrelu(SPADE) of a middle block's norm_0, then of its norm_1
+ *   CS_G_DX64:         [B][64][64][512]    conv_0 of a middle block
+ *   CS_G_H128:         [B][128][128][512]  up_0: IN(x)(1 + gamma_s) (the shortcut's .ng launch), then lrelu(SPADE norm_0)
+ *   CS_G_XS128:        [B][128][128][256]  up_0's learned shortcut x_s
+ *   CS_G_DX128, CS_G_H1_128, CS_G_O128: [B][128][128][256]  up_0's conv_0, lrelu(SPADE norm_1), block output x_s + conv_1
+ *   CS_G_BS:           B x 4194304 values: conv_s(beta) of the shortcut, [B][128][128][256] after up_0's .bs launch, [B][256][256][64] after up_1's
+ *   CS_G_H256:         [B][256][256][256]  up_1: lrelu(SPADE norm_0) (and IN(x)(1 + gamma_s) before it where the shortcut runs as three launches)
+ *   CS_G_XS256, CS_G_DX256, CS_G_H1_256: [B][256][256][64]  up_1's x_s, conv_0, lrelu(SPADE norm_1)
+ *   CS_G_O256:         [B][256][256][64]   lrelu(x_s + conv_1, 0.2): conv_img's input
+ *   CS_G_STATS:        fp32 B x 1024 values: the (mean, rstd) slot handed out last, [B][C][2] in its first B C 2 values (C: the channels of the
+ *                      tensor whose statistics-emitting conv ran last)
+ * cs_op_g_fill writes the fp16 NaN pattern CS_G_SENTINEL over the first B samples of every buffer above and over the whole statistics pool (an
+ * fp32 there reads 0x7E5A7E5A).
+ * cs_op_g_stop(e, n): the next cs_spade_decode returns (with 0) after its n-th launch, counted as the profile CSV lists them (nchw_to_nhwc16
+ * is the first; chan_stats_finish and splitk_finish count); n = 0: all of it.  That call clears the stop. */
+enum { CS_G_X0 = 0, CS_G_X1, CS_G_A64, CS_G_A128, CS_G_A256, CS_G_H64, CS_G_DX64, CS_G_H128, CS_G_XS128, CS_G_DX128, CS_G_H1_128, CS_G_O128, CS_G_BS,
+       CS_G_H256, CS_G_XS256, CS_G_DX256, CS_G_H1_256, CS_G_O256, CS_G_STATS };
+#define CS_G_SENTINEL 0x7E5A
+int cs_op_g_read(cs_engine* e, int which, int B, void* dst, void* stream);
+int cs_op_g_fill(cs_engine* e, int B, void* stream);
+int cs_op_g_stop(cs_engine* e, int n);
+
 /* The identity network's kernels one at a time (csrc/identity.hip; weights as pack._pack_A lays them out; models/arcface_models.py:10-136).
  * conv: in fp16 (in_f32: fp32, rounded to fp16 on load) contiguous [N][IH][IW][Cin] -> out fp32 / fp16 [N][OH][OW][Cout] = prelu(conv + bias), K x K
  * taps (K from 1 to 8), stride >= 1, zero padding pad < K, OH = (IH + 2 pad - K) / stride + 1; w fp16 [K * K][Cout][Cin] (pack.pack_id_conv); Cin % 32 == 0,

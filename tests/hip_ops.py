@@ -281,6 +281,40 @@ def compact2_logits(part, bias):
     return l[:, :, :, 3:3 + Ww] + bias.to(part.dtype)
 
 
+# ---- G's workspace (cs_op_g_read / cs_op_g_fill / cs_op_g_stop; layouts: include/canonswap_hip.h)
+G_NAMES = ("x0", "x1", "a64", "a128", "a256", "h64", "dx64", "h128", "xs128", "dx128", "h1_128", "o128", "bs", "h256", "xs256", "dx256", "h1_256", "o256")
+G_X0, G_X1, G_A64, G_A128, G_A256, G_H64, G_DX64, G_H128, G_XS128, G_DX128, G_H1_128, G_O128, G_BS, G_H256, G_XS256, G_DX256, G_H1_256, G_O256 = range(18)
+G_STATS = 18
+G_SHAPE = {G_X0: (64, 64, 512), G_X1: (64, 64, 512), G_A64: (64, 64, 1536), G_A128: (128, 128, 384), G_A256: (256, 256, 384), G_H64: (64, 64, 512),
+           G_DX64: (64, 64, 512), G_H128: (128, 128, 512), G_XS128: (128, 128, 256), G_DX128: (128, 128, 256), G_H1_128: (128, 128, 256),
+           G_O128: (128, 128, 256), G_BS: (256, 256, 64), G_H256: (256, 256, 256), G_XS256: (256, 256, 64), G_DX256: (256, 256, 64),
+           G_H1_256: (256, 256, 64), G_O256: (256, 256, 64)}
+G_SENTINEL = 0x7E5A
+
+
+def g_read(engine, which, B, out=None):
+    """One of G's buffers as the last cs_spade_decode left it: fp16 [B, H, W, C] (G_BS: as [B, 256, 256, 64]; after up_0's .bs launch view it as
+    [B, 128, 128, 256]), G_STATS: fp32 [B, 1024], the slot handed out last ([B][C][2] in its first B C 2 values).  out: a buffer to reuse."""
+    shape = (B, 1024) if which == G_STATS else (B,) + G_SHAPE[which]
+    if out is None:
+        out = torch.empty(shape, dtype=torch.float32 if which == G_STATS else torch.float16, device=engine.device)
+    assert out.is_contiguous() and tuple(out.shape) == shape
+    _lib.check(engine.lib.cs_op_g_read(engine.h, which, B, _p(out), _st()), "cs_op_g_read")
+    return out
+
+
+def g_fill(engine, B):
+    _lib.check(engine.lib.cs_op_g_fill(engine.h, B, _st()), "cs_op_g_fill")
+
+
+def g_decode(engine, seg, img, stop=0):
+    """cs_spade_decode into the caller's img [B, 3, 512, 512] fp32, returning after its stop-th launch (0: all of it)"""
+    assert seg.is_contiguous() and img.is_contiguous() and seg.dtype == img.dtype == torch.float32
+    _lib.check(engine.lib.cs_op_g_stop(engine.h, stop), "cs_op_g_stop")
+    _lib.check(engine.lib.cs_spade_decode(engine.h, seg.shape[0], _p(seg), _p(img), _st()), "cs_spade_decode")
+    return img
+
+
 # ---- T's identity path (cs_op_t_*; csrc/kernels.hip t_style / t_modulate, the engine's per-slot weight sets and its blend layers)
 T_WSET, T_STYLE = 0, 1
 

@@ -1,5 +1,5 @@
 """GPU box: the same frames through two builds of the library, compared bit for bit (stage outputs of the whole loop body, default and latency mode,
-W's own entry points - warp, warp_forward, animate_frames on one shared volume -, the motion extractor's raw head outputs, and the crop / warp /
+cs_spade_decode's image and launch list, W's own entry points - warp, warp_forward, animate_frames on one shared volume -, the motion extractor's raw head outputs, and the crop / warp /
 paste-back entry points on 1080p frames); the environment (an A/B knob such as CANONSWAP_WARP_FUSED=0) reaches both children:
     python tools/cmp_libs.py tools/bin/base.so ""        ("" = the shipped library)
 Each build runs in its own process (the library is chosen at import: CANONSWAP_LIB)."""
@@ -10,7 +10,7 @@ import tempfile
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CHILD = r'''
-import sys, torch
+import os, sys, tempfile, torch
 sys.path.insert(0, %r)
 from canonswap_amd import synth
 from canonswap_amd.can_swap_e2e import can_swapper
@@ -27,6 +27,15 @@ for lat in (False, True):
     for k, v in r.items():
         if torch.is_tensor(v):
             out[("lat." if lat else "") + k] = v.cpu()
+    # cs_spade_decode on its own (default and latency mode): the image and the launch list of the profile CSV (its labels, as bytes)
+    e = sw.engine
+    seg = e.warp_out(e.extract_feature_3d(args[0][:nb]))
+    out[("lat." if lat else "") + "engine.spade_decode"] = e.spade_decode(seg).cpu()
+    with tempfile.TemporaryDirectory() as td:
+        os.environ["CANONSWAP_PROFILE_CSV"] = os.path.join(td, "l.csv")
+        e.profile_begin(); e.spade_decode(seg); e.profile_end()
+        labels = " ".join(l.split(",")[1] for l in open(os.environ.pop("CANONSWAP_PROFILE_CSV")).read().splitlines()[1:])
+    out[("lat." if lat else "") + "engine.spade_decode.launches"] = torch.tensor(list(labels.encode()), dtype=torch.uint8)
     if not lat:
         # W's entry points beyond the loop body, on the same engine: cs_warp (f_out and occ), cs_warp_forward (the fused kernel also stores its
         # deformation), cs_animate_frames with ONE volume and ONE source key-point set for 3 frames (sample stride 0 in dm_sparse and in the
