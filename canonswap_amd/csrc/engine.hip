@@ -1,17 +1,10 @@
 // Host side of the gfx950 CanonSwap engine: weight registry, workspace, per-stage kernel sequencing and
 // the C ABI declared in include/canonswap_hip.h.  Stage order and argument wiring follow
 // src/can_swap_pipeline_e2e.py:242-263 and src/can_swap_e2e.py:286-312 of the reference.
-#include "common.h"
-#include "../../include/canonswap_hip.h"
+#include "engine.h"
 
 #include <cstdarg>
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
 #include <initializer_list>
-#include <map>
-#include <string>
-#include <vector>
 
 static thread_local char g_err[1024] = "";
 void cs_set_error(const char* fmt, ...)
@@ -35,157 +28,7 @@ extern "C" const char* cs_last_error(void) { return g_err; }
 // packed weight blobs of F.down0 / down1 / second carry [W_hi | W_lo], W.occ49 exists; cs_conv_desc::pool_hw.  _lib.load() refuses any other value.
 extern "C" int cs_abi_version(void) { return CS_ABI_VERSION; }
 
-#define TRY(x) do { if ((x) != 0) return -1; } while (0)
-
-namespace {
-
-constexpr int FD = 16, FH = 64, FW = 64, FC = 32;            // feature volume 32x16x64x64
-constexpr long VOL = (long)FD * FH * FW * FC;                 // 2,097,152 elements
-constexpr long VOX = (long)FD * FH * FW;                      // 65,536 voxels
-// dense motion's hourglass: level i is a [FD][S][S][DM_LW[i]] fp16 concat buffer per sample, S = 64 >> i (cs_engine::dm_l)
-constexpr int DM_LW[6] = {144, 128, 256, 512, 1024, 1024};    // concat widths per level
-constexpr long dm_level_elems(int i) { return (long)FD * (64 >> i) * (64 >> i) * DM_LW[i]; }
-static_assert(dm_level_elems(0) == 65536L * 144 && dm_level_elems(3) == 16L * 64 * 512 && dm_level_elems(5) == 16L * 4 * 1024, "hourglass level sizes");
-constexpr long DM_LOGIT_FLOATS = VOX / 4 * 220;                     // floats per sample of the mask conv's hand-over (ConvParams::kw_out, 4-column tiles)
-constexpr int IMG = 256;
-
-struct Blob { void* p = nullptr; size_t bytes = 0; bool paired = false; };     // paired: launch_pair_ragged already ran on it
-
-struct ConvL {            // one packed convolution layer
-    const half_t* w = nullptr;
-    const float* b = nullptr;
-    int Cin = 0, Cout_pad = 0, Cout = 0, KD = 1, KH = 1, KW = 1;
-    double macs_per_pos = 0;   // logical (reference) Cin*Cout*taps, for FLOP accounting
-    bool ragged = false;       // Cin % 32 == 16 and the last chunk's weights re-packed for paired taps (ConvParams::ragged)
-    std::string name;
-};
-
-struct Affine { const float* s = nullptr; const float* t = nullptr; };
-
-constexpr int MAX_SLOTS = CS_MAX_IDENTITY_SLOTS;
-// wset[s]: the fused [W; w_mod] packed weights of identity slot s (slot 0 lives in the uploaded blob, the others are allocated on
-// first use); wofs: element offsets wset[s] - wset[0] in device memory for launches that mix identities
-struct TLayer { ConvL fused; ConvL mask; const float* raw; const float* fc; const float* bias; half_t* wset[MAX_SLOTS]; long* wofs; };
-
-}  // namespace
-
-struct cs_engine {
-    int dev = 0, maxB = 1;
-    bool finalized = false;
-    bool latency_mode = false;             // single-frame latency: cross-workgroup split-K for launches that cannot fill the chip
-    bool slot_set[MAX_SLOTS] = {};
-    int* slot_dev = nullptr;               // per-sample identity slot of the current batch (device)
-    int* slot_pin = nullptr;               // pinned staging ring for slot_dev uploads
-    int slot_ring = 0;
-    std::vector<int> slot_cur;             // what slot_dev holds
-    std::map<std::string, Blob> blobs;
-    std::vector<void*> allocs;
-
-    // ---- layers
-    const float *first_w = nullptr, *first_b = nullptr;
-    ConvL f_down0, f_down1, f_second;
-    Affine f_pre0;
-    struct RB3 { ConvL c1, c2; Affine post; } f_rb[6], t_rb[6];
-    const float *cmp_w = nullptr, *cmp_b = nullptr;
-    ConvL w_enc[5], w_dec[5], w_tail, w_mask, w_occ, w_occ49, w_third, w_fourth;
-    ConvL w_dec_p[5][4];                   // the up-blocks per output phase (a, b) on the source grid
-    float occ_b = 0.f;
-    const float* mask_b = nullptr;
-    TLayer t_l[14];
-    Affine t_pre0;
-    struct S3 { ConvL c1, c2, c1sp, c2sp; const float *g1, *b1, *g2, *b2; } r_s1[3], r_s3[3];   // *sp: split-precision weights (Cin 96)
-    struct RB2 { ConvL c1, c2; Affine pre; } r_rb2[3];
-    ConvL g_fc, g_sh64, g_sh128, g_sh256, g_img;
-    // mlp_shared convs of the up blocks per output phase group on the source grid; dupc: the value also goes to the next pixel (x4 level, middle
-    // columns of a two-row phase)
-    struct ShPhase { ConvL conv; int a, b0, ph, pw; bool dupc; };
-    ShPhase g_shp[2][12]; int g_nshp[2] = {0, 0};
-    struct GB { ConvL conv; const float *bg, *bb; };
-    struct SpadeBlk { GB n0, n1, ns; ConvL c0, c1, cs, ng, bs; bool learned; int fin, fmid, fout; } g_blk[8];      // ng / bs: the learned shortcut's norm_s, see run_G
-
-    // motion extractor (optional: present when the "M.*" blobs were uploaded)
-    bool has_m = false;
-    const float *m_stem_w = nullptr, *m_stem_b = nullptr, *m_stem_g = nullptr, *m_stem_be = nullptr;
-    struct MBlk { const float *dw_w, *dw_b, *ln_g, *ln_b, *grn_g, *grn_b; ConvL pw1, pw2; };
-    struct MStage { int C, n; MBlk blk[9]; const float *ds_g, *ds_b; ConvL ds; } m_st[4];
-    const float *m_norm_g = nullptr, *m_norm_b = nullptr, *m_head_w = nullptr, *m_head_b = nullptr;
-    float *m_x = nullptr, *m_sumsq = nullptr, *m_scale = nullptr;
-    half_t *m_y = nullptr, *m_h = nullptr;   // split-precision GEMM operands [hi | lo]
-    float* m_h32 = nullptr;
-    // ArcFace identity network (optional: present when the "A.*" blobs were uploaded); its workspace holds min(max_batch, 8) images per pass
-    IdNet idn;
-    // SegFormer face parser (optional: present when the "P.*" blobs were uploaded); its workspace holds min(max_batch, P_CHUNK) images of 512 x 512 per pass
-    ParserNet psr;
-    // soft-erosion scratch (allocated on first use for the largest B*H*W seen)
-    float *se_a = nullptr, *se_b = nullptr, *se_part = nullptr; size_t se_cap = 0, se_part_cap = 0;      // se_part: 64 maxima per sample
-
-    // ---- workspace
-    half_t *f_t0, *f_p0, *f_p1;
-    float* vs[3]; half_t* va[2];
-    float* sk_buf = nullptr; size_t sk_cap = 0;      // split-K partial sums (floats)
-    half_t* vsp[2];                        // split-precision conv inputs of R's GroupNorm blocks: [hi | lo] per voxel
-    half_t *dm_comp, *dm_l[6], *dm_pre, *dm_pred;
-    float *dm_logits, *dm_deform, *dm_occ;
-    float *kpbuf;
-    half_t *w_t3, *seg16;
-    float* tmask; float* style;
-    float* stats_pool; float* stats_part; float* dm_occpart; size_t stats_slots = 0, stats_next = 0; size_t stats_slot_floats = 0;
-    half_t *g_x[2], *g_h64, *g_dx64, *g_a64, *g_a128, *g_a256, *g_h128, *g_xs128, *g_dx128, *g_h1_128, *g_o128;
-    half_t *g_h256, *g_xs256, *g_dx256, *g_h1_256, *g_o256;
-    half_t* g_bs;         // the beta term of a learned shortcut (conv_s o mlp_beta of norm_s)
-    int g_stop = 0;       // tests (cs_op_g_stop): launches the next cs_spade_decode still runs before it returns; 0: all, -1: it stopped
-    float *img_a, *img_b;
-
-    // ---- profiling
-    bool prof = false;
-    struct Rec { int fam; hipEvent_t a, b; std::string label; double flops; int amax_slot; };
-    unsigned* amax_dev = nullptr; int amax_n = 0;          // CANONSWAP_AMAX=1: per-launch |max| of the fp16 outputs of a profiled step
-    std::vector<Rec> recs;
-    std::vector<hipEvent_t> evpool;
-    size_t evnext = 0;
-    double flops = 0, flops_exec = 0;
-
-    hipEvent_t ev()
-    {
-        if (evnext == evpool.size()) { hipEvent_t e; hipEventCreate(&e); evpool.push_back(e); }
-        return evpool[evnext++];
-    }
-    template <class F> int run(int fam, hipStream_t st, F f, const char* label = "", double fl = 0)
-    {
-        if (!prof) return stop_after(f());
-        hipEvent_t a = ev(), b = ev();
-        hipEventRecord(a, st);
-        int r = f();
-        hipEventRecord(b, st);
-        recs.push_back({fam, a, b, label, fl, -1});
-        return stop_after(r);
-    }
-    // the launch that uses up g_stop ends the call like a failed one (TRY unwinds); cs_spade_decode sees g_stop < 0 and reports success
-    int stop_after(int r)
-    {
-        if (r != 0 || g_stop <= 0 || --g_stop > 0) return r;
-        g_stop = -1;
-        return -1;
-    }
-    template <class T> int alloc(T** p, size_t n)
-    {
-        void* q = nullptr;
-        hipError_t e = hipMalloc(&q, n * sizeof(T));
-        if (e != hipSuccess) { cs_set_error("hipMalloc(%zu bytes): %s", n * sizeof(T), hipGetErrorString(e)); return -1; }
-        allocs.push_back(q);
-        *p = (T*)q;
-        return 0;
-    }
-    const Blob* find(const std::string& n) const
-    {
-        auto it = blobs.find(n);
-        return it == blobs.end() ? nullptr : &it->second;
-    }
-};
-
-namespace {
-
-int need(cs_engine* e, const std::string& n, size_t bytes, const void** out)
+static int need(cs_engine* e, const std::string& n, size_t bytes, const void** out)
 {
     const Blob* b = e->find(n);
     if (!b) { cs_set_error("weights: blob '%s' was not uploaded", n.c_str()); return -1; }
@@ -194,7 +37,7 @@ int need(cs_engine* e, const std::string& n, size_t bytes, const void** out)
     return 0;
 }
 
-int get_conv(cs_engine* e, const std::string& n, int Cin, int Cout_pad, int Cout, int KD, int KH, int KW, int bias_len,
+static int get_conv(cs_engine* e, const std::string& n, int Cin, int Cout_pad, int Cout, int KD, int KH, int KW, int bias_len,
              double macs, ConvL* L)
 {
     const int nch = (Cin + 31) / 32;
@@ -209,7 +52,7 @@ int get_conv(cs_engine* e, const std::string& n, int Cin, int Cout_pad, int Cout
     return 0;
 }
 
-int get_affine(cs_engine* e, const std::string& n, int len, Affine* a)
+static int get_affine(cs_engine* e, const std::string& n, int len, Affine* a)
 {
     const void* p;
     TRY(need(e, n + ".s", (size_t)len * 4, &p)); a->s = (const float*)p;
@@ -217,7 +60,7 @@ int get_affine(cs_engine* e, const std::string& n, int len, Affine* a)
     return 0;
 }
 
-int get_f32(cs_engine* e, const std::string& n, int len, const float** out)
+static int get_f32(cs_engine* e, const std::string& n, int len, const float** out)
 {
     const void* p;
     TRY(need(e, n, (size_t)len * 4, &p));
@@ -225,28 +68,7 @@ int get_f32(cs_engine* e, const std::string& n, int len, const float** out)
     return 0;
 }
 
-TDesc td(void* p, long sN, long sD, long sH, long sW) { return TDesc{p, sN, sD, sH, sW}; }
-// contiguous [N][H][W][C]
-TDesc nhwc(void* p, int H, int W, int C) { return td(p, (long)H * W * C, 0, (long)W * C, C); }
-// feature volume [N][H][W][D][C] seen as a 3-D tensor (d stride = C) or as the 512-channel 2-D view
-TDesc hwdc3(void* p) { return td(p, VOL, FC, (long)FW * FD * FC, (long)FD * FC); }
-TDesc hwdc2(void* p) { return td(p, VOL, 0, (long)FW * FD * FC, (long)FD * FC); }
-// dense-motion tensors [N][D][H][W][stride]
-TDesc dhwc(void* p, int D, int H, int W, int stride) { return td(p, (long)D * H * W * stride, (long)H * W * stride, (long)W * stride, stride); }
-
-int ilog2(int v) { int l = 0; while ((1 << l) < v) ++l; return l; }
-
-struct ConvCall {
-    ConvParams p;
-    int cfg = -1, mode = MODE_STD;
-    int hcfg = -1;            // forced conv_halo configuration (else derived from Cout_pad)
-    int stat_nblk = 0;        // set by go(): partial blocks per sample when p.stat_out is used
-    bool cg_ck64 = false;     // grouped input channels (ConvParams::cg) on 64-channel chunks where the kernel allows it (1x1 convs, even cg)
-    double macs_per_pos = 0;
-    const char* name = "";
-};
-
-ConvCall mk(const ConvL& L, const void* in, TDesc ind, int N, int D, int H, int W, int up_shift = 0)
+ConvCall mk(const ConvL& L, const void* in, TDesc ind, int N, int D, int H, int W, int up_shift)
 {
     ConvCall c;
     memset(&c.p, 0, sizeof(c.p));
@@ -265,80 +87,37 @@ ConvCall mk(const ConvL& L, const void* in, TDesc ind, int N, int D, int H, int 
     return c;
 }
 
-void set_tile(ConvParams& p, int BM, int prefW, int prefH)
-{
-    int tw = p.W < prefW ? p.W : prefW;
-    int th = p.H < prefH ? p.H : prefH;
-    while (tw * th > BM) th >>= 1;
-    int tdd = BM / (tw * th);
-    if (tdd > p.D) tdd = p.D;
-    int tn = BM / (tw * th * tdd);
-    p.lgTW = ilog2(tw); p.lgTH = ilog2(th); p.lgTD = ilog2(tdd);
-    p.nTW = p.W / tw; p.nTH = p.H / th; p.nTD = p.D / tdd; p.nTN = (p.N + tn - 1) / tn;
-}
-
 // tile configuration of the 32->32 3x3x3 convs on the [H][W][D][C] volumes: 256 positions (4x4x16) x 32 channels; 128-position
 // tiles measured slower (more halo re-reads than the extra occupancy returns)
-int cfg_v32() { return CFG_H_256x32; }
+static int cfg_v32() { return CFG_H_256x32; }
 
-// The hourglass tail / mask conv (160 packed channels) and the first encoder block (64 channels) run 256-position tiles; the ragged last
-// chunk of those layers (Cin 144 / 112) runs paired taps.  (The A/B knobs of rounds 1-4 that selected the older forms are gone:
-// profiles/HISTORY.md section 6 keeps their records.)
-// SPADE gamma/beta convs with 128 or more modulated channels (Cout_pad % 256 == 0) on 128x256 tiles from three frames up: +0.5 % with the
-// conflict-free LDS image (neutral before it).  Those layers keep 64-channel chunks at every batch size (same K order, same bits); the
-// 64-channel ones (Cout_pad 128) run 32-channel chunks on 128x128 tiles.
-constexpr int HALO_PERSIST = 1;        // ConvParams::persist_total request of every engine launch (persistent tile walk where the kernel has one)
-constexpr int XCD_MAP = 2;             // ConvParams::xcd_map of every engine launch (+0.8 % on the step over the plain order, r02 A/B)
-
-int pick_halo_cfg(const ConvParams& p, int mode)
+// debug knob CANONSWAP_AMAX=1 (profiled steps only): largest |value| of the fp16 tensors this conv stored
+static int amax_after(cs_engine* e, const ConvCall& c, hipStream_t st)
 {
-    const int Cout_pad = p.Cout_pad;
-    if (mode == MODE_PIXSHUF) return CFG_H_256x16;
-    // 128 positions x 256 channels (64 channels per wave) only exists as the fully unrolled 3x3 / 16x8-tile kernel
-    // 2 resident 128x256 workgroups: the T blend convs (N = 1024, 4 channel blocks per tile: +4.7 %).  In round 1 three resident
-    // 128x128 workgroups were 4-14 % faster everywhere else (G 3x3 convs, fc, F down-blocks; tools/cmp_layers.py); see below
-    // (below 3 frames a 128x256 launch is 128 workgroups or fewer: 128x128 tiles put one on every CU; same K order, same bits)
-    if (mode == MODE_TBLEND && Cout_pad % 256 == 0 && p.KD == 1 && p.KH == 3 && p.KW == 3 && p.W >= 16 && p.H >= 8 && p.Cin % 32 == 0 &&
-        (long)p.N * p.H * p.W >= 3 * 4096) return CFG_H_128x256;
-    // ... and, since the round-2 epilogue / addressing work, for the other 3x3 convs with 256 or more output channels (G 512->512 with
-    // and without statistics, R's 512-channel pair, W.third): +0.7 % on the step, the same per-64-position statistics, the same bits
-    if (mode == MODE_SPADE && Cout_pad % 256 == 0 && p.KD == 1 && p.KH == 3 && p.KW == 3 && p.W >= 16 && p.H >= 8 && p.Cin % 64 == 0 &&
-        (long)p.N * p.H * p.W >= 3 * 4096) return CFG_H_128x256;
-    if ((mode == MODE_STD || mode == MODE_STDSTAT) && Cout_pad % 256 == 0 && p.KD == 1 && p.KH == 3 && p.KW == 3 &&
-        p.W >= 16 && p.H >= 8 && p.Cin % 64 == 0 && (long)p.N * p.H * p.W >= 3 * 4096) return CFG_H_128x256;
-    if (Cout_pad % 128 == 0) {
-        // a launch of 128 or fewer 128x128 workgroups leaves half of the 256 CUs idle (one frame: the 512-channel 3x3 convs at 64x64
-        // are 32 x 4): 128x64 tiles put a workgroup on every CU.  Same K order per output element, same bits.
-        // (the 1x1 convs too - F.second, W.fourth, the learned shortcuts: 64 - 128 workgroups of two or four K-steps per chunk otherwise)
-        const long tiles = ((long)p.N * p.D * p.H * p.W + 127) / 128;
-        const bool k33 = p.KH == 3 && p.KW == 3, k11 = p.KD == 1 && p.KH == 1 && p.KW == 1 && mode == MODE_STD;
-        if ((mode == MODE_STD || mode == MODE_STDSTAT) && (k33 || k11) && tiles * (Cout_pad / 128) <= 128)
-            return CFG_H_128x64;
-        // ... and the 1x1 convs up to one workgroup per CU: M's stage-3 pwconv2 and last down-sampling conv are 32 x 6 = 192 workgroups of 288 /
-        // 144 K-steps each on 128x128 tiles (0.247 -> 0.215 and 0.143 -> 0.118 ms per 64 frames, profiles/r06_q_chain_k11.txt); same bits
-        if (k11 && tiles * (Cout_pad / 128) < 256) return CFG_H_128x64;      // (up to 768 - fewer workgroups than resident slots - measured the same)
-        return CFG_H_128x128;
-    }
-    // 64 output channels at 128x128 or more (G's last up block, F's first down block): 256-position tiles (16x16), two position waves x two
-    // channel waves - a wave tile of 128 positions halves the weight bytes per MFMA of the 128x64 tile's 64-position wave tiles
-    // Same K order per output element; statistics per 16 x 4 positions as on every tile.
-    if (Cout_pad == 64 && (mode == MODE_STD || mode == MODE_STDSTAT) && p.KD == 1 && p.KH == 3 && p.KW == 3 && p.Cin % 64 == 0 && p.cg == 0 &&
-        p.H % 16 == 0 && p.W % 16 == 0 && p.H >= 128 && !p.sk_out) return CFG_H_256x64;
-    if (Cout_pad % 64 == 0) return CFG_H_128x64;
-    if (Cout_pad % 32 == 0) return CFG_H_128x32;
-    return CFG_H_128x16;
+    static const bool on = [] { const char* s = getenv("CANONSWAP_AMAX"); return s && atoi(s) != 0; }();
+    if (!on || !e->prof || e->recs.empty()) return 0;
+    if (!e->amax_dev) { if (e->alloc(&e->amax_dev, (size_t)4096)) return -1; }
+    if (e->amax_n >= 4096) return 0;
+    const ConvParams& p = c.p;
+    const bool o0 = p.out0.p && !p.out0_f32 && c.mode != MODE_PIXSHUF, o1 = p.out1.p != nullptr;
+    if (!o0 && !o1) return 0;
+    const int slot = e->amax_n++;
+    hipError_t r = hipMemsetAsync(e->amax_dev + slot, 0, sizeof(unsigned), st);
+    if (r != hipSuccess) { cs_set_error("amax memset: %s", hipGetErrorString(r)); return -1; }
+    if (o0) TRY(launch_absmax16((const half_t*)p.out0.p, p.out0, p.N, p.D, p.H, p.W, p.Cout, e->amax_dev + slot, st));
+    if (o1) TRY(launch_absmax16((const half_t*)p.out1.p, p.out1, p.N, p.D, p.H, p.W, p.Cout, e->amax_dev + slot, st));
+    for (auto it = e->recs.rbegin(); it != e->recs.rend(); ++it) if (it->fam == 0) { it->amax_slot = slot; break; }
+    return 0;
 }
 
-int amax_after(cs_engine* e, const struct ConvCall& c, hipStream_t st);
-
 constexpr int VOL32_MINB = 3;          // below three frames the plain volume convs stay on the halo kernel (see go())
-bool vol32_enabled() { static const bool on = [] { const char* s = getenv("CANONSWAP_VOL32"); return !s || atoi(s) != 0; }(); return on; }
+static bool vol32_enabled() { static const bool on = [] { const char* s = getenv("CANONSWAP_VOL32"); return !s || atoi(s) != 0; }(); return on; }
 // GroupNorm apply / hi-lo split of R's stage-3 blocks inside the consumer conv's staging (vol32 transform staging) instead of stand-alone
 // norm_act / split16 passes (CANONSWAP_VOL32_XF=0: A/B knob)
-bool vol32_xf() { static const bool on = [] { const char* s = getenv("CANONSWAP_VOL32_XF"); return !s || atoi(s) != 0; }(); return on && vol32_enabled(); }
+static bool vol32_xf() { static const bool on = [] { const char* s = getenv("CANONSWAP_VOL32_XF"); return !s || atoi(s) != 0; }(); return on && vol32_enabled(); }
 
 // Launch one convolution on conv_halo (LDS-staged input patch, register-streamed weights).
-int go(cs_engine* e, ConvCall& c, hipStream_t st, int prefW = 0, int prefH = 0)
+int go(cs_engine* e, ConvCall& c, hipStream_t st, int prefW, int prefH)
 {
     const int nph = c.p.nphase > 0 ? c.p.nphase : 1;      // grouped launch (ConvParams::nphase): macs_per_pos is one phase's
     const double fl = 2.0 * c.macs_per_pos * (double)c.p.N * c.p.D * c.p.H * c.p.W * nph;
@@ -386,50 +165,30 @@ int go(cs_engine* e, ConvCall& c, hipStream_t st, int prefW = 0, int prefH = 0)
         return amax_after(e, c, st);
     }
     if (c.p.inD == c.p.D) {
-        const int hcfg = c.hcfg >= 0 ? c.hcfg : pick_halo_cfg(c.p, c.mode);
-        const int BM = (hcfg == CFG_H_256x32 || hcfg == CFG_H_256x16 || hcfg == CFG_H_256x160 || hcfg == CFG_H_256x64) ? 256 : 128;
-        const bool is3d = c.p.KD > 1;
-        if (!prefW) { prefW = is3d ? 8 : 16; prefH = is3d ? 8 : BM / 16; }
-        set_tile(c.p, BM, prefW, prefH);
-        {   // positions covered by one wave in the epilogue -> partial-statistics blocks per sample
-            int wave_px = 64;      // waves that own 128 positions emit two partials (conv_epilogue.h, EP_SG)
-            if (hcfg == CFG_H_128x32 || hcfg == CFG_H_128x16 || hcfg == CFG_H_SK128x32) wave_px = 32;
-            c.stat_nblk = c.p.nTW * c.p.nTH * c.p.nTD * (BM / wave_px);
-        }
-        // SPADE convs run 32-channel chunks: their LDS image is then conflict-free at three workgroups per CU (conv_halo_kernel.h, halo_pad)
-        const bool spade_ck32 = c.mode == MODE_SPADE && c.p.Cout_pad % 256 != 0;
-        // (grouped input channels, ConvParams::cg: 32-channel chunks, except the 1x1 convs that ask for 64 - M's linear layers: a chunk's two
-        // halves lie side by side when cg is even; F's [W_hi | W_lo] convs keep their 32-channel chunks and with them their K order)
-        const bool k11 = c.p.KD == 1 && c.p.KH == 1 && c.p.KW == 1;
-        const bool cg64 = c.cg_ck64 && k11 && c.p.cg > 0 && !(c.p.cg & 1) && c.p.Cin % 64 == 0 && c.mode == MODE_STD;
-        const int ck = (!is3d && c.p.Cin % 64 == 0 && (c.p.cg == 0 || cg64) && !spade_ck32) ? 64 : 32;
-        c.p.xcd_map = XCD_MAP;
-        c.p.persist_total = HALO_PERSIST;
-        {   // cross-workgroup split-K when the launch cannot fill the chip (single-frame latency: the deep hourglass levels run 8-64
-            // workgroups that each stream megabytes of weights): plain bias + activation + one output only
-            // Split sums are added in another order than one workgroup's sequential accumulation, so results differ in the last
-            // bits from the batched path: the engine only does this in latency mode (cs_set_latency_mode), never silently by batch size -
-            // frames of a batch stay bit-identical to the same frames run alone.
-            const bool sk_on = e->latency_mode;
-            const int bn = hcfg == CFG_H_128x256 ? 256 : hcfg == CFG_H_128x128 ? 128 : hcfg == CFG_H_128x64 || hcfg == CFG_H_256x64 ? 64 :
-                           hcfg == CFG_H_128x160 || hcfg == CFG_H_256x160 ? 160 : hcfg == CFG_H_128x16 || hcfg == CFG_H_256x16 ? 16 : 32;
-            const long wgs = (long)c.p.nTW * c.p.nTH * c.p.nTD * c.p.nTN * (c.p.Cout_pad / bn);
-            const int nck = (c.p.Cin + ck - 1) / ck;
-            const long mtot = (long)c.p.N * c.p.D * c.p.H * c.p.W;
-            const bool plain = c.mode == MODE_STD && !c.p.res.p && !c.p.pixscale && !c.p.out1.p && !c.p.stat_out && !c.p.s2 &&
-                               c.p.act0 <= ACT_SIGMOID && c.p.out0.p && hcfg != CFG_H_SK128x32 && c.p.Cout % 4 == 0 && !c.p.spmul && !c.p.nphase &&
-                               (!c.p.pool_hw || (!c.p.out0_f32 && !(c.p.H & 1) && !(c.p.W & 1)));      // (pooled: the finishing launch averages)
-            constexpr int sk_maxwg = 64, sk_fill = 512;      // r02 sweep
-            if (sk_on && plain && wgs <= sk_maxwg && nck >= 4 && e->sk_buf) {
-                int splits = (int)(sk_fill / wgs);
-                if (splits > nck) splits = nck;
-                if (splits > 16) splits = 16;
-                while (splits > 1 && (size_t)splits * mtot * c.p.Cout_pad > e->sk_cap) --splits;
-                if (splits >= 2) {
-                    c.p.sk_out = e->sk_buf; c.p.sk_splits = splits; c.p.xcd_map = 0;
-                    TRY(e->run(0, st, [&] { return launch_conv_halo(c.p, hcfg, ck, c.mode, st); }, c.name, fl));
-                    return e->run(1, st, [&] { return launch_splitk_finish(c.p, st); }, "splitk_finish");
-                }
+        const HaloPlan plan = halo_plan(c.p, c.mode, c.hcfg, prefW, prefH, c.cg_ck64);      // (conv_plan.h: tile, chunk width, statistics blocks)
+        const int hcfg = plan.hcfg, ck = plan.ck;
+        c.stat_nblk = plan.stat_nblk;
+        // cross-workgroup split-K when the launch cannot fill the chip (single-frame latency: the deep hourglass levels run 8-64
+        // workgroups that each stream megabytes of weights): plain bias + activation + one output only
+        // Split sums are added in another order than one workgroup's sequential accumulation, so results differ in the last
+        // bits from the batched path: the engine only does this in latency mode (cs_set_latency_mode), never silently by batch size -
+        // frames of a batch stay bit-identical to the same frames run alone.
+        const long wgs = (long)c.p.nTW * c.p.nTH * c.p.nTD * c.p.nTN * (c.p.Cout_pad / halo_tile(hcfg).BN);
+        const int nck = (c.p.Cin + ck - 1) / ck;
+        const long mtot = (long)c.p.N * c.p.D * c.p.H * c.p.W;
+        const bool plain = c.mode == MODE_STD && !c.p.res.p && !c.p.pixscale && !c.p.out1.p && !c.p.stat_out && !c.p.s2 &&
+                           c.p.act0 <= ACT_SIGMOID && c.p.out0.p && hcfg != CFG_H_SK128x32 && c.p.Cout % 4 == 0 && !c.p.spmul && !c.p.nphase &&
+                           (!c.p.pool_hw || (!c.p.out0_f32 && !(c.p.H & 1) && !(c.p.W & 1)));      // (pooled: the finishing launch averages)
+        constexpr int sk_maxwg = 64, sk_fill = 512;      // r02 sweep
+        if (e->latency_mode && plain && wgs <= sk_maxwg && nck >= 4 && e->sk_buf) {
+            int splits = (int)(sk_fill / wgs);
+            if (splits > nck) splits = nck;
+            if (splits > 16) splits = 16;
+            while (splits > 1 && (size_t)splits * mtot * c.p.Cout_pad > e->sk_cap) --splits;
+            if (splits >= 2) {
+                c.p.sk_out = e->sk_buf; c.p.sk_splits = splits; c.p.xcd_map = 0;
+                TRY(e->run(0, st, [&] { return launch_conv_halo(c.p, hcfg, ck, c.mode, st); }, c.name, fl));
+                return e->run(1, st, [&] { return launch_splitk_finish(c.p, st); }, "splitk_finish");
             }
         }
         TRY(e->run(0, st, [&] { return launch_conv_halo(c.p, hcfg, ck, c.mode, st); }, c.name, fl));
@@ -439,30 +198,16 @@ int go(cs_engine* e, ConvCall& c, hipStream_t st, int prefW = 0, int prefH = 0)
     return -1;
 }
 
-float* stats_slot(cs_engine* e);
-
-// debug knob CANONSWAP_AMAX=1 (profiled steps only): largest |value| of the fp16 tensors this conv stored
-int amax_after(cs_engine* e, const ConvCall& c, hipStream_t st)
+static float* stats_slot(cs_engine* e)
 {
-    static const bool on = [] { const char* s = getenv("CANONSWAP_AMAX"); return s && atoi(s) != 0; }();
-    if (!on || !e->prof || e->recs.empty()) return 0;
-    if (!e->amax_dev) { if (e->alloc(&e->amax_dev, (size_t)4096)) return -1; }
-    if (e->amax_n >= 4096) return 0;
-    const ConvParams& p = c.p;
-    const bool o0 = p.out0.p && !p.out0_f32 && c.mode != MODE_PIXSHUF, o1 = p.out1.p != nullptr;
-    if (!o0 && !o1) return 0;
-    const int slot = e->amax_n++;
-    hipError_t r = hipMemsetAsync(e->amax_dev + slot, 0, sizeof(unsigned), st);
-    if (r != hipSuccess) { cs_set_error("amax memset: %s", hipGetErrorString(r)); return -1; }
-    if (o0) TRY(launch_absmax16((const half_t*)p.out0.p, p.out0, p.N, p.D, p.H, p.W, p.Cout, e->amax_dev + slot, st));
-    if (o1) TRY(launch_absmax16((const half_t*)p.out1.p, p.out1, p.N, p.D, p.H, p.W, p.Cout, e->amax_dev + slot, st));
-    for (auto it = e->recs.rbegin(); it != e->recs.rend(); ++it) if (it->fam == 0) { it->amax_slot = slot; break; }
-    return 0;
+    float* p = e->stats_pool + (e->stats_next % e->stats_slots) * e->stats_slot_floats;
+    e->stats_next++;
+    return p;
 }
 
 // Convolution whose epilogue also emits the Instance/GroupNorm partial sums of its stored output; returns the finished
 // (mean, rstd) slot. P = positions per sample.
-int go_stats(cs_engine* e, ConvCall& c, int C, long P, float** slot, hipStream_t st, int prefW = 0, int prefH = 0)
+static int go_stats(cs_engine* e, ConvCall& c, int C, long P, float** slot, hipStream_t st, int prefW = 0, int prefH = 0)
 {
     c.p.stat_out = e->stats_part;
     TRY(go(e, c, st, prefW, prefH));
@@ -473,15 +218,8 @@ int go_stats(cs_engine* e, ConvCall& c, int C, long P, float** slot, hipStream_t
     return e->run(1, st, [&] { return launch_chan_stats_finish(e->stats_part, nblk, N, C, 1.0 / (double)P, 1e-5f, s, st); }, "chan_stats_finish");
 }
 
-float* stats_slot(cs_engine* e)
-{
-    float* p = e->stats_pool + (e->stats_next % e->stats_slots) * e->stats_slot_floats;
-    e->stats_next++;
-    return p;
-}
-
 // (mean, rstd) per (n, c) of a [N][P][C] tensor into a fresh slot of the stats pool
-int do_stats(cs_engine* e, const void* x, int is_f32, int B, long P, int C, float** out, hipStream_t st)
+static int do_stats(cs_engine* e, const void* x, int is_f32, int B, long P, int C, float** out, hipStream_t st)
 {
     float* slot = stats_slot(e);
     *out = slot;
@@ -491,9 +229,9 @@ int do_stats(cs_engine* e, const void* x, int is_f32, int B, long P, int C, floa
 // ------------------------------------------------------------------------------------------------ F
 // AppearanceFeatureExtractor.forward (appearance_feature_extractor.py:38-48); result: fp32 HWDC in vs[*cur]
 // whole ResBlock3d per launch (vol32_fused.hip; CANONSWAP_VOL32_FUSED=0: A/B knob, two vol32 / conv_halo launches per block)
-bool vol32_fused_on() { static const bool on = [] { const char* s = getenv("CANONSWAP_VOL32_FUSED"); return !s || atoi(s) != 0; }(); return on && vol32_enabled(); }
+static bool vol32_fused_on() { static const bool on = [] { const char* s = getenv("CANONSWAP_VOL32_FUSED"); return !s || atoi(s) != 0; }(); return on && vol32_enabled(); }
 
-int run_resblocks3d(cs_engine* e, cs_engine::RB3* rb, int B, int* cur, hipStream_t st)
+static int run_resblocks3d(cs_engine* e, cs_engine::RB3* rb, int B, int* cur, hipStream_t st)
 {
     // util.py:94-102; a = relu(bn1(x)) is already in va[0]; x (fp32 residual stream) in vs[*cur]
     if (vol32_fused_on()) {      // at every batch size (one frame: 2-row segments, launch_vol32_fused); the same bits as the two-launch path below
@@ -545,7 +283,7 @@ static void wsplit_in(ConvCall& c, int cin_real)
     c.p.cg = cin_real / 32; c.p.cg_cin = cin_real; c.p.in_sG = 0;       // chunk j -> channels (j % cg) * 32 of the one input tensor
 }
 
-int run_F(cs_engine* e, int B, const float* img, int* cur, hipStream_t st)
+static int run_F(cs_engine* e, int B, const float* img, int* cur, hipStream_t st)
 {
     TRY(e->run(1, st, [&] { return launch_conv_first(img, e->first_w, e->first_b, e->f_t0, B, IMG, IMG, st); }, "conv_first"));
     e->flops += 2.0 * 3 * 64 * 9 * (double)B * IMG * IMG;
@@ -574,12 +312,12 @@ int run_F(cs_engine* e, int B, const float* img, int* cur, hipStream_t st)
 // and going through HBM as well would be 0.79 MB per frame and call for nothing - ADVICE r3).
 // warp_in / warp_o32 / warp_o16: when given, the feature warp that consumes the deformation (warping_network.py:46-62) is part of the softmax
 // kernel (dm_softmax_warp_kernel): the caller launches no grid_sample.
-bool warp_fused() { static const bool on = [] { const char* s = getenv("CANONSWAP_WARP_FUSED"); return !s || atoi(s) != 0; }(); return on; }
+static bool warp_fused() { static const bool on = [] { const char* s = getenv("CANONSWAP_WARP_FUSED"); return !s || atoi(s) != 0; }(); return on; }
 
 // CANONSWAP_DEC_PHASES_DEEP=0: A/B knob (up-blocks 0 - 2 of the hourglass as 27-tap convs on the up-sampled grid, the form of rounds 1-5)
 static bool dec_phases_deep() { static const bool on = [] { const char* s = getenv("CANONSWAP_DEC_PHASES_DEEP"); return !s || atoi(s) != 0; }(); return on; }
 
-int run_dense_motion(cs_engine* e, int B, const float* feat, const float* kp_d, const float* kp_s, hipStream_t st,
+static int run_dense_motion(cs_engine* e, int B, const float* feat, const float* kp_d, const float* kp_s, hipStream_t st,
                      const float* warp_in = nullptr, float* warp_o32 = nullptr, half_t* warp_o16 = nullptr, bool want_deform = false,
                      bool shared_feat = false, bool shared_kps = false)
 {
@@ -702,7 +440,7 @@ int run_dense_motion(cs_engine* e, int B, const float* feat, const float* kp_d, 
 }
 
 // warp_out (warping_network.py:64-71): vol16 = fp16 HWDC volume -> seg16 [B][64][64][256]
-int run_warp_out(cs_engine* e, int B, const half_t* vol16, const float* occ, hipStream_t st)
+static int run_warp_out(cs_engine* e, int B, const half_t* vol16, const float* occ, hipStream_t st)
 {
     ConvCall t3 = mk(e->w_third, vol16, hwdc2(nullptr), B, 1, 64, 64);
     t3.p.act0 = ACT_LRELU; t3.p.slope0 = 0.01f;
@@ -773,7 +511,7 @@ int t_layer(cs_engine* e, int layer, int B, const int* slots, bool mixed, const 
 // transfer_model2.forward (adaptive_modulate.py:522-554). x: fp32 vs[*cur] + fp16 copy va[0].
 // On exit: fp32 result in vs[*cur], fp16 copy in va[0].
 // slots: B host ints (identity slot per sample)
-int run_T(cs_engine* e, int B, const int* slots, int* cur, hipStream_t st)
+static int run_T(cs_engine* e, int B, const int* slots, int* cur, hipStream_t st)
 {
     bool mixed = false;
     TRY(t_slots(e, B, slots, &mixed, st));
@@ -795,14 +533,14 @@ int run_T(cs_engine* e, int B, const int* slots, int* cur, hipStream_t st)
 // weights [W_hi | W_lo | W_hi] (three 32-channel weight chunks, the hi halo staged once: ConvParams::hilo) the same fp16 MFMA kernel
 // computes W_hi x_hi + W_lo x_hi + W_hi x_lo, good to about 2^-21.  There is no switch: the plain fp16 form measured 49.5 dB on the worst
 // pool frame, below the 50 dB gate (round 6: the CANONSWAP_R_SPLIT knob is gone).
-TDesc hwdc3_split(void* p) { return td(p, VOL * 2, 64, (long)FW * FD * 64, (long)FD * 64); }
+static TDesc hwdc3_split(void* p) { return td(p, VOL * 2, 64, (long)FW * FD * 64, (long)FD * 64); }
 
 // Stage-3 blocks with the GroupNorm apply fused into the consumer convolution (vol32 transform staging, ConvParams::xf_*): per block
 //   conv1 reads  a0 = [block 0: x;  later: lrelu(gn2(y2') + x') of the previous block, written back as the new residual stream x]
 //   conv2 reads  a1 = lrelu(gn1(y1))
 // and one stand-alone norm_act closes the stage.  Five fp32-volume buffers rotate (vs[0..2] and the two split-precision buffers, which
 // this path does not use otherwise): a conv never writes a volume that it, or a neighbouring workgroup of the same launch, still reads.
-int run_stage3_xf(cs_engine* e, cs_engine::S3* blk, int B, int* cur, const Affine* last_pre, hipStream_t st)
+static int run_stage3_xf(cs_engine* e, cs_engine::S3* blk, int B, int* cur, const Affine* last_pre, hipStream_t st)
 {
     float* pool[5] = {e->vs[0], e->vs[1], e->vs[2], (float*)e->vsp[0], (float*)e->vsp[1]};
     auto pick = [&](std::initializer_list<const float*> busy) -> float* {
@@ -844,7 +582,7 @@ int run_stage3_xf(cs_engine* e, cs_engine::S3* blk, int B, int* cur, const Affin
     return 0;
 }
 
-int run_stage3(cs_engine* e, cs_engine::S3* blk, int B, int* cur, const Affine* last_pre, hipStream_t st)
+static int run_stage3(cs_engine* e, cs_engine::S3* blk, int B, int* cur, const Affine* last_pre, hipStream_t st)
 {
     if (vol32_xf()) return run_stage3_xf(e, blk, B, cur, last_pre, st);
     TRY(e->run(1, st, [&] { return launch_split16(e->vs[*cur], e->vsp[0], (long)B * VOL, st); }, "split16"));
@@ -875,7 +613,7 @@ int run_stage3(cs_engine* e, cs_engine::S3* blk, int B, int* cur, const Affine* 
     return 0;
 }
 
-int run_R(cs_engine* e, int B, int* cur, hipStream_t st)
+static int run_R(cs_engine* e, int B, int* cur, hipStream_t st)
 {
     TRY(run_stage3(e, e->r_s1, B, cur, &e->r_rb2[0].pre, st));
     for (int i = 0; i < 3; ++i) {   // ResBlock2d on the 512-channel view (util.py:120-128), LeakyReLU(0.01)
@@ -897,7 +635,7 @@ int run_R(cs_engine* e, int B, int* cur, hipStream_t st)
 
 // ------------------------------------------------------------------------------------------------ G
 // SPADEDecoder.forward (spade_generator.py:41-59). seg16: [B][64][64][256] fp16 -> img fp32 Bx3x512x512
-int spade_gb(cs_engine* e, const cs_engine::GB& gb, int C, const half_t* actv, int astride, int aoff, int B, int S,
+static int spade_gb(cs_engine* e, const cs_engine::GB& gb, int C, const half_t* actv, int astride, int aoff, int B, int S,
              const half_t* x, int xshift, const float* stats, int act, half_t* out, hipStream_t st)
 {
     // SPADE.forward (util.py:295-302): gamma/beta convs fused, modulation applied in the epilogue
@@ -918,7 +656,7 @@ int spade_gb(cs_engine* e, const cs_engine::GB& gb, int C, const half_t* actv, i
 //     conv_s(beta) = conv3x3(actv; W_s W_beta) + W_s b_beta      (one conv 128 -> fout, weights composed at load time, pack.py),
 // and only gamma has to be produced per input channel:  x_s = conv_s(IN(x)(1 + gamma)) + conv_s(beta).  Against the fused gamma/beta launch
 // this drops the 128 -> fin beta conv (half of it) for a 128 -> fout one: up_0 512 -> 256, up_1 256 -> 64 channels at 128^2 / 256^2.
-int spade_shortcut(cs_engine* e, const cs_engine::SpadeBlk& K, const half_t* actv, int astride, int aoff, int B, int S, const half_t* x,
+static int spade_shortcut(cs_engine* e, const cs_engine::SpadeBlk& K, const half_t* actv, int astride, int aoff, int B, int S, const half_t* x,
                    const float* stats, half_t* h, half_t* xs, hipStream_t st)
 {
     static const bool algebra = [] { const char* s = getenv("CANONSWAP_SHORTCUT_ALGEBRA"); return !s || atoi(s) != 0; }();
@@ -953,7 +691,7 @@ int spade_shortcut(cs_engine* e, const cs_engine::SpadeBlk& K, const half_t* act
     return go(e, cs, st);
 }
 
-int run_G(cs_engine* e, int B, const half_t* seg, float* img, hipStream_t st)
+static int run_G(cs_engine* e, int B, const half_t* seg, float* img, hipStream_t st)
 {
     ConvCall fc = mk(e->g_fc, seg, nhwc(nullptr, 64, 64, 256), B, 1, 64, 64);
     fc.p.out0 = nhwc(e->g_x[0], 64, 64, 512);
@@ -1069,23 +807,6 @@ int run_G(cs_engine* e, int B, const half_t* seg, float* img, hipStream_t st)
     return go(e, ci, st);
 }
 
-// Every entry point runs with the engine's device current and restores the caller's device on exit (the engine may be driven
-// from a thread whose current device is another GPU).
-struct DevGuard {
-    int prev = -1, dev;
-    explicit DevGuard(int d) : dev(d) { if (hipGetDevice(&prev) != hipSuccess) prev = -1; if (prev != dev) hipSetDevice(dev); }
-    ~DevGuard() { if (prev >= 0 && prev != dev) hipSetDevice(prev); }
-};
-#define ENTER(e, B) TRY(check(e, B)); DevGuard dev_guard_((e)->dev)
-
-int check(cs_engine* e, int B)
-{
-    if (!e) { cs_set_error("null engine"); return -1; }
-    if (!e->finalized) { cs_set_error("cs_finalize_weights has not been called"); return -1; }
-    if (B < 1 || B > e->maxB) { cs_set_error("batch %d outside [1, %d]", B, e->maxB); return -1; }
-    return 0;
-}
-
 // ------------------------------------------------------------------------------------------------ M
 // MotionExtractor.forward (motion_extractor.py:33-35 -> convnextv2.py:110-144): img fp32 NCHW 256x256 -> raw head outputs [B][328]
 // M's split-precision GEMMs: the activations are stored once as [hi | lo] (2 x creal channels per position) and read as the 3 x creal-channel
@@ -1096,22 +817,34 @@ static void msplit_in(ConvCall& c, int creal)
     c.cg_ck64 = true;
 }
 
-// M's three split-precision 1x1 conv forms on the stage with C channels and an H x H grid (the conv's own: the downsample's output grid);
-// run_M and cs_op_m_pointwise both build their launches here, so the operator test runs the engine's routing
-enum { M_PW1 = 0, M_PW2 = 1, M_DS = 2 };
-int m_pw2_cout_pad(int C) { return C % 64 ? (C + 127) / 128 * 128 : C; }
-static ConvCall m_pointwise(const ConvL& L, int form, const half_t* in, float* out, int B, int H, int C)
+// M's three split-precision 1x1 conv forms (engine.h) on the stage with C channels: Cin = 3 x the real input channels (C for pwconv1, 4 C for
+// pwconv2 and, after space-to-depth, for the down-sampling conv).
+// (pwconv2 of stage 0: 96 output channels in one 128-channel block - 128x128 tiles stage a position's 1152 input channels once; as three
+// 32-channel blocks on 128x32 tiles every block staged them again: 0.25 -> 0.17 ms per 64 frames; stage 1's 192 channels as two blocks instead of three 64-channel ones: 0.15 -> 0.16, not taken)
+ConvL m_pointwise_layer(int form, int C)
+{
+    ConvL L;
+    L.Cin = form == M_PW1 ? 3 * C : 12 * C;
+    L.Cout = form == M_PW1 ? 4 * C : form == M_PW2 ? C : 2 * C;
+    L.Cout_pad = form == M_PW2 && C % 64 ? (C + 127) / 128 * 128 : L.Cout;
+    L.macs_per_pos = (double)L.Cout * (L.Cin / 3);
+    return L;
+}
+
+// ... and their launch on an H x H grid (the conv's own: the downsample's output grid); run_M and cs_op_m_pointwise both build their launches here,
+// so the operator test runs the engine's routing
+ConvCall m_pointwise(const ConvL& L, int form, const half_t* in, float* out, int B, int H, int C)
 {
     const int creal = form == M_PW1 ? C : 4 * C;       // real channels of the split input
     ConvCall c = mk(L, in, nhwc(nullptr, H, H, 2 * creal), B, 1, H, H);
     msplit_in(c, creal);
-    c.p.out0 = nhwc(out, H, H, form == M_PW1 ? 4 * C : form == M_PW2 ? C : 2 * C); c.p.out0_f32 = 1;
+    c.p.out0 = nhwc(out, H, H, L.Cout); c.p.out0_f32 = 1;
     if (form == M_PW1) c.p.act0 = ACT_GELU;                                           // convnextv2.py:39-40
     if (form == M_PW2) { c.p.res = c.p.out0; c.p.res_f32 = 1; }                       // :42 + residual :45
     return c;
 }
 
-int run_M(cs_engine* e, int B, const float* img, float* out, hipStream_t st)
+static int run_M(cs_engine* e, int B, const float* img, float* out, hipStream_t st)
 {
     if (!e->has_m) { cs_set_error("the motion extractor weights (M.*) were not uploaded"); return -1; }
     if (!e->m_x) {   // workspace on first use
@@ -1150,16 +883,14 @@ int copy_dd(void* dst, const void* src, size_t bytes, hipStream_t st)
     return 0;
 }
 
-int to_hwdc(cs_engine* e, int B, const float* f, float* out32, half_t* out16, hipStream_t st)
+static int to_hwdc(cs_engine* e, int B, const float* f, float* out32, half_t* out16, hipStream_t st)
 {
     return e->run(1, st, [&] { return launch_ncdhw_to_hwdc(f, out32, out16, B, FC, FD, FH, FW, st); }, "ncdhw_to_hwdc");
 }
-int from_hwdc(cs_engine* e, int B, const float* in, float* out, hipStream_t st)
+static int from_hwdc(cs_engine* e, int B, const float* in, float* out, hipStream_t st)
 {
     return e->run(1, st, [&] { return launch_hwdc_to_ncdhw(in, out, B, FC, FD, FH, FW, st); }, "hwdc_to_ncdhw");
 }
-
-}  // namespace
 
 // =================================================================================================== C ABI
 extern "C" int cs_create(int device_id, int max_batch, cs_engine** out)
@@ -1181,9 +912,9 @@ extern "C" int cs_create(int device_id, int max_batch, cs_engine** out)
     for (int i = 0; i < 3; ++i) A(vs[i], B * VOL);
     for (int i = 0; i < 2; ++i) A(va[i], B * VOL);
     for (int i = 0; i < 2; ++i) A(vsp[i], B * VOL * 2);
-    A(dm_comp, B * VOX * 4);
+    A(dm_comp, B * DM_COMP_ELEMS);
     for (int i = 0; i < 6; ++i) A(dm_l[i], B * dm_level_elems(i));
-    A(dm_pre, B * VOX * 64); A(dm_pred, B * VOX * 144);
+    A(dm_pre, B * VOX * 64); A(dm_pred, B * DM_PRED_ELEMS);
     A(dm_logits, B * DM_LOGIT_FLOATS); A(dm_deform, B * VOX * 3); A(dm_occ, B * 4096);
     A(kpbuf, B * 21 * 3 * 2);
     A(w_t3, B * 4096 * 256); A(seg16, B * 4096 * 256);
@@ -1195,19 +926,13 @@ extern "C" int cs_create(int device_id, int max_batch, cs_engine** out)
     e->stats_slots = 48; e->stats_slot_floats = B * 512 * 2;
     A(stats_pool, e->stats_slots * e->stats_slot_floats);
     A(stats_part, B * 262144); A(dm_occpart, B * 4096 * 64);
-    for (int i = 0; i < 2; ++i) A(g_x[i], B * 4096 * 512);
-    A(g_h64, B * 4096 * 512); A(g_dx64, B * 4096 * 512); A(g_a64, B * 4096 * 1536);
-    A(g_a128, B * 16384 * 384); A(g_a256, B * 65536 * 384);
-    A(g_h128, B * 16384 * 512); A(g_xs128, B * 16384 * 256); A(g_dx128, B * 16384 * 256); A(g_h1_128, B * 16384 * 256);
-    A(g_o128, B * 16384 * 256);
-    A(g_h256, B * 65536 * 256); A(g_xs256, B * 65536 * 64); A(g_dx256, B * 65536 * 64); A(g_h1_256, B * 65536 * 64);
-    A(g_o256, B * 65536 * 64);
-    A(g_bs, B * 65536 * 64);
+    for (int which = CS_G_X0; which <= CS_G_O256; ++which)      // G's workspace (engine.h)
+        if (e->alloc(g_buf(e, which).p, B * g_buf(e, which).elems) != 0) { cs_destroy(e); return -1; }
     A(img_a, B * 3 * 512 * 512); A(img_b, B * 3 * 512 * 512);
 #undef A
     // the concat buffers carry zero pad channels that are never written: clear once
     CS_CHECK_HIP(hipMemset(e->dm_l[0], 0, B * dm_level_elems(0) * sizeof(half_t)));
-    CS_CHECK_HIP(hipMemset(e->dm_pred, 0, B * VOX * 144 * sizeof(half_t)));
+    CS_CHECK_HIP(hipMemset(e->dm_pred, 0, B * DM_PRED_ELEMS * sizeof(half_t)));
     *out = e;
     return 0;
 }
@@ -1246,6 +971,10 @@ extern "C" int cs_finalize_weights(cs_engine* e)
     e->has_m = e->find("M.stem.w") != nullptr;
     if (e->has_m) {
         static const int dims[4] = {96, 192, 384, 768}, depths[4] = {3, 3, 9, 3};
+        auto get_m = [&](const std::string& name, int form, int C, ConvL* L) -> int {      // a split-precision 1x1 conv (m_pointwise_layer)
+            const ConvL g = m_pointwise_layer(form, C);
+            return get_conv(e, name, g.Cin, g.Cout_pad, g.Cout, 1, 1, 1, g.Cout, g.macs_per_pos, L);
+        };
         TRY(get_f32(e, "M.stem.w", 48 * 96, &e->m_stem_w)); TRY(get_f32(e, "M.stem.b", 96, &e->m_stem_b));
         TRY(get_f32(e, "M.stem.ln.g", 96, &e->m_stem_g)); TRY(get_f32(e, "M.stem.ln.b", 96, &e->m_stem_be));
         for (int i = 0; i < 4; ++i) {
@@ -1259,16 +988,14 @@ extern "C" int cs_finalize_weights(cs_engine* e)
                 TRY(get_f32(e, q + ".dw.w", 49 * C, &K.dw_w)); TRY(get_f32(e, q + ".dw.b", C, &K.dw_b));
                 TRY(get_f32(e, q + ".ln.g", C, &K.ln_g)); TRY(get_f32(e, q + ".ln.b", C, &K.ln_b));
                 TRY(get_f32(e, q + ".grn.g", 4 * C, &K.grn_g)); TRY(get_f32(e, q + ".grn.b", 4 * C, &K.grn_b));
-                TRY(get_conv(e, q + ".pw1", 3 * C, 4 * C, 4 * C, 1, 1, 1, 4 * C, (double)C * 4 * C, &K.pw1));   // split-precision: 3 x Cin
-                // (stage 0: 96 output channels in one 128-channel block - 128x128 tiles stage a position's 1152 input channels once; as three
-                // 32-channel blocks on 128x32 tiles every block staged them again: 0.25 -> 0.17 ms per 64 frames; stage 1's 192 channels as two blocks instead of three 64-channel ones: 0.15 -> 0.16, not taken)
-                TRY(get_conv(e, q + ".pw2", 12 * C, m_pw2_cout_pad(C), C, 1, 1, 1, C, (double)C * 4 * C, &K.pw2));
+                TRY(get_m(q + ".pw1", M_PW1, C, &K.pw1));
+                TRY(get_m(q + ".pw2", M_PW2, C, &K.pw2));
             }
             if (i < 3) {
                 snprintf(n, sizeof n, "M.ds%d", i);
                 const std::string q(n);
                 TRY(get_f32(e, q + ".ln.g", C, &S.ds_g)); TRY(get_f32(e, q + ".ln.b", C, &S.ds_b));
-                TRY(get_conv(e, q, 12 * C, 2 * C, 2 * C, 1, 1, 1, 2 * C, (double)4 * C * 2 * C, &S.ds));
+                TRY(get_m(q, M_DS, C, &S.ds));
             }
         }
         TRY(get_f32(e, "M.norm.g", 768, &e->m_norm_g)); TRY(get_f32(e, "M.norm.b", 768, &e->m_norm_b));
@@ -1537,19 +1264,18 @@ extern "C" int cs_set_identity(cs_engine* e, int slot, const float* id, void* st
     if (slot < 0 || slot >= MAX_SLOTS) { cs_set_error("cs_set_identity: slot %d outside [0, %d)", slot, MAX_SLOTS); return -1; }
     hipStream_t st = (hipStream_t)stream;
     DevGuard guard(e->dev);
-    const size_t fused_elems = (size_t)(512 / 32) * 9 * 1024 * 32;       // packed [kstep][1024 rows][32]
     for (int i = 0; i < 14; ++i) {
         TLayer& L = e->t_l[i];
         if (!L.wset[slot]) {     // first use of this slot: own buffer for the fused [W; w_mod] rows
             half_t* w = nullptr;
-            TRY(e->alloc(&w, fused_elems));
+            TRY(e->alloc(&w, T_FUSED_ELEMS));
             L.wset[slot] = w;
             const long ofs = w - L.wset[0];
             CS_CHECK_HIP(hipMemcpy(L.wofs + slot, &ofs, sizeof(long), hipMemcpyHostToDevice));
         }
         // the shared W rows come from slot 0's blob: copied on the slot's first use AND after every cs_finalize_weights (a new
         // checkpoint clears slot_set; an old copy would pair the previous W rows with the new w_mod rows - ADVICE r2)
-        if (slot != 0 && !e->slot_set[slot]) TRY(copy_dd(L.wset[slot], L.wset[0], fused_elems * sizeof(half_t), st));
+        if (slot != 0 && !e->slot_set[slot]) TRY(copy_dd(L.wset[slot], L.wset[0], T_FUSED_ELEMS * sizeof(half_t), st));
         TRY(e->run(1, st, [&] { return launch_t_style(id, L.fc, e->style + i * 512, 1, st); }, "t_style"));
         TRY(e->run(1, st, [&] { return launch_t_modulate(L.raw, e->style + i * 512, L.wset[slot], i, st); }, "t_modulate"));
     }
@@ -1723,355 +1449,6 @@ extern "C" int cs_animate_frames(cs_engine* e, int B, const float* f, int nf, co
     return 0;
 }
 
-// ---- image-space steps around the generator
-static int soft_erosion_impl(cs_engine* e, int B, int H, int W, const void* mask, int mask_u8, const float* w, int ksize, float thr, int iters,
-                             float* soft_out, uint8_t* hard_out, int per_sample, void* stream, const char* who)
-{
-    if (!e || !mask || !w || !soft_out || B < 1 || H < 1 || W < 1) { cs_set_error("%s: bad arguments", who); return -1; }
-    if (B > 65535 || H > 65535 * 32) { cs_set_error("%s: %d x %d x %d exceeds the launch grid", who, B, H, W); return -1; }      // grid (W/64, H/32, B)
-    DevGuard guard(e->dev);
-    const size_t need = (size_t)B * H * W, need_part = (size_t)64 * B;      // launch_soft_erosion: 64 partial maxima per sample
-    // grow-only scratch; buffers of earlier sizes stay owned by the engine until cs_destroy
-    if (need > e->se_cap) {
-        if (e->alloc(&e->se_a, need) || e->alloc(&e->se_b, need)) return -1;
-        e->se_cap = need;
-    }
-    if (need_part > e->se_part_cap) {
-        if (e->alloc(&e->se_part, need_part)) return -1;
-        e->se_part_cap = need_part;
-    }
-    hipStream_t st = (hipStream_t)stream;
-    return e->run(1, st, [&] { return launch_soft_erosion(mask, mask_u8, e->se_a, e->se_b, w, e->se_part, soft_out, hard_out, B, H, W, ksize, thr, iters,
-                                                          per_sample, st); }, "soft_erosion");
-}
-
-extern "C" int cs_soft_erosion(cs_engine* e, int B, int H, int W, const float* mask, const float* w, int ksize, float thr, int iters,
-                               float* soft_out, uint8_t* hard_out, void* stream)
-{
-    return soft_erosion_impl(e, B, H, W, mask, 0, w, ksize, thr, iters, soft_out, hard_out, 0, stream, "cs_soft_erosion");
-}
-
-extern "C" int cs_soft_erosion_frames(cs_engine* e, int B, int H, int W, const void* masks, int masks_u8, const float* w, int ksize, float thr,
-                                      int iters, float* soft_out, uint8_t* hard_out, void* stream)
-{
-    return soft_erosion_impl(e, B, H, W, masks, masks_u8 != 0, w, ksize, thr, iters, soft_out, hard_out, 1, stream, "cs_soft_erosion_frames");
-}
-
-extern "C" int cs_prepare_crops(cs_engine* e, int B, const uint8_t* crops, int Hc, int Wc, float* out, void* stream)
-{
-    if (!e || !crops || !out || B < 1) { cs_set_error("cs_prepare_crops: bad arguments"); return -1; }
-    if (!((Hc == 256 && Wc == 256) || (Hc == 512 && Wc == 512))) {
-        cs_set_error("cs_prepare_crops: crops must be 256x256 or 512x512 (got %dx%d)", Hc, Wc);
-        return -1;
-    }
-    DevGuard guard(e->dev);
-    hipStream_t st = (hipStream_t)stream;
-    return e->run(1, st, [&] { return launch_prepare_crops(crops, out, B, Hc, Wc, Hc / 256, st); }, "prepare_crops");
-}
-
-extern "C" int cs_warp_affine_u8(cs_engine* e, const uint8_t* src, int Hs, int Ws, const double M[6], uint8_t* dst, int Hd, int Wd, void* stream)
-{
-    if (!e || !src || !dst || !M || Hs < 1 || Ws < 1 || Hd < 1 || Wd < 1) { cs_set_error("cs_warp_affine_u8: bad arguments"); return -1; }
-    DevGuard guard(e->dev);
-    hipStream_t st = (hipStream_t)stream;
-    return e->run(1, st, [&] { return launch_paste(src, nullptr, nullptr, Hs, Ws, M, nullptr, dst, Hd, Wd, st); }, "warp_affine_u8");
-}
-
-extern "C" int cs_warp_affine_f32(cs_engine* e, const float* src, int Hs, int Ws, const double M[6], float* dst, int Hd, int Wd, void* stream)
-{
-    if (!e || !src || !dst || !M || Hs < 1 || Ws < 1 || Hd < 1 || Wd < 1) { cs_set_error("cs_warp_affine_f32: bad arguments"); return -1; }
-    DevGuard guard(e->dev);
-    hipStream_t st = (hipStream_t)stream;
-    return e->run(1, st, [&] { return launch_warp_f32(src, Hs, Ws, M, dst, Hd, Wd, st); }, "warp_affine_f32");
-}
-
-extern "C" int cs_paste_back(cs_engine* e, const uint8_t* crop, const float* mask_crop, const float* mask_ori, int Hc, int Wc,
-                             const double M_c2o[6], const uint8_t* img_ori, uint8_t* out, int Ho, int Wo, void* stream)
-{
-    if (!e || !crop || !M_c2o || !img_ori || !out || Hc < 1 || Wc < 1 || Ho < 1 || Wo < 1) { cs_set_error("cs_paste_back: bad arguments"); return -1; }
-    if ((mask_crop != nullptr) == (mask_ori != nullptr)) { cs_set_error("cs_paste_back: pass exactly one of mask_crop / mask_ori"); return -1; }
-    DevGuard guard(e->dev);
-    hipStream_t st = (hipStream_t)stream;
-    return e->run(1, st, [&] { return launch_paste(crop, mask_crop, mask_ori, Hc, Wc, M_c2o, img_ori, out, Ho, Wo, st); }, "paste_back");
-}
-
-extern "C" int cs_paste_back_batch(cs_engine* e, int B, const uint8_t* crops, const float* masks_crop, int Hc, int Wc, const double* M_c2o,
-                                   const uint8_t* imgs_ori, uint8_t* out, int Ho, int Wo, void* stream)
-{
-    if (!e || !crops || !masks_crop || !M_c2o || !imgs_ori || !out || B < 1 || Hc < 1 || Wc < 1 || Ho < 1 || Wo < 1) {
-        cs_set_error("cs_paste_back_batch: bad arguments");
-        return -1;
-    }
-    DevGuard guard(e->dev);
-    hipStream_t st = (hipStream_t)stream;
-    return e->run(1, st, [&] { return launch_paste_batch(crops, masks_crop, Hc, Wc, M_c2o, imgs_ori, out, B, Ho, Wo, st); }, "paste_back_batch");
-}
-
-extern "C" int cs_motion_keypoints(cs_engine* e, int B, const float* raw, float* x_t, float* x_can, float* rot, void* stream)
-{
-    if (!e || !raw || !x_t || !x_can || B < 1) { cs_set_error("cs_motion_keypoints: bad arguments"); return -1; }
-    DevGuard guard(e->dev);
-    hipStream_t st = (hipStream_t)stream;
-    return e->run(1, st, [&] { return launch_m_keypoints(raw, x_t, x_can, rot, B, st); }, "m_keypoints");
-}
-
-// ---- the device-side frame of the video-to-image pipeline around cs_animate_frames (can_swap_pipeline_v2i.py:285-321)
-extern "C" int cs_resize_half_bilinear(cs_engine* e, int B, int C, const float* img, int H, int W, float* out, void* stream)
-{
-    if (!e || !img || !out || B < 1 || C < 1 || H < 2 || W < 2) { cs_set_error("cs_resize_half_bilinear: bad arguments"); return -1; }
-    if (H % 2 || W % 2) { cs_set_error("cs_resize_half_bilinear: H and W must be even (got %dx%d)", H, W); return -1; }
-    DevGuard guard(e->dev);
-    hipStream_t st = (hipStream_t)stream;
-    return e->run(1, st, [&] { return launch_resize_half(img, out, (long)B * C, H, W, st); }, "resize_half");
-}
-
-extern "C" int cs_motion_keypoints_driven(cs_engine* e, int B, const float* raw_driving, const float* raw_pose, const float* kp, float* x_t,
-                                          void* stream)
-{
-    if (!e || !raw_driving || !raw_pose || !kp || !x_t || B < 1) { cs_set_error("cs_motion_keypoints_driven: bad arguments"); return -1; }
-    DevGuard guard(e->dev);
-    hipStream_t st = (hipStream_t)stream;
-    return e->run(1, st, [&] { return launch_m_keypoints_driven(raw_driving, raw_pose, kp, x_t, B, st); }, "m_keypoints_driven");
-}
-
-extern "C" int cs_paste_back_shared(cs_engine* e, int B, const uint8_t* crops, int Hc, int Wc, const float* mask_ori, const double M_c2o[6],
-                                    const uint8_t* img_ori, uint8_t* out, int Ho, int Wo, void* stream)
-{
-    if (!e || !crops || !mask_ori || !M_c2o || !img_ori || !out || B < 1 || Hc < 1 || Wc < 1 || Ho < 1 || Wo < 1) {
-        cs_set_error("cs_paste_back_shared: bad arguments");
-        return -1;
-    }
-    // 32-bit byte offsets inside one crop; eight frames per grid row
-    if ((long)Hc * Wc * 3 >= (1L << 31) || B > 65535 * 8) { cs_set_error("cs_paste_back_shared: crop %dx%d or B = %d exceeds the kernel's limits", Hc, Wc, B); return -1; }
-    DevGuard guard(e->dev);
-    hipStream_t st = (hipStream_t)stream;
-    return e->run(1, st, [&] { return launch_paste_shared(crops, Hc, Wc, mask_ori, M_c2o, img_ori, out, B, Ho, Wo, st); }, "paste_back_shared");
-}
-
-// ---- the crop in front of both chains (crop.py:429-455 per frame, cropper.py:196-209)
-extern "C" int cs_crop_frames(cs_engine* e, int B, const uint8_t* frames, int Ho, int Wo, const double* M_o2c, int dsize, uint8_t* crops, float* I_out,
-                              void* stream)
-{
-    if (!e || !frames || !M_o2c || !crops || B < 1 || Ho < 1 || Wo < 1) { cs_set_error("cs_crop_frames: bad arguments"); return -1; }
-    if (dsize < 4 || dsize % 4 || dsize > 16384) { cs_set_error("cs_crop_frames: dsize %d (a multiple of 4 from 4 to 16384)", dsize); return -1; }
-    if (I_out && dsize != 256 && dsize != 512) { cs_set_error("cs_crop_frames: I_out goes with dsize 256 or 512 (got %d)", dsize); return -1; }
-    DevGuard guard(e->dev);
-    hipStream_t st = (hipStream_t)stream;
-    return e->run(1, st, [&] { return launch_crop_batch(frames, Ho, Wo, M_o2c, nullptr, dsize, crops, I_out, B, st); }, "crop_frames");
-}
-
-// ---- several faces per frame: face b is cut from, and pasted into, frame frame_index[b]
-// frame_index: B host ints, non-decreasing, in [0, F).  Sets the error and returns nonzero otherwise; nothing has been launched then.
-static int check_frame_index(const char* who, const int* frame_index, int B, int F)
-{
-    for (int b = 0; b < B; ++b) {
-        if (frame_index[b] < 0 || frame_index[b] >= F) {
-            cs_set_error("%s: frame_index[%d] = %d outside [0, %d)", who, b, frame_index[b], F);
-            return -1;
-        }
-        if (b && frame_index[b] < frame_index[b - 1]) {
-            cs_set_error("%s: frame_index decreases at %d (%d after %d): the faces of a frame are contiguous, frames in order", who, b, frame_index[b],
-                         frame_index[b - 1]);
-            return -1;
-        }
-    }
-    return 0;
-}
-
-extern "C" int cs_crop_faces(cs_engine* e, int B, int F, const uint8_t* frames, int Ho, int Wo, const int* frame_index, const double* M_o2c,
-                             int dsize, uint8_t* crops, float* I_out, void* stream)
-{
-    if (!e || !frames || !frame_index || !M_o2c || !crops || B < 1 || F < 1 || Ho < 1 || Wo < 1) {
-        cs_set_error("cs_crop_faces: bad arguments (B = %d faces, F = %d frames)", B, F);
-        return -1;
-    }
-    if (dsize < 4 || dsize % 4 || dsize > 16384) { cs_set_error("cs_crop_faces: dsize %d (a multiple of 4 from 4 to 16384)", dsize); return -1; }
-    if (I_out && dsize != 256 && dsize != 512) { cs_set_error("cs_crop_faces: I_out goes with dsize 256 or 512 (got %d)", dsize); return -1; }
-    if (check_frame_index("cs_crop_faces", frame_index, B, F)) return -1;
-    DevGuard guard(e->dev);
-    hipStream_t st = (hipStream_t)stream;
-    return e->run(1, st, [&] { return launch_crop_batch(frames, Ho, Wo, M_o2c, frame_index, dsize, crops, I_out, B, st); }, "crop_faces");
-}
-
-extern "C" int cs_paste_back_faces(cs_engine* e, int B, int F, const uint8_t* crops, const float* masks_crop, int Hc, int Wc, const int* frame_index,
-                                   const double* M_c2o, const uint8_t* imgs_ori, uint8_t* out, int Ho, int Wo, void* stream)
-{
-    // B == 0: no face at all, the frames are copied; crops, masks, index and matrices are then not read and may be NULL
-    if (!e || !imgs_ori || !out || B < 0 || F < 1 || Ho < 1 || Wo < 1 || (B > 0 && (!crops || !masks_crop || !frame_index || !M_c2o || Hc < 1 || Wc < 1))) {
-        cs_set_error("cs_paste_back_faces: bad arguments (B = %d faces, F = %d frames)", B, F);
-        return -1;
-    }
-    if (check_frame_index("cs_paste_back_faces", frame_index, B, F)) return -1;
-    DevGuard guard(e->dev);
-    hipStream_t st = (hipStream_t)stream;
-    return e->run(1, st, [&] { return launch_paste_faces(crops, masks_crop, Hc, Wc, M_c2o, frame_index, imgs_ori, out, B, F, Ho, Wo, st); },
-                  "paste_back_faces");
-}
-
-// ---- the face mask from the parser's logits (can_swap_pipeline_e2e.py:183-190, can_swap_pipeline_v2i.py:76-83)
-extern "C" int cs_face_masks(cs_engine* e, int B, int C, const float* logits, int h, int w, int scale, uint32_t valid_bits, uint8_t* masks,
-                             uint8_t* labels, void* stream)
-{
-    if (!e || !logits) { cs_set_error("cs_face_masks: bad arguments"); return -1; }
-    if (scale != 1 && scale != 2 && scale != 4) { cs_set_error("cs_face_masks: scale %d (1, 2 and 4 are built)", scale); return -1; }
-    if (C < 1 || C > 32) { cs_set_error("cs_face_masks: %d classes outside [1, 32]", C); return -1; }
-    if (B < 1 || h < 1 || w < 1) { cs_set_error("cs_face_masks: B = %d, h = %d, w = %d (each at least 1)", B, h, w); return -1; }
-    if (!masks && !labels) { cs_set_error("cs_face_masks: both outputs are NULL"); return -1; }
-    DevGuard guard(e->dev);
-    hipStream_t st = (hipStream_t)stream;
-    return e->run(1, st, [&] { return launch_face_masks(logits, B, C, h, w, scale, valid_bits, masks, labels, st); }, "face_masks");
-}
-
-// ---- the parser's input (can_swap_pipeline_e2e.py:171 + :180, can_swap_pipeline_v2i.py:73): everything is refused before any launch
-extern "C" int cs_parser_input(cs_engine* e, int B, const uint8_t* crops, int Hc, int Wc, int halve, const float* lut, float* pixel_values,
-                               uint8_t* resized_u8, void* stream)
-{
-    if (!e || !crops || !lut) { cs_set_error("cs_parser_input: NULL %s", !e ? "engine" : !crops ? "crops" : "lut"); return -1; }
-    if (!pixel_values && !resized_u8) { cs_set_error("cs_parser_input: both outputs are NULL"); return -1; }
-    if (B < 1 || Hc < 1 || Wc < 1) { cs_set_error("cs_parser_input: B = %d, Hc = %d, Wc = %d (each at least 1)", B, Hc, Wc); return -1; }
-    if (halve != 0 && halve != 1) { cs_set_error("cs_parser_input: halve %d (0 or 1)", halve); return -1; }
-    if (halve && ((Hc | Wc) & 1)) { cs_set_error("cs_parser_input: %dx%d crops cannot be halved (odd size)", Hc, Wc); return -1; }
-    const long Ho = halve ? Hc : 2L * Hc, Wo = halve ? Wc : 2L * Wc;
-    if (Ho > 16384 || Wo > 16384) { cs_set_error("cs_parser_input: output %ldx%ld above 16384 a side", Ho, Wo); return -1; }
-    DevGuard guard(e->dev);
-    hipStream_t st = (hipStream_t)stream;
-    return e->run(1, st, [&] { return launch_parser_input(crops, B, Hc, Wc, halve, lut, pixel_values, resized_u8, st); }, "parser_input");
-}
-
-// ---- the side-by-side video frame (src/utils/video.py:84-109; can_swap_pipeline_e2e.py:290, can_swap_pipeline_v2i.py:328): everything is refused
-// before any launch
-extern "C" int cs_concat_frames(cs_engine* e, int B, int P, int S, const void* const* panels, const int* kinds, const int* shared, uint8_t* out,
-                                void* stream)
-{
-    if (!e || !out || !panels || !kinds || !shared) {
-        cs_set_error("cs_concat_frames: NULL %s", !e ? "engine" : !out ? "out" : !panels ? "panels" : !kinds ? "kinds" : "shared");
-        return -1;
-    }
-    if (B < 1) { cs_set_error("cs_concat_frames: B = %d (at least 1)", B); return -1; }
-    if (P < 1 || P > 4) { cs_set_error("cs_concat_frames: P = %d (1 to 4 panels)", P); return -1; }
-    if (S < 4 || S % 4 || S > 16384) { cs_set_error("cs_concat_frames: S = %d (a multiple of 4 from 4 to 16384)", S); return -1; }
-    for (int p = 0; p < P; ++p) {
-        if (kinds[p] < 0 || kinds[p] > 3) { cs_set_error("cs_concat_frames: kind %d of panel %d (0 to 3)", kinds[p], p); return -1; }
-        if (!panels[p]) { cs_set_error("cs_concat_frames: NULL panel %d", p); return -1; }
-    }
-    DevGuard guard(e->dev);
-    hipStream_t st = (hipStream_t)stream;
-    return e->run(1, st, [&] { return launch_concat_frames(panels, kinds, shared, B, P, S, out, st); }, "concat_frames");
-}
-
-// ---- the face detector's input (scrfd.py:224-235, :154) and decode (scrfd.py:160-218, :239-303): everything is refused before any launch
-extern "C" int cs_det_input(cs_engine* e, int F, const uint8_t* frames, int Ho, int Wo, int Hd, int Wd, int swap_rb, const float* lut, float* blob,
-                            void* stream)
-{
-    if (!e || !frames || !lut || !blob) {
-        cs_set_error("cs_det_input: NULL %s", !e ? "engine" : !frames ? "frames" : !lut ? "lut" : "blob");
-        return -1;
-    }
-    if (F < 1 || Ho < 1 || Wo < 1) { cs_set_error("cs_det_input: F = %d, Ho = %d, Wo = %d (each at least 1)", F, Ho, Wo); return -1; }
-    if (Hd < 1 || Wd < 1 || Hd > 16384 || Wd > 16384) { cs_set_error("cs_det_input: det size %dx%d (Hd x Wd) outside [1, 16384] a side", Hd, Wd); return -1; }
-    int nh, nw;
-    det_letterbox(Ho, Wo, Hd, Wd, &nh, &nw);
-    if (nh < 1 || nw < 1) { cs_set_error("cs_det_input: a %dx%d frame resizes to %dx%d inside %dx%d (empty)", Ho, Wo, nh, nw, Hd, Wd); return -1; }
-    DevGuard guard(e->dev);
-    hipStream_t st = (hipStream_t)stream;
-    return e->run(1, st, [&] { return launch_det_input(frames, F, Ho, Wo, Hd, Wd, swap_rb != 0, lut, blob, st); }, "det_input");
-}
-
-extern "C" int cs_det_decode(cs_engine* e, int F, int n_levels, const int* strides, int num_anchors, const void* const* outs, int Hd, int Wd,
-                             float det_scale, float det_thresh, float nms_thresh, int max_num, int metric_max, int Ho, int Wo, int max_faces,
-                             float* det, float* kps, int* count, void* stream)
-{
-    if (!e || !strides || !outs || !det || !count) {
-        cs_set_error("cs_det_decode: NULL %s", !e ? "engine" : !strides ? "strides" : !outs ? "outs" : !det ? "det" : "count");
-        return -1;
-    }
-    static const int S5[5] = {8, 16, 32, 64, 128};
-    bool layout = (n_levels == 3 && num_anchors == 2) || (n_levels == 5 && num_anchors == 1);
-    for (int l = 0; layout && l < n_levels; ++l) layout = strides[l] == S5[l];
-    if (!layout) {
-        cs_set_error("cs_det_decode: layout of %d levels with %d anchors is not 3 levels (8, 16, 32) x 2 or 5 levels (8 .. 128) x 1", n_levels, num_anchors);
-        return -1;
-    }
-    if (F < 1 || Ho < 1 || Wo < 1) { cs_set_error("cs_det_decode: F = %d, Ho = %d, Wo = %d (each at least 1)", F, Ho, Wo); return -1; }
-    if (Hd < 1 || Wd < 1 || Hd > 16384 || Wd > 16384) { cs_set_error("cs_det_decode: det size %dx%d (Hd x Wd) outside [1, 16384] a side", Hd, Wd); return -1; }
-    if (max_faces < 1 || max_faces > CS_DET_MAX_FACES) { cs_set_error("cs_det_decode: max_faces %d outside [1, %d]", max_faces, CS_DET_MAX_FACES); return -1; }
-    if (max_num < 0 || max_num > max_faces) { cs_set_error("cs_det_decode: max_num %d outside [0, max_faces = %d]", max_num, max_faces); return -1; }
-    if (!(det_scale > 0.f) || det_scale > 3.0e38f) { cs_set_error("cs_det_decode: det_scale %g is not a positive finite number", (double)det_scale); return -1; }
-    if (det_thresh != det_thresh || nms_thresh != nms_thresh) { cs_set_error("cs_det_decode: a threshold is NaN"); return -1; }
-    int nk = 0;
-    for (int l = 0; l < n_levels; ++l) {
-        if (!outs[l] || !outs[n_levels + l]) { cs_set_error("cs_det_decode: NULL %s pointer of level %d", !outs[l] ? "score" : "bbox", l); return -1; }
-        nk += outs[2 * n_levels + l] != nullptr;
-    }
-    if (nk != 0 && nk != n_levels) { cs_set_error("cs_det_decode: %d of %d kps pointers are NULL (all or none)", n_levels - nk, n_levels); return -1; }
-    if (kps && !nk) { cs_set_error("cs_det_decode: kps output given without kps pointers in outs"); return -1; }
-    DevGuard guard(e->dev);
-    hipStream_t st = (hipStream_t)stream;
-    return e->run(1, st, [&] {
-        return launch_det_decode(F, n_levels, strides, num_anchors, outs, Hd, Wd, det_scale, det_thresh, nms_thresh, max_num, metric_max != 0, Ho, Wo,
-                                 max_faces, det, kps, count, st);
-    }, "det_decode");
-}
-
-// ---- getid on the engine (can_swap_e2e.py:102-107): nearest resize to 112 x 112, the ArcFace network, L2 normalisation.  Everything is refused
-// before any launch; more than the workspace's images run as several passes.
-static int identity_impl(cs_engine* e, const char* who, int B, const float* img, const uint8_t* u8, const float* lut, int H, int W, float* id_out,
-                         float* raw_out, void* stream)
-{
-    if (!e) { cs_set_error("%s: NULL engine", who); return -1; }
-    if (!e->finalized) { cs_set_error("%s: cs_finalize_weights has not been called", who); return -1; }
-    if (!e->idn.present) { cs_set_error("%s: the engine holds no identity network (no 'A.*' blobs: pass the 'arcface' state-dict)", who); return -1; }
-    if (B < 1 || B > e->maxB) { cs_set_error("%s: batch %d outside [1, %d]", who, B, e->maxB); return -1; }
-    if (!img && !u8) { cs_set_error("%s: NULL input", who); return -1; }
-    if (u8 && !lut) { cs_set_error("%s: NULL lut", who); return -1; }
-    if (H < 1 || W < 1 || H > 16384 || W > 16384) { cs_set_error("%s: H = %d, W = %d (each from 1 to 16384)", who, H, W); return -1; }
-    if (!id_out && !raw_out) { cs_set_error("%s: both outputs are NULL", who); return -1; }
-    DevGuard guard(e->dev);
-    hipStream_t st = (hipStream_t)stream;
-    IdNet& A = e->idn;
-    for (int b0 = 0; b0 < B; b0 += A.cap) {
-        const int nb = B - b0 < A.cap ? B - b0 : A.cap;
-        const size_t ofs = (size_t)b0 * 3 * H * W;
-        TRY(e->run(1, st, [&] { return launch_id_input(img ? img + ofs : nullptr, u8 ? u8 + ofs : nullptr, lut, A.in16, nb, H, W, st); }, "id_input"));
-        TRY(e->run(1, st, [&] { return idnet_forward(A, nb, id_out ? id_out + (size_t)b0 * 512 : nullptr, raw_out ? raw_out + (size_t)b0 * 512 : nullptr, st); },
-                   "identity"));
-    }
-    return 0;
-}
-
-extern "C" int cs_identity(cs_engine* e, int B, const float* img, int H, int W, float* id_out, float* raw_out, void* stream)
-{
-    return identity_impl(e, "cs_identity", B, img, nullptr, nullptr, H, W, id_out, raw_out, stream);
-}
-
-extern "C" int cs_identity_u8(cs_engine* e, int B, const uint8_t* crops, int H, int W, const float* lut, float* id_out, float* raw_out, void* stream)
-{
-    return identity_impl(e, "cs_identity_u8", B, nullptr, crops, lut, H, W, id_out, raw_out, stream);
-}
-
-// ---- the SegFormer face parser on the engine (can_swap_pipeline_e2e.py:178-182: model(pixel_values).logits): pixel_values fp32 NCHW -> logits fp32
-// [B][L][H / 4][W / 4].  Everything is refused before any launch; more than the workspace's images run as several passes.
-extern "C" int cs_parser(cs_engine* e, int B, const float* pixel_values, int H, int W, float* logits_out, void* stream)
-{
-    if (!e) { cs_set_error("cs_parser: NULL engine"); return -1; }
-    if (!e->finalized) { cs_set_error("cs_parser: cs_finalize_weights has not been called"); return -1; }
-    if (!e->psr.present) { cs_set_error("cs_parser: the engine holds no face parser (no 'P.*' blobs: pass the 'parser' state-dict)"); return -1; }
-    if (B < 1 || B > e->maxB) { cs_set_error("cs_parser: batch %d outside [1, %d]", B, e->maxB); return -1; }
-    if (!pixel_values || !logits_out) { cs_set_error("cs_parser: NULL pointer"); return -1; }
-    ParserNet& P = e->psr;
-    if (H < 32 || W < 32 || H % 32 || W % 32) { cs_set_error("cs_parser: H = %d, W = %d (each a multiple of 32)", H, W); return -1; }
-    if ((long)H * W > (long)P.maxH * P.maxW) { cs_set_error("cs_parser: %d x %d exceeds the workspace's %d x %d", H, W, P.maxH, P.maxW); return -1; }
-    if ((H / 32) * (W / 32) > 256) { cs_set_error("cs_parser: %d keys per stage (at most 256: inputs up to 512 x 512)", (H / 32) * (W / 32)); return -1; }
-    DevGuard guard(e->dev);
-    hipStream_t st = (hipStream_t)stream;
-    for (int b0 = 0; b0 < B; b0 += P.cap) {
-        const int nb = B - b0 < P.cap ? B - b0 : P.cap;
-        TRY(e->run(1, st, [&] { return launch_p_input(pixel_values + (size_t)b0 * 3 * H * W, P.in16, nb, H, W, st); }, "parser_input16"));
-        TRY(e->run(1, st, [&] { return parser_forward(P, nb, H, W, logits_out + (size_t)b0 * P.L * (H / 4) * (W / 4), st); }, "parser"));
-    }
-    return 0;
-}
-
 extern "C" int cs_profile_begin(cs_engine* e)
 {
     if (!e) { cs_set_error("null engine"); return -1; }
@@ -2118,381 +1495,4 @@ extern "C" int cs_profile_exec_flops(cs_engine* e, double* flops)
     if (!e || !flops) { cs_set_error("cs_profile_exec_flops: bad arguments"); return -1; }
     *flops = e->flops_exec;
     return 0;
-}
-
-// ---- operator level
-extern "C" int cs_op_conv(const cs_conv_desc* d, void* stream)
-{
-    ConvCall c;
-    memset(&c.p, 0, sizeof(c.p));
-    ConvParams& p = c.p;
-    p.in = (const half_t*)d->in; p.zero = cs_zero_page(); p.in_sN = d->in_sN; p.in_sD = d->in_sD; p.in_sH = d->in_sH; p.in_sW = d->in_sW;
-    p.N = d->N; p.D = d->D; p.H = d->H; p.W = d->W; p.inD = d->D; p.Cin = d->Cin; p.nchunks = (d->Cin + 31) / 32; p.up_shift = d->up_shift;
-    p.KD = d->KD; p.KH = d->KH; p.KW = d->KW; p.PD = d->KD / 2; p.PH = d->KH / 2; p.PW = d->KW / 2;
-    p.wgt = (const half_t*)d->wgt; p.Cout_pad = d->Cout_pad; p.Cout = d->Cout;
-    p.bias = d->bias; p.bias2 = d->bias2; p.act0 = d->act0; p.slope0 = d->slope0;
-    p.res = td((void*)d->res, d->res_sN, d->res_sD, d->res_sH, d->res_sW); p.res_f32 = d->res_f32; p.res_shift = d->res_shift;
-    p.pixscale = d->pixscale; p.ps_stride = d->ps_stride ? d->ps_stride : 1;
-    p.out0 = td(d->out0, d->out0_sN, d->out0_sD, d->out0_sH, d->out0_sW); p.out0_f32 = d->out0_f32;
-    p.s2 = d->s2; p.t2 = d->t2; p.act1 = d->act1; p.slope1 = d->slope1;
-    p.out1 = td(d->out1, d->out1_sN, d->out1_sD, d->out1_sH, d->out1_sW);
-    p.stats = d->stats;
-    p.hilo = d->hilo; p.stat_out = d->stat_out; p.pool_hw = d->pool_hw;
-    if (d->xf_kind) {       // transform staging (vol32): the fp32 source volumes share out0's strides
-        p.xf_kind = d->xf_kind;
-        p.xf_y = td((void*)d->xf_y, d->out0_sN, d->out0_sD, d->out0_sH, d->out0_sW);
-        p.xf_res = td((void*)d->xf_res, d->out0_sN, d->out0_sD, d->out0_sH, d->out0_sW);
-        p.xf_out = td((void*)d->xf_out, d->out0_sN, d->out0_sD, d->out0_sH, d->out0_sW);
-        p.xf_stats = d->xf_stats; p.xf_gamma = d->xf_gamma; p.xf_beta = d->xf_beta; p.xf_slope = d->xf_slope;
-    }
-    c.mode = d->mode;
-    if (d->mode == 5) { c.mode = MODE_STD; p.spmul = 1; }     // out0 = act0(IN(res) (1 + conv + bias)): ConvParams::spmul
-    if (d->cfg == CFG_VOL32) return launch_vol32(p, (hipStream_t)stream);
-    if (d->cfg == CFG_WIDE) return launch_conv_wide(p, c.mode, (hipStream_t)stream);
-    if (d->cfg == CFG_LAT) return launch_conv_lat(p, c.mode, (hipStream_t)stream);
-    if (d->cfg >= 10 || d->cfg == -2) {      // conv_halo
-        const int hcfg = d->cfg >= 10 ? d->cfg : pick_halo_cfg(p, c.mode);
-        const int BM = (hcfg == CFG_H_256x32 || hcfg == CFG_H_256x16 || hcfg == CFG_H_256x160 || hcfg == CFG_H_256x64) ? 256 : 128;
-        const bool is3d = p.KD > 1;
-        set_tile(p, BM, d->tile_w ? d->tile_w : (is3d ? 8 : 16), d->tile_h ? d->tile_h : (is3d ? 8 : BM / 16));
-        const int ck = d->ck ? d->ck : ((!is3d && p.Cin % 64 == 0) ? 64 : 32);
-        p.xcd_map = d->xcd_map > 0 ? d->xcd_map - 1 : XCD_MAP;
-        p.persist_total = HALO_PERSIST;
-        p.ragged = d->ragged;
-        p.ep_general = d->ep_general;
-        return launch_conv_halo(p, hcfg, ck, c.mode, (hipStream_t)stream);
-    }
-    cs_set_error("cs_op_conv: cfg %d is not a conv_halo configuration (the conv_igemm cross-check kernel lives in the test-only library)", d->cfg);
-    return -1;
-}
-
-extern "C" int cs_op_resblock3d(const void* a, const float* x, float* out0, void* out1, int N, int H, int W, const void* w1, const void* w2,
-                                const float* b1, const float* b2, const float* s2, const float* t2, int act1, float slope1, void* stream)
-{
-    ResBlock3dCall c;
-    c.a = (const half_t*)a; c.x = x; c.out0 = out0; c.out1 = (half_t*)out1;
-    c.sN = (long)H * W * 512; c.sH = (long)W * 512; c.sW = 512;
-    c.w1 = (const half_t*)w1; c.w2 = (const half_t*)w2; c.b1 = b1; c.b2 = b2; c.s2 = s2; c.t2 = t2; c.act1 = act1; c.slope1 = slope1;
-    c.N = N; c.H = H; c.W = W;
-    return launch_vol32_fused(c, (hipStream_t)stream);
-}
-
-extern "C" int cs_op_t_mask(const void* x, const void* wpacked, const float* bias, float* tmask, int N, int H, int W, void* stream)
-{
-    return launch_t_mask((const half_t*)x, (const half_t*)wpacked, bias, tmask, N, H, W, (hipStream_t)stream);
-}
-
-// ---- operator level: T's per-identity precompute (csrc/kernels.hip) without an engine, what cs_set_identity left in an engine (cs_op_t_read), and
-// one blend layer of T on the caller's buffers through the engine's routing (cs_op_t_layer)
-extern "C" int cs_op_t_style(const float* id, const float* fc, float* style, int nlayers, void* stream)
-{
-    if (!id || !fc || !style || nlayers < 1) { cs_set_error("cs_op_t_style: bad arguments"); return -1; }
-    return launch_t_style(id, fc, style, nlayers, (hipStream_t)stream);
-}
-
-extern "C" int cs_op_t_modulate(const float* wraw, const float* style, void* packed, void* stream)
-{
-    if (!wraw || !style || !packed) { cs_set_error("cs_op_t_modulate: bad arguments"); return -1; }
-    return launch_t_modulate(wraw, style, (half_t*)packed, 0, (hipStream_t)stream);
-}
-
-extern "C" int cs_op_t_read(cs_engine* e, int layer, int slot, int which, void* dst, void* stream)
-{
-    if (!e || !e->finalized) { cs_set_error("cs_op_t_read: engine not finalized"); return -1; }
-    if (!dst) { cs_set_error("cs_op_t_read: null destination"); return -1; }
-    if (layer < 0 || layer >= 14) { cs_set_error("cs_op_t_read: layer %d outside [0, 14)", layer); return -1; }
-    if (slot < 0 || slot >= MAX_SLOTS) { cs_set_error("cs_op_t_read: identity slot %d outside [0, %d)", slot, MAX_SLOTS); return -1; }
-    if (!e->slot_set[slot]) { cs_set_error("cs_op_t_read: cs_set_identity has not been called for slot %d", slot); return -1; }
-    DevGuard guard(e->dev);
-    if (which == CS_T_WSET) return copy_dd(dst, e->t_l[layer].wset[slot], (size_t)144 * 1024 * 32 * sizeof(half_t), (hipStream_t)stream);
-    if (which == CS_T_STYLE) return copy_dd(dst, e->style + layer * 512, 512 * sizeof(float), (hipStream_t)stream);
-    cs_set_error("cs_op_t_read: no buffer %d", which);
-    return -1;
-}
-
-extern "C" int cs_op_t_layer(cs_engine* e, int layer, int B, const int* slots, const void* in16, const float* res32, float* tmask_out, void* out16,
-                             float* out32, void* stream)
-{
-    ENTER(e, B);
-    if (layer < 0 || layer >= 14) { cs_set_error("cs_op_t_layer: layer %d outside [0, 14)", layer); return -1; }
-    const bool conv2 = layer % 2 == 1;
-    if (!slots || !in16 || !tmask_out || !out16 || (conv2 && (!res32 || !out32)) || (!conv2 && (res32 || out32))) {
-        cs_set_error("cs_op_t_layer: bad arguments (conv2 layers take res32 and out32, conv1 layers neither)");
-        return -1;
-    }
-    hipStream_t st = (hipStream_t)stream;
-    bool mixed = false;
-    TRY(t_slots(e, B, slots, &mixed, st));
-    return t_layer(e, layer, B, slots, mixed, (const half_t*)in16, res32, tmask_out, (half_t*)out16, out32, st);
-}
-
-extern "C" int cs_op_pair_ragged(void* w, int Cout_pad, int nchunks, int KD, int KH, int KW, void* stream)
-{
-    return launch_pair_ragged((half_t*)w, Cout_pad, nchunks, KD, KH, KW, (hipStream_t)stream);
-}
-
-extern "C" int cs_op_grid_sample3d(const float* in_hwdc, const float* grid, float* out32, void* out16, int N, int D, int H, int W,
-                                   void* stream)
-{
-    return launch_grid_sample(in_hwdc, grid, out32, (half_t*)out16, N, D, H, W, (hipStream_t)stream);
-}
-
-extern "C" long cs_op_chan_stats_partial_floats(int N, long P, int C) { return chan_stats_partial_floats(N, P, C); }
-
-extern "C" int cs_op_chan_stats(const void* x, int is_f32, int N, long P, int C, float eps, float* partials, float* stats, void* stream)
-{
-    return launch_chan_stats(x, is_f32, N, P, C, eps, partials, stats, (hipStream_t)stream);
-}
-
-// ---- operator level: the motion extractor's kernels (csrc/motion.hip) without an engine, and its 1x1 convs through the engine's routing
-extern "C" int cs_op_m_stem(const float* img, const float* w, const float* b, const float* g, const float* be, float* x, int N, int HI, int WI,
-                            void* stream)
-{
-    return launch_m_stem(img, w, b, g, be, x, N, HI, WI, (hipStream_t)stream);
-}
-
-extern "C" int cs_op_m_dwln(const float* x, const float* wt, const float* b, const float* g, const float* be, void* y, int N, int H, int W, int C,
-                            void* stream)
-{
-    return launch_m_dwln(x, wt, b, g, be, (half_t*)y, N, H, W, C, (hipStream_t)stream);
-}
-
-extern "C" int cs_op_m_ln_s2d(const float* x, const float* g, const float* be, void* y, int N, int H, int W, int C, void* stream)
-{
-    return launch_m_ln_s2d(x, g, be, (half_t*)y, N, H, W, C, (hipStream_t)stream);
-}
-
-extern "C" int cs_op_m_grn(const float* h, const float* gamma, const float* beta, float* sumsq, float* scale, void* out, int N, int P, int C,
-                           void* stream)
-{
-    return launch_m_grn(h, gamma, beta, sumsq, scale, (half_t*)out, N, P, C, (hipStream_t)stream);
-}
-
-extern "C" int cs_op_m_head(const float* x, const float* g, const float* be, const float* hw, const float* hb, float* out, int N, int P, void* stream)
-{
-    return launch_m_head(x, g, be, hw, hb, out, N, P, (hipStream_t)stream);
-}
-
-extern "C" int cs_op_m_pointwise(cs_engine* e, int form, const void* in, const void* wpacked, const float* bias, float* out, int N, int H, int C,
-                                 void* stream)
-{
-    if (!e) { cs_set_error("null engine"); return -1; }
-    if ((C != 96 && C != 192 && C != 384 && C != 768) || form < M_PW1 || form > M_DS || (form == M_DS && C == 768) || N < 1 || H < 1) {
-        cs_set_error("cs_op_m_pointwise: no such layer (form %d, C %d, N %d, H %d)", form, C, N, H);
-        return -1;
-    }
-    DevGuard guard(e->dev);
-    ConvL L;      // the geometry cs_finalize_weights gives M's layers
-    L.w = (const half_t*)wpacked; L.b = bias;
-    L.Cin = form == M_PW1 ? 3 * C : 12 * C;
-    L.Cout = form == M_PW1 ? 4 * C : form == M_PW2 ? C : 2 * C;
-    L.Cout_pad = form == M_PW2 ? m_pw2_cout_pad(C) : L.Cout;
-    L.macs_per_pos = (double)L.Cout * (L.Cin / 3);
-    L.name = form == M_PW1 ? "m_pw1" : form == M_PW2 ? "m_pw2" : "m_ds";
-    ConvCall c = m_pointwise(L, form, (const half_t*)in, out, N, H, C);
-    return go(e, c, (hipStream_t)stream);
-}
-
-// ---- operator level: the dense-motion kernels of W (csrc/kernels.hip) without an engine, and the engine's dense-motion buffers as the last
-// call left them (cs_op_dm_read): the tests run W through the public entry points and check each layer on the engine's own input
-extern "C" int cs_op_dm_compress(const float* f_hwdc, const float* w, const float* b, void* comp, int N, int D, int H, int W, void* stream)
-{
-    if (!f_hwdc || !w || !b || !comp || N < 1 || D < 1 || H < 1 || W < 1) { cs_set_error("cs_op_dm_compress: bad arguments"); return -1; }
-    return launch_dm_compress(f_hwdc, w, b, (half_t*)comp, N, D, H, W, (hipStream_t)stream);
-}
-
-extern "C" int cs_op_dm_sparse(const void* comp, int shared_comp, const float* kp_d, const float* kp_s, int shared_kps, void* out, int ostride,
-                               int N, int D, int H, int W, void* stream)
-{
-    if (!comp || !kp_d || !kp_s || !out || N < 1 || D < 2 || H < 2 || W < 2 || ostride < 112) { cs_set_error("cs_op_dm_sparse: bad arguments"); return -1; }
-    return launch_dm_sparse((const half_t*)comp, kp_d, kp_s, (half_t*)out, ostride, N, D, H, W, (hipStream_t)stream, shared_comp != 0, shared_kps != 0);
-}
-
-extern "C" int cs_op_dm_softmax_warp(const float* part, const float* bias, const float* kp_d, const float* kp_s, int shared_kps, const float* in_hwdc,
-                                     int shared_in, float* out32, void* out16, float* deform, int N, int D, int H, int W, void* stream)
-{
-    if (!part || !bias || !kp_d || !kp_s || !in_hwdc || N < 1 || H < 2) { cs_set_error("cs_op_dm_softmax_warp: bad arguments"); return -1; }
-    if (W & 3) { cs_set_error("cs_op_dm_softmax_warp: compact-2 partials need a width that is a multiple of 4"); return -1; }
-    return launch_dm_softmax_warp(part, bias, kp_d, kp_s, in_hwdc, out32, (half_t*)out16, deform, N, D, H, W, (hipStream_t)stream, shared_in != 0, shared_kps != 0);
-}
-
-extern "C" int cs_op_occ_finish(const float* part, int taps, float bias, float* occ, int N, int H, int W, void* stream)
-{
-    if (!part || !occ || N < 1 || H < 1 || W < 1) { cs_set_error("cs_op_occ_finish: bad arguments"); return -1; }
-    if (taps == 49) return launch_occ_finish49(part, bias, occ, N, H, W, (hipStream_t)stream);
-    if (taps == 7) return launch_occ_finish(part, bias, occ, N, H, W, (hipStream_t)stream);
-    cs_set_error("cs_op_occ_finish: taps %d (7 or 49)", taps);
-    return -1;
-}
-
-extern "C" int cs_op_dm_read(cs_engine* e, int which, int B, void* dst, void* stream)
-{
-    ENTER(e, B);
-    if (!dst) { cs_set_error("cs_op_dm_read: null destination"); return -1; }
-    const void* src; size_t bytes;
-    if (which == CS_DM_COMP) { src = e->dm_comp; bytes = (size_t)B * VOX * 4 * sizeof(half_t); }
-    else if (which >= CS_DM_L0 && which <= CS_DM_L0 + 5) { src = e->dm_l[which - CS_DM_L0]; bytes = (size_t)B * dm_level_elems(which - CS_DM_L0) * sizeof(half_t); }
-    else if (which == CS_DM_PRED) { src = e->dm_pred; bytes = (size_t)B * VOX * 144 * sizeof(half_t); }
-    else if (which == CS_DM_LOGITS) { src = e->dm_logits; bytes = (size_t)B * DM_LOGIT_FLOATS * sizeof(float); }
-    else { cs_set_error("cs_op_dm_read: no buffer %d", which); return -1; }
-    return copy_dd(dst, src, bytes, (hipStream_t)stream);
-}
-
-// ---- operator level: G's workspace as the last cs_spade_decode left it (cs_op_g_read), a sentinel over all of it (cs_op_g_fill) and a stop after
-// the n-th launch of the next cs_spade_decode (cs_op_g_stop): the tests check every step of run_G on the engine's own input to it
-namespace {
-struct GBuf { void* p; size_t elems; };      // elements per sample
-GBuf g_buf(cs_engine* e, int which)
-{
-    switch (which) {
-    case CS_G_X0: return {e->g_x[0], (size_t)4096 * 512};
-    case CS_G_X1: return {e->g_x[1], (size_t)4096 * 512};
-    case CS_G_A64: return {e->g_a64, (size_t)4096 * 1536};
-    case CS_G_A128: return {e->g_a128, (size_t)16384 * 384};
-    case CS_G_A256: return {e->g_a256, (size_t)65536 * 384};
-    case CS_G_H64: return {e->g_h64, (size_t)4096 * 512};
-    case CS_G_DX64: return {e->g_dx64, (size_t)4096 * 512};
-    case CS_G_H128: return {e->g_h128, (size_t)16384 * 512};
-    case CS_G_XS128: return {e->g_xs128, (size_t)16384 * 256};
-    case CS_G_DX128: return {e->g_dx128, (size_t)16384 * 256};
-    case CS_G_H1_128: return {e->g_h1_128, (size_t)16384 * 256};
-    case CS_G_O128: return {e->g_o128, (size_t)16384 * 256};
-    case CS_G_BS: return {e->g_bs, (size_t)65536 * 64};
-    case CS_G_H256: return {e->g_h256, (size_t)65536 * 256};
-    case CS_G_XS256: return {e->g_xs256, (size_t)65536 * 64};
-    case CS_G_DX256: return {e->g_dx256, (size_t)65536 * 64};
-    case CS_G_H1_256: return {e->g_h1_256, (size_t)65536 * 64};
-    case CS_G_O256: return {e->g_o256, (size_t)65536 * 64};
-    }
-    return {nullptr, 0};
-}
-}  // namespace
-
-extern "C" int cs_op_g_read(cs_engine* e, int which, int B, void* dst, void* stream)
-{
-    ENTER(e, B);
-    if (!dst) { cs_set_error("cs_op_g_read: null destination"); return -1; }
-    if (which == CS_G_STATS) {      // the slot stats_slot() handed out last
-        const float* slot = e->stats_pool + ((e->stats_next + e->stats_slots - 1) % e->stats_slots) * e->stats_slot_floats;
-        return copy_dd(dst, slot, (size_t)B * 512 * 2 * sizeof(float), (hipStream_t)stream);
-    }
-    const GBuf b = g_buf(e, which);
-    if (!b.p) { cs_set_error("cs_op_g_read: no buffer %d", which); return -1; }
-    return copy_dd(dst, b.p, (size_t)B * b.elems * sizeof(half_t), (hipStream_t)stream);
-}
-
-extern "C" int cs_op_g_fill(cs_engine* e, int B, void* stream)
-{
-    ENTER(e, B);
-    for (int which = CS_G_X0; which <= CS_G_O256; ++which) {
-        const GBuf b = g_buf(e, which);
-        CS_CHECK_HIP(hipMemsetD16Async((hipDeviceptr_t)b.p, CS_G_SENTINEL, (size_t)B * b.elems, (hipStream_t)stream));
-    }
-    CS_CHECK_HIP(hipMemsetD16Async((hipDeviceptr_t)e->stats_pool, CS_G_SENTINEL, e->stats_slots * e->stats_slot_floats * 2, (hipStream_t)stream));
-    return 0;
-}
-
-extern "C" int cs_op_g_stop(cs_engine* e, int n)
-{
-    if (!e || n < 0) { cs_set_error("cs_op_g_stop: bad arguments"); return -1; }
-    e->g_stop = n;
-    return 0;
-}
-
-// ---- operator level: the identity network's kernels (csrc/identity.hip) without an engine, and the activations the last cs_identity pass left
-extern "C" int cs_op_id_conv(const void* in, int in_f32, int N, int IH, int IW, int Cin, int K, int stride, int pad, const void* w, const float* bias,
-                             int Cout, const float* slope, void* out, int out_f32, void* stream)
-{
-    IdConvCall c{};
-    c.in = in; c.in_f32 = in_f32; c.N = N; c.IH = IH; c.IW = IW; c.Cin = Cin; c.K = K; c.stride = stride; c.pad = pad;
-    if (K < 1 || stride < 1 || IH + 2 * pad < K || IW + 2 * pad < K) { cs_set_error("cs_op_id_conv: bad arguments"); return -1; }
-    c.OH = (IH + 2 * pad - K) / stride + 1; c.OW = (IW + 2 * pad - K) / stride + 1;
-    c.w = (const half_t*)w; c.bias = bias; c.Cout = Cout; c.slope = slope; c.out = out; c.out_f32 = out_f32;
-    return launch_id_conv(c, (hipStream_t)stream);
-}
-
-extern "C" int cs_op_id_maxpool(const float* in, const float* s, const float* t, float* x, void* a16, int B, int IH, int IW, int C, void* stream)
-{
-    return launch_id_maxpool(in, s, t, x, (half_t*)a16, B, IH, IW, C, (hipStream_t)stream);
-}
-
-extern "C" int cs_op_id_se_tail(const float* out, long sN, long sH, long sW, int B, int H, int W, int C, const float* w1, const float* b1,
-                                const float* w2, const float* b2, const float* slopes, const float* res, const float* s, const float* t, float* se,
-                                float* x, void* a16, void* stream)
-{
-    if (!slopes) { cs_set_error("cs_op_id_se_tail: NULL slopes"); return -1; }
-    TRY(launch_id_se(out, sN, sH, sW, B, H, W, C, w1, b1, slopes + 1, w2, b2, se, (hipStream_t)stream));
-    return launch_id_tail(out, sN, sH, sW, se, res, slopes, s, t, x, (half_t*)a16, B, H, W, C, (hipStream_t)stream);
-}
-
-extern "C" int cs_op_id_embed(const void* a16, const void* w, const float* bias, float* part, float* raw, float* idn, int B, void* stream)
-{
-    return launch_id_embed((const half_t*)a16, (const half_t*)w, bias, part, raw, idn, B, (hipStream_t)stream);
-}
-
-extern "C" int cs_op_identity_read(cs_engine* e, int which, int B, float* dst, void* stream)
-{
-    if (!e || !e->idn.present) { cs_set_error("cs_op_identity_read: no engine, or no identity network in it"); return -1; }
-    const IdNet& A = e->idn;
-    if (!dst) { cs_set_error("cs_op_identity_read: null destination"); return -1; }
-    if (B < 1 || B > A.lastB) { cs_set_error("cs_op_identity_read: %d samples, the last pass held %d", B, A.lastB); return -1; }
-    DevGuard guard(e->dev);
-    hipStream_t st = (hipStream_t)stream;
-    if (which == CS_ID_STEM) return launch_id_to_nchw(A.stem_x, 0, dst, B, 64, 55 * 55, st);
-    if (which >= CS_ID_LAYER1 && which < CS_ID_LAYER1 + 4) {
-        const int l = which - CS_ID_LAYER1;
-        return launch_id_to_nchw(A.layer_x[l], 0, dst, B, IDNET_C[l], IDNET_HW[l] * IDNET_HW[l], st);
-    }
-    if (which == CS_ID_PREFC) return launch_id_to_nchw(A.a16, 1, dst, B, 512, 49, st);
-    cs_set_error("cs_op_identity_read: no activation %d", which);
-    return -1;
-}
-
-// ---- operator level: the face parser's kernels (csrc/parser.hip) without an engine, and the activations the last cs_parser pass left
-extern "C" int cs_op_parser_input(const float* pixel_values, void* out16, int B, int H, int W, void* stream)
-{
-    return launch_p_input(pixel_values, (half_t*)out16, B, H, W, (hipStream_t)stream);
-}
-
-extern "C" int cs_op_parser_gemm(const void* a16, const void* w16, const float* bias, int M, int K, int N, int mode, void* out, int P, int L, void* stream)
-{
-    PGemmCall g{(const half_t*)a16, (const half_t*)w16, bias, out, M, K, N, mode, P, L};
-    return launch_p_gemm(g, (hipStream_t)stream);
-}
-
-extern "C" int cs_op_parser_layernorm(const float* in, const float* g, const float* b, float eps, long M, int C, float* out32, void* out16, void* stream)
-{
-    return launch_p_ln(in, g, b, eps, M, C, out32, (half_t*)out16, (hipStream_t)stream);
-}
-
-extern "C" int cs_op_parser_attention(const void* q16, const void* kv16, void* ctx16, int B, int Nq, int Nk, int heads, int d, void* stream)
-{
-    return launch_p_attn((const half_t*)q16, (const half_t*)kv16, (half_t*)ctx16, B, Nq, Nk, heads, d, (hipStream_t)stream);
-}
-
-extern "C" int cs_op_parser_dwgelu(const void* in16, const float* w, const float* bias, void* out16, int B, int H, int W, int C, void* stream)
-{
-    return launch_p_dwgelu((const half_t*)in16, w, bias, (half_t*)out16, B, H, W, C, (hipStream_t)stream);
-}
-
-extern "C" int cs_op_parser_upadd(const float* p0, const float* p1, const float* p2, const float* p3, void* out16, int B, int H, int W, int D, void* stream)
-{
-    return launch_p_upadd(p0, p1, p2, p3, (half_t*)out16, B, H, W, D, (hipStream_t)stream);
-}
-
-extern "C" int cs_op_parser_read(cs_engine* e, int which, int B, float* dst, void* stream)
-{
-    if (!e || !e->psr.present) { cs_set_error("cs_op_parser_read: no engine, or no face parser in it"); return -1; }
-    const ParserNet& P = e->psr;
-    if (!dst) { cs_set_error("cs_op_parser_read: null destination"); return -1; }
-    if (B < 1 || B > P.lastB) { cs_set_error("cs_op_parser_read: %d samples, the last pass held %d", B, P.lastB); return -1; }
-    DevGuard guard(e->dev);
-    hipStream_t st = (hipStream_t)stream;
-    if (which >= CS_PARSER_STAGE0 && which < CS_PARSER_STAGE0 + 4) {
-        const int s = which - CS_PARSER_STAGE0;
-        return launch_p_to_nchw(P.st32[s], dst, B, P.st[s].C, (long)(P.lastH >> (s + 2)) * (P.lastW >> (s + 2)), st);
-    }
-    if (which == CS_PARSER_PRE) return launch_nhwc16_to_nchw(P.pre16, dst, B, P.D, (P.lastH / 4) * (P.lastW / 4), st);
-    cs_set_error("cs_op_parser_read: no activation %d", which);
-    return -1;
 }

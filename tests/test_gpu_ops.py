@@ -180,9 +180,12 @@ def test_conv_tblend(kern):
     assert ops.rel_err(_from_cl(out)[:, :, 0], ref) < 2e-3
 
 
-@pytest.mark.parametrize("kern", KERNELS + ["halo256"])
+# conv_halo's chunk width: ck = 64 is forced (on 128x128 tiles an instantiation only this test reaches), ck = 0 is the engine's choice - 32-channel
+# chunks for the 64 modulated channels (Cout_pad 128) of "halo", what G's 64-channel SPADE layers run; 64 for the 128 of "halo256"
+@pytest.mark.parametrize("kern,ck", [pytest.param("igemm", 0, id="igemm"), pytest.param("halo", 64, id="halo"), pytest.param("halo256", 64, id="halo256"),
+                                     pytest.param("halo", 0, id="halo-ck0"), pytest.param("halo256", 0, id="halo256-ck0")])
 @pytest.mark.parametrize("xshift", [0, 1])
-def test_conv_spade(xshift, kern):
+def test_conv_spade(xshift, kern, ck):
     """gamma/beta convs + instance-norm modulation epilogue == SPADE.forward (util.py:295-302) + leaky_relu(0.2)."""
     import hip_ops as ops
     from canonswap_amd import pack
@@ -204,7 +207,7 @@ def test_conv_spade(xshift, kern):
     wp = torch.from_numpy(pack.pack_conv(pack.interleave16(wg.numpy(), wb.numpy()), 2 * Cc)).to(DEV)
     out = torch.zeros(N, 1, S, S, Cc, dtype=torch.float16, device=DEV)
     ops.conv(_to_cl(actv).to(DEV), wp, 2 * Cc, Cc, (1, 3, 3), bias=bg.to(DEV), bias2=bb.to(DEV), res=xd.unsqueeze(1), res_shift=xshift,
-             stats=stats, act0="lrelu", slope0=0.2, out0=out, mode=2, cfg=17 if kern == "halo256" else _cfg(kern, 0, 10))
+             stats=stats, act0="lrelu", slope0=0.2, out0=out, mode=2, cfg=17 if kern == "halo256" else _cfg(kern, 0, 10), ck=ck)
     torch.cuda.synchronize()
     assert ops.rel_err(_from_cl(out)[:, :, 0], ref) < 3e-3
 

@@ -164,7 +164,7 @@ def test_abi_declares_the_identity_entry_points():
         assert m, f"{name}: no declaration with a comment above it"
         assert re.search(r"(arcface_models|can_swap_e2e|can_swap_pipeline_e2e)\.py:\d+", m.group(1)), f"{name}: the comment names no reference file:line"
     eng = open(os.path.join(ROOT, "canonswap_amd", "csrc", "engine.hip")).read()
-    head = eng[:eng.index("#define TRY")]
+    head = eng[:eng.index('extern "C" int cs_abi_version')]
     for name in ENTRY_POINTS[:3]:
         assert name in head, f"{name}: not in the entry-point list at the top of engine.hip"
     assert any(s.endswith("identity.hip") for s in _lib.SOURCES)

@@ -192,7 +192,7 @@ def test_abi_declares_the_parser_entry_points():
         assert name in _lib.ABI_SYMBOLS, name
         assert re.search(r"\*/\s*(?:enum[^;]*;\s*)?int " + name + r"\(", hdr, re.S), f"{name}: no declaration with a comment above it"
     eng = open(os.path.join(ROOT, "canonswap_amd", "csrc", "engine.hip")).read()
-    head = eng[:eng.index("#define TRY")]
+    head = eng[:eng.index('extern "C" int cs_abi_version')]
     for name in ENTRY_POINTS[:2]:
         assert name in head, f"{name}: not in the entry-point list at the top of engine.hip"
     assert any(s.endswith("parser.hip") for s in _lib.SOURCES)
