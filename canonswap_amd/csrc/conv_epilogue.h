@@ -64,8 +64,6 @@ __device__ __forceinline__ void load4(const TDesc& t, int is_f32, long off, floa
     }
 }
 
-// Ablation build (tools/build_variant.py, not the product): -DCS_EP_NOSTORE puts every epilogue store behind a runtime condition
-// that is never true (what the stores cost: profiles/r02_store_ablation.txt).
 // fp32 -> fp16 of values the epilogue computed: round-to-nearest-even of the fp32 RESULT.  Left to itself hipcc folds a preceding fma
 // into v_fma_mix{lo,hi}_f16 (one rounding, straight from the exact product-sum to fp16; an instruction-selection pattern, not governed by
 // the contraction pragma) for some elements and not for others, depending on the code around it - the branch-free copies of the epilogue
@@ -156,11 +154,6 @@ __device__ __forceinline__ constexpr int ep_pair_of(int mode, int wch)
 // lgTW, lgTH, lgTD, lgS, mW, mH, mD (the tile decomposition: compile-time constants in the static-shape kernels, which turns the
 // per-block coordinates below into constants), wch, l15, l4, tile_lin (linear index of the position tile) and the template constants
 // WCH, BM, MODE, EP_EARLY (+ ep_xpre from CONV_EPILOGUE_EARLY_FETCH; false elsewhere), EP_PAIR (ep_pair_of(MODE, WCH) where the kernel permutes its weight rows accordingly, else 0).
-#if defined(CS_EP_NOSTORE)
-#define EP_STORE_COND && (p.N < 0)
-#else
-#define EP_STORE_COND
-#endif
 // SPADE kernels fetch the tensor they modulate (x, fp16) for the wave's WHOLE tile at kernel start, where the round trip hides behind
 // the first halo wait, instead of after the main loop where every wave of the CU would sit through it at the same time (the
 // workgroups of a CU run in lock step; profiles/r02_timeline_*.txt: "epi first block").  16 more live registers in the main loop:
@@ -539,7 +532,7 @@ _Pragma("unroll") \
                 } \
             } \
             const bool ep_hold = EP_PAIR != 0 && !ep_second(EP_PAIR, ci) && (EPALL || cb + 4 < p.Cout);      /* first half of a complete pair */ \
-            if (ep_has_o0 && ep_pool_lane && (!EP_POOL_HB || (pi & 1)) EP_STORE_COND) { \
+            if (ep_has_o0 && ep_pool_lane && (!EP_POOL_HB || (pi & 1))) { \
                 if (ep_m0 && ep_hold) { \
 _Pragma("unroll") \
                     for (int r = 0; r < 4; ++r) ep_vh[r] = v[r]; \
@@ -560,13 +553,11 @@ _Pragma("unroll") \
                     const float a = fmaf(v[r], ((const float*)&ep_s2[ci])[r], ((const float*)&ep_t2[ci])[r]);   /* explicit: every copy of the epilogue fuses alike */ \
                     u[r] = lin_act(a, ep_sl1); \
                 } \
-                if (true EP_STORE_COND) { \
-                    if (ep_m1 && ep_hold) { \
+                if (ep_m1 && ep_hold) { \
 _Pragma("unroll") \
-                        for (int r = 0; r < 4; ++r) ep_uh[r] = u[r]; \
-                    } else if (ep_m1 && ep_second(EP_PAIR, ci)) store8(p.out1, 0, (long)(ob1 + (unsigned)(cb - 4)), ep_uh, u); \
-                    else store4(p.out1, 0, (long)(ob1 + (unsigned)cb), u); \
-                } \
+                    for (int r = 0; r < 4; ++r) ep_uh[r] = u[r]; \
+                } else if (ep_m1 && ep_second(EP_PAIR, ci)) store8(p.out1, 0, (long)(ob1 + (unsigned)(cb - 4)), ep_uh, u); \
+                else store4(p.out1, 0, (long)(ob1 + (unsigned)cb), u); \
             } \
         } \
         EP_SLICE_FENCE \

@@ -96,20 +96,13 @@ template <> struct StaticShape<15> { static constexpr int KD = 1, KH = 1, KW = 1
 //     permutation, for the volume tiles; it costs 20 % / 11 % more LDS and is used where the occupancy stays the same (halo_pad).
 template <int CK, int WPX, int WCH, int WVP, int ST, int MODE> constexpr int halo_pad()
 {
-#ifdef CS_LDS_V1
-    return 1;
-#else
     if (CK == 64 && WCH == 4 && WPX == 8 && ST == 1) return 2;                       // 128x256 tiles (T, wide G / R convs): 2 workgroups per CU
     if (CK == 32 && WCH == 5 && WPX == 8 && (ST == 7 || ST == 8 || ST == 9)) return 2;           // 256x160 tiles: 1 workgroup per CU
     if (CK == 64 && WCH == 2 && WPX == 8 && WVP == 2 && ST == 16) return 2;           // 256x64 2-D tiles: 2 workgroups per CU (2 x 52 KB)
     // SPADE gamma/beta convs (128x128, three workgroups per CU): the 64-channel image would not fit three times with two pad slots
     // (173 KB) and measured slower at two workgroups; with 32-channel chunks it does (104 KB) - the engine launches them that way
     if (CK == 32 && WCH == 2 && WPX == 8 && ST == 1 && MODE == MODE_SPADE) return 2;
-#ifdef CS_LDS_V32
-    if (CK == 32 && WCH == 2 && WPX == 4 && WVP == 4 && ST == 3) return 2;            // 256x32 volume tiles: 3 -> 2 workgroups per CU
-#endif
     return 1;
-#endif
 }
 // pieces per thread whose source offsets are kept in registers = ceil(halo voxels * slots per voxel / 256)
 template <int ST, int PAD> constexpr int halo_hi()
@@ -120,14 +113,10 @@ template <int ST, int PAD> constexpr int halo_hi()
 // position (0..15 within its block) that lane l15 works on
 template <int ST, int PAD> __host__ __device__ constexpr int halo_lane_pos(int l)
 {
-#ifdef CS_LDS_V1
-    return l;
-#else
     using SS = StaticShape<ST>;
     if (ST == 0 || SS::KW != 3 || SS::LW > 3 || SS::LW < 2) return l;
     if (SS::LW == 2 && PAD == 2) return ((l & 1) << 1) | ((l & 2) << 2) | ((l >> 2) & 1) | ((l & 8) >> 1);      // bits (1,3,0,2)
     return ((l & 1) << 1) | ((l & 2) << 1) | ((l >> 2) & 1) | (l & 8);                                          // bits (1,2,0,3)
-#endif
 }
 
 // compile-time loop: f(std::integral_constant<int, 0>{}), ..., f(std::integral_constant<int, N - 1>{}) - the K-steps of the ASMR kernels need
@@ -204,11 +193,7 @@ __global__ void __launch_bounds__(256, (WCH == 4 ? 2 : ((WCH == 2 && WPX == 8 &&
     constexpr bool EP_POOLK2 = halo_pool2d<CK, WPX, WCH, WVP, MODE, SK, ST>();
     // ConvParams::spmul: the 128 x 256 tiles the gamma convs of G's two learned shortcuts run on
     constexpr bool XSK = ST == 1 && !SK && MODE == MODE_STD && CK == 64 && WCH == 4 && WPX == 8 && WVP == 1;       // ConvParams::xs_w (the fused shortcut epilogue)
-#ifdef CS_NO_SPMUL_FAST
-    constexpr bool EP_SPMUL_K = false;
-#else
     constexpr bool EP_SPMUL_K = ST == 1 && !SK && MODE == MODE_STD && CK == 64 && WCH == 4 && WPX == 8 && WVP == 1;
-#endif
     // G.up_1.conv_1 (64 -> 64 at 256 x 256; res + out1 = lrelu(.), no out0) ran the general epilogue: 21 000 of a wave's 41 000 cycles against
     // 10 000 of main loop (profiles/r06_q_timeline_b64.txt); only the 2-D 256x64 kernel carries the copy
     constexpr bool EP_O1ONLY_K = ST == 16 && !SK && MODE == MODE_STD;
@@ -237,14 +222,6 @@ __global__ void __launch_bounds__(256, (WCH == 4 ? 2 : ((WCH == 2 && WPX == 8 &&
     TL_STAMP(0);
 #endif
 
-#ifdef CS_DEPHASE        // experiment: workgroups of the first dispatch round in an odd wave slot start CS_DEPHASE x 1024 cycles late
-    if (MODE == MODE_SPADE && WCH == 4) {
-        unsigned hwid;
-        asm volatile("s_getreg_b32 %0, hwreg(HW_REG_HW_ID)" : "=s"(hwid));
-        if ((hwid & 1u) && (int)(blockIdx.x + blockIdx.y * gridDim.x) < 512)
-            for (int i = 0; i < CS_DEPHASE; ++i) __builtin_amdgcn_s_sleep(16);
-    }
-#endif
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     // grouped launch (ConvParams::nphase): blockIdx.z picks the phase's weights, leading padding and output offset
@@ -257,22 +234,14 @@ __global__ void __launch_bounds__(256, (WCH == 4 ? 2 : ((WCH == 2 && WPX == 8 &&
     const int wpx = SK ? 0 : wave % WVP, wch = SK ? 0 : wave / WVP;
     const int l15 = lane & 15, l4 = lane >> 4;
     const int l15p = halo_lane_pos<ST, PAD>(l15);      // the position of its 16-position blocks this lane works on
-#ifdef CS_NO_PAIR                               // A/B builds (tools/build_variant.py)
-    constexpr int EP_PAIR = 0;
-#else
     constexpr int EP_PAIR = ep_pair_of(MODE, WCH);     // weight-row permutation / joint stores of channel pairs (conv_epilogue.h)
-#endif
 
     // ---- persistent mode (the ASMR kernels, ConvParams::persist_total > 0; see the ASMR block below): the workgroup walks a list of tiles.
     // XCD x owns persist_total / 8 consecutive entries of the launch order (as in xcd_map 2), its workgroups take them round robin, so the
     // tiles in flight in an XCD are neighbours; the state below lives across tiles: the weight ring (the last steps of a tile fetch the
     // first steps of the next one: the weights are the same), the staging offsets / buffer of the tile being staged (the next tile's first
     // chunk is staged under the last chunk's MFMAs), the LDS buffer parity.
-#ifdef CS_NO_ASMRING
-    constexpr bool ASMRK = false;
-#else
     constexpr bool ASMRK = DB && !SK && CK == 32 && WCH == 5 && WPX == 8 && WVP == 2 && (ST == 7 || ST == 8 || ST == 9) && MODE == MODE_STD;
-#endif
     u4_t wr_p[ASMRK ? 3 : 1][ASMRK ? WCH : 1];
     unsigned poffb[ASMRK ? HI : 1];
     __amdgpu_buffer_rsrc_t rsrc_p;
@@ -420,17 +389,9 @@ __global__ void __launch_bounds__(256, (WCH == 4 ? 2 : ((WCH == 2 && WPX == 8 &&
 
     // SPADE: fetch the modulated tensor of the whole tile now (conv_epilogue.h); only the 3-waves-per-SIMD 128x128 kernel has the
     // 16 registers to spare, and launch_halo_st refuses an fp32 operand for it
-#ifdef CS_NO_EARLY
-    constexpr bool EP_EARLY = false;
-#else
     constexpr bool EP_EARLY = (MODE == MODE_SPADE) && !SK && ST != 0 && WCH == 2 && WPX == 8;
-#endif
     // branch-free copies of the epilogue for the tensor combinations of the engine's hot layers (conv_epilogue.h, CONV_EPILOGUE)
-#ifdef CS_NO_EPFAST
-    constexpr bool EP_FAST = false;
-#else
     constexpr bool EP_FAST = !SK && ST != 0 && (WCH == 4 || WCH == 5 || (WCH == 2 && WPX == 8) || ST == 15);
-#endif
     constexpr int EP_WPX0 = WPX;
     const int ep_wpx0 = wpx;
     CONV_EPILOGUE_EARLY_FETCH()
@@ -454,39 +415,23 @@ __global__ void __launch_bounds__(256, (WCH == 4 ? 2 : ((WCH == 2 && WPX == 8 &&
         // of 6 steps carried over the chunk boundary: R's 2-D convs 0.251 -> 0.215 ms, G's 512 -> 512 convs -9 % on the one-frame step
         // (profiles/r05_e_ab_lat_ring.txt).  The 128 x 128 tiles (T, SPADE; 168-register budget) lose with the deeper ring: not taken there.
         constexpr bool LATK = CK == 64 && WCH == 2 && WPX == 4 && ST == 1 && !SK;
-#ifdef CS_PFS3
-        constexpr int PFS = NS < 3 ? NS : 3;
-#else
         constexpr int PFS = NS < 3 ? NS : (WCH * WPX <= 4 ? (NS < 8 ? NS : 8) : (LATK ? (NS < 6 ? NS : 6) : 3));
-#endif
         // The ring is carried over the chunk boundary in the kernels that run one wave per SIMD (256-position tiles), where a chunk is a
         // whole number of ring turns (3x3x3 x 32 channels: 27 steps): the last PFS steps of a chunk fetch the first PFS steps of the next
         // one into the slots these expect, so the first MFMA behind the chunk barrier does not wait for an L2 round trip (wload_at clamps
         // the chunk index: behind the last chunk the fetches repeat its first steps and are dropped).  The ragged chunk has another step
         // count, but it is the last one.  Hourglass tail and first encoder block -4 %, +0.25 % on the step; with two or three waves per
         // SIMD the others fill that gap already and the longer live ranges cost the 128x256 kernels 12-24 bytes of scratch: -0.2 %
-        // (profiles/r03_n_ab_wcarry.txt; -DCS_NO_WCARRY is the A/B switch).  Where a chunk is not a whole number of ring turns (the mask conv:
+        // (profiles/r03_n_ab_wcarry.txt).  Where a chunk is not a whole number of ring turns (the mask conv:
         // 49 steps) the slot a step s of the last turn frees takes the next chunk's step s % PFS - the step that slot serves there.
-#ifdef CS_NO_WCARRY
-        constexpr bool WCARRY = false;
-#else
-#ifdef CS_WCARRY_MULT
-        constexpr bool WCARRY = (NS % PFS == 0) && NS >= 2 * PFS && WPX == 8 && WVP == 2;
-#else
         constexpr bool WCARRY = NS >= 2 * PFS && ((WPX == 8 && WVP == 2) || LATK);
-#endif
-#endif
         constexpr int SHW = (1 << SS::LW) + SS::KW - 1, SHH = (1 << SS::LH) + SS::KH - 1;
         // ---- ASMR: the 256 x 160 tiles (hourglass tail, mask conv: one workgroup per CU, one wave per SIMD) stream their weight ring with
         // loads the compiler does not track and stage the next chunk's halo piece by piece UNDER the MFMAs, through buffer-addressed LDS
         // DMA - conv_wide.hip's scheme (see there) inside this kernel's tile / epilogue machinery.  With compiler-tracked loads every wait
         // for a weight fragment becomes vmcnt(0) while an LDS DMA is in flight, so the halo could only be staged as a burst of 15 pieces
         // at the chunk's head (13 % of a tail chunk) followed by a full drain.  Same K order, same bits.
-#ifdef CS_NO_ASMRING
-        constexpr bool ASMR = false;
-#else
         constexpr bool ASMR = DB && WCH == 5 && WPX == 8 && WVP == 2 && (ST == 7 || ST == 8 || ST == 9) && MODE == MODE_STD && PFS == 3;
-#endif
         if constexpr (ASMR) {
             static_assert(SK == false && KH32 == 1, "ASMR: 32-channel chunks");
             constexpr int HSTRIDE = HI * 4096;       // LDS bytes between the two buffers: the last piece's lanes beyond the image land in the gap
@@ -592,11 +537,7 @@ __global__ void __launch_bounds__(256, (WCH == 4 ? 2 : ((WCH == 2 && WPX == 8 &&
                 halo_static_for<NSC>([&](auto stc) {
                     constexpr int st = decltype(stc)::value;
                     {   // wait for this step's ring slot; the count: halo_ring_young (below the kernel)
-#ifdef CS_ASMR_DEBUG0
-                        constexpr int NY = 0;
-#else
                         constexpr int NY = halo_ring_young<WCH, PFS, HI, ST0>(st, NSC, NS, true);
-#endif
                         asm volatile("s_waitcnt vmcnt(%5)" : "+v"(wr[st % PFS][0]), "+v"(wr[st % PFS][1]), "+v"(wr[st % PFS][2]), "+v"(wr[st % PFS][3]),
                                                              "+v"(wr[st % PFS][4]) : "n"(NY));
                     }
@@ -712,16 +653,8 @@ __global__ void __launch_bounds__(256, (WCH == 4 ? 2 : ((WCH == 2 && WPX == 8 &&
             // block): the LDS reads of the other half and the reload of the weight slot the PREVIOUS step used go out between the MFMAs of a
             // half instead of as a block ahead of them.  A block of 4 ds_reads + 5 global loads is 50 - 100 cycles of idle matrix pipe per
             // 20 MFMAs when no other wave shares the SIMD: tail 2.25 -> 2.15 ms, mask 3.46 -> 3.33 ms per 32 frames, +1 % on the step
-            // (profiles/r03_n_ab_ilv.txt; -DCS_NO_ILV is the A/B switch, -DCS_ILV_ALL extends it to every static kernel)
-#if defined(CS_NO_ILV)
-            constexpr bool ILV = false;
-#elif defined(CS_ILV_ALL)
-            constexpr bool ILV = (WPX >= 2);
-#elif defined(CS_ILV_128)
-            constexpr bool ILV = (WPX == 8 && WVP == 2) || (WPX == 8 && WCH == 2 && WVP == 1);
-#else
+            // (profiles/r03_n_ab_ilv.txt)
             constexpr bool ILV = (WPX == 8 && WVP == 2);
-#endif
 #pragma unroll
             for (int st = 0; st < NSC; ++st) {
                 const int toff = toff_of(st);
@@ -1224,11 +1157,7 @@ static int launch_halo_st(const ConvParams& p, hipStream_t st)
     constexpr bool big = (BM == 256 && WCH == 5);
     // (double-buffering the three 52 KB chunks of the split-precision volume convs - one workgroup per CU instead of three single-
     // buffered ones - measured 3 % slower on the whole step: profiles/r02_notes.md)
-#ifndef CS_NO_ASMRING
     constexpr bool asmr = WCH == 5 && WPX == 8 && WVP == 2 && (ST == 7 || ST == 8 || ST == 9) && MODE == MODE_STD && !SK;      // see the kernel (ASMR)
-#else
-    constexpr bool asmr = false;
-#endif
     // (the ASMR kernels' two buffers are HI DMA pieces each: the 4 x 8 x 8 mask tile's 2 x 76 KB fit the 160 KB of a CU)
     const bool db = nck > 1 && (asmr ? 2 * HI * 4096 <= 160 * 1024 : 2 * HV * VS <= (big || (WCH == 4 && PAD == 2) ? 128 : 64) * 1024) && HV * SLP <= 256 * HI;
     size_t lds = (size_t)(db ? 2 : 1) * HV * VS + 16;

@@ -135,18 +135,13 @@ __global__ void __launch_bounds__(256) m_dwln_kernel(const float* __restrict__ x
     static_assert(K % KC == 0, "channel groups per chunk");
     const int lane = threadIdx.x & 63;
     const int runs_per_row = W / DWP;                                   // W is 64, 32, 16 or 8
-#ifdef DW_HROWS      /* A/B: the first form - the four waves of a workgroup own four consecutive runs of one row */
-    const long run = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (run >= (long)N * H * runs_per_row) return;
-    const int w0 = (int)(run % runs_per_row) * DWP, h0 = (int)((run / runs_per_row) % H), n = (int)(run / ((long)runs_per_row * H));
-#else
-    // the four waves of a workgroup own the same columns of four consecutive rows: their 7-row windows overlap (10 input rows instead of 28
-    // through the CU's L1: 1.32 -> 1.26 ms per 64 frames, same bits); H is a multiple of 4 (launcher)
+    // the four waves of a workgroup own the same columns of four consecutive rows: their 7-row windows overlap (10 input rows
+    // through the CU's L1 instead of the 28 of four consecutive runs of one row, the first form: 1.32 -> 1.26 ms per 64 frames, same bits);
+    // H is a multiple of 4 (launcher)
     const long item = blockIdx.x;
     if (item >= (long)N * (H >> 2) * runs_per_row) return;
     const int w0 = (int)(item % runs_per_row) * DWP, h0 = (int)((item / runs_per_row) % (H >> 2)) * 4 + (int)(threadIdx.x >> 6),
               n = (int)(item / ((long)runs_per_row * (H >> 2)));
-#endif
     float acc[DWP][K];
 #pragma unroll
     for (int p = 0; p < DWP; ++p)

@@ -45,11 +45,7 @@ enum { V_EPI_F16 = 0,    // out0 fp16 = act0(conv + bias)                       
 // of the plain kernel 0.7 us of MFMA work: with one row of look-ahead the first build of this kernel ran at the rate of one DMA round
 // trip per step (profiles/r03_b_layers_b32.csv: 124 / 190 us per conv against 46 us of MFMA time).
 template <bool SPLIT, int EPI = 0> struct VRing {
-#ifdef V32_K6
-    static constexpr int K = SPLIT ? 2 : (EPI == 0 ? 6 : 4);
-#else
-    static constexpr int K = SPLIT ? 2 : 4;
-#endif                     // look-ahead in rows (split: 143 KB of LDS at K = 2; its step is 3x longer)
+    static constexpr int K = SPLIT ? 2 : 4;                     // look-ahead in rows (split: 143 KB of LDS at K = 2; its step is 3x longer)
     static constexpr int RING = K + 2;
     static constexpr int QS = ((RING * V_RS + 16 + 255) / 256) * 256;      // q plane stride: a multiple of 256 bytes (bank-conflict freedom)
     static constexpr int IMG = 4 * QS;                          // one image (four q planes)
@@ -166,9 +162,6 @@ __global__ void __launch_bounds__(256, 1) vol32_kernel(const Vol32Params p)
         const int idx = j * 64 + lane, col = idx / 17, ds = idx % 17;
         s_on[j] = idx < V_NC * 17 && ds != 0;
         s_off[j] = col * p.in_sW + (ds - 1) * VOX + wave * 8;
-#ifdef V32_EXP_COAL        /* timing experiment only (wrong results): consecutive lanes fetch consecutive 16-byte pieces */
-        s_off[j] = col * p.in_sW + ((ds - 1) * 8 + wave * 128) % 512;
-#endif
     }
     const int lanebase = l4 * QS + l15 * 16 + (2 * wave) * V_CS;         // fragment reads: q plane l4, depth l15, this wave's first column
     const unsigned lane_el = (unsigned)(l15 * 32 + l4 * 8);              // epilogue: element offset of this lane inside a column
@@ -364,14 +357,6 @@ __global__ void __launch_bounds__(256, 1) vol32_kernel(const Vol32Params p)
             // input row h + K into the slot row h - 2 left at the last barrier; residual row h + K into the slot this wave read last step
             int sk = s0 + K + 1; sk -= sk >= RING ? RING : 0;
             int rk = r0 + K; rk -= rk >= R::RROWS ? R::RROWS : 0;
-#ifdef V32_NOSPREAD
-            stage_row(h + K, sk, rk);
-            asm volatile("" ::: "memory");
-            TLS(2);
-            if (have) flush();
-            asm volatile("" ::: "memory");
-            TLS(3);
-#endif
             f4_t rr[2][2];                           // residual of this step's outputs, from LDS (landed at least two steps ago)
             if constexpr (EPI == V_EPI_RES) {
 #pragma unroll
@@ -394,25 +379,15 @@ __global__ void __launch_bounds__(256, 1) vol32_kernel(const Vol32Params p)
             h8_t fa[4], fb[4];
             h8_t wa[SPLIT ? 3 : 1][2], wb[SPLIT ? 3 : 1][2];           // W_lo fragments of a group (pass 1)
             // group sequence.  Plain: 9 (kd, kh) groups.  Split precision (the halo kernel's chunk order): three passes of 9
-            // groups - W_hi x_hi, W_lo x_hi, W_hi x_lo.  Merged order (-DV32_MERGE): (W_hi x_hi, W_lo x_hi) alternate per group on the SAME four activation
-            // fragments, then the W_hi x_lo pass - 126 instead of 162 LDS reads per step; the pass that streams W_lo from LDS drops from 10 to
-            // 6 reads per 12 MFMAs.  Another (fixed) summation order per output element than conv_halo's hilo kernel: equal to ~1e-7.
-#ifdef V32_MERGE         /* A/B switch: measured 467.7 vs 467.2 frames/s (profiles/r03_l_ab.txt) - not worth another summation order */
-            constexpr bool MERGE = SPLIT;
-#else
-            constexpr bool MERGE = false;
-#endif
-            auto g_pass = [](int G2) { return MERGE ? (G2 < 18 ? (G2 & 1) : 2) : G2 / 9; };
-            auto g_idx = [](int G2) { return MERGE ? (G2 < 18 ? (G2 >> 1) : G2 - 18) : G2 % 9; };
-            auto g_buf = [](int G2) { return MERGE ? (G2 < 18 ? ((G2 >> 1) & 1) : ((G2 - 17) & 1)) : (G2 & 1); };
-            auto g_newb = [](int G2) { return MERGE ? !(G2 < 18 && (G2 & 1)) : true; };
+            // groups - W_hi x_hi, W_lo x_hi, W_hi x_lo.  (A merged order - (W_hi x_hi, W_lo x_hi) alternating per group on the SAME four activation
+            // fragments, then the W_hi x_lo pass: 126 instead of 162 LDS reads per step, the pass that streams W_lo from LDS at 6 instead of 10
+            // reads per 12 MFMAs - measured 467.7 vs 467.2 frames/s (profiles/r03_l_ab.txt): not worth another summation order per output
+            // element than conv_halo's hilo kernel.)
             auto rd = [&](h8_t (&f)[4], h8_t (&wl2)[SPLIT ? 3 : 1][2], int G2) {      // G2: compile-time after unrolling
-                const int pass = g_pass(G2), g = g_idx(G2), kd = g / 3, kh = g % 3;
+                const int pass = G2 / 9, g = G2 % 9, kd = g / 3, kh = g % 3;
                 const int img = (SPLIT && pass == 2) ? IMG : 0;
-                if (g_newb(G2)) {
 #pragma unroll
-                    for (int i = 0; i < 4; ++i) f[i] = *(const h8_t*)(smem + rb[kh] + img + i * V_CS + kd * 16);
-                }
+                for (int i = 0; i < 4; ++i) f[i] = *(const h8_t*)(smem + rb[kh] + img + i * V_CS + kd * 16);
                 if constexpr (SPLIT) {
                     if (pass == 1) {
 #pragma unroll
@@ -425,22 +400,17 @@ __global__ void __launch_bounds__(256, 1) vol32_kernel(const Vol32Params p)
             rd(fa, wa, 0);
 #pragma unroll
             for (int G2 = 0; G2 < NG; ++G2) {
-                h8_t (&cur)[4] = g_buf(G2) ? fb : fa;
+                h8_t (&cur)[4] = (G2 & 1) ? fb : fa;
                 h8_t (&wcur)[SPLIT ? 3 : 1][2] = (G2 & 1) ? wb : wa;
                 h8_t (&wnxt)[SPLIT ? 3 : 1][2] = (G2 & 1) ? wa : wb;
-#ifndef V32_XF_NOIL
                 // transform staging: the conversion of piece G2 / 2 of row h + 2 (VALU + two ds_writes) shares the scheduling region of this
                 // group's MFMAs and is spread between them (below)
                 if constexpr (XF != 0) { if (G2 >= XW0 && G2 < XW0 + 9) xf_write(h + 2, sk, (G2 - XW0) / 3, (G2 - XW0) % 3); }
-#endif
                 if (G2 + 1 < NG) {
-                    h8_t (&nxt)[4] = g_buf(G2 + 1) ? fb : fa;
+                    h8_t (&nxt)[4] = (G2 & 1) ? fa : fb;
                     rd(nxt, wnxt, G2 + 1);
                 }
-#ifdef V32_NOINTERLEAVE
-                __builtin_amdgcn_sched_barrier(0);
-#endif
-                const int pass = g_pass(G2), g = g_idx(G2);
+                const int pass = G2 / 9, g = G2 % 9;
 #pragma unroll
                 for (int kw = 0; kw < 3; ++kw)
 #pragma unroll
@@ -450,16 +420,11 @@ __global__ void __launch_bounds__(256, 1) vol32_kernel(const Vol32Params p)
                             const h8_t a = (SPLIT && pass == 1) ? wcur[SPLIT ? kw : 0][ci] : wr[g * 3 + kw][ci];
                             acc[c][ci] = __builtin_amdgcn_mfma_f32_16x16x32_f16(a, cur[kw + c], acc[c][ci], 0, 0, 0);
                         }
-#ifndef V32_NOINTERLEAVE
                 // the LDS reads of the next group go out BETWEEN this group's 12 MFMAs (one wave per SIMD: a block of reads ahead of the
                 // MFMAs is 30 - 80 cycles of idle matrix pipe per group): one read per MFMA until they are out, then the remaining MFMAs
                 if (G2 + 1 < NG) {
-                    const int nrd = (g_newb(G2 + 1) ? 4 : 0) + ((SPLIT && g_pass(G2 + 1) == 1) ? 6 : 0);
-#ifndef V32_XF_NOIL
+                    const int nrd = 4 + ((SPLIT && (G2 + 1) / 9 == 1) ? 6 : 0);
                     const bool conv_here = XF != 0 && G2 >= XW0 && G2 < XW0 + 9;
-#else
-                    const bool conv_here = false;
-#endif
 #pragma unroll
                     for (int i = 0; i < 11; ++i) {
                         __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);       // one MFMA
@@ -467,13 +432,11 @@ __global__ void __launch_bounds__(256, 1) vol32_kernel(const Vol32Params p)
                         if (conv_here) __builtin_amdgcn_sched_group_barrier(0x002, 4, 0);     // a few VALU instructions of the conversion
                     }
                 }
-#endif
                 __builtin_amdgcn_sched_barrier(0);
-#ifndef V32_NOSPREAD
                 // the step's memory instructions (DMA pieces of row h + K first, then the stores of row h - 1: the order the counted wait
                 // assumes) are spread over the MFMA groups: a wave that issues them back to back waits for the address pipeline to take
                 // each one (150 - 350 cycles apiece at the head of a step) with nothing else to run; spread out, the residual-conv and
-                // split-precision kernels lose 18 % / 11 % of their cycles (profiles/r03_d_vol32_probe_spread.txt; -DV32_NOSPREAD is the A/B switch)
+                // split-precision kernels lose 18 % / 11 % of their cycles (profiles/r03_d_vol32_probe_spread.txt)
                 if constexpr (XF == 0) {
                     constexpr int NM = ND + NS;
 #pragma unroll
@@ -488,14 +451,10 @@ __global__ void __launch_bounds__(256, 1) vol32_kernel(const Vol32Params p)
                     // transform staging: the stores of row h - 1 first (groups 0 .. NS - 1), then the loads of row h + 2 (groups XL0, +2, +4), its
                     // conversion into slot sk late in the step (groups XW0 .. XW0 + 8, three parts per piece): the only memory instructions
                     // younger than a piece's loads at its conversion are the other pieces' loads and write-backs - the compiler counts them
-#ifdef V32_XF_NOIL
-                    if (G2 >= XW0 && G2 < XW0 + 9) xf_write(h + 2, sk, (G2 - XW0) / 3, (G2 - XW0) % 3);
-#endif
                     if (G2 < NS && have) store_piece(G2);
                     if (G2 >= XL0 && G2 < XL0 + 6 && ((G2 - XL0) & 1) == 0) xf_load(h + 2, (G2 - XL0) >> 1);
                     __builtin_amdgcn_sched_barrier(0);
                 }
-#endif
             }
             TLS(4);
             // ---- epilogue arithmetic (conv_epilogue.h formulas, same order of operations); the stores follow after the barrier

@@ -244,9 +244,6 @@ __global__ void __launch_bounds__(512, 2) vol32_fused_kernel(const FusedParams p
                             }
                         }
                         __builtin_amdgcn_sched_barrier(0);
-#ifdef F_SPREAD
-                        if (g < 8) { dma_k(tt, g); __builtin_amdgcn_sched_barrier(0); }
-#endif
                     }
                     FTL(2);
                     // h = relu(conv1 + b1) as fp16 (what the two-launch path stores); outside the volume h is conv2's zero padding
@@ -262,32 +259,20 @@ __global__ void __launch_bounds__(512, 2) vol32_fused_kernel(const FusedParams p
                     }
                     FTL(4);
                 }
-#ifdef F_SPREAD
-                if (!c1_on) {
-#pragma unroll
-                    for (int k = 0; k < 8; ++k) dma_k(tt, k);
-                }
-                // the 8 DMA instructions of the LAST step must have landed (rows / residuals the next step reads); this step's may stay in flight
-                f_wait_vm<8>();
-                FTL(6);
-#else
                 // the DMA instructions issued at the end of the last step are a whole step old: everything this wave has in flight may drain
                 f_wait_vm<0>();
                 FTL(6);
 #pragma unroll
                 for (int k = 0; k < 8; ++k) dma_k(tt, k);
                 FTL(3);
-#endif
             } else {
                 // ---------------- conv2: finish output row hprev, then accumulate output row tt - 2 from h rows tt - 3 .. tt - 1
                 const bool st_on = pend;
                 if (pend) { finish_math(); pend = false; }
-#ifndef F_SPREAD
                 if (st_on) {
 #pragma unroll
                     for (int k = 0; k < 8; ++k) store_k(k);
                 }
-#endif
                 FTL(3);
                 if (c2_on) {
                     const int ro = tt - 2;
@@ -320,19 +305,10 @@ __global__ void __launch_bounds__(512, 2) vol32_fused_kernel(const FusedParams p
                             }
                         }
                         __builtin_amdgcn_sched_barrier(0);
-#ifdef F_SPREAD
-                        if (g < 8 && st_on) { store_k(g); __builtin_amdgcn_sched_barrier(0); }
-#endif
                     }
                     pend = true; hprev = ro;
                     FTL(2);
                 }
-#ifdef F_SPREAD
-                else if (st_on) {
-#pragma unroll
-                    for (int k = 0; k < 8; ++k) store_k(k);
-                }
-#endif
             }
             sa = sa + 1 == F_ARING ? 0 : sa + 1;
             asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");      // this wave's LDS traffic (the h row) is done
