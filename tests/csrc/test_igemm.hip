@@ -1,4 +1,4 @@
-// Test-only library (libcanonswap_test.so, built by canonswap_amd/_lib.py build_test_lib): the first-generation implicit-GEMM
+// Test-only library (libcanonswap_test.so, built by canonswap_amd/_build.py build_test_lib): the first-generation implicit-GEMM
 // conv kernel, kept as an independently written cross-check of conv_halo in the operator tests (tests/test_gpu_ops.py).  It is NOT
 // linked into libcanonswap_hip.so and no product path reaches it.
 #include "conv_igemm.hip"

@@ -33,7 +33,7 @@ def undefinable_switches(root):
                     if not name.startswith("__"):
                         tested.setdefault(name, []).append(f"{os.path.relpath(path, root)}:{no}")
             no += line.count("\n") + 1
-    users = [os.path.join(root, "canonswap_amd", "_lib.py")]
+    users = [os.path.join(root, "canonswap_amd", "_build.py")]
     for sub in ("tools", "tests"):
         for d, dirs, files in os.walk(os.path.join(root, sub)):
             dirs[:] = [x for x in dirs if x not in ("golden", "__pycache__")]

@@ -15,22 +15,14 @@ import concat_ref as CR
 import parser_input_ref as PR
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-NARGS = 9      # e, B, P, S, panels, kinds, shared, out, stream
 
 
-def test_entry_point_is_declared_bound_and_exported_and_the_abi_version_stays():
-    from canonswap_amd import _lib
+def test_header_comment_cites_the_reference_and_the_engine_lists_the_entry_point():
+    """(The entry point's types, arity and export: test_abi_cpu.py.)"""
     header = open(os.path.join(ROOT, "include", "canonswap_hip.h")).read()
-    assert re.search(r"#define\s+CS_ABI_VERSION\s+4\b", header)
-    decl = {m.group(1): m.group(2) for m in re.finditer(r"\bint\s+(cs_[a-z0-9_]+)\s*\(([^)]*)\)\s*;", re.sub(r"/\*.*?\*/", "", header, flags=re.S))}
-    assert "cs_concat_frames" in decl and len(decl["cs_concat_frames"].split(",")) == NARGS, decl.get("cs_concat_frames")
     comment = re.findall(r"/\*(?:(?!\*/).)*\*/\s*int cs_concat_frames", header, flags=re.S)      # the comment right above the declaration
     assert comment and "video.py:84-109" in comment[0] and "can_swap_pipeline_e2e.py:290" in comment[0] and "can_swap_pipeline_v2i.py:328" in comment[0]
     assert ">> 16" in comment[0] and "PARITY UNPINNED" in comment[0] and "no engine scratch" in comment[0]
-    assert _lib.ABI_VERSION == 4 and "cs_concat_frames" in _lib.ABI_SYMBOLS
-    lib = _lib.load()
-    assert lib.cs_abi_version() == 4
-    assert hasattr(lib, "cs_concat_frames") and len(lib.cs_concat_frames.argtypes) == NARGS
     engine = open(os.path.join(ROOT, "canonswap_amd", "csrc", "engine.hip")).read()
     assert "cs_concat_frames" in engine.split("extern \"C\" int cs_abi_version")[0]          # the entry-point list at the top
 

@@ -116,21 +116,10 @@ def test_wrong_arguments_raise():
             crop.transform_pts(pts, m)
 
 
-# ---- the C ABI of the device step
-NARGS = 10      # e, B, frames, Ho, Wo, M_o2c, dsize, crops, I_out, stream
-
-
-def test_entry_point_is_declared_bound_and_exported_and_the_abi_version_stays():
-    from canonswap_amd import _lib
+# ---- the C ABI of the device step (its types, arity and export: test_abi_cpu.py)
+def test_header_comment_of_the_entry_point_cites_the_reference():
     header = open(os.path.join(ROOT, "include", "canonswap_hip.h")).read()
-    assert re.search(r"#define\s+CS_ABI_VERSION\s+4\b", header)
-    decl = {m.group(1): m.group(2) for m in re.finditer(r"\bint\s+(cs_[a-z0-9_]+)\s*\(([^)]*)\)\s*;", re.sub(r"/\*.*?\*/", "", header, flags=re.S))}
-    assert "cs_crop_frames" in decl and len(decl["cs_crop_frames"].split(",")) == NARGS, decl.get("cs_crop_frames")
-    assert re.search(r"crop\.py:429-455.*?cropper\.py:196-209.*?int cs_crop_frames", header, flags=re.S)      # the header comment cites the reference
-    assert _lib.ABI_VERSION == 4 and "cs_crop_frames" in _lib.ABI_SYMBOLS
-    lib = _lib.load()
-    assert lib.cs_abi_version() == 4
-    assert hasattr(lib, "cs_crop_frames") and len(lib.cs_crop_frames.argtypes) == NARGS
+    assert re.search(r"crop\.py:429-455.*?cropper\.py:196-209.*?int cs_crop_frames", header, flags=re.S)
 
 
 def test_python_names_import():

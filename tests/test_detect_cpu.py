@@ -15,7 +15,6 @@ import detect_ref as DR
 import parser_input_ref as PR
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-NARGS = {"cs_det_input": 11, "cs_det_decode": 20}
 
 
 def _bits(a):
@@ -23,17 +22,12 @@ def _bits(a):
 
 
 # ------------------------------------------------------------------------------------------------ the C ABI
-def test_entry_points_are_declared_bound_and_exported_and_the_abi_version_stays():
-    from canonswap_amd import _lib
+def test_header_comments_cite_the_reference_and_the_caps_and_the_kernel_file_are_in_place():
+    """(The entry points' types, arity and export: test_abi_cpu.py.)"""
+    from canonswap_amd import _build, _lib
     header = open(os.path.join(ROOT, "include", "canonswap_hip.h")).read()
-    assert re.search(r"#define\s+CS_ABI_VERSION\s+4\b", header)
-    decl = {m.group(1): m.group(2) for m in re.finditer(r"\bint\s+(cs_[a-z0-9_]+)\s*\(([^)]*)\)\s*;", re.sub(r"/\*.*?\*/", "", header, flags=re.S))}
-    lib = _lib.load()
-    assert lib.cs_abi_version() == 4 and _lib.ABI_VERSION == 4
     engine = open(os.path.join(ROOT, "canonswap_amd", "csrc", "engine.hip")).read()
-    for name, n in NARGS.items():
-        assert name in decl and len(decl[name].split(",")) == n, decl.get(name)
-        assert name in _lib.ABI_SYMBOLS and hasattr(lib, name) and len(getattr(lib, name).argtypes) == n
+    for name in ("cs_det_input", "cs_det_decode"):
         assert name in engine.split("extern \"C\" int cs_abi_version")[0]                # the entry-point list at the top
     comment = re.findall(r"/\*(?:(?!\*/).)*\*/\s*int cs_det_input", header, flags=re.S)[0]
     assert "scrfd.py:224-235" in comment and "scrfd.py:154" in comment and "PARITY UNPINNED" in comment and ">> 16" in comment
@@ -44,7 +38,7 @@ def test_entry_points_are_declared_bound_and_exported_and_the_abi_version_stays(
     assert int(re.search(r"#define\s+CS_DET_MAX_FACES\s+(\d+)", header).group(1)) == _lib.DET_MAX_FACES == 256
     kernel = open(os.path.join(ROOT, "canonswap_amd", "csrc", "detect.hip")).read()
     assert "#pragma clang fp contract(off)" in kernel and "fmaf" not in kernel.split("#include")[1]      # how contraction is prevented is said and done
-    assert os.path.join(_lib.CSRC, "detect.hip") in _lib.SOURCES
+    assert os.path.join(_build.CSRC, "detect.hip") in _build.SOURCES
 
 
 def test_python_names_import():

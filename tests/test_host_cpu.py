@@ -63,31 +63,20 @@ def test_build_blobs_names_and_sizes(state_dicts_np):
         assert name in blobs, name
 
 
-def test_c_abi_library_exports_every_declared_symbol():
-    from canonswap_amd import _lib
-    lib = _lib.load()
-    header = open(os.path.join(ROOT, "include", "canonswap_hip.h")).read()
-    declared = set(re.findall(r"\b(cs_[a-z0-9_]+)\s*\(", header))
-    assert declared == set(_lib.ABI_SYMBOLS)
-    for s in declared:
-        assert hasattr(lib, s), s
-    assert lib.cs_abi_version() == _lib.ABI_VERSION == 4
-
-
 def test_isa_check_of_the_hand_counted_weight_rings():
     """The objects the shipped library was linked from (canonswap_amd/build/): every untracked ring load is covered by a counted wait that
     is deep enough for it before an MFMA reads it (the check marks a register waited only when its load is older than the
     N youngest VMEM ops of `s_waitcnt vmcnt(N)`)."""
-    from canonswap_amd import _lib
-    if not os.path.isdir(_lib.OBJ_DIR) or not os.path.exists(os.path.join(_lib.OBJ_DIR, "conv_wide.o")):
+    from canonswap_amd import _build, _isa
+    if not os.path.isdir(_build.OBJ_DIR) or not os.path.exists(os.path.join(_build.OBJ_DIR, "conv_wide.o")):
         pytest.skip("no object files next to the library (prebuilt .so only)")
-    seen = _lib.isa_check()
+    seen = _isa.isa_check()
     assert len(seen) >= 70 and any("conv_wide_kernel" in k for k in seen)
 
 
 def test_isa_check_rejects_a_wait_that_is_too_shallow(tmp_path, monkeypatch):
     """A counted wait whose immediate leaves the consumed load among the outstanding ones must fail the check."""
-    from canonswap_amd import _lib
+    from canonswap_amd import _isa
     asm = """0000000000001000 <conv_wide_kernel_fake>:
 	global_load_dwordx4 v[10:13], v[0:1], off
 	global_load_dwordx4 v[14:17], v[0:1], off
@@ -106,11 +95,11 @@ def test_isa_check_rejects_a_wait_that_is_too_shallow(tmp_path, monkeypatch):
         return fake_run
 
     (tmp_path / "fake.o").write_bytes(b"")
-    monkeypatch.setattr(_lib.subprocess, "run", fake_run_factory(0))
-    assert _lib._isa_check_ring(str(tmp_path), "objdump", "fake.o", r"conv_wide_kernel_fake", 2) == {"conv_wide_kernel_fake": 2}
-    monkeypatch.setattr(_lib.subprocess, "run", fake_run_factory(1))       # vmcnt(1): the second load may still be in flight
+    monkeypatch.setattr(_isa.subprocess, "run", fake_run_factory(0))
+    assert _isa._isa_check_ring(str(tmp_path), "objdump", "fake.o", r"conv_wide_kernel_fake", 2) == {"conv_wide_kernel_fake": 2}
+    monkeypatch.setattr(_isa.subprocess, "run", fake_run_factory(1))       # vmcnt(1): the second load may still be in flight
     with pytest.raises(RuntimeError, match="no vmcnt wait"):
-        _lib._isa_check_ring(str(tmp_path), "objdump", "fake.o", r"conv_wide_kernel_fake", 2)
+        _isa._isa_check_ring(str(tmp_path), "objdump", "fake.o", r"conv_wide_kernel_fake", 2)
 
 
 @pytest.mark.skipif(torch.cuda.is_available(), reason="checks the no-GPU failure mode")

@@ -11,23 +11,15 @@ import multi_face_ref as MF
 from oracle import cv_ref as R
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-NARGS = {"cs_crop_faces": 12, "cs_paste_back_faces": 14}
 
 
-def test_entry_points_are_declared_bound_and_exported_and_the_abi_version_stays():
-    from canonswap_amd import _lib
+def test_header_cites_the_reference_and_both_entry_points_take_a_frame_index():
+    """(The entry points' types, arity and export: test_abi_cpu.py.)"""
     header = open(os.path.join(ROOT, "include", "canonswap_hip.h")).read()
-    assert re.search(r"#define\s+CS_ABI_VERSION\s+4\b", header)
     decl = {m.group(1): m.group(2) for m in re.finditer(r"\bint\s+(cs_[a-z0-9_]+)\s*\(([^)]*)\)\s*;", re.sub(r"/\*.*?\*/", "", header, flags=re.S))}
     assert re.search(r"face_detect_crop_multi\.py:63-99.*?crop\.py:515-529.*?int cs_crop_faces", header, flags=re.S)      # the comment cites the reference
-    assert _lib.ABI_VERSION == 4
-    lib = _lib.load()
-    assert lib.cs_abi_version() == 4
-    for name, n in NARGS.items():
-        assert name in decl and len(decl[name].split(",")) == n, decl.get(name)
+    for name in ("cs_crop_faces", "cs_paste_back_faces"):
         assert "frame_index" in decl[name]
-        assert name in _lib.ABI_SYMBOLS
-        assert hasattr(lib, name) and len(getattr(lib, name).argtypes) == n
 
 
 def test_python_names_import():

@@ -185,22 +185,15 @@ def test_build_blobs_takes_the_optional_parser(sd_np, blobs):
 
 
 def test_abi_declares_the_parser_entry_points():
-    from canonswap_amd import _lib
+    from canonswap_amd import _build
     hdr = open(os.path.join(ROOT, "include", "canonswap_hip.h")).read()
-    assert "#define CS_ABI_VERSION 4" in hdr and _lib.ABI_VERSION == 4
-    for name in ENTRY_POINTS:
-        assert name in _lib.ABI_SYMBOLS, name
+    for name in ENTRY_POINTS:          # (their types, arity and export: test_abi_cpu.py)
         assert re.search(r"\*/\s*(?:enum[^;]*;\s*)?int " + name + r"\(", hdr, re.S), f"{name}: no declaration with a comment above it"
     eng = open(os.path.join(ROOT, "canonswap_amd", "csrc", "engine.hip")).read()
     head = eng[:eng.index('extern "C" int cs_abi_version')]
     for name in ENTRY_POINTS[:2]:
         assert name in head, f"{name}: not in the entry-point list at the top of engine.hip"
-    assert any(s.endswith("parser.hip") for s in _lib.SOURCES)
-    if os.path.exists(_lib.LIB_PATH):
-        import ctypes
-        lib = ctypes.CDLL(_lib.LIB_PATH)
-        for name in ENTRY_POINTS:
-            assert hasattr(lib, name), f"{name}: not exported"
+    assert any(s.endswith("parser.hip") for s in _build.SOURCES)
 
 
 def test_synthetic_weights_are_not_degenerate(sd_np, cfg, pv, f64):

@@ -5,9 +5,9 @@ import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
-from canonswap_amd import _lib  # noqa: E402
+from canonswap_amd import _build  # noqa: E402
 
 name, flags = sys.argv[1], sys.argv[2:]
 os.makedirs(os.path.join(ROOT, "ab"), exist_ok=True)
 out = os.path.join(ROOT, "ab", name + ".so")
-print(_lib.build(lib_path=out, extra_flags=flags, obj_dir=os.path.join(ROOT, "canonswap_amd", "build_" + name)))
+print(_build.build(lib_path=out, extra_flags=flags, obj_dir=os.path.join(ROOT, "canonswap_amd", "build_" + name)))
