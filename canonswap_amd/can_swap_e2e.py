@@ -308,6 +308,17 @@ class can_swapper(object):
     def paste_back_faces(self, crops, masks_crop, M_c2o, frame_index, imgs_ori, out=None):      # crop.py:515-529 once per face of a frame, in order
         return tail.paste_back_faces(self.engine, crops, masks_crop, M_c2o, frame_index, imgs_ori, out=out)
 
+    def swap_video(self, frames, lmk, source_id=None, *, driver=None, **kw):
+        """The pipeline's loop over a whole video (can_swap_pipeline_e2e.py:155-319), host frames in, host frames out, the copies overlapped
+        with the generator: video.VideoSwapper.swap_video (kw: out, slots, frame_index, masks, parse, logits_fn, the crop's configuration).
+        driver: a VideoSwapper of this swapper (its batch, chain and slots); without one a default driver is made once and kept."""
+        from . import video
+        if driver is None:
+            driver = getattr(self, "_video", None)
+            if driver is None:
+                driver = self._video = video.VideoSwapper(self)
+        return driver.swap_video(frames, lmk, source_id, **kw)
+
     # ---- stages
     def extract_feature_3d(self, x: torch.Tensor) -> torch.Tensor:                      # (:165-172)
         return self.engine.extract_feature_3d(x)

@@ -31,6 +31,9 @@ Several faces per frame, or none (frame_index: the frame of each face, non-decre
 frames_out = chain(c["crops"], None, c["M_c2o"], frames, slots=slot_of_face, parse=True, frame_index=fi)["frames"] - F frames in, F frames out,
 every face of a frame pasted in order in one pass, a frame without a face returned as it came.
 
+Frames that start and end in host memory - a whole video: video.VideoSwapper drives this loop in batches, with the upload of the next batch and
+the download of the last one beside the generator (video.py).
+
 AnimateChain below is the same for the second program, inference_v2i.py (src/can_swap_pipeline_v2i.py: one source image animated by a
 driving video, the driving identity swapped in); its table stands in the class's docstring.
 
