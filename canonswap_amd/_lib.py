@@ -9,6 +9,8 @@ from __future__ import annotations
 import ctypes as C
 import os
 
+import torch          # before the library is loaded, see load()
+
 from ._build import LIB_PATH, TEST_LIB_PATH
 
 ABI_VERSION = 4          # CS_ABI_VERSION of include/canonswap_hip.h
@@ -50,7 +52,7 @@ ABI = {
     "cs_create": (ci, [ci, ci, pvp]),
     "cs_destroy": (None, [vp]),
     "cs_last_error": (C.c_char_p, []),
-    "cs_abi_version": (ci, []),
+    "cs_abi_version": (ci, []),          # the one c_int that is a value, not a status (STATUS below)
     "cs_upload": (ci, [vp, C.c_char_p, vp, C.c_size_t]),
     "cs_finalize_weights": (ci, [vp]),
     "cs_set_identity": (ci, [vp, ci, vp, vp]),
@@ -132,6 +134,11 @@ ABI = {
     "cs_op_parser_upadd": (ci, [vp, vp, vp, vp, vp, ci, ci, ci, ci, vp]),
     "cs_op_parser_read": (ci, [vp, ci, ci, vp, vp]),
 }
+STATUS = frozenset(name for name, (restype, _) in ABI.items() if restype is ci and name != "cs_abi_version")      # 0, or the text is in cs_last_error()
+# The header's stream parameters are all the last one, `void* stream`; every entry has one but these (tests/test_abi_cpu.py reads the names).
+TAKES_STREAM = frozenset(ABI) - {"cs_create", "cs_destroy", "cs_last_error", "cs_abi_version", "cs_upload", "cs_finalize_weights", "cs_set_latency_mode",
+                                 "cs_profile_begin", "cs_profile_end", "cs_profile_exec_flops", "cs_op_chan_stats_partial_floats", "cs_op_g_stop"}
+_PTR_SLOTS = {name: tuple(t in (vp, C.c_char_p) or issubclass(t, C._Pointer) for t in argtypes) for name, (_, argtypes) in ABI.items()}      # or a number
 del vp, ci, cf, cl, cd, pi, pd, pvp
 ABI_SYMBOLS = list(ABI)
 # tests only; an A/B build of an older tree - CANONSWAP_LIB, tools/cmp_libs.py - has none of the three: load() binds them where they exist
@@ -151,8 +158,7 @@ def load():
     # The process must hold ONE HIP runtime.  This package's callers pass torch tensors and torch's stream, and torch carries its own
     # libamdhip64 / libhsa-runtime64: imported first, its copies satisfy this library's NEEDED entries too.  Loaded the other way round (this
     # library first - `python __graft_entry__.py smoke`, whose build() checks the ABI before anything imports torch) the system runtime and
-    # torch's both initialise and cs_create sees 0 devices.
-    import torch  # noqa: F401
+    # torch's both initialise and cs_create sees 0 devices.  Hence the import of torch at the top of this module.
     lib = C.CDLL(LIB_PATH)
     if lib.cs_abi_version() != ABI_VERSION:
         raise RuntimeError(f"{LIB_PATH} speaks C-ABI version {lib.cs_abi_version()}, this package binds version {ABI_VERSION} "
@@ -184,3 +190,24 @@ def load_test_lib():
 def check(rc: int, what: str):
     if rc != 0:
         raise RuntimeError(f"{what} failed: {load().cs_last_error().decode(errors='replace')}")
+
+
+def call(name, *args, what=None, device=None):
+    """The one way into the library: entry point `name` of ABI with exactly its arguments, checked before the library is touched.  A torch tensor
+    stands for its address: in a pointer slot only, and only from a GPU (device=: from that one); None is NULL; the rest goes to ctypes as it is
+    (contiguity and dtype are the caller's).  A nonzero status raises RuntimeError("<what or name> failed: <cs_last_error>"); values are returned."""
+    argtypes = ABI[name][1]
+    if len(args) != len(argtypes):
+        raise TypeError(f"{name} takes {len(argtypes)} arguments, {len(args)} given")
+    args = list(args)
+    for i, a in enumerate(args):
+        if isinstance(a, torch.Tensor):
+            if not _PTR_SLOTS[name][i]:
+                raise TypeError(f"{name}: argument {i} is a tensor where the entry point takes a number")
+            if not a.is_cuda or (device is not None and a.device != device):
+                raise TypeError(f"{name}: argument {i} is a tensor on {a.device}, not on {device or 'a GPU'}: its address means nothing to the kernels")
+            args[i] = C.c_void_p(a.data_ptr())
+    r = getattr(load(), name)(*args)
+    if r != 0 and name in STATUS:
+        check(r, what or name)
+    return r

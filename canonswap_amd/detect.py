@@ -22,7 +22,7 @@ import numpy as np
 import torch
 
 from . import _lib, align
-from .engine import Engine, _ptr
+from .engine import Engine
 
 DET_MEAN, DET_STD = 127.5, 128.0                    # SCRFD.input_mean / input_std (scrfd.py:107-108)
 LAYOUTS = {3: ((8, 16, 32), 2), 5: ((8, 16, 32, 64, 128), 1)}      # levels -> (strides, anchors per cell) (scrfd.py:114-131)
@@ -108,8 +108,7 @@ def det_input(e: Engine, frames, det_size=(640, 640), swap_rb=SWAP_RB, mean=DET_
     t = t.to(e.device).contiguous()
     blob = e._out(out, (F, 3, Hd, Wd), torch.float32)
     lut = _det_lut_on(e, mean, std)
-    with torch.cuda.device(e.device):
-        _lib.check(e.lib.cs_det_input(e.h, F, _ptr(t), Ho, Wo, Hd, Wd, int(bool(swap_rb)), _ptr(lut), _ptr(blob), e._stream()), "cs_det_input")
+    e._call("cs_det_input", F, t, Ho, Wo, Hd, Wd, int(bool(swap_rb)), lut, blob)
     return blob
 
 
@@ -163,10 +162,8 @@ def det_decode(e: Engine, outs, det_size, det_scale, frame_hw, det_thresh=0.5, n
     kps = torch.empty((F, max_faces, 5, 2), dtype=torch.float32, device=e.device) if has_kps else None
     count = torch.empty((F,), dtype=torch.int32, device=e.device)
     ptrs = (C.c_void_p * (3 * n_levels))(*([t.data_ptr() for t in ts] + [None] * (3 * n_levels - len(ts))))
-    with torch.cuda.device(e.device):
-        _lib.check(e.lib.cs_det_decode(e.h, F, n_levels, (C.c_int * n_levels)(*strides), na, ptrs, Hd, Wd, float(det_scale), float(det_thresh),
-                                       float(nms_thresh), max_num, int(metric == "max"), Ho, Wo, max_faces, _ptr(det), _ptr(kps), _ptr(count),
-                                       e._stream()), "cs_det_decode")
+    e._call("cs_det_decode", F, n_levels, (C.c_int * n_levels)(*strides), na, ptrs, Hd, Wd, float(det_scale), float(det_thresh),
+            float(nms_thresh), max_num, int(metric == "max"), Ho, Wo, max_faces, det, kps, count)
     cnt = count.cpu().numpy()
     for f, c in enumerate(cnt):
         if c == -1:

@@ -27,19 +27,18 @@ class Engine:
         self.lib = _lib.load()
         self.device = torch.device(f"cuda:{device_id}")
         self.max_batch = max_batch
-        h = C.c_void_p()
-        _lib.check(self.lib.cs_create(device_id, max_batch, C.byref(h)), "cs_create")
-        self.h = h
+        self.h = C.c_void_p()
+        _lib.call("cs_create", device_id, max_batch, C.byref(self.h))
         self.latency_mode = bool(latency_mode)
         if latency_mode:         # BASELINE configs[1]: the one-frame forms (conv_lat, split-K, 2-row volume segments; see cs_set_latency_mode)
-            _lib.check(self.lib.cs_set_latency_mode(h, 1), "cs_set_latency_mode")
+            self._call("cs_set_latency_mode", 1)
         self._ids = []            # resident identities: [slot, device copy (512,), last tensor seen, its _version, use tick]
         self._tick = 0
         self.parser_cfg = None    # geometry of the face parser the loaded blobs hold ("P.cfg"), or None
 
     def close(self):
         if getattr(self, "h", None):
-            self.lib.cs_destroy(self.h)
+            _lib.call("cs_destroy", self.h)
             self.h = None
 
     def __del__(self):
@@ -58,8 +57,8 @@ class Engine:
         (bench.py packs on rank 0 and hands the blobs over through /dev/shm)."""
         for name, arr in blobs.items():
             arr = np.ascontiguousarray(arr)
-            _lib.check(self.lib.cs_upload(self.h, name.encode(), arr.ctypes.data_as(C.c_void_p), arr.nbytes), f"cs_upload({name})")
-        _lib.check(self.lib.cs_finalize_weights(self.h), "cs_finalize_weights")
+            self._call("cs_upload", name.encode(), arr.ctypes.data_as(C.c_void_p), arr.nbytes, what=f"cs_upload({name})")
+        self._call("cs_finalize_weights")
         self._ids = []
         if "P.cfg" in blobs:
             c = [int(v) for v in np.asarray(blobs["P.cfg"]).reshape(-1)]
@@ -67,6 +66,14 @@ class Engine:
 
     def _stream(self):
         return C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+
+    def _call(self, name, *args, what=None):
+        """Entry point `name` on this engine: the handle first, torch's current stream of the engine's device last where the entry point takes
+        one, tensors from that device only (_lib.call), under the package's one device guard (the C side keeps its own)."""
+        if name in _lib.TAKES_STREAM:
+            args += (self._stream(),)
+        with torch.cuda.device(self.device):
+            return _lib.call(name, self.h, *args, what=what, device=self.device)
 
     def _in(self, t, shape_tail=None):
         if not isinstance(t, torch.Tensor):
@@ -105,8 +112,7 @@ class Engine:
         if sid.shape[0] != 1:
             raise ValueError("set_identity takes one identity; pass several rows to swap()/swap_frames() instead")
         sid = sid[0].contiguous().clone()
-        with torch.cuda.device(self.device):
-            _lib.check(self.lib.cs_set_identity(self.h, slot, _ptr(sid), self._stream()), "cs_set_identity")
+        self._call("cs_set_identity", slot, sid)
         self._ids = [r for r in self._ids if r[0] != slot]
         self._multi = None
         self._tick += 1
@@ -174,7 +180,7 @@ class Engine:
     def extract_feature_3d(self, img):
         img = self._in(img, (3, 256, 256))
         out = self._new(img.shape[0], 32, 16, 64, 64)
-        _lib.check(self.lib.cs_extract_feature_3d(self.h, img.shape[0], _ptr(img), _ptr(out), self._stream()), "cs_extract_feature_3d")
+        self._call("cs_extract_feature_3d", img.shape[0], img, out)
         return out
 
     def warp(self, f, kp_source, kp_driving):
@@ -182,7 +188,7 @@ class Engine:
         self._same_batch(f, ks, kd)
         B = f.shape[0]
         out, occ = self._new(B, 32, 16, 64, 64), self._new(B, 1, 64, 64)
-        _lib.check(self.lib.cs_warp(self.h, B, _ptr(f), _ptr(ks), _ptr(kd), _ptr(out), _ptr(occ), self._stream()), "cs_warp")
+        self._call("cs_warp", B, f, ks, kd, out, occ)
         return out, occ
 
     def warp_out(self, f, occ=None):
@@ -191,7 +197,7 @@ class Engine:
         occ = None if occ is None else self._in(occ, (1, 64, 64))
         self._same_batch(f, occ)
         seg = self._new(B, 256, 64, 64)
-        _lib.check(self.lib.cs_warp_out(self.h, B, _ptr(f), _ptr(occ), _ptr(seg), self._stream()), "cs_warp_out")
+        self._call("cs_warp_out", B, f, occ, seg)
         return seg
 
     def swap(self, f, source_id=None):
@@ -200,13 +206,13 @@ class Engine:
         B = f.shape[0]
         slots = self.identity_slots(source_id, B) if source_id is not None else self._default_slots(B)
         out = self._new(*f.shape)
-        _lib.check(self.lib.cs_swap_ids(self.h, self._slot_array(slots), B, _ptr(f), _ptr(out), self._stream()), "cs_swap_ids")
+        self._call("cs_swap_ids", self._slot_array(slots), B, f, out)
         return out
 
     def refine(self, f):
         f = self._in(f, (32, 16, 64, 64))
         out = self._new(*f.shape)
-        _lib.check(self.lib.cs_refine(self.h, f.shape[0], _ptr(f), _ptr(out), self._stream()), "cs_refine")
+        self._call("cs_refine", f.shape[0], f, out)
         return out
 
     def warp_forward(self, f, kp_driving, kp_source):
@@ -214,14 +220,13 @@ class Engine:
         self._same_batch(f, ks, kd)
         B = f.shape[0]
         occ, deform, seg = self._new(B, 1, 64, 64), self._new(B, 16, 64, 64, 3), self._new(B, 256, 64, 64)
-        _lib.check(self.lib.cs_warp_forward(self.h, B, _ptr(f), _ptr(kd), _ptr(ks), _ptr(occ), _ptr(deform), _ptr(seg),
-                                            self._stream()), "cs_warp_forward")
+        self._call("cs_warp_forward", B, f, kd, ks, occ, deform, seg)
         return {"occlusion_map": occ, "deformation": deform, "out": seg}
 
     def spade_decode(self, seg):
         seg = self._in(seg, (256, 64, 64))
         img = self._new(seg.shape[0], 3, 512, 512)
-        _lib.check(self.lib.cs_spade_decode(self.h, seg.shape[0], _ptr(seg), _ptr(img), self._stream()), "cs_spade_decode")
+        self._call("cs_spade_decode", seg.shape[0], seg, img)
         return img
 
     def motion_extract(self, img):
@@ -241,21 +246,21 @@ class Engine:
         B = raw.shape[0]
         x_t, x_can = (self._out(o, (B, 21, 3), torch.float32) for o in (out if out is not None else (None, None)))
         rot = self._new(B, 3, 3) if want_rot else None
-        _lib.check(self.lib.cs_motion_keypoints(self.h, B, _ptr(raw), _ptr(x_t), _ptr(x_can), _ptr(rot), self._stream()), "cs_motion_keypoints")
+        self._call("cs_motion_keypoints", B, raw, x_t, x_can, rot)
         return (x_t, x_can, rot) if want_rot else (x_t, x_can)
 
     def motion_extract_raw(self, img, out=None):
         """cs_motion_extract without the per-head split: (B, 328) fp32."""
         img = self._in(img, (3, 256, 256))
         out = self._out(out, (img.shape[0], 328), torch.float32)
-        _lib.check(self.lib.cs_motion_extract(self.h, img.shape[0], _ptr(img), _ptr(out), self._stream()), "cs_motion_extract")
+        self._call("cs_motion_extract", img.shape[0], img, out)
         return out
 
     def pack_u8(self, img):
         img = self._in(img)
         B, _, H, W = img.shape
         out = self._new(B, H, W, 3, dtype=torch.uint8)
-        _lib.check(self.lib.cs_pack_u8(self.h, B, _ptr(img), _ptr(out), H, W, self._stream()), "cs_pack_u8")
+        self._call("cs_pack_u8", B, img, out, H, W)
         return out
 
     def unpack_u8(self, img_u8):
@@ -266,7 +271,7 @@ class Engine:
         t = t.to(self.device).contiguous()
         B, H, W, _ = t.shape
         out = self._new(B, 3, H, W)
-        _lib.check(self.lib.cs_unpack_u8(self.h, B, _ptr(t), _ptr(out), H, W, self._stream()), "cs_unpack_u8")
+        self._call("cs_unpack_u8", B, t, out, H, W)
         return out
 
     def swap_frames(self, img, x_t, x_can, source_id=None, want_f32=True, want_u8=False, debug=False,
@@ -289,8 +294,7 @@ class Engine:
         out_u8 = self._out(out_u8, (B, 512, 512, 3), torch.uint8) if (want_u8 or out_u8 is not None) else None
         rec = self._out(out_rec, (B, 3, 512, 512), torch.float32) if (debug or out_rec is not None) else None
         swp = self._out(out_swap, (B, 3, 512, 512), torch.float32) if (debug or out_swap is not None) else None
-        _lib.check(self.lib.cs_swap_frames_ids(self.h, self._slot_array(slots), B, _ptr(img), _ptr(x_t), _ptr(x_can), _ptr(out_f32),
-                                               _ptr(out_u8), _ptr(rec), _ptr(swp), self._stream()), "cs_swap_frames_ids")
+        self._call("cs_swap_frames_ids", self._slot_array(slots), B, img, x_t, x_can, out_f32, out_u8, rec, swp)
         res = {"out": out_f32, "out_u8": out_u8}
         if debug or rec is not None or swp is not None:
             res.update(rec_can=rec, swap_can=swp)
@@ -306,8 +310,7 @@ class Engine:
             raise ValueError("f and kp_source must hold 1 or B entries")
         out_f32 = self._out(out_f32, (B, 3, 512, 512), torch.float32) if (want_f32 or out_f32 is not None) else None
         out_u8 = self._out(out_u8, (B, 512, 512, 3), torch.uint8) if (want_u8 or out_u8 is not None) else None
-        _lib.check(self.lib.cs_animate_frames(self.h, B, _ptr(f), f.shape[0], _ptr(kp_source), kp_source.shape[0], _ptr(kp_driving),
-                                              _ptr(out_f32), _ptr(out_u8), self._stream()), "cs_animate_frames")
+        self._call("cs_animate_frames", B, f, f.shape[0], kp_source, kp_source.shape[0], kp_driving, out_f32, out_u8)
         return {"out": out_f32, "out_u8": out_u8}
 
     def resize_half_bilinear(self, img, out=None):
@@ -320,7 +323,7 @@ class Engine:
         if B < 1 or Cc < 1 or H < 2 or W < 2 or H % 2 or W % 2:
             raise ValueError(f"resize_half_bilinear: H and W must be even and the tensor not empty, got {tuple(img.shape)}")
         out = self._out(out, (B, Cc, H // 2, W // 2), torch.float32)
-        _lib.check(self.lib.cs_resize_half_bilinear(self.h, B, Cc, _ptr(img), H, W, _ptr(out), self._stream()), "cs_resize_half_bilinear")
+        self._call("cs_resize_half_bilinear", B, Cc, img, H, W, out)
         return out
 
     def motion_keypoints_driven(self, raw_driving, raw_pose, kp, out=None):
@@ -335,8 +338,7 @@ class Engine:
         raw_pose = raw_pose.to(self.device).contiguous().float()
         kp = kp.to(self.device).contiguous().float()
         x_t = self._out(out, (B, 21, 3), torch.float32)
-        _lib.check(self.lib.cs_motion_keypoints_driven(self.h, B, _ptr(raw_driving), _ptr(raw_pose), _ptr(kp), _ptr(x_t), self._stream()),
-                   "cs_motion_keypoints_driven")
+        self._call("cs_motion_keypoints_driven", B, raw_driving, raw_pose, kp, x_t)
         return x_t
 
     # ---------------------------------------------------------------- identity network (getid)
@@ -372,11 +374,10 @@ class Engine:
     def _identity(self, B, img, u8, lut, H, W, normalize, want_raw, out):
         idn = self._out(out, (B, 512), torch.float32) if normalize else None
         raw = (self._out(None if normalize else out, (B, 512), torch.float32)) if (want_raw or not normalize) else None
-        with torch.cuda.device(self.device):
-            if u8 is None:
-                _lib.check(self.lib.cs_identity(self.h, B, _ptr(img), H, W, _ptr(idn), _ptr(raw), self._stream()), "cs_identity")
-            else:
-                _lib.check(self.lib.cs_identity_u8(self.h, B, _ptr(u8), H, W, _ptr(lut), _ptr(idn), _ptr(raw), self._stream()), "cs_identity_u8")
+        if u8 is None:
+            self._call("cs_identity", B, img, H, W, idn, raw)
+        else:
+            self._call("cs_identity_u8", B, u8, H, W, lut, idn, raw)
         if normalize:
             return (idn, raw) if want_raw else idn
         return raw
@@ -385,7 +386,7 @@ class Engine:
         """cs_op_identity_read: activation `which` (0 stem, 1-4 layer1-4, 5 pre-fc) of the last identity pass as fp32 NCHW (tests)."""
         shape = [(64, 55, 55), (64, 55, 55), (128, 28, 28), (256, 14, 14), (512, 7, 7), (512, 7, 7)][which]
         dst = self._new(B, *shape)
-        _lib.check(self.lib.cs_op_identity_read(self.h, which, B, _ptr(dst), self._stream()), "cs_op_identity_read")
+        self._call("cs_op_identity_read", which, B, dst)
         return dst
 
     # ---------------------------------------------------------------- face parser (SegFormer)
@@ -407,8 +408,7 @@ class Engine:
         if H % 32 or W % 32:
             raise ValueError(f"parser: H = {H}, W = {W} (each a multiple of 32)")
         logits = self._out(out, (B, self.parser_cfg["L"], H // 4, W // 4), torch.float32)
-        with torch.cuda.device(self.device):
-            _lib.check(self.lib.cs_parser(self.h, B, _ptr(pv), H, W, _ptr(logits), self._stream()), "cs_parser")
+        self._call("cs_parser", B, pv, H, W, logits)
         return logits
 
     def parser_read(self, which: int, B: int, H: int, W: int):
@@ -419,17 +419,16 @@ class Engine:
         c = self.parser_cfg
         shape = (c["D"], H // 4, W // 4) if which == 4 else (c["widths"][which], H >> (which + 2), W >> (which + 2))
         dst = self._new(B, *shape)
-        _lib.check(self.lib.cs_op_parser_read(self.h, which, B, _ptr(dst), self._stream()), "cs_op_parser_read")
+        self._call("cs_op_parser_read", which, B, dst)
         return dst
 
     # ---------------------------------------------------------------- measurement
     def profile_begin(self):
-        _lib.check(self.lib.cs_profile_begin(self.h), "cs_profile_begin")
+        self._call("cs_profile_begin")
 
     def profile_end(self):
-        ms, cnt, fl = (C.c_double * 3)(), (C.c_long * 3)(), C.c_double()
-        _lib.check(self.lib.cs_profile_end(self.h, ms, cnt, C.byref(fl)), "cs_profile_end")
-        ex = C.c_double()
-        _lib.check(self.lib.cs_profile_exec_flops(self.h, C.byref(ex)), "cs_profile_exec_flops")
+        ms, cnt, fl, ex = (C.c_double * 3)(), (C.c_long * 3)(), C.c_double(), C.c_double()
+        self._call("cs_profile_end", ms, cnt, C.byref(fl))
+        self._call("cs_profile_exec_flops", C.byref(ex))
         return {"exec_flops": ex.value,"conv_ms": ms[0], "other_ms": ms[1], "warp_ms": ms[2], "conv_launches": cnt[0], "other_launches": cnt[1],
                 "warp_launches": cnt[2], "conv_flops": fl.value}

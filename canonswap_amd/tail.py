@@ -30,9 +30,8 @@ import ctypes as C
 import numpy as np
 import torch
 
-from . import _lib
 from . import crop as crop_geometry
-from .engine import Engine, _ptr
+from .engine import Engine
 
 
 def _m6(M, B=None):
@@ -86,8 +85,7 @@ def face_masks(e: Engine, logits, valid=FACE_VALID, size=(512, 512), out=None, w
     want_labels = want_labels or out_labels is not None
     masks = e._out(out, (B, H, W), torch.uint8)
     labels = e._out(out_labels, (B, H, W), torch.uint8) if want_labels else None
-    with torch.cuda.device(e.device):
-        _lib.check(e.lib.cs_face_masks(e.h, B, Cn, _ptr(t), h, w, s, bits, _ptr(masks), _ptr(labels), e._stream()), "cs_face_masks")
+    e._call("cs_face_masks", B, Cn, t, h, w, s, bits, masks, labels)
     return {"masks": masks, "labels": labels} if want_labels else masks
 
 
@@ -179,8 +177,7 @@ def parser_input(e: Engine, crops_u8, halve=None, mean=PARSER_MEAN, std=PARSER_S
     pv = e._out(out, (B, 3, Ho, Wo), torch.float32)
     u8 = e._out(out_u8, (B, Ho, Wo, 3), torch.uint8) if want_u8 else None
     lut = _parser_lut_on(e, mean, std, rescale)
-    with torch.cuda.device(e.device):
-        _lib.check(e.lib.cs_parser_input(e.h, B, _ptr(t), H, W, int(halve), _ptr(lut), _ptr(pv), _ptr(u8), e._stream()), "cs_parser_input")
+    e._call("cs_parser_input", B, t, H, W, int(halve), lut, pv, u8)
     return {"pixel_values": pv, "resized_u8": u8} if want_u8 else pv
 
 
@@ -235,9 +232,7 @@ def concat_frames(e: Engine, panels, kinds=None, shared=None, out=None):
     ts = [t.to(e.device).contiguous() for t in ts]
     out = e._out(out, (B, S, P * S, 3), torch.uint8)
     ptrs = (C.c_void_p * P)(*[t.data_ptr() for t in ts])
-    with torch.cuda.device(e.device):
-        _lib.check(e.lib.cs_concat_frames(e.h, B, P, S, ptrs, (C.c_int * P)(*kinds), (C.c_int * P)(*shared), _ptr(out), e._stream()),
-                   "cs_concat_frames")
+    e._call("cs_concat_frames", B, P, S, ptrs, (C.c_int * P)(*kinds), (C.c_int * P)(*shared), out)
     return out
 
 
@@ -262,9 +257,7 @@ class SoftErosion:
         N, _, H, W = m.shape
         soft = torch.empty_like(m)
         hard = torch.empty((N, 1, H, W), dtype=torch.uint8, device=e.device)
-        with torch.cuda.device(e.device):
-            _lib.check(e.lib.cs_soft_erosion(e.h, N, H, W, _ptr(m), _ptr(self.weight), self.kernel_size, float(self.threshold),
-                                             self.iterations, _ptr(soft), _ptr(hard), e._stream()), "cs_soft_erosion")
+        e._call("cs_soft_erosion", N, H, W, m, self.weight, self.kernel_size, float(self.threshold), self.iterations, soft, hard)
         return soft, hard.bool()
 
     forward = __call__
@@ -285,9 +278,7 @@ def soft_erosion_frames(e: Engine, masks, weight, kernel_size=21, threshold=0.9,
     out = e._out(out, (B, H, W), torch.float32)
     if weight.dtype != torch.float32 or weight.numel() != kernel_size * kernel_size or not weight.is_contiguous() or weight.device != e.device:
         raise ValueError("weight must be the contiguous kernel_size x kernel_size fp32 kernel on the engine's device")
-    with torch.cuda.device(e.device):
-        _lib.check(e.lib.cs_soft_erosion_frames(e.h, B, H, W, _ptr(m), int(m.dtype == torch.uint8), _ptr(weight), kernel_size, float(threshold),
-                                                iterations, _ptr(out), None, e._stream()), "cs_soft_erosion_frames")
+    e._call("cs_soft_erosion_frames", B, H, W, m, int(m.dtype == torch.uint8), weight, kernel_size, float(threshold), iterations, out, None)
     return out
 
 
@@ -304,9 +295,7 @@ def paste_back_batch(e: Engine, crops, masks_crop, M_c2o, imgs_ori, out=None):
         raise ValueError("masks_crop must be (B, Hc, Wc) and imgs_ori must hold B frames")
     mm, mp = _m6(M_c2o, B)
     out = e._out(out, ori.shape, torch.uint8)
-    with torch.cuda.device(e.device):
-        _lib.check(e.lib.cs_paste_back_batch(e.h, B, _ptr(crops), _ptr(mc), crops.shape[1], crops.shape[2], mp,
-                                             _ptr(ori), _ptr(out), ori.shape[1], ori.shape[2], e._stream()), "cs_paste_back_batch")
+    e._call("cs_paste_back_batch", B, crops, mc, crops.shape[1], crops.shape[2], mp, ori, out, ori.shape[1], ori.shape[2])
     return out
 
 
@@ -326,9 +315,7 @@ def paste_back_shared(e: Engine, crops, M_c2o, img_ori, mask_ori, out=None):
     B = crops.shape[0]
     out = e._out(out, (B,) + tuple(ori.shape), torch.uint8)
     mm, mp = _m6(M_c2o)
-    with torch.cuda.device(e.device):
-        _lib.check(e.lib.cs_paste_back_shared(e.h, B, _ptr(crops), crops.shape[1], crops.shape[2], _ptr(mo), mp, _ptr(ori), _ptr(out),
-                                              ori.shape[0], ori.shape[1], e._stream()), "cs_paste_back_shared")
+    e._call("cs_paste_back_shared", B, crops, crops.shape[1], crops.shape[2], mo, mp, ori, out, ori.shape[0], ori.shape[1])
     return out
 
 
@@ -345,8 +332,7 @@ def warp_affine_u8(e: Engine, img, M, dsize):
     Wd, Hd = int(dsize[0]), int(dsize[1])
     dst = torch.empty((Hd, Wd, 3), dtype=torch.uint8, device=e.device)
     m, mp = _m6(M)
-    with torch.cuda.device(e.device):
-        _lib.check(e.lib.cs_warp_affine_u8(e.h, _ptr(src), src.shape[0], src.shape[1], mp, _ptr(dst), Hd, Wd, e._stream()), "cs_warp_affine_u8")
+    e._call("cs_warp_affine_u8", src, src.shape[0], src.shape[1], mp, dst, Hd, Wd)
     return dst
 
 
@@ -357,8 +343,7 @@ def prepare_paste_back(e: Engine, mask_crop, crop_M_c2o, dsize):
     Wd, Hd = int(dsize[0]), int(dsize[1])
     dst = torch.empty((Hd, Wd), dtype=torch.float32, device=e.device)
     mm, mp = _m6(crop_M_c2o)
-    with torch.cuda.device(e.device):
-        _lib.check(e.lib.cs_warp_affine_f32(e.h, _ptr(m), m.shape[0], m.shape[1], mp, _ptr(dst), Hd, Wd, e._stream()), "cs_warp_affine_f32")
+    e._call("cs_warp_affine_f32", m, m.shape[0], m.shape[1], mp, dst, Hd, Wd)
     return dst
 
 
@@ -370,9 +355,7 @@ def paste_back(e: Engine, img_crop, M_c2o, img_ori, mask_ori):
         raise ValueError("mask_ori must have the size of img_ori")
     out = torch.empty_like(ori)
     mm, mp = _m6(M_c2o)
-    with torch.cuda.device(e.device):
-        _lib.check(e.lib.cs_paste_back(e.h, _ptr(crop), None, _ptr(mo), crop.shape[0], crop.shape[1], mp, _ptr(ori), _ptr(out),
-                                       ori.shape[0], ori.shape[1], e._stream()), "cs_paste_back")
+    e._call("cs_paste_back", crop, None, mo, crop.shape[0], crop.shape[1], mp, ori, out, ori.shape[0], ori.shape[1])
     return out
 
 
@@ -384,9 +367,7 @@ def paste_back_fused(e: Engine, img_crop, mask_crop, M_c2o, img_ori):
         raise ValueError("mask_crop must have the size of img_crop")
     out = torch.empty_like(ori)
     mm, mp = _m6(M_c2o)
-    with torch.cuda.device(e.device):
-        _lib.check(e.lib.cs_paste_back(e.h, _ptr(crop), _ptr(mc), None, crop.shape[0], crop.shape[1], mp, _ptr(ori), _ptr(out),
-                                       ori.shape[0], ori.shape[1], e._stream()), "cs_paste_back")
+    e._call("cs_paste_back", crop, mc, None, crop.shape[0], crop.shape[1], mp, ori, out, ori.shape[0], ori.shape[1])
     return out
 
 
@@ -401,8 +382,7 @@ def prepare_crops(e: Engine, crops_u8, out=None) -> torch.Tensor:
     t = t.to(e.device).contiguous()
     B, H, W, _ = t.shape
     out = e._out(out, (B, 3, 256, 256), torch.float32)
-    with torch.cuda.device(e.device):
-        _lib.check(e.lib.cs_prepare_crops(e.h, B, _ptr(t), H, W, _ptr(out), e._stream()), "cs_prepare_crops")
+    e._call("cs_prepare_crops", B, t, H, W, out)
     return out
 
 
@@ -421,8 +401,7 @@ def crop_frames_M(e: Engine, frames, M_o2c, dsize, out=None, want_I=False, out_I
     want_I = want_I or out_I is not None
     crops = e._out(out, (B, dsize, dsize, 3), torch.uint8)
     I = e._out(out_I, (B, 3, 256, 256), torch.float32) if want_I else None
-    with torch.cuda.device(e.device):
-        _lib.check(e.lib.cs_crop_frames(e.h, B, _ptr(fr), fr.shape[1], fr.shape[2], mp, dsize, _ptr(crops), _ptr(I), e._stream()), "cs_crop_frames")
+    e._call("cs_crop_frames", B, fr, fr.shape[1], fr.shape[2], mp, dsize, crops, I)
     return {"crops": crops, "I": I} if want_I else {"crops": crops}
 
 
@@ -477,9 +456,7 @@ def crop_faces_M(e: Engine, frames, M_o2c, frame_index, dsize, out=None, want_I=
     want_I = want_I or out_I is not None
     crops = e._out(out, (B, dsize, dsize, 3), torch.uint8)
     I = e._out(out_I, (B, 3, 256, 256), torch.float32) if want_I else None
-    with torch.cuda.device(e.device):
-        _lib.check(e.lib.cs_crop_faces(e.h, B, F, _ptr(fr), fr.shape[1], fr.shape[2], _index_ptr(idx), mp, dsize, _ptr(crops), _ptr(I), e._stream()),
-                   "cs_crop_faces")
+    e._call("cs_crop_faces", B, F, fr, fr.shape[1], fr.shape[2], _index_ptr(idx), mp, dsize, crops, I)
     return {"crops": crops, "I": I} if want_I else {"crops": crops}
 
 
@@ -514,10 +491,8 @@ def paste_back_faces(e: Engine, crops, masks_crop, M_c2o, frame_index, imgs_ori,
         raise ValueError(f"M_c2o must be (B,2,3) or (B,3,3) for the {B} faces, got {tuple(np.shape(M_c2o))}")
     mm, mp = _m6(M_c2o, B) if B else (None, None)
     out = e._out(out, ori.shape, torch.uint8)
-    with torch.cuda.device(e.device):
-        _lib.check(e.lib.cs_paste_back_faces(e.h, B, F, _ptr(crops) if B else None, _ptr(mc) if B else None, crops.shape[1], crops.shape[2],
-                                             _index_ptr(idx) if B else None, mp, _ptr(ori), _ptr(out), ori.shape[1], ori.shape[2], e._stream()),
-                   "cs_paste_back_faces")
+    e._call("cs_paste_back_faces", B, F, crops if B else None, mc if B else None, crops.shape[1], crops.shape[2],
+            _index_ptr(idx) if B else None, mp, ori, out, ori.shape[1], ori.shape[2])
     return out
 
 

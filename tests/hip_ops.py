@@ -9,8 +9,9 @@ from canonswap_amd import _lib, pack
 ACT = {"none": 0, "relu": 1, "lrelu": 2, "sigmoid": 3, "gelu": 4}
 
 
-def _p(t):
-    return C.c_void_p(0 if t is None else t.data_ptr())
+def op(name, *args):
+    """A handle-less operator hook on torch's current stream (tensors: any GPU tensor, _lib.call)"""
+    return _lib.call(name, *args, C.c_void_p(torch.cuda.current_stream().cuda_stream))
 
 
 def strides_cl(t):
@@ -23,7 +24,6 @@ def conv(x, wpacked, cout_pad, cout, k, *, cin=None, bias=None, bias2=None, act0
          pixscale=None, ps_stride=1, out0=None, s2=None, t2=None, act1="none", slope1=0.0, out1=None, stats=None,
          mode=0, cfg=-1, up_shift=0, tile=(0, 0), out_dims=None, ck=0, xcd_map=None, ragged=False, hilo=False, stat_out=None, xf=None, ep_general=False, pool_hw=False):
     """x: [N, D, H, W, C] fp16 view (C contiguous). out0/out1/res: 5-D channels-last views. k = (KD, KH, KW)."""
-    lib = _lib.load()
     d = _lib.ConvDesc()
     N, D, H, W = out_dims if out_dims is not None else x.shape[:4]
     d.in_ = x.data_ptr()
@@ -67,30 +67,25 @@ def conv(x, wpacked, cout_pad, cout, k, *, cin=None, bias=None, bias2=None, act0
         for k in ("y", "res", "out", "stats", "gamma", "beta"):
             setattr(d, "xf_" + k, 0 if xf.get(k) is None else xf[k].data_ptr())
         d.xf_slope = xf.get("slope", 0.0)
-    st = C.c_void_p(torch.cuda.current_stream().cuda_stream)
     if -1 <= cfg <= 3:        # the independently written cross-check kernel (tests/csrc/conv_igemm.hip, test-only library)
         tl = _lib.load_test_lib()
-        if tl.cs_test_conv_igemm(C.byref(d), st) != 0:
+        if tl.cs_test_conv_igemm(C.byref(d), C.c_void_p(torch.cuda.current_stream().cuda_stream)) != 0:
             raise RuntimeError("cs_test_conv_igemm failed: " + tl.cs_test_last_error().decode(errors="replace"))
         return
-    _lib.check(lib.cs_op_conv(C.byref(d), st), "cs_op_conv")
+    op("cs_op_conv", C.byref(d))
 
 
 def t_mask(x, wpacked, bias):
     """x: [N, H, W, 512] fp16 -> sigmoid(conv3x3(x) + bias[0]) as [N, H, W] fp32 (cs_op_t_mask writes at stride 4)"""
-    lib = _lib.load()
     N, H, W, _ = x.shape
     out = torch.full((N, H, W, 4), -1.0, dtype=torch.float32, device=x.device)
-    st = C.c_void_p(torch.cuda.current_stream().cuda_stream)
-    _lib.check(lib.cs_op_t_mask(_p(x), _p(wpacked), _p(bias), _p(out), N, H, W, st), "cs_op_t_mask")
+    op("cs_op_t_mask", x, wpacked, bias, out, N, H, W)
     return out
 
 
 def pair_ragged(wpacked, cout_pad, cin, k):
     """In place: the engine's load-time re-packing of the last chunk of a Cin % 32 == 16 layer (paired taps)."""
-    lib = _lib.load()
-    st = C.c_void_p(torch.cuda.current_stream().cuda_stream)
-    _lib.check(lib.cs_op_pair_ragged(C.c_void_p(wpacked.data_ptr()), cout_pad, (cin + 31) // 32, k[0], k[1], k[2], st), "cs_op_pair_ragged")
+    op("cs_op_pair_ragged", wpacked, cout_pad, (cin + 31) // 32, k[0], k[1], k[2])
     return wpacked
 
 
@@ -99,24 +94,20 @@ def packed_weight(w, cout_pad, device):
 
 
 def grid_sample(inp_hwdc, grid):
-    lib = _lib.load()
     N, H, W, D, Cc = inp_hwdc.shape
     out32 = torch.empty_like(inp_hwdc)
     out16 = torch.empty(inp_hwdc.shape, dtype=torch.float16, device=inp_hwdc.device)
-    st = C.c_void_p(torch.cuda.current_stream().cuda_stream)
-    _lib.check(lib.cs_op_grid_sample3d(_p(inp_hwdc), _p(grid), _p(out32), _p(out16), N, D, H, W, st), "cs_op_grid_sample3d")
+    op("cs_op_grid_sample3d", inp_hwdc, grid, out32, out16, N, D, H, W)
     return out32, out16
 
 
 def chan_stats(x, eps=1e-5, with_partials=False):
     """x: [N, P, C] fp16/fp32 contiguous -> [N, C, 2] = (mean, 1/sqrt(var + eps)), biased variance
     (with_partials: also the first pass's partial sums [N, blocks, C, 2])."""
-    lib = _lib.load()
     N, P, Cc = x.shape
     stats = torch.zeros(N, Cc, 2, dtype=torch.float32, device=x.device)
-    part = torch.empty(lib.cs_op_chan_stats_partial_floats(N, P, Cc), dtype=torch.float32, device=x.device)
-    st = C.c_void_p(torch.cuda.current_stream().cuda_stream)
-    _lib.check(lib.cs_op_chan_stats(_p(x), int(x.dtype == torch.float32), N, P, Cc, eps, _p(part), _p(stats), st), "cs_op_chan_stats")
+    part = torch.empty(_lib.call("cs_op_chan_stats_partial_floats", N, P, Cc), dtype=torch.float32, device=x.device)
+    op("cs_op_chan_stats", x, int(x.dtype == torch.float32), N, P, Cc, eps, part, stats)
     return (stats, part.view(N, -1, Cc, 2)) if with_partials else stats
 
 
@@ -129,16 +120,12 @@ def rel_err(a, b):
 M_PW1, M_PW2, M_DS = 0, 1, 2
 
 
-def _st():
-    return C.c_void_p(torch.cuda.current_stream().cuda_stream)
-
-
 def m_stem(img, w, b, g, be):
     """img fp32 [N, 3, HI, WI] -> x fp32 [N, HI/4, WI/4, 96]"""
     assert img.is_contiguous()
     N, _, HI, WI = img.shape
     x = torch.empty(N, HI // 4, WI // 4, 96, dtype=torch.float32, device=img.device)
-    _lib.check(_lib.load().cs_op_m_stem(_p(img), _p(w), _p(b), _p(g), _p(be), _p(x), N, HI, WI, _st()), "cs_op_m_stem")
+    op("cs_op_m_stem", img, w, b, g, be, x, N, HI, WI)
     return x
 
 
@@ -146,7 +133,7 @@ def m_dwln(x, wt, b, g, be, y):
     """x fp32 [N, H, W, C] -> y (caller's fp16 buffer of N H W 2C values): split(LayerNorm(dwconv7x7(x)))"""
     assert x.is_contiguous() and y.is_contiguous()
     N, H, W, Cc = x.shape
-    _lib.check(_lib.load().cs_op_m_dwln(_p(x), _p(wt), _p(b), _p(g), _p(be), _p(y), N, H, W, Cc, _st()), "cs_op_m_dwln")
+    op("cs_op_m_dwln", x, wt, b, g, be, y, N, H, W, Cc)
     return y
 
 
@@ -155,7 +142,7 @@ def m_ln_s2d(x, g, be):
     assert x.is_contiguous()
     N, H, W, Cc = x.shape
     y = torch.empty(N, H // 2, W // 2, 8 * Cc, dtype=torch.float16, device=x.device)
-    _lib.check(_lib.load().cs_op_m_ln_s2d(_p(x), _p(g), _p(be), _p(y), N, H, W, Cc, _st()), "cs_op_m_ln_s2d")
+    op("cs_op_m_ln_s2d", x, g, be, y, N, H, W, Cc)
     return y
 
 
@@ -166,7 +153,7 @@ def m_grn(h, gamma, beta):
     sumsq = torch.empty(N * 16 * Cc, dtype=torch.float32, device=h.device)
     scale = torch.empty(N * Cc, dtype=torch.float32, device=h.device)
     out = torch.empty(N, P, 2 * Cc, dtype=torch.float16, device=h.device)
-    _lib.check(_lib.load().cs_op_m_grn(_p(h), _p(gamma), _p(beta), _p(sumsq), _p(scale), _p(out), N, P, Cc, _st()), "cs_op_m_grn")
+    op("cs_op_m_grn", h, gamma, beta, sumsq, scale, out, N, P, Cc)
     return out
 
 
@@ -175,7 +162,7 @@ def m_head(x, g, be, hw, hb):
     assert x.is_contiguous()
     N, P, _ = x.shape
     out = torch.empty(N, 328, dtype=torch.float32, device=x.device)
-    _lib.check(_lib.load().cs_op_m_head(_p(x), _p(g), _p(be), _p(hw), _p(hb), _p(out), N, P, _st()), "cs_op_m_head")
+    op("cs_op_m_head", x, g, be, hw, hb, out, N, P)
     return out
 
 
@@ -184,8 +171,7 @@ def m_pointwise(engine, form, x, wpacked, bias, out, C_stage):
     out fp32 [N, H, H, Cout] (form M_PW2: holds the residual and is updated in place)."""
     assert x.is_contiguous() and out.is_contiguous()
     N, H = x.shape[0], x.shape[1]
-    _lib.check(engine.lib.cs_op_m_pointwise(engine.h, form, _p(x), _p(wpacked), _p(bias), _p(out), N, H, C_stage, _st()),
-               "cs_op_m_pointwise")
+    engine._call("cs_op_m_pointwise", form, x, wpacked, bias, out, N, H, C_stage)
     return out
 
 
@@ -211,7 +197,7 @@ def dm_compress(f_hwdc, w, b, comp):
     """f fp32 [N, H, W, D, 32] -> comp (caller's fp16 buffer [N, D, H, W, 4])"""
     assert f_hwdc.is_contiguous() and comp.is_contiguous()
     N, Hh, Ww, D, _ = f_hwdc.shape
-    _lib.check(_lib.load().cs_op_dm_compress(_p(f_hwdc), _p(w), _p(b), _p(comp), N, D, Hh, Ww, _st()), "cs_op_dm_compress")
+    op("cs_op_dm_compress", f_hwdc, w, b, comp, N, D, Hh, Ww)
     return comp
 
 
@@ -219,23 +205,21 @@ def dm_sparse(comp, kp_d, kp_s, out, N, shared_comp=False, shared_kps=False):
     """comp fp16 [1 or N, D, H, W, 4] -> out [N, D, H, W, ostride] fp16 view whose channels [0, 112) receive dm_sparse's output"""
     assert comp.is_contiguous() and kp_d.is_contiguous() and kp_s.is_contiguous()
     _, D, Hh, Ww, _ = comp.shape
-    _lib.check(_lib.load().cs_op_dm_sparse(_p(comp), int(shared_comp), _p(kp_d), _p(kp_s), int(shared_kps), _p(out), out.stride(3),
-                                           N, D, Hh, Ww, _st()), "cs_op_dm_sparse")
+    op("cs_op_dm_sparse", comp, int(shared_comp), kp_d, kp_s, int(shared_kps), out, out.stride(3), N, D, Hh, Ww)
     return out
 
 
 def dm_softmax_warp(part, bias, kp_d, kp_s, inp, N, D, Hh, Ww, shared_kps=False, shared_in=False, out32=None, out16=None, deform=None):
     """part: compact-2 fp32 [N, D, H, W/4, 10, 22]; inp fp32 HWDC [1 or N, H, W, D, 32]"""
     assert part.is_contiguous() and inp.is_contiguous()
-    _lib.check(_lib.load().cs_op_dm_softmax_warp(_p(part), _p(bias), _p(kp_d), _p(kp_s), int(shared_kps), _p(inp), int(shared_in), _p(out32),
-                                                 _p(out16), _p(deform), N, D, Hh, Ww, _st()), "cs_op_dm_softmax_warp")
+    op("cs_op_dm_softmax_warp", part, bias, kp_d, kp_s, int(shared_kps), inp, int(shared_in), out32, out16, deform, N, D, Hh, Ww)
 
 
 def occ_finish(part, taps, bias, occ):
     """part fp32 [N, H, W, 64 (taps 49) or 16 (taps 7)] -> occ (caller's fp32 buffer [N, H, W])"""
     assert part.is_contiguous() and occ.is_contiguous()
     N, Hh, Ww, _ = part.shape
-    _lib.check(_lib.load().cs_op_occ_finish(_p(part), taps, float(bias), _p(occ), N, Hh, Ww, _st()), "cs_op_occ_finish")
+    op("cs_op_occ_finish", part, taps, float(bias), occ, N, Hh, Ww)
     return occ
 
 
@@ -251,7 +235,7 @@ def dm_read(engine, which, B):
         out = torch.empty(B, 16, 64, 64, 144, dtype=torch.float16, device=dev)
     else:
         out = torch.empty(B, 16, 64, 16, 10, 22, dtype=torch.float32, device=dev)
-    _lib.check(engine.lib.cs_op_dm_read(engine.h, which, B, _p(out), _st()), "cs_op_dm_read")
+    engine._call("cs_op_dm_read", which, B, out)
     return out
 
 
@@ -299,19 +283,19 @@ def g_read(engine, which, B, out=None):
     if out is None:
         out = torch.empty(shape, dtype=torch.float32 if which == G_STATS else torch.float16, device=engine.device)
     assert out.is_contiguous() and tuple(out.shape) == shape
-    _lib.check(engine.lib.cs_op_g_read(engine.h, which, B, _p(out), _st()), "cs_op_g_read")
+    engine._call("cs_op_g_read", which, B, out)
     return out
 
 
 def g_fill(engine, B):
-    _lib.check(engine.lib.cs_op_g_fill(engine.h, B, _st()), "cs_op_g_fill")
+    engine._call("cs_op_g_fill", B)
 
 
 def g_decode(engine, seg, img, stop=0):
     """cs_spade_decode into the caller's img [B, 3, 512, 512] fp32, returning after its stop-th launch (0: all of it)"""
     assert seg.is_contiguous() and img.is_contiguous() and seg.dtype == img.dtype == torch.float32
-    _lib.check(engine.lib.cs_op_g_stop(engine.h, stop), "cs_op_g_stop")
-    _lib.check(engine.lib.cs_spade_decode(engine.h, seg.shape[0], _p(seg), _p(img), _st()), "cs_spade_decode")
+    engine._call("cs_op_g_stop", stop)
+    engine._call("cs_spade_decode", seg.shape[0], seg, img)
     return img
 
 
@@ -322,14 +306,14 @@ T_WSET, T_STYLE = 0, 1
 def t_style(idv, fc, style, nlayers):
     """idv fp32 [512], fc fp32 nlayers x (2 * (512 * 512 + 512)) -> style (caller's fp32 buffer of nlayers * 512 values)"""
     assert idv.is_contiguous() and fc.is_contiguous() and style.is_contiguous()
-    _lib.check(_lib.load().cs_op_t_style(_p(idv), _p(fc), _p(style), nlayers, _st()), "cs_op_t_style")
+    op("cs_op_t_style", idv, fc, style, nlayers)
     return style
 
 
 def t_modulate(wraw, style, packed):
     """wraw fp32 [512, 9, 512], style fp32 [512] -> the modulated rows of packed (caller's fp16 buffer [144, 1024, 32])"""
     assert wraw.is_contiguous() and style.is_contiguous() and packed.is_contiguous()
-    _lib.check(_lib.load().cs_op_t_modulate(_p(wraw), _p(style), _p(packed), _st()), "cs_op_t_modulate")
+    op("cs_op_t_modulate", wraw, style, packed)
     return packed
 
 
@@ -337,7 +321,7 @@ def t_read(engine, layer, slot, which):
     """The slot's fused weight set fp16 [144, 1024, 32] (T_WSET) or the layer's last style vector fp32 [512] (T_STYLE) of a live engine"""
     out = torch.empty((144, 1024, 32), dtype=torch.float16, device=engine.device) if which == T_WSET else \
         torch.empty(512, dtype=torch.float32, device=engine.device)
-    _lib.check(engine.lib.cs_op_t_read(engine.h, layer, slot, which, _p(out), _st()), "cs_op_t_read")
+    engine._call("cs_op_t_read", layer, slot, which, out)
     return out
 
 
@@ -347,7 +331,7 @@ def t_layer(engine, layer, slots, x16, res32, tmask, out16, out32):
     B = x16.shape[0]
     assert len(slots) == B and all(t is None or t.is_contiguous() for t in (x16, res32, tmask, out16, out32))
     arr = (C.c_int * B)(*[int(s) for s in slots])
-    _lib.check(engine.lib.cs_op_t_layer(engine.h, layer, B, arr, _p(x16), _p(res32), _p(tmask), _p(out16), _p(out32), _st()), "cs_op_t_layer")
+    engine._call("cs_op_t_layer", layer, B, arr, x16, res32, tmask, out16, out32)
 
 
 def t_rows(kind):

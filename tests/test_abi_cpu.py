@@ -73,6 +73,12 @@ def render_header(text):
     return lines
 
 
+def stream_entries(text):
+    """The header's prototypes whose last parameter is named `stream`."""
+    text = re.sub(r"//[^\n]*", " ", re.sub(r"/\*.*?\*/", " ", text, flags=re.S))
+    return {name for name, params in re.findall(r"\b(cs_\w+)\s*\(([^)]*)\)\s*;", text) if re.search(r"\bstream\s*$", params)}
+
+
 def _ctypes_class(t, owner):
     if t in CTYPES_CLASS:
         return CTYPES_CLASS[t]
@@ -144,10 +150,21 @@ DOCTORED = {      # name that must be reported -> (pattern, replacement) applied
     "cs_op_id_se_tail": (r"(int cs_op_id_se_tail\(const float\* out, )long sN, long sH, long sW", r"\1int sN, int sH, int sW"),
     "slope0": (r"int act0; float slope0;", r"float slope0; int act0;"),      # (both keep their class: only the order tells)
     "ps_stride": (r" int ps_stride;", r""),
+    "cs_pack_u8": (r"(int cs_pack_u8\([^)]*void\* )stream\)", r"\1st)"),      # (every class stays: only the stream comparison tells)
 }
+RENAMED_STREAM = "cs_pack_u8"
 
 
-@pytest.mark.parametrize("name", list(DOCTORED))
+def test_the_marked_entries_are_the_headers_stream_parameters(header):
+    from canonswap_amd import _lib
+    assert stream_entries(header) == set(_lib.TAKES_STREAM) and len(_lib.TAKES_STREAM) == 72
+    assert all(_lib.ABI[name][1][-1] is C.c_void_p for name in _lib.TAKES_STREAM)
+    bad = _sub(*DOCTORED[RENAMED_STREAM], header)
+    assert render_header(bad) == render_header(header)
+    assert set(_lib.TAKES_STREAM) - stream_entries(bad) == {RENAMED_STREAM} and not stream_entries(bad) - set(_lib.TAKES_STREAM)
+
+
+@pytest.mark.parametrize("name", [n for n in DOCTORED if n != RENAMED_STREAM])
 def test_the_check_can_fail(header, name):
     from canonswap_amd import _lib
     pattern, repl = DOCTORED[name]

@@ -257,9 +257,8 @@ def test_640_the_candidate_cap_is_met_exactly(engine):
     count = torch.zeros(2, dtype=torch.int32, device="cuda")                             # through the C ABI: -1 for the frame over the cap only
     det = torch.zeros((2, 8, 5), device="cuda")
     ptrs = (C.c_void_p * 9)(*[t.data_ptr() for t in outs])
-    rc = engine.lib.cs_det_decode(engine.h, 2, 3, (C.c_int * 3)(8, 16, 32), 2, ptrs, 640, 640, 1.0, 0.5, 0.4, 5, 0, 640, 640, 8, C.c_void_p(det.data_ptr()),
-                                  None, C.c_void_p(count.data_ptr()), engine._stream())
-    assert rc == 0 and count.tolist() == [5, -1]
+    engine._call("cs_det_decode", 2, 3, (C.c_int * 3)(8, 16, 32), 2, ptrs, 640, 640, 1.0, 0.5, 0.4, 5, 0, 640, 640, 8, det, None, count)
+    assert count.tolist() == [5, -1]
 
 
 def test_640_the_survivor_cap_is_met_exactly(engine):

@@ -125,13 +125,10 @@ def test_valid_sets(eng):
     assert torch.equal(tail.face_masks(eng, lg, valid=odd, size=size).cpu(), torch.isin(labels, torch.tensor(odd)).to(torch.uint8))
     assert torch.equal(tail.face_masks(eng, lg, valid=odd + (19, 25, 31), size=size), tail.face_masks(eng, lg, valid=odd, size=size))      # bits >= C
     # masks alone, labels alone (straight through the C entry point: the Python wrapper always asks for masks) and both: the same bytes
-    import ctypes as C
-    from canonswap_amd.engine import _ptr
     only_l = torch.full((3, 20, 28), 99, dtype=torch.uint8, device=eng.device)
     only_m = torch.full((3, 20, 28), 99, dtype=torch.uint8, device=eng.device)
-    st = C.c_void_p(torch.cuda.current_stream().cuda_stream)
-    assert eng.lib.cs_face_masks(eng.h, 3, 19, _ptr(lg), 5, 7, 4, tail.valid_bits(tail.FACE_VALID), None, _ptr(only_l), st) == 0
-    assert eng.lib.cs_face_masks(eng.h, 3, 19, _ptr(lg), 5, 7, 4, tail.valid_bits(tail.FACE_VALID), _ptr(only_m), None, st) == 0
+    eng._call("cs_face_masks", 3, 19, lg, 5, 7, 4, tail.valid_bits(tail.FACE_VALID), None, only_l)
+    eng._call("cs_face_masks", 3, 19, lg, 5, 7, 4, tail.valid_bits(tail.FACE_VALID), only_m, None)
     assert torch.equal(only_l, both["labels"]) and torch.equal(only_m, both["masks"])
 
 

@@ -6,7 +6,6 @@ Tolerance of every comparison with the network in it: relative L2 error per row 
 and linear layers; the engine also stores activations and the folded BatchNorm scales in fp16 - about one more rounding of that size per
 layer - and sums in another order.  tests/test_identity_cpu.py shows that real mistakes are more than 10 x above this bound.
 The kernels alone have bounds from their number formats, stated where they are used."""
-import ctypes as C
 
 import numpy as np
 import pytest
@@ -15,17 +14,10 @@ import torch.nn.functional as F
 
 import identity_ref as R
 from chain_helpers import _occupy
+from hip_ops import op
 
 pytestmark = pytest.mark.gpu
 FACTOR = 4.0
-
-
-def _p(t):
-    return C.c_void_p(0 if t is None else t.data_ptr())
-
-
-def _st():
-    return C.c_void_p(torch.cuda.current_stream().cuda_stream)
 
 
 # ------------------------------------------------------------------------------------------------ shared inputs and references (computed once)
@@ -125,8 +117,7 @@ def _rand(shape, seed, lo=-1.0, hi=1.0):
 def test_conv_alone(case):
     """fp16 operands, fp32 accumulation of K = taps x Cin products (four partial sums, added in order): |error| <= (K + 4) 2^-24 sum |a w| in
     the worst case, plus the output's own rounding (fp32: 2^-24, fp16: 2^-11).  Odd extents, stride 2, more than one workgroup along both axes."""
-    from canonswap_amd import _lib, pack
-    lib = _lib.load()
+    from canonswap_amd import pack
     N, IH, IW, Cin, Cout, K, stride, pad, in_f32, out_f32, act = {
         "3x3_s2_odd": (2, 9, 7, 64, 128, 3, 2, 1, 0, 1, False),
         "1x1_s2_f32": (1, 13, 13, 64, 128, 1, 2, 0, 1, 1, False),
@@ -143,9 +134,7 @@ def test_conv_alone(case):
     OH, OW = (IH + 2 * pad - K) // stride + 1, (IW + 2 * pad - K) // stride + 1
     out = torch.full((N, OH, OW, Cout), float("nan"), dtype=torch.float32 if out_f32 else torch.float16, device="cuda")
     bd, sd = b.cuda(), slope.cuda()          # named: a temporary's block would be handed to the next allocation while the pointer is still in use
-    rc = lib.cs_op_id_conv(_p(xin), in_f32, N, IH, IW, Cin, K, stride, pad, _p(wp), _p(bd), Cout, _p(sd) if act else None, _p(out),
-                           out_f32, _st())
-    assert rc == 0, lib.cs_last_error()
+    op("cs_op_id_conv", xin, in_f32, N, IH, IW, Cin, K, stride, pad, wp, bd, Cout, sd if act else None, out, out_f32)
     x64, w64 = x.half().double(), w.half().double()
     want = F.conv2d(x64, w64, b.double(), stride=stride, padding=pad)
     mag = F.conv2d(x64.abs(), w64.abs(), stride=stride, padding=pad) + b.double().abs()[None, :, None, None]
@@ -159,16 +148,13 @@ def test_conv_alone(case):
 
 def test_maxpool_alone():
     """110 -> 55: the maximum is exact; the fp16 copy is fp16(fma(x, s, t))."""
-    from canonswap_amd import _lib
-    lib = _lib.load()
     B, IH, IW, Cc = 2, 110, 110, 64
     x = _rand((B, IH, IW, Cc), 5, -3, 3)
     s, t = _rand((Cc,), 6, 0.5, 1.5), _rand((Cc,), 7)
     xo = torch.empty((B, 55, 55, Cc), dtype=torch.float32, device="cuda")
     ao = torch.empty((B, 55, 55, Cc), dtype=torch.float16, device="cuda")
     xd, sd, td = x.cuda(), s.cuda(), t.cuda()
-    rc = lib.cs_op_id_maxpool(_p(xd), _p(sd), _p(td), _p(xo), _p(ao), B, IH, IW, Cc, _st())
-    assert rc == 0, lib.cs_last_error()
+    op("cs_op_id_maxpool", xd, sd, td, xo, ao, B, IH, IW, Cc)
     want = F.max_pool2d(x.permute(0, 3, 1, 2), 2, 2).permute(0, 2, 3, 1)
     assert torch.equal(xo.cpu(), want)
     a64 = want.double() * s.double() + t.double()
@@ -181,8 +167,6 @@ def test_se_and_block_tail_alone(Cc, E, strided):
     """SE gate + tail on a dense map, and on the even positions of a stride-1 map of odd extent 2E - 1.  Bounds: the fp32 mean of P values is
     within P 2^-24 mean|v| of the exact one in the worst case (P <= 3025: 1.8e-4); two unit-gain linear layers and the sigmoid (slope <= 1/4)
     carry at most that into the gate: |se - ref| <= 1e-4.  x = prelu(out se + res): 1e-4 |out| + 2^-22 (|out| + |res|); the fp16 copy adds 2^-11."""
-    from canonswap_amd import _lib
-    lib = _lib.load()
     B, R_ = 2, Cc // 16
     full = 2 * E - 1 if strided else E
     step = 2 if strided else 1
@@ -198,9 +182,7 @@ def test_se_and_block_tail_alone(Cc, E, strided):
     g = [v.cuda() for v in (big, w1, b1, w2, b2, slopes, res, s, t)]
     sW = Cc * step
     sH = full * Cc * step
-    rc = lib.cs_op_id_se_tail(_p(g[0]), full * full * Cc, sH, sW, B, E, E, Cc, _p(g[1]), _p(g[2]), _p(g[3]), _p(g[4]), _p(g[5]), _p(g[6]), _p(g[7]),
-                              _p(g[8]), _p(se), _p(xo), _p(ao), _st())
-    assert rc == 0, lib.cs_last_error()
+    op("cs_op_id_se_tail", g[0], full * full * Cc, sH, sW, B, E, E, Cc, g[1], g[2], g[3], g[4], g[5], g[6], g[7], g[8], se, xo, ao)
     o = big[:, ::step, ::step].double()
     assert o.shape[1] == E
     y = F.linear(o.mean(dim=(1, 2)), w1.double(), b1.double())
@@ -221,8 +203,6 @@ def test_se_and_block_tail_alone(Cc, E, strided):
 def test_embedding_alone(B):
     """fc over 49 slices of 512 products each, fp32: |error| <= (512 + 49 + 1) 2^-24 sum |a w| in the worst case; the normalised rows equal
     F.normalize of the raw ones to fp32 rounding (512-term sum of squares: 2^-15 relative is generous by 100 x)."""
-    from canonswap_amd import _lib
-    lib = _lib.load()
     a = _rand((B, 49, 512), 20, -3, 3).half()
     w = _rand((49, 512, 512), 21, -0.011, 0.011).half()
     bias = _rand((512,), 22)
@@ -230,8 +210,7 @@ def test_embedding_alone(B):
     raw = torch.empty((B, 512), dtype=torch.float32, device="cuda")
     idn = torch.empty((B, 512), dtype=torch.float32, device="cuda")
     ad, wd, bd = a.cuda(), w.cuda(), bias.cuda()
-    rc = lib.cs_op_id_embed(_p(ad), _p(wd), _p(bd), _p(part), _p(raw), _p(idn), B, _st())
-    assert rc == 0, lib.cs_last_error()
+    op("cs_op_id_embed", ad, wd, bd, part, raw, idn, B)
     want = torch.einsum("bpc,poc->bo", a.double(), w.double()) + bias.double()
     mag = torch.einsum("bpc,poc->bo", a.double().abs(), w.double().abs()) + bias.double().abs()
     err = (raw.double().cpu() - want).abs()
@@ -240,7 +219,7 @@ def test_embedding_alone(B):
     n = F.normalize(raw.double(), p=2, dim=1).cpu()
     assert float((idn.double().cpu() - n).abs().max()) <= 2.0 ** -15 * float(n.abs().max())
     raw2 = torch.empty_like(raw)
-    assert lib.cs_op_id_embed(_p(ad), _p(wd), _p(bd), _p(part), _p(raw2), None, B, _st()) == 0
+    op("cs_op_id_embed", ad, wd, bd, part, raw2, None, B)
     assert torch.equal(raw, raw2)
 
 
@@ -365,27 +344,26 @@ def test_an_injected_module_keeps_precedence_and_can_move_onto_the_engine(swappe
 
 def test_bad_arguments_are_refused_before_any_launch(swapper, imgs):
     eng = swapper.engine
-    lib = eng.lib
     x = imgs[:1].cuda()
     out = torch.full((4, 512), 7.0, device="cuda")
     lut = torch.zeros((3, 256), device="cuda")
     u8 = torch.zeros((1, 8, 8, 3), dtype=torch.uint8, device="cuda")
     bad = [
-        lambda: lib.cs_identity(eng.h, 0, _p(x), 112, 112, _p(out), None, _st()),
-        lambda: lib.cs_identity(eng.h, 5, _p(x), 112, 112, _p(out), None, _st()),
-        lambda: lib.cs_identity(eng.h, 1, _p(x), 0, 112, _p(out), None, _st()),
-        lambda: lib.cs_identity(eng.h, 1, _p(x), 112, -3, _p(out), None, _st()),
-        lambda: lib.cs_identity(eng.h, 1, None, 112, 112, _p(out), None, _st()),
-        lambda: lib.cs_identity(eng.h, 1, _p(x), 112, 112, None, None, _st()),
-        lambda: lib.cs_identity(None, 1, _p(x), 112, 112, _p(out), None, _st()),
-        lambda: lib.cs_identity_u8(eng.h, 1, _p(u8), 8, 8, None, _p(out), None, _st()),
-        lambda: lib.cs_identity_u8(eng.h, 1, None, 8, 8, _p(lut), _p(out), None, _st()),
-        lambda: lib.cs_op_identity_read(eng.h, 9, 1, _p(out), _st()),
+        ("cs_identity", eng.h, 0, x, 112, 112, out, None),
+        ("cs_identity", eng.h, 5, x, 112, 112, out, None),
+        ("cs_identity", eng.h, 1, x, 0, 112, out, None),
+        ("cs_identity", eng.h, 1, x, 112, -3, out, None),
+        ("cs_identity", eng.h, 1, None, 112, 112, out, None),
+        ("cs_identity", eng.h, 1, x, 112, 112, None, None),
+        ("cs_identity", None, 1, x, 112, 112, out, None),
+        ("cs_identity_u8", eng.h, 1, u8, 8, 8, None, out, None),
+        ("cs_identity_u8", eng.h, 1, None, 8, 8, lut, out, None),
+        ("cs_op_identity_read", eng.h, 9, 1, out),
     ]
     eng.identity(x)
-    for i, f in enumerate(bad):
-        assert f() != 0, i
-        assert len(lib.cs_last_error()) > 10, i
+    for name, *args in bad:
+        with pytest.raises(RuntimeError, match=rf"(?s){name} failed: .{{11}}"):      # a message of more than 10 characters
+            op(name, *args)
     torch.cuda.synchronize()
     assert bool((out == 7.0).all())
     with pytest.raises(ValueError):

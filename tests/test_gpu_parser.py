@@ -5,8 +5,6 @@ Tolerance of every comparison with the network in it: at most 4 x the distance o
 same input (measured here on the CPU; a property of the restatement, never of the engine) - relative L2 per image for the logits and the
 stage outputs, and max-abs over max |logit| for the logits.  The emulation rounds only the operands of the matmuls; the engine also stores
 activations in fp16 and sums in another order.  tests/test_parser_cpu.py shows that real mistakes are more than 10 x above this bound."""
-import ctypes as C
-
 import numpy as np
 import pytest
 import torch
@@ -14,19 +12,12 @@ import torch
 import chain_helpers
 import parser_ref as R
 from chain_helpers import _affine
+from hip_ops import op
 
 pytestmark = pytest.mark.gpu
 FACTOR = 4.0
 HEADS = {"num_attention_heads": [1, 2, 5, 8]}
 H0, W0 = 64, 96
-
-
-def _p(t):
-    return C.c_void_p(0 if t is None else t.data_ptr())
-
-
-def _st():
-    return C.c_void_p(torch.cuda.current_stream().cuda_stream)
 
 
 @pytest.fixture(scope="module")
@@ -143,30 +134,31 @@ def test_product_extent(swapper, sd_np, cfg):
 
 # ------------------------------------------------------------------------------------------------ refusals, each before any launch
 def test_refusals(swapper, state_dicts):
-    from canonswap_amd import _lib
     from canonswap_amd.engine import Engine
-    lib = _lib.load()
     e = swapper.engine
     x = torch.zeros(1, 3, 96, 96, device="cuda")
     out = torch.full((1, 19, 24, 24), 7.0, device="cuda")
-    err = lambda: lib.cs_last_error().decode()
-    assert lib.cs_parser(e.h, 1, _p(x), 72, 96, _p(out), _st()) != 0 and "multiple of 32" in err()
-    assert lib.cs_parser(e.h, 0, _p(x), 96, 96, _p(out), _st()) != 0 and "batch 0" in err()
-    assert lib.cs_parser(e.h, 10, _p(x), 96, 96, _p(out), _st()) != 0 and "batch 10" in err()
-    assert lib.cs_parser(e.h, 1, None, 96, 96, _p(out), _st()) != 0 and "NULL" in err()
-    assert lib.cs_parser(e.h, 1, _p(x), 96, 96, None, _st()) != 0 and "NULL" in err()
-    assert lib.cs_parser(e.h, 1, _p(x), 544, 512, _p(out), _st()) != 0 and "exceeds" in err()
-    assert lib.cs_parser(None, 1, _p(x), 96, 96, _p(out), _st()) != 0
+
+    def refused(word, *args):
+        with pytest.raises(RuntimeError, match=word):
+            op(*args)
+    refused("multiple of 32", "cs_parser", e.h, 1, x, 72, 96, out)
+    refused("batch 0", "cs_parser", e.h, 0, x, 96, 96, out)
+    refused("batch 10", "cs_parser", e.h, 10, x, 96, 96, out)
+    refused("NULL", "cs_parser", e.h, 1, None, 96, 96, out)
+    refused("NULL", "cs_parser", e.h, 1, x, 96, 96, None)
+    refused("exceeds", "cs_parser", e.h, 1, x, 544, 512, out)
+    refused("cs_parser failed", "cs_parser", None, 1, x, 96, 96, out)
     with pytest.raises(ValueError, match="multiple of 32"):
         e.parser(torch.zeros(1, 3, 72, 96))
     bare = Engine(0, max_batch=1)
-    assert lib.cs_parser(bare.h, 1, _p(x), 96, 96, _p(out), _st()) != 0 and "cs_finalize_weights has not been called" in err()
+    refused("cs_finalize_weights has not been called", "cs_parser", bare.h, 1, x, 96, 96, out)
     with pytest.raises(RuntimeError, match="no face parser"):
         bare.parser(x)
     bare.load_state_dicts(state_dicts)
     assert not bare.has_parser
-    assert lib.cs_parser(bare.h, 1, _p(x), 96, 96, _p(out), _st()) != 0 and "holds no face parser" in err()
-    assert lib.cs_op_parser_read(bare.h, 0, 1, _p(out), _st()) != 0
+    refused("holds no face parser", "cs_parser", bare.h, 1, x, 96, 96, out)
+    refused("cs_op_parser_read failed", "cs_op_parser_read", bare.h, 0, 1, out)
     bare.close()
     torch.cuda.synchronize()
     assert bool((out == 7.0).all())

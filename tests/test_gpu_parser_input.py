@@ -76,7 +76,6 @@ def test_either_output_alone_gives_the_same_bits(eng, name, halve):
     """Straight through the C entry point: pixel_values alone, resized_u8 alone; sentinel-filled buffers longer than needed stay untouched
     outside the output."""
     from canonswap_amd import tail
-    from canonswap_amd.engine import _ptr
     ref = PR.reference(name, "random", halve)
     crops = _t(ref["crops"]).cuda()
     B, Hc, Wc, _ = crops.shape
@@ -84,9 +83,8 @@ def test_either_output_alone_gives_the_same_bits(eng, name, halve):
     lut = _t(tail.parser_lut()).cuda()
     pv = torch.full((pad + n + pad,), -7.0, dtype=torch.float32, device=eng.device)
     u8 = torch.full((pad + n + pad,), 0xAB, dtype=torch.uint8, device=eng.device)
-    st = C.c_void_p(torch.cuda.current_stream().cuda_stream)
-    assert eng.lib.cs_parser_input(eng.h, B, _ptr(crops), Hc, Wc, halve, _ptr(lut), _ptr(pv[pad:]), None, st) == 0
-    assert eng.lib.cs_parser_input(eng.h, B, _ptr(crops), Hc, Wc, halve, _ptr(lut), None, _ptr(u8[pad:]), st) == 0
+    eng._call("cs_parser_input", B, crops, Hc, Wc, halve, lut, pv[pad:], None)
+    eng._call("cs_parser_input", B, crops, Hc, Wc, halve, lut, None, u8[pad:])
     _check({"pixel_values": pv[pad:pad + n].view(ref["pixel_values"].shape), "resized_u8": u8[pad:pad + n].view(ref["resized_u8"].shape)}, ref, name)
     assert bool((pv[:pad] == -7.0).all()) and bool((pv[pad + n:] == -7.0).all())
     assert bool((u8[:pad] == 0xAB).all()) and bool((u8[pad + n:] == 0xAB).all())

@@ -2,32 +2,22 @@
 cs_op_id_conv) against float64 on operands that fp16 holds exactly.  Every bound comes from the number formats and is derived in its test's
 docstring: u16 = 2^-11 (one fp16 rounding), u32 = 2^-24 (one fp32 rounding)."""
 import ctypes as C
+import re
 
 import numpy as np
 import pytest
 import torch
 import torch.nn.functional as F
 
+from hip_ops import op
+
 pytestmark = pytest.mark.gpu
 U16, U32 = 2.0 ** -11, 2.0 ** -24
-
-
-def _p(t):
-    return C.c_void_p(0 if t is None else t.data_ptr())
-
-
-def _st():
-    return C.c_void_p(torch.cuda.current_stream().cuda_stream)
 
 
 def _rand(shape, seed, lo=-1.0, hi=1.0):
     r = np.random.Generator(np.random.PCG64(seed))
     return torch.from_numpy(r.uniform(lo, hi, size=shape).astype(np.float32))
-
-
-def _lib():
-    from canonswap_amd import _lib
-    return _lib.load()
 
 
 # ------------------------------------------------------------------------------------------------ token GEMM
@@ -38,7 +28,6 @@ def test_gemm(M, K, N, mode):
     """fp16 operands are exact in float64; the K products are accumulated in fp32 in one order: |error| <= (K + 2) u32 sum |a w| in the worst
     case, the bias (and residual) additions add u32 |value| each, the fp16 store u16 |value|.  M = 1, 54, 300: a tail tile alone, a tail below
     one tile, two full tiles and a tail; N = 320 and 64 take the 64-column tile, 1280 the 128-column one.  Rows past M must stay untouched."""
-    lib = _lib()
     a, w, b = _rand((M, K), 1).half(), _rand((N, K), 2, -0.3, 0.3).half(), _rand((N,), 3)
     res = _rand((M, N), 4, -2, 2)
     pad = 3
@@ -49,8 +38,7 @@ def test_gemm(M, K, N, mode):
         if mode == 1:
             out[:M] = res.cuda()
     ad, wd, bd = a.cuda(), w.cuda(), b.cuda()
-    rc = lib.cs_op_parser_gemm(_p(ad), _p(wd), _p(bd), M, K, N, mode, _p(out), 0, 0, _st())
-    assert rc == 0, lib.cs_last_error()
+    op("cs_op_parser_gemm", ad, wd, bd, M, K, N, mode, out, 0, 0)
     want = a.double() @ w.double().T + b.double()
     mag = a.double().abs() @ w.double().abs().T + b.double().abs()
     if mode == 1:
@@ -66,14 +54,12 @@ def test_gemm(M, K, N, mode):
 def test_gemm_classifier_epilogue(M, P):
     """The classifier: 19 real classes in 64 packed rows, written as fp32 NCHW [M / P][19][P] - only the real classes: the 19 x P floats of every
     image are all that is written (the buffer ends there, with a sentinel behind it).  Bound as in test_gemm, K = 320."""
-    lib = _lib()
     K, N, L = 320, 64, 19
     a, w, b = _rand((M, K), 5).half(), _rand((N, K), 6, -0.3, 0.3).half(), _rand((N,), 7)
     w[L:] = 0
     out = torch.full((M // P * L * P + 64,), float("nan"), dtype=torch.float32, device="cuda")
     ad, wd, bd = a.cuda(), w.cuda(), b.cuda()
-    rc = lib.cs_op_parser_gemm(_p(ad), _p(wd), _p(bd), M, K, N, 3, _p(out), P, L, _st())
-    assert rc == 0, lib.cs_last_error()
+    op("cs_op_parser_gemm", ad, wd, bd, M, K, N, 3, out, P, L)
     want = (a.double() @ w.double().T + b.double())[:, :L].reshape(M // P, P, L).permute(0, 2, 1)
     mag = (a.double().abs() @ w.double().abs().T + b.double().abs())[:, :L].reshape(M // P, P, L).permute(0, 2, 1)
     got = out.double().cpu()
@@ -82,14 +68,14 @@ def test_gemm_classifier_epilogue(M, P):
 
 
 def test_gemm_refuses_bad_shapes():
-    lib = _lib()
     t = torch.zeros(64 * 64, dtype=torch.float16, device="cuda")
     o = torch.zeros(64 * 64, dtype=torch.float32, device="cuda")
     for M, K, N, mode, msg in ((0, 64, 64, 0, "bad arguments"), (4, 48, 64, 0, "K = 48"), (4, 64, 96, 0, "N = 96"), (4, 64, 64, 7, "no epilogue"),
                                (4, 64, 64, 3, "NCHW")):
-        assert lib.cs_op_parser_gemm(_p(t), _p(t), None, M, K, N, mode, _p(o), 0, 0, _st()) != 0
-        assert msg in lib.cs_last_error().decode()
-    assert lib.cs_op_parser_gemm(None, _p(t), None, 4, 64, 64, 0, _p(o), 0, 0, _st()) != 0
+        with pytest.raises(RuntimeError, match=re.escape(msg)):
+            op("cs_op_parser_gemm", t, t, None, M, K, N, mode, o, 0, 0)
+    with pytest.raises(RuntimeError, match="cs_op_parser_gemm failed"):
+        op("cs_op_parser_gemm", None, t, None, 4, 64, 64, 0, o, 0, 0)
 
 
 # ------------------------------------------------------------------------------------------------ LayerNorm
@@ -101,7 +87,6 @@ def test_layernorm(C_, M):
     |y - ref| <= |g| ((dm + 2 u32 |d|) / s + (|d| / s) (n u32 + dm^2 / (2 s^2) + 4 u32)) + 2 u32 (|y| + |b|), s = sqrt(var + eps); the fp16 copy adds
     u16 |y|.  Token 0 is the constant 0.75 (variance 0: the output is b exactly), token 1 is 1e3 times a random token, token 2 a random token
     around 1e3 (where a one-pass variance would lose everything)."""
-    lib = _lib()
     eps = 1e-5
     x = _rand((M, C_), 11, -2, 2)
     x[0] = 0.75
@@ -112,8 +97,7 @@ def test_layernorm(C_, M):
     o32 = torch.full((M + 1, C_), float("nan"), dtype=torch.float32, device="cuda")
     o16 = torch.full((M + 1, C_), float("nan"), dtype=torch.float16, device="cuda")
     xd, gd, bd = x.cuda(), g.cuda(), b.cuda()
-    rc = lib.cs_op_parser_layernorm(_p(xd), _p(gd), _p(bd), C.c_float(eps), M, C_, _p(o32), _p(o16), _st())
-    assert rc == 0, lib.cs_last_error()
+    op("cs_op_parser_layernorm", xd, gd, bd, C.c_float(eps), M, C_, o32, o16)
     x64 = x.double()
     mean = x64.mean(1, keepdim=True)
     d = x64 - mean
@@ -140,7 +124,6 @@ def test_attention(Nq, Nk, heads, d):
     + 2^-25 (fp16 rounding, the scores' error through exp twice - numerator and sum -, expf, the sum's own additions, fp16's subnormal step);
     the output adds (Nk + 34) u32 sum P |v| for its accumulation and u16 |out| for the store.  With Nk = 6 the keys 6 .. 31 of the MFMA tile are
     padding: the memory behind each sample's six rows holds the next sample's rows, and NaN behind the last one."""
-    lib = _lib()
     B, Cc = 2, heads * d
     g = torch.Generator().manual_seed(100 + Nq + Nk)
     q = (torch.randn(B, Nq, Cc, generator=g) * 1.6).half()
@@ -149,8 +132,7 @@ def test_attention(Nq, Nk, heads, d):
     kvbuf[:B * Nk] = kv.reshape(B * Nk, 2 * Cc).cuda()
     out = torch.full((B * Nq + 1, Cc), float("nan"), dtype=torch.float16, device="cuda")
     qd = q.cuda()
-    rc = lib.cs_op_parser_attention(_p(qd), _p(kvbuf), _p(out), B, Nq, Nk, heads, d, _st())
-    assert rc == 0, lib.cs_last_error()
+    op("cs_op_parser_attention", qd, kvbuf, out, B, Nq, Nk, heads, d)
     sp = lambda t: t.double().reshape(B, -1, heads, d).transpose(1, 2)
     qq, kk, vv = sp(q), sp(kv[..., :Cc]), sp(kv[..., Cc:])
     sc = qq @ kk.transpose(-1, -2)
@@ -170,13 +152,13 @@ def test_attention(Nq, Nk, heads, d):
 
 
 def test_attention_refuses_what_it_cannot_run():
-    lib = _lib()
     t = torch.zeros(1024, dtype=torch.float16, device="cuda")
-    assert lib.cs_op_parser_attention(_p(t), _p(t), _p(t), 1, 4, 257, 1, 64, _st()) != 0
-    assert "257 keys" in lib.cs_last_error().decode()
-    assert lib.cs_op_parser_attention(_p(t), _p(t), _p(t), 1, 4, 4, 1, 48, _st()) != 0
-    assert "head dimension 48" in lib.cs_last_error().decode()
-    assert lib.cs_op_parser_attention(_p(t), None, _p(t), 1, 4, 4, 1, 64, _st()) != 0
+    with pytest.raises(RuntimeError, match="257 keys"):
+        op("cs_op_parser_attention", t, t, t, 1, 4, 257, 1, 64)
+    with pytest.raises(RuntimeError, match="head dimension 48"):
+        op("cs_op_parser_attention", t, t, t, 1, 4, 4, 1, 48)
+    with pytest.raises(RuntimeError, match="cs_op_parser_attention failed"):
+        op("cs_op_parser_attention", t, None, t, 1, 4, 4, 1, 64)
 
 
 # ------------------------------------------------------------------------------------------------ depth-wise conv + GELU
@@ -186,14 +168,12 @@ def test_dwconv_gelu(H, W, Cc):
     """fp16 input, fp32 weights (exact in float64), nine fused multiply-adds on the bias in fp32: the sum is within 10 u32 (sum |v w| + |b|);
     GELU's slope is at most 1.13; erff is within 4 ulp (2^-21), the two products of 0.5 v (1 + erf) add 3 u32 |y|, the store u16 |y|.  The 2 x 3
     map is all border; on 16 x 24 the border ring and the interior are asserted one after the other."""
-    lib = _lib()
     B = 2
     x = _rand((B, H, W, Cc), 21, -2, 2).half()
     w, b = _rand((9, Cc), 22, -0.6, 0.6), _rand((Cc,), 23, -0.2, 0.2)
     out = torch.full((B * H * W + 1, Cc), float("nan"), dtype=torch.float16, device="cuda")
     xd, wd, bd = x.cuda(), w.cuda(), b.cuda()
-    rc = lib.cs_op_parser_dwgelu(_p(xd), _p(wd), _p(bd), _p(out), B, H, W, Cc, _st())
-    assert rc == 0, lib.cs_last_error()
+    op("cs_op_parser_dwgelu", xd, wd, bd, out, B, H, W, Cc)
     x64 = x.double().permute(0, 3, 1, 2)
     w64 = w.double().T.reshape(Cc, 1, 3, 3)
     v = F.conv2d(x64, w64, b.double(), padding=1, groups=Cc)
@@ -216,7 +196,6 @@ def test_patch_and_sr_convs(case):
     29 zero channels and a 3 x 3 / 2 / 1 patch embedding, through cs_op_id_conv: K^2 Cin products in four partial sums added in order,
     |error| <= (K^2 Cin + 4) u32 sum |a w| + u32 |value| (fp32 output)."""
     from canonswap_amd import pack
-    lib = _lib()
     N, IH, IW, Cin, real, Cout, K, stride, padn = {
         "sr8": (2, 16, 24, 64, 64, 64, 8, 8, 0), "sr4": (2, 8, 12, 128, 128, 128, 4, 4, 0), "sr2": (2, 4, 6, 320, 320, 320, 2, 2, 0),
         "stem7": (2, 64, 96, 32, 3, 64, 7, 4, 3), "patch3": (2, 16, 24, 64, 64, 128, 3, 2, 1)}[case]
@@ -231,8 +210,7 @@ def test_patch_and_sr_convs(case):
     OH, OW = (IH + 2 * padn - K) // stride + 1, (IW + 2 * padn - K) // stride + 1
     out = torch.full((N * OH * OW + 1, Cout), float("nan"), dtype=torch.float32, device="cuda")
     bd = b.cuda()
-    rc = lib.cs_op_id_conv(_p(xin), 0, N, IH, IW, Cin, K, stride, padn, _p(wp), _p(bd), Cout, None, _p(out), 1, _st())
-    assert rc == 0, lib.cs_last_error()
+    op("cs_op_id_conv", xin, 0, N, IH, IW, Cin, K, stride, padn, wp, bd, Cout, None, out, 1)
     x64, w64 = x.double(), w.half().double()
     want = F.conv2d(x64, w64, b.double(), stride=stride, padding=padn)
     mag = F.conv2d(x64.abs(), w64.abs(), b.double().abs(), stride=stride, padding=padn)
@@ -245,11 +223,9 @@ def test_patch_and_sr_convs(case):
 
 # ------------------------------------------------------------------------------------------------ decode head: up-sample and add
 def _upadd(ps, B, H, W, D):
-    lib = _lib()
     out = torch.full((B * H * W + 1, D), float("nan"), dtype=torch.float16, device="cuda")
     dev = [p.contiguous().cuda() for p in ps]
-    rc = lib.cs_op_parser_upadd(_p(dev[0]), _p(dev[1]), _p(dev[2]), _p(dev[3]), _p(out), B, H, W, D, _st())
-    assert rc == 0, lib.cs_last_error()
+    op("cs_op_parser_upadd", dev[0], dev[1], dev[2], dev[3], out, B, H, W, D)
     assert bool(torch.isnan(out[B * H * W:]).all())
     return out[:B * H * W].reshape(B, H, W, D).cpu()
 
@@ -295,13 +271,11 @@ def test_upadd_clamped_taps():
 
 def test_input_layout():
     """pixel_values fp32 NCHW -> fp16 [B][H][W][32]: the three channels rounded once, 29 zeros."""
-    lib = _lib()
     B, H, W = 2, 5, 7
     pv = _rand((B, 3, H, W), 60, -2.5, 2.5)
     out = torch.full((B * H * W + 1, 32), float("nan"), dtype=torch.float16, device="cuda")
     pd = pv.cuda()
-    rc = lib.cs_op_parser_input(_p(pd), _p(out), B, H, W, _st())
-    assert rc == 0, lib.cs_last_error()
+    op("cs_op_parser_input", pd, out, B, H, W)
     got = out[:B * H * W].reshape(B, H, W, 32).cpu()
     assert torch.equal(got[..., :3], pv.permute(0, 2, 3, 1).half()) and not bool(got[..., 3:].any())
     assert bool(torch.isnan(out[B * H * W:]).all())

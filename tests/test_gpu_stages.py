@@ -171,11 +171,10 @@ def test_swap_without_identity_is_an_error(state_dicts):
 
 
 def test_missing_weights_are_an_error():
-    from canonswap_amd import _lib
     from canonswap_amd.engine import Engine
     e = Engine(0, max_batch=1)
     with pytest.raises(RuntimeError, match="was not uploaded"):
-        _lib.check(e.lib.cs_finalize_weights(e.h), "cs_finalize_weights")
+        e._call("cs_finalize_weights")
     with pytest.raises(RuntimeError, match="cs_finalize_weights has not been called"):
         e.extract_feature_3d(torch.zeros(1, 3, 256, 256).cuda())
     e.close()

@@ -578,8 +578,7 @@ def test_blend_layer_latency_mode(eng, tb, captured, layer):
     conv_lat launch on the read-back set."""
     x16, res32 = _layer_io(captured, layer)
     measured = {"mask": [], "f32": [], "f16x": []}
-    from canonswap_amd import _lib
-    _lib.check(eng.lib.cs_set_latency_mode(eng.h, 1), "cs_set_latency_mode")
+    eng._call("cs_set_latency_mode", 1)
     try:
         for b, slot in ((0, 0), (1, 3)):
             r = None if res32 is None else res32[b:b + 1].contiguous()
@@ -589,5 +588,5 @@ def test_blend_layer_latency_mode(eng, tb, captured, layer):
             e16, e32 = _explicit(eng, tb, layer, slot, x16[b], None if res32 is None else res32[b], tm, 32)
             assert _bits_equal(e16, o16[0]) and _bits_equal(e32, None if o32 is None else o32[0]), (b, "not the bits of conv_lat")
     finally:
-        _lib.check(eng.lib.cs_set_latency_mode(eng.h, 0), "cs_set_latency_mode")
+        eng._call("cs_set_latency_mode", 0)
     print(f"\n{LAYERS[layer]} latency: worst mask {max(measured['mask']):.3e} fp32 {max(measured['f32'] or [0]):.3e} fp16x {max(measured['f16x']):.3e}")

@@ -124,14 +124,12 @@ def test_driven_keypoints_reduce_to_cs_motion_keypoints(swapper_m):
 def test_driven_keypoints_beyond_one_wavefronts_frames(swapper_m):
     """A wavefront walks 16 frames.  37 rows in one call of the C entry point (which, like cs_motion_keypoints, is not bound to the engine's
     max_batch) == the rows through the Python binding four at a time, bit for bit; and the binding checks its buffers."""
-    from canonswap_amd import _lib
-    from canonswap_amd.engine import _ptr
     e = swapper_m.engine
     N = 37
     raw, pose = _raw_heads(N, 8).cuda(), _raw_heads(1, 9).cuda()
     kp = _raw_heads(1, 10)[:, :63].reshape(21, 3).cuda()
     got = torch.full((N + 1, 21, 3), -7.0, device=e.device)
-    _lib.check(e.lib.cs_motion_keypoints_driven(e.h, N, _ptr(raw), _ptr(pose), _ptr(kp), _ptr(got), e._stream()), "cs_motion_keypoints_driven")
+    e._call("cs_motion_keypoints_driven", N, raw, pose, kp, got)
     for b in range(0, N, 4):
         assert torch.equal(got[b:min(b + 4, N)], e.motion_keypoints_driven(raw[b:b + 4], pose, kp)), b
     assert (got[N] == -7.0).all()                           # nothing behind the last row

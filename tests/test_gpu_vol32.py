@@ -248,16 +248,11 @@ def test_engine_refine_with_and_without_transform_staging(state_dicts, tmp_path)
 
 
 def _resblock_fused(a16, x32, w1p, w2p, b1, b2, s2, t2, act1):
-    import ctypes as C
-    from canonswap_amd import _lib
-    lib = _lib.load()
     N, H, W, D, Cc = a16.shape
     out0 = torch.full((N, H, W, D, Cc), 3.0, dtype=torch.float32, device=DEV)
     out1 = torch.full((N, H, W, D, Cc), 3.0, dtype=torch.float16, device=DEV)
-    p = lambda t: C.c_void_p(0 if t is None else t.data_ptr())
-    st = C.c_void_p(torch.cuda.current_stream().cuda_stream)
-    _lib.check(lib.cs_op_resblock3d(p(a16), p(x32), p(out0), p(out1), N, H, W, p(w1p), p(w2p), p(b1), p(b2), p(s2), p(t2),
-                                    {"none": 0, "relu": 1}[act1], 0.0, st), "cs_op_resblock3d")
+    import hip_ops as ops
+    ops.op("cs_op_resblock3d", a16, x32, out0, out1, N, H, W, w1p, w2p, b1, b2, s2, t2, {"none": 0, "relu": 1}[act1], 0.0)
     torch.cuda.synchronize()
     return out0, out1
 
