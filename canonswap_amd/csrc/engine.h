@@ -2,6 +2,7 @@
 // image-space entry points) and engine_ops.hip (the cs_op_* test hooks) share.  Kernel sources do not include it.
 #pragma once
 #include "conv_plan.h"
+#include "knobs.h"
 #include "../../include/canonswap_hip.h"
 
 #include <cstdio>
@@ -47,6 +48,7 @@ struct cs_engine {
     int dev = 0, maxB = 1;
     bool finalized = false;
     bool latency_mode = false;             // single-frame latency: cross-workgroup split-K for launches that cannot fill the chip
+    Knobs knobs{};                         // the A/B switches this engine runs under (knobs.h): the environment as cs_create found it
     bool slot_set[MAX_SLOTS] = {};
     int* slot_dev = nullptr;               // per-sample identity slot of the current batch (device)
     int* slot_pin = nullptr;               // pinned staging ring for slot_dev uploads

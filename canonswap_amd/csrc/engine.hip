@@ -94,8 +94,7 @@ static int cfg_v32() { return CFG_H_256x32; }
 // debug knob CANONSWAP_AMAX=1 (profiled steps only): largest |value| of the fp16 tensors this conv stored
 static int amax_after(cs_engine* e, const ConvCall& c, hipStream_t st)
 {
-    static const bool on = [] { const char* s = getenv("CANONSWAP_AMAX"); return s && atoi(s) != 0; }();
-    if (!on || !e->prof || e->recs.empty()) return 0;
+    if (!e->knobs.amax || !e->prof || e->recs.empty()) return 0;
     if (!e->amax_dev) { if (e->alloc(&e->amax_dev, (size_t)4096)) return -1; }
     if (e->amax_n >= 4096) return 0;
     const ConvParams& p = c.p;
@@ -111,10 +110,6 @@ static int amax_after(cs_engine* e, const ConvCall& c, hipStream_t st)
 }
 
 constexpr int VOL32_MINB = 3;          // below three frames the plain volume convs stay on the halo kernel (see go())
-static bool vol32_enabled() { static const bool on = [] { const char* s = getenv("CANONSWAP_VOL32"); return !s || atoi(s) != 0; }(); return on; }
-// GroupNorm apply / hi-lo split of R's stage-3 blocks inside the consumer conv's staging (vol32 transform staging) instead of stand-alone
-// norm_act / split16 passes (CANONSWAP_VOL32_XF=0: A/B knob)
-static bool vol32_xf() { static const bool on = [] { const char* s = getenv("CANONSWAP_VOL32_XF"); return !s || atoi(s) != 0; }(); return on && vol32_enabled(); }
 
 // Launch one convolution on conv_halo (LDS-staged input patch, register-streamed weights).
 int go(cs_engine* e, ConvCall& c, hipStream_t st, int prefW, int prefH)
@@ -135,7 +130,7 @@ int go(cs_engine* e, ConvCall& c, hipStream_t st, int prefW, int prefH)
     // (below three frames the strips of a launch cover a quarter of the CUs or less: the plain convs - bit-identical on either kernel - stay
     // on the halo kernel there, one frame 6.75 -> 6.5 ms; the statistics / transform-staging convs of R always run vol32: their partial
     // statistics are laid out per kernel, and a frame's bits must not depend on the batch it is part of)
-    if (vol32_enabled() && vol32_supported(c.p) && (c.p.N >= VOL32_MINB || c.p.stat_out || c.p.xf_kind)) {
+    if (e->knobs.vol32 && vol32_supported(c.p) && (c.p.N >= VOL32_MINB || c.p.stat_out || c.p.xf_kind)) {
         if (e->latency_mode && c.p.stat_out) c.p.v32_srows = 2;      // 2-row segments: 256 items on one frame's 64 x 64 volume (common.h)
         c.stat_nblk = vol32_stat_nblk(c.p);
         TRY(e->run(0, st, [&] { return launch_vol32(c.p, st); }, c.name, fl));
@@ -147,7 +142,7 @@ int go(cs_engine* e, ConvCall& c, hipStream_t st, int prefW, int prefH)
     // gamma / beta convs stay on conv_halo's 128 x 256 tiles (CANONSWAP_WIDE=2 moves them too): their K is two chunks (Cin = 128), so a tile
     // is 40 % epilogue, which two resident workgroups overlap and one persistent workgroup per CU cannot: 1.01 - 1.04x the time
     // (profiles/r04_c_ab_wide.txt).
-    static const int wide_on = [] { const char* s = getenv("CANONSWAP_WIDE"); return s ? atoi(s) : 1; }();
+    const int wide_on = e->knobs.wide;
     if (wide_on && !e->latency_mode && c.hcfg < 0 && (c.mode != MODE_SPADE || wide_on >= 2)) {
         if (conv_wide_supported(c.p, c.mode) && (long)c.p.N * (c.p.H / 16) * (c.p.W / 16) * (c.p.Cout_pad / 256) >= 512) {
             c.stat_nblk = (c.p.W / 16) * (c.p.H / 8) * 2;      // partial-statistics blocks per sample: 64 positions each, in the 16 x 8 tiles' order
@@ -229,12 +224,10 @@ static int do_stats(cs_engine* e, const void* x, int is_f32, int B, long P, int 
 // ------------------------------------------------------------------------------------------------ F
 // AppearanceFeatureExtractor.forward (appearance_feature_extractor.py:38-48); result: fp32 HWDC in vs[*cur]
 // whole ResBlock3d per launch (vol32_fused.hip; CANONSWAP_VOL32_FUSED=0: A/B knob, two vol32 / conv_halo launches per block)
-static bool vol32_fused_on() { static const bool on = [] { const char* s = getenv("CANONSWAP_VOL32_FUSED"); return !s || atoi(s) != 0; }(); return on && vol32_enabled(); }
-
 static int run_resblocks3d(cs_engine* e, cs_engine::RB3* rb, int B, int* cur, hipStream_t st)
 {
     // util.py:94-102; a = relu(bn1(x)) is already in va[0]; x (fp32 residual stream) in vs[*cur]
-    if (vol32_fused_on()) {      // at every batch size (one frame: 2-row segments, launch_vol32_fused); the same bits as the two-launch path below
+    if (e->knobs.vol32_fused) {     // at every batch size (one frame: 2-row segments, launch_vol32_fused); the same bits as the two-launch path below
         // block i reads a from va[i & 1] and leaves the next block's a in va[(i + 1) & 1] (a neighbouring workgroup still reads the halo
         // columns of the input while this one stores): six blocks end in va[0] again
         for (int i = 0; i < 6; ++i) {
@@ -311,12 +304,8 @@ static int run_F(cs_engine* e, int B, const float* img, int* cur, hipStream_t st
 // e->dm_deform / e->dm_occ (the deformation only when the fused kernel is not used or the caller wants it: in the fused kernel it lives in LDS
 // and going through HBM as well would be 0.79 MB per frame and call for nothing - ADVICE r3).
 // warp_in / warp_o32 / warp_o16: when given, the feature warp that consumes the deformation (warping_network.py:46-62) is part of the softmax
-// kernel (dm_softmax_warp_kernel): the caller launches no grid_sample.
-static bool warp_fused() { static const bool on = [] { const char* s = getenv("CANONSWAP_WARP_FUSED"); return !s || atoi(s) != 0; }(); return on; }
-
+// kernel (dm_softmax_warp_kernel): the caller launches no grid_sample (CANONSWAP_WARP_FUSED=0: A/B knob, dm_softmax + grid_sample).
 // CANONSWAP_DEC_PHASES_DEEP=0: A/B knob (up-blocks 0 - 2 of the hourglass as 27-tap convs on the up-sampled grid, the form of rounds 1-5)
-static bool dec_phases_deep() { static const bool on = [] { const char* s = getenv("CANONSWAP_DEC_PHASES_DEEP"); return !s || atoi(s) != 0; }(); return on; }
-
 static int run_dense_motion(cs_engine* e, int B, const float* feat, const float* kp_d, const float* kp_s, hipStream_t st,
                      const float* warp_in = nullptr, float* warp_o32 = nullptr, half_t* warp_o16 = nullptr, bool want_deform = false,
                      bool shared_feat = false, bool shared_kps = false)
@@ -351,7 +340,7 @@ static int run_dense_motion(cs_engine* e, int B, const float* feat, const float*
         // the batched mode - on 128x128 tiles (4x4x8 / 8x8x2 positions, static shapes 17 / 13): 12 of 27 taps, 0.66 -> 0.32 ms per 64-frame launch
         // for up-block 2.  In latency mode these three keep the 27-tap form: their launches are 8 - 64 workgroups there and run split-K, which a
         // grouped launch does not.
-        if (i >= 3 || (!e->latency_mode && dec_phases_deep())) {
+        if (i >= 3 || (!e->latency_mode && e->knobs.dec_phases_deep)) {
             // the nearest (1,2,2) up-sampling makes the three row / column taps read two source rows / columns: one 3x2x2 conv per
             // output phase (y, x) = (2i + a, 2j + b) on the source grid, 12 of 27 taps (pack.upsampled_conv3d_phases)
             // The four phases differ in their weights, their leading padding and their offset into the output only: ONE launch, blockIdx.z =
@@ -359,8 +348,7 @@ static int run_dense_motion(cs_engine* e, int B, const float* feat, const float*
             // 32 / 64 tiles each with a finishing launch behind it (8 launches of 14 + 7 us per level: profiles/r05_l_phase_group.txt); the
             // same bits as four launches at every batch size (tests/test_gpu_ops.py).
             const int lwo = DM_LW[lv - 1];
-            static const bool grouped = [] { const char* s = getenv("CANONSWAP_PHASE_GROUP"); return !s || atoi(s) != 0; }();      // =0: four launches (tests: same bits)
-            if (!grouped) {
+            if (!e->knobs.phase_group) {      // CANONSWAP_PHASE_GROUP=0: four launches (tests: same bits)
                 for (int ab = 0; ab < 4; ++ab) {
                     const int a = ab >> 1, b = ab & 1;
                     ConvCall q1 = mk(e->w_dec_p[i][ab], e->dm_l[lv], dhwc(nullptr, FD, Si, Si, DM_LW[lv]), B, FD, Si, Si);
@@ -406,7 +394,7 @@ static int run_dense_motion(cs_engine* e, int B, const float* feat, const float*
     m.p.kw_out = e->dm_logits;
     m.hcfg = CFG_H_256x160;
     TRY(go(e, m, st, 4, 8));     // no halo along W (KW = 1)
-    if (warp_in && warp_fused()) {
+    if (warp_in && e->knobs.warp_fused) {
         TRY(e->run(2, st, [&] { return launch_dm_softmax_warp(e->dm_logits, e->mask_b, kp_d, kp_s, warp_in, warp_o32, warp_o16, want_deform ? e->dm_deform : nullptr, B, FD, FH, FW, st, shared_feat, shared_kps); },
                    "dm_softmax_warp"));
     } else {
@@ -584,7 +572,9 @@ static int run_stage3_xf(cs_engine* e, cs_engine::S3* blk, int B, int* cur, cons
 
 static int run_stage3(cs_engine* e, cs_engine::S3* blk, int B, int* cur, const Affine* last_pre, hipStream_t st)
 {
-    if (vol32_xf()) return run_stage3_xf(e, blk, B, cur, last_pre, st);
+    // GroupNorm apply / hi-lo split of R's stage-3 blocks inside the consumer conv's staging (vol32 transform staging) instead of stand-alone
+    // norm_act / split16 passes (CANONSWAP_VOL32_XF=0: A/B knob)
+    if (e->knobs.vol32_xf) return run_stage3_xf(e, blk, B, cur, last_pre, st);
     TRY(e->run(1, st, [&] { return launch_split16(e->vs[*cur], e->vsp[0], (long)B * VOL, st); }, "split16"));
     for (int i = 0; i < 3; ++i) {   // ResBlock3D_stage3_leak (util.py:528-544)
         const int y = (*cur + 1) % 3, nxt = (*cur + 2) % 3;
@@ -659,8 +649,7 @@ static int spade_gb(cs_engine* e, const cs_engine::GB& gb, int C, const half_t* 
 static int spade_shortcut(cs_engine* e, const cs_engine::SpadeBlk& K, const half_t* actv, int astride, int aoff, int B, int S, const half_t* x,
                    const float* stats, half_t* h, half_t* xs, hipStream_t st)
 {
-    static const bool algebra = [] { const char* s = getenv("CANONSWAP_SHORTCUT_ALGEBRA"); return !s || atoi(s) != 0; }();
-    if (!algebra) {        // the reference's order: fused gamma/beta launch, then conv_s
+    if (!e->knobs.shortcut_algebra) {        // CANONSWAP_SHORTCUT_ALGEBRA=0, the reference's order: fused gamma/beta launch, then conv_s
         TRY(spade_gb(e, K.ns, K.fin, actv, astride, aoff, B, S, x, 1, stats, ACT_NONE, h, st));
         ConvCall cs = mk(K.cs, h, nhwc(nullptr, S, S, K.fin), B, 1, S, S);
         cs.p.out0 = nhwc(xs, S, S, K.fout);
@@ -675,8 +664,7 @@ static int spade_shortcut(cs_engine* e, const cs_engine::SpadeBlk& K, const half
     ng.p.stats = stats;
     // up_1 (256 -> 64 channels): one 128 x 256 tile holds every channel of h for its positions, conv_s runs inside that epilogue and h is never
     // stored (ConvParams::xs_w, conv_halo_kernel.h XSK; CANONSWAP_SHORTCUT_FUSE=0: three launches)
-    static const bool fuse = [] { const char* s = getenv("CANONSWAP_SHORTCUT_FUSE"); return !s || atoi(s) != 0; }();
-    if (fuse && K.fin == 256 && K.fout <= 64 && K.cs.Cout_pad == 64 && pick_halo_cfg(ng.p, MODE_STD) == CFG_H_128x256) {
+    if (e->knobs.shortcut_fuse && K.fin == 256 && K.fout <= 64 && K.cs.Cout_pad == 64 && pick_halo_cfg(ng.p, MODE_STD) == CFG_H_128x256) {
         ng.p.xs_w = K.cs.w; ng.p.xs_cout = K.fout;
         ng.p.xs_res = nhwc(e->g_bs, S, S, K.fout); ng.p.xs_out = nhwc(xs, S, S, K.fout);
         ng.macs_per_pos += K.cs.macs_per_pos;
@@ -705,7 +693,7 @@ static int run_G(cs_engine* e, int B, const half_t* seg, float* img, hipStream_t
     // source grid and per group of column phases (pack.upsampled_conv_phases): 16/36 and 36/144 of the taps, same result
     // Phases with the same taps and channel count differ in their weights, their leading padding and their output offset only: up to four
     // of them per launch (ConvParams::nphase) - 16 phase convs in 5 launches (4 | 4 + 2 + 4 + 2); at one frame a phase alone is 96 workgroups.
-    static const bool sh_grouped = [] { const char* s = getenv("CANONSWAP_PHASE_GROUP"); return !s || atoi(s) != 0; }();      // =0: one launch per phase (tests: same bits)
+    const bool sh_grouped = e->knobs.phase_group;      // CANONSWAP_PHASE_GROUP=0: one launch per phase (tests: same bits)
     for (int lv = 0; lv < 2; ++lv) {
         const int sc = lv ? 4 : 2, S = 64 * sc;
         half_t* dst = lv ? e->g_a256 : e->g_a128;
@@ -713,8 +701,7 @@ static int run_G(cs_engine* e, int B, const half_t* seg, float* img, hipStream_t
         // x4 level: output rows 4i + 1 and 4i + 2 read source row i alone - the same taps, the same summed weights (pack.upsampled_conv_phases),
         // the same values.  The a = 1 launches write both rows (out1 = the row below, through the identity second affine); the a = 2 phases
         // are not launched: 12 phase convs -> 9, same bits (CANONSWAP_SHARED_DEDUP=0: A/B, all twelve)
-        static const bool dedup = [] { const char* s = getenv("CANONSWAP_SHARED_DEDUP"); return !s || atoi(s) != 0; }();
-        const bool dd = dedup && sc == 4;
+        const bool dd = e->knobs.shared_dedup && sc == 4;
         for (int k = 0; k < e->g_nshp[lv]; ++k) {
             if (dd && e->g_shp[lv][k].a == 2) done[k] = true;
             if (done[k]) continue;
@@ -906,6 +893,7 @@ extern "C" int cs_create(int device_id, int max_batch, cs_engine** out)
     DevGuard guard(device_id);
     cs_engine* e = new cs_engine();
     e->dev = device_id; e->maxB = max_batch;
+    e->knobs = knobs_from_env();      // the A/B switches are taken here, once per engine; no launch reads the environment
     const size_t B = (size_t)max_batch;
 #define A(ptr, n) if (e->alloc(&e->ptr, (size_t)(n)) != 0) { cs_destroy(e); return -1; }
     A(f_t0, B * 65536 * 64); A(f_p0, B * 16384 * 128); A(f_p1, B * 4096 * 256);

@@ -1,5 +1,8 @@
 """What the chain and motion tests share (test_gpu_chain.py, test_gpu_v2i_chain.py, test_gpu_motion.py): the weights with M, the swapper
-their module-scope fixtures hand out, synthetic geometry and masks, and the two stream helpers of the ordering tests."""
+their module-scope fixtures hand out, synthetic geometry and masks, and the two stream helpers of the ordering tests; and the swapper of the
+tests that hold two forms of a stage to each other (an engine created under CANONSWAP_* switches)."""
+import contextlib
+
 import numpy as np
 import torch
 
@@ -12,6 +15,25 @@ def motion_state_dicts():
 def swapper_b4(sds):
     from canonswap_amd.can_swap_e2e import can_swapper
     return can_swapper(None, state_dicts=sds, max_batch=4)
+
+
+@contextlib.contextmanager
+def swapper_with_env(monkeypatch, sds, env, **kw):
+    """can_swapper(None, state_dicts=sds, **kw) created with the variables of `env` set (value None: removed).  The environment is put back right
+    after construction, before the first launch: an engine takes its switches at cs_create (csrc/knobs.h), so every comparison on this helper
+    also holds the other form to having been chosen there.  The engine is closed on exit."""
+    from canonswap_amd.can_swap_e2e import can_swapper
+    with monkeypatch.context() as m:
+        for k, v in env.items():
+            if v is None:
+                m.delenv(k, raising=False)
+            else:
+                m.setenv(k, v)
+        sw = can_swapper(None, state_dicts=sds, **kw)
+    try:
+        yield sw
+    finally:
+        sw.engine.close()
 
 
 def _affine(k, Ho, Wo):

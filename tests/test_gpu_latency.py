@@ -6,6 +6,8 @@ import numpy as np
 import pytest
 import torch
 
+from chain_helpers import swapper_with_env
+
 pytestmark = pytest.mark.gpu
 
 
@@ -39,42 +41,36 @@ def test_latency_mode_frame(state_dicts):
         lat.engine.close(); std.engine.close()
 
 
-@pytest.mark.parametrize("B,lat", [(2, False), (1, True)])
-def test_grouped_phase_launch_equals_four_launches(state_dicts, B, lat, tmp_path):
-    """The four output phases of the hourglass' two last up-sampling convs (util.py:142-147 on the source grid) run as ONE conv_halo launch
-    (ConvParams::nphase, blockIdx.z = phase: weights, leading padding and output offset per phase); CANONSWAP_PHASE_GROUP=0 (subprocess: the knob
-    is read once per process) launches them one by one - in latency mode as split-K convs with their finishing launches.  Batched path: the
-    same bits.  Latency mode: the grouped launch runs the whole K loop in one workgroup where the four launches split it: agreement to 2e-3 on the
-    deformation / occlusion map and beyond 60 dB on the image, as between the two modes."""
-    import os
-    import subprocess
-    import sys
+def _phase_group_inputs(state_dicts, B):
+    """(f_ref repeated B times, x_can, x_t): what test_grouped_phase_launch_equals_four_launches puts through warp_decode"""
     from canonswap_amd import synth
-    from canonswap_amd.can_swap_e2e import can_swapper
     from oracle import canonswap_ref as O
     inp = synth.make_frame_inputs(B, seed=1234, size=256)
     args = [torch.from_numpy(inp[k]) for k in ("img", "x_t", "x_can")]
     idv = torch.from_numpy(synth.make_identity(7))
     with torch.no_grad():
         ref = O.swap_frame(state_dicts, *[a[:1] for a in args], idv)
-    f_ref = ref["f_ref"].repeat(B, 1, 1, 1, 1)
-    sw = can_swapper(None, state_dicts=state_dicts, max_batch=B, latency_mode=lat)
-    try:
-        wd = sw.warp_decode(f_ref.cuda(), args[2].cuda(), args[1].cuda())
-        got = {k: wd[k].cpu() for k in ("deformation", "occlusion_map", "out")}
-    finally:
-        sw.engine.close()
-    f_in, f_off = str(tmp_path / "pg_in.pt"), str(tmp_path / "pg_off.pt")
-    torch.save({"f": f_ref, "kc": args[2], "kt": args[1]}, f_in)
-    code = ("import torch, sys; sys.path.insert(0, %r); from canonswap_amd import synth; from canonswap_amd.can_swap_e2e import can_swapper;"
-            "sd = synth.to_torch(synth.make_state_dicts(0)); sw = can_swapper(None, state_dicts=sd, max_batch=%d, latency_mode=%r);"
-            "d = torch.load(sys.argv[2]); wd = sw.warp_decode(d['f'].cuda(), d['kc'].cuda(), d['kt'].cuda());"
-            "torch.save({k: wd[k].cpu() for k in ('deformation', 'occlusion_map', 'out')}, sys.argv[1])"
-            ) % (os.path.dirname(os.path.dirname(os.path.abspath(__file__))), B, lat)
-    env = dict(os.environ, CANONSWAP_PHASE_GROUP="0")
-    r = subprocess.run([sys.executable, "-c", code, f_off, f_in], env=env, capture_output=True, text=True, timeout=600)
-    assert r.returncode == 0, r.stderr[-2000:]
-    want = torch.load(f_off)
+    return ref["f_ref"].repeat(B, 1, 1, 1, 1), args[2], args[1]
+
+
+def _warp_decode(sw, f_ref, x_can, x_t):
+    wd = sw.warp_decode(f_ref.cuda(), x_can.cuda(), x_t.cuda())
+    return {k: wd[k].cpu() for k in ("deformation", "occlusion_map", "out")}
+
+
+@pytest.mark.parametrize("B,lat", [(2, False), (1, True)])
+def test_grouped_phase_launch_equals_four_launches(state_dicts, B, lat, monkeypatch):
+    """The four output phases of the hourglass' two last up-sampling convs (util.py:142-147 on the source grid) run as ONE conv_halo launch
+    (ConvParams::nphase, blockIdx.z = phase: weights, leading padding and output offset per phase); an engine created under
+    CANONSWAP_PHASE_GROUP=0 launches them one by one - in latency mode as split-K convs with their finishing launches.  Batched path: the
+    same bits.  Latency mode: the grouped launch runs the whole K loop in one workgroup where the four launches split it: agreement to 2e-3 on the
+    deformation / occlusion map and beyond 60 dB on the image, as between the two modes."""
+    from oracle import canonswap_ref as O
+    wd_in = _phase_group_inputs(state_dicts, B)
+    with swapper_with_env(monkeypatch, state_dicts, {}, max_batch=B, latency_mode=lat) as sw:
+        got = _warp_decode(sw, *wd_in)
+    with swapper_with_env(monkeypatch, state_dicts, {"CANONSWAP_PHASE_GROUP": "0"}, max_batch=B, latency_mode=lat) as off:
+        want = _warp_decode(off, *wd_in)
     for k in got:
         if lat and k == "out":
             assert O.psnr(got[k], want[k]) > 60.0
@@ -82,6 +78,30 @@ def test_grouped_phase_launch_equals_four_launches(state_dicts, B, lat, tmp_path
             assert float((got[k] - want[k]).abs().max()) < 2e-3, k
         else:
             assert torch.equal(got[k], want[k]), (k, float((got[k] - want[k]).abs().max()))
+
+
+def test_switches_belong_to_the_engine(state_dicts, monkeypatch):
+    """A switch is a property of the engine that was created under it (cs_create reads them, csrc/knobs.h), not of the process or of whichever
+    launch comes first: A default, B created under CANONSWAP_PHASE_GROUP=0 - the environment is back before any launch -, C default and created
+    after B.  A, B, A again, C through warp_decode: the same bits four times (the forms agree bit for bit in the batched path, test above); B
+    launches more convs (four per grouped hourglass level, one per mlp_shared phase), A both times and C the same number."""
+    wd_in = _phase_group_inputs(state_dicts, 2)
+
+    def profiled(sw):
+        sw.engine.profile_begin()
+        out = _warp_decode(sw, *wd_in)
+        return out, sw.engine.profile_end()["conv_launches"]
+
+    with swapper_with_env(monkeypatch, state_dicts, {}, max_batch=2) as a, \
+            swapper_with_env(monkeypatch, state_dicts, {"CANONSWAP_PHASE_GROUP": "0"}, max_batch=2) as b, \
+            swapper_with_env(monkeypatch, state_dicts, {}, max_batch=2) as c:
+        runs = [profiled(sw) for sw in (a, b, a, c)]
+    for out, _ in runs[1:]:
+        for k in out:
+            assert torch.equal(out[k], runs[0][0][k]), k
+    n_a, n_b, n_a2, n_c = (n for _, n in runs)
+    assert n_b > n_a, (n_a, n_b)
+    assert n_a == n_a2 == n_c, (n_a, n_a2, n_c)
 
 
 @pytest.fixture(scope="module")
@@ -120,27 +140,24 @@ def test_latency_mode_worst_pool_frames(state_dicts, pool_modes, frame):
 
 @pytest.mark.parametrize("knob,lat", [("CANONSWAP_VOL32_XF=0", 0), ("CANONSWAP_WIDE=2", 0), ("CANONSWAP_WIDE=0", 0),
                                       ("CANONSWAP_SHARED_DEDUP=0", 0), ("CANONSWAP_DEC_PHASES_DEEP=0", 0)])
-def test_knob_product_paths_through_swap_frames(state_dicts, knob, lat, tmp_path):
+def test_knob_product_paths_through_swap_frames(state_dicts, knob, lat, monkeypatch):
     """The knobs that select another PRODUCT path (R's GroupNorm apply as its own launch instead of inside the consumer conv's staging; SPADE
-    gamma / beta on conv_wide: the same bits) and the one that takes conv_wide out, through swap_frames in a process of their own, on pool frames
-    0 and 63; mlp_shared with every row phase launched (the same bits as the de-duplicated form) and the hourglass' up-blocks 0 - 2 as 27-tap convs.
+    gamma / beta on conv_wide: the same bits) and the one that takes conv_wide out, through swap_frames of an engine created under them, on pool
+    frames 0 and 63 (seed 1000, identity 7: the bench's pool), one frame per call, against an engine created with the variable removed;
+    mlp_shared with every row phase launched (the same bits as the de-duplicated form) and the hourglass' up-blocks 0 - 2 as 27-tap convs.
     (CANONSWAP_R_SPLIT=0 - R without its split-precision passes - measured 49.5 dB on frame 63 here and was removed: round 6.)"""
-    import os
-    import subprocess
-    import sys
     from canonswap_amd import synth
     from oracle import canonswap_ref as O
-    here = os.path.dirname(os.path.abspath(__file__))
     k, v = knob.split("=")
-    outs = {}
-    base_env = {kk: vv for kk, vv in os.environ.items() if kk != k}
-    for tag, env in (("knob", dict(base_env, **{k: v})), ("base", base_env)):
-        f = str(tmp_path / f"{tag}.pt")
-        r = subprocess.run([sys.executable, os.path.join(here, "run_frame.py"), f, str(lat), "0", "63"], env=env, capture_output=True, text=True, timeout=900)
-        assert r.returncode == 0, r.stderr[-2000:]
-        outs[tag] = torch.load(f)
     inp = synth.make_frame_inputs(64, seed=1000, size=256)
     idv = torch.from_numpy(synth.make_identity(7))
+    outs = {}
+    for tag, env in (("knob", {k: v}), ("base", {k: None})):
+        with swapper_with_env(monkeypatch, state_dicts, env, max_batch=1, latency_mode=bool(lat)) as sw:
+            outs[tag] = {}
+            for j in (0, 63):
+                g = [torch.from_numpy(inp[kk][j:j + 1]).cuda() for kk in ("img", "x_t", "x_can")]
+                outs[tag][j] = sw.swap_frames(*g, idv.cuda())["out"].cpu()
     for j in (0, 63):
         a = [torch.from_numpy(inp[kk][j:j + 1]) for kk in ("img", "x_t", "x_can")]
         with torch.no_grad():

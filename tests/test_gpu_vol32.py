@@ -10,6 +10,8 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+from chain_helpers import swapper_with_env
+
 pytestmark = pytest.mark.gpu
 
 DEV = "cuda:0"
@@ -105,27 +107,17 @@ def test_vol32_strided_views_and_untouched_neighbours():
     assert bool((big_out[1::2] == -7.0).all())
 
 
-def test_engine_resblocks_use_vol32_and_match_halo_path(state_dicts, monkeypatch, tmp_path):
+def test_engine_resblocks_use_vol32_and_match_halo_path(state_dicts, monkeypatch):
     """The appearance feature extractor (12 of these convolutions) through the engine with the kernel on (default) and off
-    (CANONSWAP_VOL32=0 is read once per process, so the second engine runs in a subprocess): identical bits."""
-    import os
-    import subprocess
-    import sys
+    (a second engine created under CANONSWAP_VOL32=0): identical bits."""
     from canonswap_amd import synth
     from canonswap_amd.can_swap_e2e import can_swapper
     inp = synth.make_frame_inputs(2, seed=31, size=256)
     img = torch.from_numpy(inp["img"])
     sw = can_swapper(None, state_dicts=state_dicts, max_batch=2)
     got = sw.extract_feature_3d(img.cuda()).cpu()
-    code = ("import torch, sys; sys.path.insert(0, %r); from canonswap_amd import synth; from canonswap_amd.can_swap_e2e import can_swapper;"
-            "sd = synth.to_torch(synth.make_state_dicts(0)); sw = can_swapper(None, state_dicts=sd, max_batch=2);"
-            "img = torch.from_numpy(synth.make_frame_inputs(2, seed=31, size=256)['img']);"
-            "torch.save(sw.extract_feature_3d(img.cuda()).cpu(), sys.argv[1])") % os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    path = str(tmp_path / "vol32_off.pt")
-    env = dict(os.environ, CANONSWAP_VOL32="0")
-    r = subprocess.run([sys.executable, "-c", code, path], env=env, capture_output=True, text=True, timeout=600)
-    assert r.returncode == 0, r.stderr[-2000:]
-    want = torch.load(path)
+    with swapper_with_env(monkeypatch, state_dicts, {"CANONSWAP_VOL32": "0"}, max_batch=2) as off:
+        want = off.extract_feature_3d(img.cuda()).cpu()
     assert torch.equal(got, want)
 
 
@@ -223,27 +215,17 @@ def test_vol32_transform_staging(kind, with_res, N, H, W):
     assert bool((yd.cpu() == y).all())
 
 
-def test_engine_refine_with_and_without_transform_staging(state_dicts, tmp_path):
+def test_engine_refine_with_and_without_transform_staging(state_dicts, monkeypatch):
     """R (adaptive_modulate.py:721-733) with the GroupNorm apply inside the conv staging (default) against the stand-alone norm_act / split16
-    passes (CANONSWAP_VOL32_XF=0, second engine in a subprocess): both use the same fixed operation sequence (common.h gn_lrelu), the
+    passes (a second engine created under CANONSWAP_VOL32_XF=0): both use the same fixed operation sequence (common.h gn_lrelu), the
     convs and their statistics are the same kernels - identical bits."""
-    import os
-    import subprocess
-    import sys
     from canonswap_amd.can_swap_e2e import can_swapper
     r = _rng(21)
     f = torch.from_numpy((0.08 * r.standard_normal((2, 32, 16, 64, 64))).astype(np.float32))
-    xf_in, xf_off = str(tmp_path / "xf_in.pt"), str(tmp_path / "xf_off.pt")
-    torch.save(f, xf_in)
     sw = can_swapper(None, state_dicts=state_dicts, max_batch=2)
     got = sw.refine_module(f.cuda()).cpu()
-    code = ("import torch, sys; sys.path.insert(0, %r); from canonswap_amd import synth; from canonswap_amd.can_swap_e2e import can_swapper;"
-            "sd = synth.to_torch(synth.make_state_dicts(0)); sw = can_swapper(None, state_dicts=sd, max_batch=2);"
-            "torch.save(sw.refine_module(torch.load(sys.argv[2]).cuda()).cpu(), sys.argv[1])") % os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    env = dict(os.environ, CANONSWAP_VOL32_XF="0")
-    rr = subprocess.run([sys.executable, "-c", code, xf_off, xf_in], env=env, capture_output=True, text=True, timeout=600)
-    assert rr.returncode == 0, rr.stderr[-2000:]
-    want = torch.load(xf_off)
+    with swapper_with_env(monkeypatch, state_dicts, {"CANONSWAP_VOL32_XF": "0"}, max_batch=2) as off:
+        want = off.refine_module(f.cuda()).cpu()
     assert torch.equal(got, want), float((got - want).abs().max())
 
 
@@ -291,12 +273,9 @@ def test_fused_resblock3d_equals_two_launches(N, H, W, post):
 
 
 @pytest.mark.parametrize("B", [3, 1])
-def test_engine_feature_extractor_fused_vs_two_launches(state_dicts, B, tmp_path):
+def test_engine_feature_extractor_fused_vs_two_launches(state_dicts, B, monkeypatch):
     """F (appearance_feature_extractor.py:38-48: six ResBlock3d) and T's six through the engine with the fused kernel (default, at every
-    batch size) and with two launches per block (CANONSWAP_VOL32_FUSED=0, subprocess): identical bits."""
-    import os
-    import subprocess
-    import sys
+    batch size) and with two launches per block (a second engine created under CANONSWAP_VOL32_FUSED=0): identical bits."""
     from canonswap_amd import synth
     from canonswap_amd.can_swap_e2e import can_swapper
     inp = synth.make_frame_inputs(B, seed=33, size=256)
@@ -305,14 +284,7 @@ def test_engine_feature_extractor_fused_vs_two_launches(state_dicts, B, tmp_path
     sw = can_swapper(None, state_dicts=state_dicts, max_batch=B)
     f = sw.extract_feature_3d(img.cuda())
     got = torch.cat([f.cpu(), sw.swap_module(f, idv.cuda()).cpu()])
-    code = ("import torch, sys; sys.path.insert(0, %r); from canonswap_amd import synth; from canonswap_amd.can_swap_e2e import can_swapper;"
-            "sd = synth.to_torch(synth.make_state_dicts(0)); sw = can_swapper(None, state_dicts=sd, max_batch=%d);"
-            "img = torch.from_numpy(synth.make_frame_inputs(%d, seed=33, size=256)['img']); idv = torch.from_numpy(synth.make_identity(7));"
-            "f = sw.extract_feature_3d(img.cuda()); torch.save(torch.cat([f.cpu(), sw.swap_module(f, idv.cuda()).cpu()]), sys.argv[1])"
-            ) % (os.path.dirname(os.path.dirname(os.path.abspath(__file__))), B, B)
-    env = dict(os.environ, CANONSWAP_VOL32_FUSED="0")
-    path = str(tmp_path / "fused_off.pt")
-    r = subprocess.run([sys.executable, "-c", code, path], env=env, capture_output=True, text=True, timeout=600)
-    assert r.returncode == 0, r.stderr[-2000:]
-    want = torch.load(path)
+    with swapper_with_env(monkeypatch, state_dicts, {"CANONSWAP_VOL32_FUSED": "0"}, max_batch=B) as off:
+        f = off.extract_feature_3d(img.cuda())
+        want = torch.cat([f.cpu(), off.swap_module(f, idv.cuda()).cpu()])
     assert torch.equal(got, want), float((got - want).abs().max())
