@@ -121,6 +121,12 @@ ABI = {
     "cs_op_g_read": (ci, [vp, ci, ci, vp, vp]),
     "cs_op_g_fill": (ci, [vp, ci, vp]),
     "cs_op_g_stop": (ci, [vp, ci]),
+    "cs_op_v_read": (ci, [vp, ci, ci, vp, vp]),
+    "cs_op_v_fill": (ci, [vp, ci, vp]),
+    "cs_op_v_stop": (ci, [vp, ci]),
+    "cs_op_conv_first": (ci, [vp, vp, vp, vp, ci, ci, ci, vp]),
+    "cs_op_norm_act": (ci, [vp, vp, vp, vp, vp, cf, vp, vp, vp, vp, ci, ci, cf, ci, cl, ci, vp]),
+    "cs_op_split16": (ci, [vp, vp, cl, vp]),
     "cs_op_id_conv": (ci, [vp, ci, ci, ci, ci, ci, ci, ci, ci, vp, vp, ci, vp, vp, ci, vp]),
     "cs_op_id_maxpool": (ci, [vp, vp, vp, vp, vp, ci, ci, ci, ci, vp]),
     "cs_op_id_se_tail": (ci, [vp, cl, cl, cl, ci, ci, ci, ci, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
@@ -137,12 +143,13 @@ ABI = {
 STATUS = frozenset(name for name, (restype, _) in ABI.items() if restype is ci and name != "cs_abi_version")      # 0, or the text is in cs_last_error()
 # The header's stream parameters are all the last one, `void* stream`; every entry has one but these (tests/test_abi_cpu.py reads the names).
 TAKES_STREAM = frozenset(ABI) - {"cs_create", "cs_destroy", "cs_last_error", "cs_abi_version", "cs_upload", "cs_finalize_weights", "cs_set_latency_mode",
-                                 "cs_profile_begin", "cs_profile_end", "cs_profile_exec_flops", "cs_op_chan_stats_partial_floats", "cs_op_g_stop"}
+                                 "cs_profile_begin", "cs_profile_end", "cs_profile_exec_flops", "cs_op_chan_stats_partial_floats", "cs_op_g_stop", "cs_op_v_stop"}
 _PTR_SLOTS = {name: tuple(t in (vp, C.c_char_p) or issubclass(t, C._Pointer) for t in argtypes) for name, (_, argtypes) in ABI.items()}      # or a number
 del vp, ci, cf, cl, cd, pi, pd, pvp
 ABI_SYMBOLS = list(ABI)
-# tests only; an A/B build of an older tree - CANONSWAP_LIB, tools/cmp_libs.py - has none of the three: load() binds them where they exist
-ABI_OPTIONAL = ("cs_op_g_read", "cs_op_g_fill", "cs_op_g_stop")
+# tests only; an A/B build of an older tree - CANONSWAP_LIB, tools/cmp_libs.py - has none of these: load() binds them where they exist
+ABI_OPTIONAL = ("cs_op_g_read", "cs_op_g_fill", "cs_op_g_stop", "cs_op_v_read", "cs_op_v_fill", "cs_op_v_stop", "cs_op_conv_first", "cs_op_norm_act",
+                "cs_op_split16")
 _lib = None
 
 

@@ -109,7 +109,7 @@ struct cs_engine {
     half_t *g_x[2], *g_h64, *g_dx64, *g_a64, *g_a128, *g_a256, *g_h128, *g_xs128, *g_dx128, *g_h1_128, *g_o128;
     half_t *g_h256, *g_xs256, *g_dx256, *g_h1_256, *g_o256;
     half_t* g_bs;         // the beta term of a learned shortcut (conv_s o mlp_beta of norm_s)
-    int g_stop = 0;       // tests (cs_op_g_stop): launches the next cs_spade_decode still runs before it returns; 0: all, -1: it stopped
+    int g_stop = 0;       // tests (cs_op_g_stop / cs_op_v_stop): launches the next cs_spade_decode / cs_extract_feature_3d / cs_refine still runs before it returns; 0: all, -1: it stopped
     float *img_a, *img_b;
 
     // ---- profiling
@@ -136,12 +136,19 @@ struct cs_engine {
         recs.push_back({fam, a, b, label, fl, -1});
         return stop_after(r);
     }
-    // the launch that uses up g_stop ends the call like a failed one (TRY unwinds); cs_spade_decode sees g_stop < 0 and reports success
+    // the launch that uses up g_stop ends the call like a failed one (TRY unwinds); the entry point sees g_stop < 0 and reports success (stop_result)
     int stop_after(int r)
     {
         if (r != 0 || g_stop <= 0 || --g_stop > 0) return r;
         g_stop = -1;
         return -1;
+    }
+    // what an entry point that honours the stop returns for the status r of its launches: a stop is success, and the counter is 0 afterwards
+    int stop_result(int r)
+    {
+        if (g_stop < 0) r = 0;
+        g_stop = 0;
+        return r;
     }
     template <class T> int alloc(T** p, size_t n)
     {
@@ -202,6 +209,19 @@ inline GBuf g_buf(cs_engine* e, int which)
         {&e->g_dx256, 65536 * 64}, {&e->g_h1_256, 65536 * 64}, {&e->g_o256, 65536 * 64}};
     static_assert(sizeof t / sizeof *t == CS_G_O256 + 1 && CS_G_X0 == 0 && CS_G_BS == 12, "one row per CS_G_* buffer, in the enum's order");
     return which >= CS_G_X0 && which <= CS_G_O256 ? t[which] : GBuf{nullptr, 0};
+}
+
+// The volume workspace of F and R: buffer `which` (CS_V_T0 .. CS_V_SP1 of canonswap_hip.h) and its bytes per sample.  cs_op_v_read and
+// cs_op_v_fill copy and fill by it.
+struct VBuf { void* p; size_t bytes; };
+inline VBuf v_buf(cs_engine* e, int which)
+{
+    const VBuf t[] = {      // in the order of CS_V_T0 .. CS_V_SP1
+        {e->f_t0, (size_t)65536 * 64 * 2}, {e->f_p0, (size_t)16384 * 128 * 2}, {e->f_p1, (size_t)4096 * 256 * 2},
+        {e->vs[0], (size_t)VOL * 4}, {e->vs[1], (size_t)VOL * 4}, {e->vs[2], (size_t)VOL * 4}, {e->va[0], (size_t)VOL * 2}, {e->va[1], (size_t)VOL * 2},
+        {e->vsp[0], (size_t)VOL * 4}, {e->vsp[1], (size_t)VOL * 4}};
+    static_assert(sizeof t / sizeof *t == CS_V_SP1 + 1 && CS_V_T0 == 0 && CS_V_S0 == 3 && CS_V_STATS == CS_V_SP1 + 1, "one row per CS_V_* buffer, in the enum's order");
+    return which >= CS_V_T0 && which <= CS_V_SP1 ? t[which] : VBuf{nullptr, 0};
 }
 
 // Every entry point runs with the engine's device current and restores the caller's device on exit (the engine may be driven

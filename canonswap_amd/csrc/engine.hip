@@ -1276,8 +1276,9 @@ extern "C" int cs_extract_feature_3d(cs_engine* e, int B, const float* img, floa
     ENTER(e, B);
     hipStream_t st = (hipStream_t)stream;
     int cur = 0;
-    TRY(run_F(e, B, img, &cur, st));
-    return from_hwdc(e, B, e->vs[cur], f_out, st);
+    int r = run_F(e, B, img, &cur, st);
+    if (r == 0) r = from_hwdc(e, B, e->vs[cur], f_out, st);
+    return e->stop_result(r);      // cs_op_v_stop: stopped where the test asked
 }
 
 extern "C" int cs_warp(cs_engine* e, int B, const float* f, const float* kp_source, const float* kp_driving, float* f_out,
@@ -1324,9 +1325,10 @@ extern "C" int cs_refine(cs_engine* e, int B, const float* f, float* f_out, void
     ENTER(e, B);
     hipStream_t st = (hipStream_t)stream;
     int cur = 0;
-    TRY(to_hwdc(e, B, f, e->vs[0], e->va[0], st));
-    TRY(run_R(e, B, &cur, st));
-    return from_hwdc(e, B, e->vs[cur], f_out, st);
+    int r = to_hwdc(e, B, f, e->vs[0], e->va[0], st);
+    if (r == 0) r = run_R(e, B, &cur, st);
+    if (r == 0) r = from_hwdc(e, B, e->vs[cur], f_out, st);
+    return e->stop_result(r);      // cs_op_v_stop: stopped where the test asked
 }
 
 extern "C" int cs_warp_forward(cs_engine* e, int B, const float* f, const float* kp_driving, const float* kp_source,
@@ -1349,9 +1351,7 @@ extern "C" int cs_spade_decode(cs_engine* e, int B, const float* seg, float* img
     hipStream_t st = (hipStream_t)stream;
     int r = e->run(1, st, [&] { return launch_nchw_to_nhwc16(seg, e->seg16, B, 256, 4096, st); }, "nchw_to_nhwc16");
     if (r == 0) r = run_G(e, B, e->seg16, img_out, st);
-    if (e->g_stop < 0) r = 0;      // cs_op_g_stop: stopped where the test asked
-    e->g_stop = 0;
-    return r;
+    return e->stop_result(r);      // cs_op_g_stop: stopped where the test asked
 }
 
 extern "C" int cs_motion_extract(cs_engine* e, int B, const float* img, float* out, void* stream)

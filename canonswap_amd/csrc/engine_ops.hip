@@ -243,6 +243,61 @@ extern "C" int cs_op_g_stop(cs_engine* e, int n)
     return 0;
 }
 
+// ---- operator level: the volume workspace of F and R as the last cs_extract_feature_3d / cs_refine left it (cs_op_v_read), a sentinel over all of
+// it (cs_op_v_fill) and a stop after the n-th launch of the next of the two (cs_op_v_stop): the tests check every step of run_F and run_R on the
+// engine's own input to it
+extern "C" int cs_op_v_read(cs_engine* e, int which, int B, void* dst, void* stream)
+{
+    ENTER(e, B);
+    if (!dst) { cs_set_error("cs_op_v_read: null destination"); return -1; }
+    if (which == CS_V_STATS) {      // the slot stats_slot() handed out last
+        const float* slot = e->stats_pool + ((e->stats_next + e->stats_slots - 1) % e->stats_slots) * e->stats_slot_floats;
+        return copy_dd(dst, slot, (size_t)B * 512 * 2 * sizeof(float), (hipStream_t)stream);
+    }
+    const VBuf b = v_buf(e, which);
+    if (!b.p) { cs_set_error("cs_op_v_read: no buffer %d", which); return -1; }
+    return copy_dd(dst, b.p, (size_t)B * b.bytes, (hipStream_t)stream);
+}
+
+extern "C" int cs_op_v_fill(cs_engine* e, int B, void* stream)
+{
+    ENTER(e, B);
+    for (int which = CS_V_T0; which <= CS_V_SP1; ++which) {
+        const VBuf b = v_buf(e, which);
+        CS_CHECK_HIP(hipMemsetD16Async((hipDeviceptr_t)b.p, CS_G_SENTINEL, (size_t)B * b.bytes / 2, (hipStream_t)stream));
+    }
+    CS_CHECK_HIP(hipMemsetD16Async((hipDeviceptr_t)e->stats_pool, CS_G_SENTINEL, e->stats_slots * e->stats_slot_floats * 2, (hipStream_t)stream));
+    return 0;
+}
+
+extern "C" int cs_op_v_stop(cs_engine* e, int n)
+{
+    if (!e || n < 0) { cs_set_error("cs_op_v_stop: bad arguments"); return -1; }
+    e->g_stop = n;
+    return 0;
+}
+
+// ---- operator level: the three kernels of F and R that run outside the conv kernels (csrc/kernels.hip), without an engine
+extern "C" int cs_op_conv_first(const float* img, const float* w, const float* b, void* out16, int N, int H, int W, void* stream)
+{
+    if (!img || !w || !b || !out16 || N < 1 || H < 1 || W < 1) { cs_set_error("cs_op_conv_first: bad arguments"); return -1; }
+    return launch_conv_first(img, w, b, (half_t*)out16, N, H, W, (hipStream_t)stream);
+}
+
+extern "C" int cs_op_norm_act(const float* y, const float* stats, const float* gamma, const float* beta, const float* res, float slope, float* out32,
+                              void* out16, const float* s2, const float* t2, int period2, int act2, float slope2, int N, long per_n, int split,
+                              void* stream)
+{
+    if (!y || !stats || !gamma || !beta || (!out32 && !out16) || (!s2) != (!t2) || N < 1 || per_n < 1) { cs_set_error("cs_op_norm_act: bad arguments"); return -1; }
+    return launch_norm_act(y, stats, gamma, beta, res, slope, out32, (half_t*)out16, s2, t2, period2, act2, slope2, N, per_n, (hipStream_t)stream, split);
+}
+
+extern "C" int cs_op_split16(const float* x, void* out16, long n, void* stream)
+{
+    if (!x || !out16 || n < 32 || n % 32) { cs_set_error("cs_op_split16: bad arguments (n: whole voxels of 32 channels)"); return -1; }
+    return launch_split16(x, (half_t*)out16, n, (hipStream_t)stream);
+}
+
 // ---- operator level: the identity network's kernels (csrc/identity.hip) without an engine, and the activations the last cs_identity pass left
 extern "C" int cs_op_id_conv(const void* in, int in_f32, int N, int IH, int IW, int Cin, int K, int stride, int pad, const void* w, const float* bias,
                              int Cout, const float* slope, void* out, int out_f32, void* stream)

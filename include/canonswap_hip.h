@@ -482,6 +482,39 @@ int cs_op_g_read(cs_engine* e, int which, int B, void* dst, void* stream);
 int cs_op_g_fill(cs_engine* e, int B, void* stream);
 int cs_op_g_stop(cs_engine* e, int n);
 
+/* The volume workspace of F (cs_extract_feature_3d) and R (cs_refine), for tests that check both launch by launch on the engine's own tensors.
+ * cs_op_v_read copies one buffer, as the last call left it, to dst on `stream`; B: samples to copy (<= max_batch).  Volumes are HWDC,
+ * [B][64][64][16][32] (the 512-channel 2-D view: channel d * 32 + c):
+ *   CS_V_T0:             fp16 [B][256][256][64]   F: conv_first
+ *   CS_V_P0:             fp16 [B][128][128][128]  F: down_blocks.0 (pooled)
+ *   CS_V_P1:             fp16 [B][64][64][256]    F: down_blocks.1 (pooled)
+ *   CS_V_S0 .. CS_V_S2:  fp32 volumes: the residual stream and the conv outputs that rotate through them
+ *   CS_V_A0, CS_V_A1:    fp16 volumes: the pre-activated copies the fp16 convs read
+ *   CS_V_SP0, CS_V_SP1:  B x 4194304 fp16 values, the split-precision [hi | lo] inputs of R's stage-3 convs; in the default (transform-staging)
+ *                        path R uses each as one more fp32 volume [B][64][64][16][32] at the sample stride of an fp32 volume
+ *   CS_V_STATS:          fp32 B x 1024 values: the (mean, rstd) slot handed out last, [B][32][2] in its first B 64 values (as CS_G_STATS)
+ * cs_op_v_fill writes the 16-bit pattern CS_G_SENTINEL over the first B samples of every buffer above and over the whole statistics pool.
+ * cs_op_v_stop(e, n): the next cs_extract_feature_3d or cs_refine returns (with 0) after its n-th launch, counted as the profile CSV lists them
+ * (the layout launches ncdhw_to_hwdc / hwdc_to_ncdhw and chan_stats_finish count); stopped before its last launch the call leaves f_out
+ * untouched; n = 0: all of it.  That call clears the stop.  (One counter serves cs_op_g_stop and cs_op_v_stop: the next of the three entry
+ * points uses it up.) */
+enum { CS_V_T0 = 0, CS_V_P0, CS_V_P1, CS_V_S0, CS_V_S1, CS_V_S2, CS_V_A0, CS_V_A1, CS_V_SP0, CS_V_SP1, CS_V_STATS };
+int cs_op_v_read(cs_engine* e, int which, int B, void* dst, void* stream);
+int cs_op_v_fill(cs_engine* e, int B, void* stream);
+int cs_op_v_stop(cs_engine* e, int n);
+/* Three kernels of these stages alone (csrc/kernels.hip), on the caller's buffers.
+ * conv_first: img fp32 [N][3][H][W] -> out16 fp16 [N][H][W][64] = relu(conv3x3(img; w [64][27] fp32, input channel major) + b [64]), zero padding
+ * (first.conv with first.norm folded, appearance_feature_extractor.py:22,39)
+ * norm_act: GroupNorm(32, 32) apply + residual + LeakyReLU on N samples of per_n fp32 values, channel = index % 32 (util.py:531-540):
+ *   v = lrelu((y - mean) rstd gamma + beta [+ res], slope), (mean, rstd) = stats [N][32][2]; out32 = v; out16 = fp16(act2(v s2[i % period2] +
+ *   t2[i % period2])) (s2 NULL: fp16(v)); split != 0: out16 receives the pair [hi(32) | lo(32)] per voxel, hi = fp16(v), lo = fp16(v - hi).
+ *   res, out32, out16, s2 / t2 may be NULL.  Refused: per_n no multiple of 32 or (with s2) of period2, split with s2.
+ * split16: x fp32, n values (a multiple of 32) -> out16 fp16, 2 n values: [hi(32) | lo(32)] per voxel of 32 channels */
+int cs_op_conv_first(const float* img, const float* w, const float* b, void* out16, int N, int H, int W, void* stream);
+int cs_op_norm_act(const float* y, const float* stats, const float* gamma, const float* beta, const float* res, float slope, float* out32,
+                   void* out16, const float* s2, const float* t2, int period2, int act2, float slope2, int N, long per_n, int split, void* stream);
+int cs_op_split16(const float* x, void* out16, long n, void* stream);
+
 /* The identity network's kernels one at a time (csrc/identity.hip; weights as pack._pack_A lays them out; models/arcface_models.py:10-136).
  * conv: in fp16 (in_f32: fp32, rounded to fp16 on load) contiguous [N][IH][IW][Cin] -> out fp32 / fp16 [N][OH][OW][Cout] = prelu(conv + bias), K x K
  * taps (K from 1 to 8), stride >= 1, zero padding pad < K, OH = (IH + 2 pad - K) / stride + 1; w fp16 [K * K][Cout][Cin] (pack.pack_id_conv); Cin % 32 == 0,

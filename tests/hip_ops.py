@@ -299,6 +299,67 @@ def g_decode(engine, seg, img, stop=0):
     return img
 
 
+# ---- the volume workspace of F and R (cs_op_v_read / cs_op_v_fill / cs_op_v_stop; layouts: include/canonswap_hip.h)
+V_NAMES = ("t0", "p0", "p1", "s0", "s1", "s2", "a0", "a1", "sp0", "sp1")
+V_T0, V_P0, V_P1, V_S0, V_S1, V_S2, V_A0, V_A1, V_SP0, V_SP1 = range(10)
+V_STATS = 10
+V_SHAPE = {V_T0: (256, 256, 64), V_P0: (128, 128, 128), V_P1: (64, 64, 256), V_A0: (64, 64, 16, 32), V_A1: (64, 64, 16, 32)}
+V_F32 = (V_S0, V_S1, V_S2, V_SP0, V_SP1)          # fp32 volumes [64, 64, 16, 32] (SP0 / SP1: as R's transform-staging path uses them)
+
+
+def v_read(engine, which, B, out=None):
+    """One buffer of the volume workspace as the last cs_extract_feature_3d / cs_refine left it: fp16 [B, H, W, C] or [B, 64, 64, 16, 32], the fp32
+    volumes (SP0 / SP1 among them) fp32 [B, 64, 64, 16, 32]; V_STATS: fp32 [B, 1024], the slot handed out last ([B][32][2] in its first B 64 values)"""
+    if which == V_STATS:
+        shape, dt = (B, 1024), torch.float32
+    elif which in V_F32:
+        shape, dt = (B, 64, 64, 16, 32), torch.float32
+    else:
+        shape, dt = (B,) + V_SHAPE[which], torch.float16
+    if out is None:
+        out = torch.empty(shape, dtype=dt, device=engine.device)
+    assert out.is_contiguous() and tuple(out.shape) == shape and out.dtype == dt
+    engine._call("cs_op_v_read", which, B, out)
+    return out
+
+
+def v_fill(engine, B):
+    engine._call("cs_op_v_fill", B)
+
+
+def v_run(engine, entry, x, out, stop=0):
+    """cs_extract_feature_3d (x: images [B, 3, 256, 256]) or cs_refine (x: volumes [B, 32, 16, 64, 64]) into the caller's out [B, 32, 16, 64, 64],
+    returning after its stop-th launch (0: all of it)"""
+    assert entry in ("cs_extract_feature_3d", "cs_refine") and x.is_contiguous() and out.is_contiguous() and x.dtype == out.dtype == torch.float32
+    engine._call("cs_op_v_stop", stop)
+    engine._call(entry, x.shape[0], x, out)
+    return out
+
+
+def conv_first(img, w, b, out16):
+    """img fp32 [N, 3, H, W], w fp32 [64, 27], b fp32 [64] -> out16 (caller's fp16 buffer of N H W 64 values)"""
+    assert img.is_contiguous() and w.is_contiguous() and out16.is_contiguous()
+    N, _, Hh, Ww = img.shape
+    op("cs_op_conv_first", img, w, b, out16, N, Hh, Ww)
+    return out16
+
+
+def norm_act(y, stats, gamma, beta, res=None, slope=0.01, out32=None, out16=None, s2=None, t2=None, period2=512, act2="none", slope2=0.0, split=False,
+             per_n=None):
+    """y fp32 [N, per_n] (channel = index % 32), stats fp32 [N, 32, 2] -> out32 / out16 (caller's buffers; split: out16 holds 2 N per_n values)"""
+    assert y.is_contiguous()
+    N = y.shape[0]
+    op("cs_op_norm_act", y, stats, gamma, beta, res, slope, out32, out16, s2, t2, period2, ACT[act2], slope2, N, y[0].numel() if per_n is None else per_n,
+       int(split))
+
+
+def split16_op(x, out16):
+    """x fp32, n values -> out16 (caller's fp16 buffer of 2 n values): [hi(32) | lo(32)] per voxel"""
+    assert x.is_contiguous() and out16.is_contiguous()
+    op("cs_op_split16", x, out16, x.numel())
+    return out16
+
+
 # ---- T's identity path (cs_op_t_*; csrc/kernels.hip t_style / t_modulate, the engine's per-slot weight sets and its blend layers)
 T_WSET, T_STYLE = 0, 1
 

@@ -114,7 +114,7 @@ def header():
 
 def test_header_equals_binding(header):
     from canonswap_amd import _lib
-    assert _lib.ABI_SYMBOLS == list(_lib.ABI) and len(_lib.ABI) == 84 and len(_lib.ConvDesc._fields_) == 65
+    assert _lib.ABI_SYMBOLS == list(_lib.ABI) and len(_lib.ABI) == 90 and len(_lib.ConvDesc._fields_) == 65
     assert mismatches(render_header(header), render_binding(_lib), "canonswap_amd/_lib.py") == []
     assert render_header(header) == render_binding(_lib)
     assert _lib.load().cs_abi_version() == _lib.ABI_VERSION == 4
@@ -157,7 +157,7 @@ RENAMED_STREAM = "cs_pack_u8"
 
 def test_the_marked_entries_are_the_headers_stream_parameters(header):
     from canonswap_amd import _lib
-    assert stream_entries(header) == set(_lib.TAKES_STREAM) and len(_lib.TAKES_STREAM) == 72
+    assert stream_entries(header) == set(_lib.TAKES_STREAM) and len(_lib.TAKES_STREAM) == 77
     assert all(_lib.ABI[name][1][-1] is C.c_void_p for name in _lib.TAKES_STREAM)
     bad = _sub(*DOCTORED[RENAMED_STREAM], header)
     assert render_header(bad) == render_header(header)
