@@ -1,4 +1,4 @@
-"""ctypes binding of libcanonswap_hip.so (C ABI: include/canonswap_hip.h).
+"""ctypes binding of libcanonswap_hip.so (C ABI: include/canonswap_hip.h, and include/canonswap_landmarks.h beside it).
 
 The library is the product: if it cannot be loaded, every entry point raises -- there is no CPU or
 PyTorch fallback (the CPU restatement under oracle/ is test infrastructure only).  The in-tree build is _build.py,
@@ -17,6 +17,7 @@ ABI_VERSION = 4          # CS_ABI_VERSION of include/canonswap_hip.h
 MAX_IDENTITY_SLOTS = 8      # CS_MAX_IDENTITY_SLOTS (include/canonswap_hip.h)
 DET_MAX_CAND = 1024         # CS_DET_MAX_CAND: candidates per frame cs_det_decode takes
 DET_MAX_FACES = 256         # CS_DET_MAX_FACES: the largest max_faces of cs_det_decode
+LMK_ABI_VERSION = 1         # CS_LMK_ABI_VERSION of include/canonswap_landmarks.h
 
 
 class ConvDesc(C.Structure):
@@ -42,6 +43,11 @@ class ConvDesc(C.Structure):
         ("xf_stats", C.c_void_p), ("xf_gamma", C.c_void_p), ("xf_beta", C.c_void_p), ("xf_slope", C.c_float),
         ("ep_general", C.c_int), ("pool_hw", C.c_int),
     ]
+
+
+class LmkLayout(C.Structure):
+    """Mirror of cs_lmk_layout (include/canonswap_landmarks.h); passed by value."""
+    _fields_ = [("n_eye", C.c_int), ("left", C.c_int * 4), ("right", C.c_int * 4), ("lip", C.c_int * 2)]
 
 
 vp, ci, cf, cl, cd = C.c_void_p, C.c_int, C.c_float, C.c_long, C.c_double
@@ -140,11 +146,20 @@ ABI = {
     "cs_op_parser_upadd": (ci, [vp, vp, vp, vp, vp, ci, ci, ci, ci, vp]),
     "cs_op_parser_read": (ci, [vp, ci, ci, vp, vp]),
 }
-STATUS = frozenset(name for name, (restype, _) in ABI.items() if restype is ci and name != "cs_abi_version")      # 0, or the text is in cs_last_error()
+# The landmark runner's entry points: a table of their own beside ABI, as their header stands beside canonswap_hip.h (the reason is stated there);
+# tests/test_landmarks_cpu.py compares it with include/canonswap_landmarks.h class by class.  load() binds it, call() takes names from either table.
+ABI_LANDMARKS = {
+    "cs_lmk_abi_version": (ci, []),      # a value, not a status
+    "cs_lmk_input": (ci, [vp, ci, ci, vp, ci, ci, pi, vp, ci, LmkLayout, ci, cf, cf, ci, ci, vp, vp, vp, vp, vp]),
+    "cs_lmk_decode": (ci, [vp, ci, vp, ci, vp, ci, vp, vp, vp]),
+}
+TAKES_STREAM_LANDMARKS = frozenset({"cs_lmk_input", "cs_lmk_decode"})
+_TABLES = {**ABI, **ABI_LANDMARKS}
+STATUS = frozenset(name for name, (restype, _) in _TABLES.items() if restype is ci and name not in ("cs_abi_version", "cs_lmk_abi_version"))      # 0, or the text is in cs_last_error()
 # The header's stream parameters are all the last one, `void* stream`; every entry has one but these (tests/test_abi_cpu.py reads the names).
 TAKES_STREAM = frozenset(ABI) - {"cs_create", "cs_destroy", "cs_last_error", "cs_abi_version", "cs_upload", "cs_finalize_weights", "cs_set_latency_mode",
                                  "cs_profile_begin", "cs_profile_end", "cs_profile_exec_flops", "cs_op_chan_stats_partial_floats", "cs_op_g_stop", "cs_op_v_stop"}
-_PTR_SLOTS = {name: tuple(t in (vp, C.c_char_p) or issubclass(t, C._Pointer) for t in argtypes) for name, (_, argtypes) in ABI.items()}      # or a number
+_PTR_SLOTS = {name: tuple(t in (vp, C.c_char_p) or issubclass(t, C._Pointer) for t in argtypes) for name, (_, argtypes) in _TABLES.items()}      # or a number
 del vp, ci, cf, cl, cd, pi, pd, pvp
 ABI_SYMBOLS = list(ABI)
 # tests only; an A/B build of an older tree - CANONSWAP_LIB, tools/cmp_libs.py - has none of these: load() binds them where they exist
@@ -170,11 +185,17 @@ def load():
     if lib.cs_abi_version() != ABI_VERSION:
         raise RuntimeError(f"{LIB_PATH} speaks C-ABI version {lib.cs_abi_version()}, this package binds version {ABI_VERSION} "
                            "(include/canonswap_hip.h: CS_ABI_VERSION): rebuild with __graft_entry__.build()")
-    for name, (restype, argtypes) in ABI.items():
-        if name in ABI_OPTIONAL and not hasattr(lib, name):
+    # An A/B library of an older tree (CANONSWAP_LIB, tools/cmp_libs.py) has no landmark entry points: there the second table is bound where it
+    # exists, and a call of a missing name raises AttributeError.  The in-tree library must carry all of it.
+    ab_without = bool(os.environ.get("CANONSWAP_LIB")) and not hasattr(lib, "cs_lmk_abi_version")
+    for name, (restype, argtypes) in _TABLES.items():
+        if (name in ABI_OPTIONAL or (ab_without and name in ABI_LANDMARKS)) and not hasattr(lib, name):
             continue
         f = getattr(lib, name)          # (a missing symbol raises AttributeError here)
         f.restype, f.argtypes = restype, argtypes
+    if not ab_without and lib.cs_lmk_abi_version() != LMK_ABI_VERSION:
+        raise RuntimeError(f"{LIB_PATH} speaks version {lib.cs_lmk_abi_version()} of include/canonswap_landmarks.h, this package binds version "
+                           f"{LMK_ABI_VERSION}: rebuild with __graft_entry__.build()")
     _lib = lib
     return lib
 
@@ -200,10 +221,10 @@ def check(rc: int, what: str):
 
 
 def call(name, *args, what=None, device=None):
-    """The one way into the library: entry point `name` of ABI with exactly its arguments, checked before the library is touched.  A torch tensor
+    """The one way into the library: entry point `name` of ABI or ABI_LANDMARKS with exactly its arguments, checked before the library is touched.  A torch tensor
     stands for its address: in a pointer slot only, and only from a GPU (device=: from that one); None is NULL; the rest goes to ctypes as it is
     (contiguity and dtype are the caller's).  A nonzero status raises RuntimeError("<what or name> failed: <cs_last_error>"); values are returned."""
-    argtypes = ABI[name][1]
+    argtypes = _TABLES[name][1]
     if len(args) != len(argtypes):
         raise TypeError(f"{name} takes {len(argtypes)} arguments, {len(args)} given")
     args = list(args)

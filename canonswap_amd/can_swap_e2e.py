@@ -19,7 +19,7 @@ import os
 import numpy as np
 import torch
 
-from . import detect, pack, tail
+from . import detect, landmarks, pack, tail
 from .engine import Engine
 
 
@@ -298,6 +298,12 @@ class can_swapper(object):
 
     def det_decode(self, outs, det_size, det_scale, frame_hw, **kw):                    # scrfd.py:160-218 + :239-303: the detector's outputs -> faces
         return detect.det_decode(self.engine, outs, det_size, det_scale, frame_hw, **kw)
+
+    def lmk_input(self, frames, lmk, frame_index=None, **kw):                           # human_landmark_runner.py:62 + :76: landmarks -> the network's input
+        return landmarks.lmk_input(self.engine, frames, lmk, frame_index, **kw)
+
+    def lmk_decode(self, out_pts, M, **kw):                                             # human_landmark_runner.py:82-83: the network's points -> landmarks
+        return landmarks.lmk_decode(self.engine, out_pts, M, **kw)
 
     def crop_frames(self, frames, lmk, **kw):                                           # crop.py:429-455 of B frames (cropper.py:196-204)
         return tail.crop_frames(self.engine, frames, lmk, **kw)

@@ -264,6 +264,13 @@ int launch_det_decode(int F, int n_levels, const int* strides, int num_anchors, 
                       float det_thresh, float nms_thresh, int max_num, int metric_max, int Ho, int Wo, int max_faces, float* det, float* kps,
                       int* count, hipStream_t st);
 
+// ---- the landmark runner's input and decode (landmarks.hip; include/canonswap_landmarks.h)
+struct cs_lmk_layout;
+int launch_lmk_input(const unsigned char* frames, int Ho, int Wo, const int* frame_index, const float* lmk, int N, const cs_lmk_layout& L, int dsize,
+                     float scale, float vy_ratio, int flag_do_rot, int status_mark, float* M, float* inp, unsigned char* crops, int* status, int B,
+                     hipStream_t st);
+int launch_lmk_decode(const float* out_pts, int Np, const float* M, int dsize, const int* status, float* lmk, int B, hipStream_t st);
+
 // ---- motion extractor pieces (motion.hip)
 int launch_m_keypoints(const float* raw, float* x_t, float* x_can, float* rot, int N, hipStream_t st);
 int launch_m_keypoints_driven(const float* raw_driving, const float* raw_pose, const float* kp, float* x_t, int N, hipStream_t st);

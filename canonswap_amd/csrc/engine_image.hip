@@ -1,6 +1,8 @@
 // The image-space entry points of the C ABI around the generator: soft erosion, crops, warps, paste-back, key-points, resize, face masks, parser
-// input, concat, the detector's input and decode, the identity network and the face parser.  Argument checks and one launch each.
+// input, concat, the detector's input and decode, the landmark runner's input and decode, the identity network and the face parser.  Argument checks
+// and one launch each.
 #include "engine.h"
+#include "../../include/canonswap_landmarks.h"
 
 // ---- image-space steps around the generator
 static int soft_erosion_impl(cs_engine* e, int B, int H, int W, const void* mask, int mask_u8, const float* w, int ksize, float thr, int iters,
@@ -290,6 +292,58 @@ extern "C" int cs_det_decode(cs_engine* e, int F, int n_levels, const int* strid
         return launch_det_decode(F, n_levels, strides, num_anchors, outs, Hd, Wd, det_scale, det_thresh, nms_thresh, max_num, metric_max != 0, Ho, Wo,
                                  max_faces, det, kps, count, st);
     }, "det_decode");
+}
+
+// ---- the landmark runner's input (human_landmark_runner.py:62, :76) and decode (:82-83): everything is refused before any launch; neither call
+// uses engine scratch or synchronises, B and F are not bound by max_batch
+extern "C" int cs_lmk_input(cs_engine* e, int B, int F, const uint8_t* frames, int Ho, int Wo, const int* frame_index, const float* lmk, int N,
+                            cs_lmk_layout layout, int dsize, float scale, float vy_ratio, int flag_do_rot, int status_mark, float* M, float* inp,
+                            uint8_t* crops, int* status, void* stream)
+{
+    if (!e || !frames || !frame_index || !lmk || !M || !inp || !status) {
+        cs_set_error("cs_lmk_input: NULL %s", !e ? "engine" : !frames ? "frames" : !frame_index ? "frame_index" : !lmk ? "lmk" : !M ? "M" : !inp ? "inp" : "status");
+        return -1;
+    }
+    if (B < 1 || F < 1 || Ho < 1 || Wo < 1) { cs_set_error("cs_lmk_input: B = %d, F = %d, Ho = %d, Wo = %d (each at least 1)", B, F, Ho, Wo); return -1; }
+    if (dsize < 4 || dsize % 4 || dsize > 16384) { cs_set_error("cs_lmk_input: dsize %d (a multiple of 4 from 4 to 16384)", dsize); return -1; }
+    if (N < 1 || N > (1 << 20)) { cs_set_error("cs_lmk_input: N = %d landmarks outside [1, 2^20]", N); return -1; }
+    if (layout.n_eye < 1 || layout.n_eye > 4) { cs_set_error("cs_lmk_input: layout.n_eye %d outside [1, 4]", layout.n_eye); return -1; }
+    for (int i = 0; i < layout.n_eye; ++i)
+        if (layout.left[i] < 0 || layout.left[i] >= N || layout.right[i] < 0 || layout.right[i] >= N) {
+            cs_set_error("cs_lmk_input: layout eye index %d (%d, %d) outside [0, N = %d)", i, layout.left[i], layout.right[i], N);
+            return -1;
+        }
+    if (layout.lip[0] < 0 || layout.lip[0] >= N || layout.lip[1] < 0 || layout.lip[1] >= N) {
+        cs_set_error("cs_lmk_input: layout lip indices (%d, %d) outside [0, N = %d)", layout.lip[0], layout.lip[1], N);
+        return -1;
+    }
+    if (!(scale > 0.f) || scale > 3.0e38f) { cs_set_error("cs_lmk_input: scale %g is not a positive finite number", (double)scale); return -1; }
+    if (!(fabsf(vy_ratio) <= 3.0e38f)) { cs_set_error("cs_lmk_input: vy_ratio %g is not finite", (double)vy_ratio); return -1; }
+    if (status_mark == 0) { cs_set_error("cs_lmk_input: status_mark 0 (a refused face is marked with a non-zero value)"); return -1; }
+    for (int b = 0; b < B; ++b)
+        if (frame_index[b] < 0 || frame_index[b] >= F) {
+            cs_set_error("cs_lmk_input: frame_index[%d] = %d outside [0, %d)", b, frame_index[b], F);
+            return -1;
+        }
+    DevGuard guard(e->dev);
+    hipStream_t st = (hipStream_t)stream;
+    return e->run(1, st, [&] {
+        return launch_lmk_input(frames, Ho, Wo, frame_index, lmk, N, layout, dsize, scale, vy_ratio, flag_do_rot != 0, status_mark, M, inp, crops, status,
+                                B, st);
+    }, "lmk_input");
+}
+
+extern "C" int cs_lmk_decode(cs_engine* e, int B, const float* out_pts, int Np, const float* M, int dsize, const int* status, float* lmk, void* stream)
+{
+    if (!e || !out_pts || !M || !status || !lmk) {
+        cs_set_error("cs_lmk_decode: NULL %s", !e ? "engine" : !out_pts ? "out_pts" : !M ? "M" : !status ? "status" : "lmk");
+        return -1;
+    }
+    if (B < 1 || Np < 1 || Np > (1 << 20)) { cs_set_error("cs_lmk_decode: B = %d, Np = %d (B at least 1, Np in [1, 2^20])", B, Np); return -1; }
+    if (dsize < 4 || dsize % 4 || dsize > 16384) { cs_set_error("cs_lmk_decode: dsize %d (a multiple of 4 from 4 to 16384)", dsize); return -1; }
+    DevGuard guard(e->dev);
+    hipStream_t st = (hipStream_t)stream;
+    return e->run(1, st, [&] { return launch_lmk_decode(out_pts, Np, M, dsize, status, lmk, B, st); }, "lmk_decode");
 }
 
 // ---- getid on the engine (can_swap_e2e.py:102-107): nearest resize to 112 x 112, the ArcFace network, L2 normalisation.  Everything is refused

@@ -1,0 +1,62 @@
+// The bilinear tap of cv2.warpAffine (INTER_LINEAR, BORDER_CONSTANT 0) on 8-bit images and the staging value u8 / 255, shared by the warp, paste and
+// crop kernels of imgops.hip and the landmark runner's crop of landmarks.hip: one text, so that a crop cut by either file has the same bits.
+// Device code only.  The including file turns fp contraction off (#pragma clang fp contract(off)) BEFORE it includes this header.
+#pragma once
+
+// a byte as the networks' fp32 input: / 255, clipped (can_swap_e2e.py:126-163, human_landmark_runner.py:76)
+__device__ __forceinline__ float staged_value(int v) { return fminf(fmaxf((float)v / 255.f, 0.f), 1.f); }
+
+// ---------------------------------------------------------------------------------------------- cv2.warpAffine, INTER_LINEAR
+struct AffineInv { double m[6]; };      // destination -> source map (what warpAffine derives from M)
+
+// OpenCV's fixed-point source coordinate of destination pixel (x, y): AB_BITS = 10, INTER_BITS = 5 (imgwarp.cpp warpAffine)
+__device__ __forceinline__ void affine_coords(const AffineInv& A, int x, int y, int& sx, int& sy, int& fx, int& fy)
+{
+    const double AB = 1024.0;
+    const long adelta = (long)rint(A.m[0] * (double)x * AB);
+    const long bdelta = (long)rint(A.m[3] * (double)x * AB);
+    const long X0 = (long)rint((A.m[1] * (double)y + A.m[2]) * AB) + 16;     // AB_SCALE / INTER_TAB_SIZE / 2
+    const long Y0 = (long)rint((A.m[4] * (double)y + A.m[5]) * AB) + 16;
+    const long X = (X0 + adelta) >> 5, Y = (Y0 + bdelta) >> 5;
+    long ix = X >> 5, iy = Y >> 5;
+    ix = ix < -32768 ? -32768 : (ix > 32767 ? 32767 : ix);
+    iy = iy < -32768 ? -32768 : (iy > 32767 ? 32767 : iy);
+    sx = (int)ix; sy = (int)iy; fx = (int)(X & 31); fy = (int)(Y & 31);
+}
+
+// The bilinear read of one destination pixel (remapBilinear, BORDER_CONSTANT 0): the taps are the source elements (sy, sx), (sy, sx + 1),
+// (sy + 1, sx), (sy + 1, sx + 1) with the 5-bit fractions fx, fy; a tap outside the source reads 0.  Every warp, paste and crop kernel
+// of imgops.hip and landmarks.hip forms its taps here and reads them through tap_u8x3 (below) or tap_f32 (imgops.hip).
+struct Tap {
+    long o00;                   // element offset of tap (sy, sx); dereferenced only where a tap lies inside
+    int fx, fy;
+    bool y0, y1, x0, x1;        // rows sy, sy + 1 and columns sx, sx + 1 inside the source
+    bool outside;               // all four taps outside: an 8-bit read gives 0, a float read 0.f
+};
+
+__device__ __forceinline__ Tap tap_at(const AffineInv& A, int x, int y, int Hs, int Ws)
+{
+    Tap t;
+    int sx, sy;
+    affine_coords(A, x, y, sx, sy, t.fx, t.fy);
+    t.o00 = (long)sy * Ws + sx;
+    t.y0 = (unsigned)sy < (unsigned)Hs; t.y1 = (unsigned)(sy + 1) < (unsigned)Hs;
+    t.x0 = (unsigned)sx < (unsigned)Ws; t.x1 = (unsigned)(sx + 1) < (unsigned)Ws;
+    t.outside = sx < -1 || sy < -1 || sx >= Ws || sy >= Hs;
+    return t;
+}
+
+// 8-bit image, 3 interleaved channels, rows of Ws pixels: 15-bit weights (sum 1 << 15), rounded to nearest (remapBilinear, uchar)
+__device__ __forceinline__ void tap_u8x3(const unsigned char* __restrict__ src, int Ws, const Tap& t, int (&res)[3])
+{
+    const int w00 = (32 - t.fy) * (32 - t.fx) * 32, w01 = (32 - t.fy) * t.fx * 32, w10 = t.fy * (32 - t.fx) * 32, w11 = t.fy * t.fx * 32;
+    const unsigned char* p = src + t.o00 * 3;
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+        const int t00 = (t.y0 && t.x0) ? p[c] : 0;
+        const int t01 = (t.y0 && t.x1) ? p[3 + c] : 0;
+        const int t10 = (t.y1 && t.x0) ? p[(long)Ws * 3 + c] : 0;
+        const int t11 = (t.y1 && t.x1) ? p[(long)Ws * 3 + 3 + c] : 0;
+        res[c] = (t00 * w00 + t01 * w01 + t10 * w10 + t11 * w11 + (1 << 14)) >> 15;
+    }
+}
