@@ -6,12 +6,12 @@ import subprocess
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
-SOURCES = [os.path.join(CSRC, f) for f in ("conv_halo.hip", "conv_wide.hip", "conv_lat.hip", "vol32.hip", "vol32_fused.hip", "kernels.hip", "motion.hip", "imgops.hip", "detect.hip", "landmarks.hip", "identity.hip", "parser.hip", "engine.hip", "engine_image.hip", "engine_ops.hip")]
+SOURCES = [os.path.join(CSRC, f) for f in ("conv_halo.hip", "conv_wide.hip", "conv_lat.hip", "vol32.hip", "vol32_fused.hip", "kernels.hip", "motion.hip", "imgops.hip", "detect.hip", "landmarks.hip", "yuv.hip", "identity.hip", "parser.hip", "engine.hip", "engine_image.hip", "engine_ops.hip")]
 # test-only cross-check kernel (the first-generation implicit-GEMM conv): its own library, never linked into the product
 TEST_SRC = os.path.join(os.path.dirname(HERE), "tests", "csrc", "test_igemm.hip")
 TEST_LIB_PATH = os.path.join(os.path.dirname(HERE), "tests", "libcanonswap_test.so")
-HEADERS = [os.path.join(CSRC, f) for f in ("common.h", "conv_epilogue.h", "conv_halo_kernel.h", "conv_plan.h", "engine.h", "knobs.h", "lmk_geometry.h", "warp_taps.h")] + \
-          [os.path.join(os.path.dirname(HERE), "include", f) for f in ("canonswap_hip.h", "canonswap_landmarks.h")]
+HEADERS = [os.path.join(CSRC, f) for f in ("common.h", "conv_epilogue.h", "conv_halo_kernel.h", "conv_plan.h", "engine.h", "knobs.h", "lmk_geometry.h", "warp_taps.h", "yuv_math.h")] + \
+          [os.path.join(os.path.dirname(HERE), "include", f) for f in ("canonswap_hip.h", "canonswap_landmarks.h", "canonswap_yuv.h")]
 HALO_NGROUPS = 8          # conv_halo.hip is compiled once per -DHALO_GROUP=k (slices of its instantiation table)
 OBJ_DIR = os.path.join(HERE, "build")
 LIB_PATH = os.environ.get("CANONSWAP_LIB") or os.path.join(HERE, "libcanonswap_hip.so")      # CANONSWAP_LIB: A/B builds (tools/)

@@ -1,4 +1,4 @@
-"""ctypes binding of libcanonswap_hip.so (C ABI: include/canonswap_hip.h, and include/canonswap_landmarks.h beside it).
+"""ctypes binding of libcanonswap_hip.so (C ABI: include/canonswap_hip.h, and include/canonswap_landmarks.h and include/canonswap_yuv.h beside it).
 
 The library is the product: if it cannot be loaded, every entry point raises -- there is no CPU or
 PyTorch fallback (the CPU restatement under oracle/ is test infrastructure only).  The in-tree build is _build.py,
@@ -18,6 +18,7 @@ MAX_IDENTITY_SLOTS = 8      # CS_MAX_IDENTITY_SLOTS (include/canonswap_hip.h)
 DET_MAX_CAND = 1024         # CS_DET_MAX_CAND: candidates per frame cs_det_decode takes
 DET_MAX_FACES = 256         # CS_DET_MAX_FACES: the largest max_faces of cs_det_decode
 LMK_ABI_VERSION = 1         # CS_LMK_ABI_VERSION of include/canonswap_landmarks.h
+YUV_ABI_VERSION = 1         # CS_YUV_ABI_VERSION of include/canonswap_yuv.h
 
 
 class ConvDesc(C.Structure):
@@ -154,8 +155,16 @@ ABI_LANDMARKS = {
     "cs_lmk_decode": (ci, [vp, ci, vp, ci, vp, ci, vp, vp, vp]),
 }
 TAKES_STREAM_LANDMARKS = frozenset({"cs_lmk_input", "cs_lmk_decode"})
-_TABLES = {**ABI, **ABI_LANDMARKS}
-STATUS = frozenset(name for name, (restype, _) in _TABLES.items() if restype is ci and name not in ("cs_abi_version", "cs_lmk_abi_version"))      # 0, or the text is in cs_last_error()
+# The 4:2:0 conversions, the third table: include/canonswap_yuv.h, compared class by class by tests/test_yuv_cpu.py.
+ABI_YUV = {
+    "cs_yuv_abi_version": (ci, []),      # a value, not a status
+    "cs_yuv_to_rgb": (ci, [vp, ci, vp, ci, ci, ci, ci, ci, vp, vp]),
+    "cs_rgb_to_yuv": (ci, [vp, ci, vp, ci, ci, ci, ci, ci, ci, vp, vp]),
+}
+TAKES_STREAM_YUV = frozenset({"cs_yuv_to_rgb", "cs_rgb_to_yuv"})
+_TABLES = {**ABI, **ABI_LANDMARKS, **ABI_YUV}
+STATUS = frozenset(name for name, (restype, _) in _TABLES.items()
+                   if restype is ci and name not in ("cs_abi_version", "cs_lmk_abi_version", "cs_yuv_abi_version"))      # 0, or the text is in cs_last_error()
 # The header's stream parameters are all the last one, `void* stream`; every entry has one but these (tests/test_abi_cpu.py reads the names).
 TAKES_STREAM = frozenset(ABI) - {"cs_create", "cs_destroy", "cs_last_error", "cs_abi_version", "cs_upload", "cs_finalize_weights", "cs_set_latency_mode",
                                  "cs_profile_begin", "cs_profile_end", "cs_profile_exec_flops", "cs_op_chan_stats_partial_floats", "cs_op_g_stop", "cs_op_v_stop"}
@@ -185,17 +194,24 @@ def load():
     if lib.cs_abi_version() != ABI_VERSION:
         raise RuntimeError(f"{LIB_PATH} speaks C-ABI version {lib.cs_abi_version()}, this package binds version {ABI_VERSION} "
                            "(include/canonswap_hip.h: CS_ABI_VERSION): rebuild with __graft_entry__.build()")
-    # An A/B library of an older tree (CANONSWAP_LIB, tools/cmp_libs.py) has no landmark entry points: there the second table is bound where it
-    # exists, and a call of a missing name raises AttributeError.  The in-tree library must carry all of it.
-    ab_without = bool(os.environ.get("CANONSWAP_LIB")) and not hasattr(lib, "cs_lmk_abi_version")
+    # An A/B library of an older tree (CANONSWAP_LIB, tools/cmp_libs.py) may have no landmark or no 4:2:0 entry points: there each further table
+    # is bound where it exists, and a call of a missing name raises AttributeError.  The in-tree library must carry all of them.
+    ab = bool(os.environ.get("CANONSWAP_LIB"))
+    beside = [(ABI_LANDMARKS, "cs_lmk_abi_version", LMK_ABI_VERSION, "include/canonswap_landmarks.h"),
+              (ABI_YUV, "cs_yuv_abi_version", YUV_ABI_VERSION, "include/canonswap_yuv.h")]
+    absent = set()
+    for table, version_call, _, _ in beside:
+        if ab and not hasattr(lib, version_call):
+            absent |= set(table)
     for name, (restype, argtypes) in _TABLES.items():
-        if (name in ABI_OPTIONAL or (ab_without and name in ABI_LANDMARKS)) and not hasattr(lib, name):
+        if (name in ABI_OPTIONAL or name in absent) and not hasattr(lib, name):
             continue
         f = getattr(lib, name)          # (a missing symbol raises AttributeError here)
         f.restype, f.argtypes = restype, argtypes
-    if not ab_without and lib.cs_lmk_abi_version() != LMK_ABI_VERSION:
-        raise RuntimeError(f"{LIB_PATH} speaks version {lib.cs_lmk_abi_version()} of include/canonswap_landmarks.h, this package binds version "
-                           f"{LMK_ABI_VERSION}: rebuild with __graft_entry__.build()")
+    for table, version_call, version, header in beside:
+        if version_call not in absent and getattr(lib, version_call)() != version:
+            raise RuntimeError(f"{LIB_PATH} speaks version {getattr(lib, version_call)()} of {header}, this package binds version "
+                               f"{version}: rebuild with __graft_entry__.build()")
     _lib = lib
     return lib
 
@@ -221,7 +237,7 @@ def check(rc: int, what: str):
 
 
 def call(name, *args, what=None, device=None):
-    """The one way into the library: entry point `name` of ABI or ABI_LANDMARKS with exactly its arguments, checked before the library is touched.  A torch tensor
+    """The one way into the library: entry point `name` of ABI, ABI_LANDMARKS or ABI_YUV with exactly its arguments, checked before the library is touched.  A torch tensor
     stands for its address: in a pointer slot only, and only from a GPU (device=: from that one); None is NULL; the rest goes to ctypes as it is
     (contiguity and dtype are the caller's).  A nonzero status raises RuntimeError("<what or name> failed: <cs_last_error>"); values are returned."""
     argtypes = _TABLES[name][1]

@@ -293,6 +293,12 @@ class can_swapper(object):
     def concat_frames(self, panels, **kw):                                              # video.py:84-109: the side-by-side frames, panels left to right
         return tail.concat_frames(self.engine, panels, **kw)
 
+    def yuv_to_rgb(self, yuv, **kw):                                                    # NV12 / I420 frames as the codec has them -> RGB frames
+        return tail.yuv_to_rgb(self.engine, yuv, **kw)
+
+    def rgb_to_yuv(self, rgb, **kw):                                                    # and back; keep=: untouched 2 x 2 blocks keep their bytes
+        return tail.rgb_to_yuv(self.engine, rgb, **kw)
+
     def det_input(self, frames, **kw):                                                  # scrfd.py:224-235 + :154: frames -> the detector's blob
         return detect.det_input(self.engine, frames, **kw)
 
@@ -316,7 +322,8 @@ class can_swapper(object):
 
     def swap_video(self, frames, lmk, source_id=None, *, driver=None, **kw):
         """The pipeline's loop over a whole video (can_swap_pipeline_e2e.py:155-319), host frames in, host frames out, the copies overlapped
-        with the generator: video.VideoSwapper.swap_video (kw: out, slots, frame_index, masks, parse, logits_fn, the crop's configuration).
+        with the generator: video.VideoSwapper.swap_video (kw: out, slots, frame_index, masks, parse, logits_fn, the crop's configuration; pixel_format "nv12" / "i420" with matrix and
+        full_range: 4:2:0 frames in and out, converted on the device).
         driver: a VideoSwapper of this swapper (its batch, chain and slots); without one a default driver is made once and kept."""
         from . import video
         if driver is None:

@@ -271,6 +271,11 @@ int launch_lmk_input(const unsigned char* frames, int Ho, int Wo, const int* fra
                      hipStream_t st);
 int launch_lmk_decode(const float* out_pts, int Np, const float* M, int dsize, const int* status, float* lmk, int B, hipStream_t st);
 
+// ---- 4:2:0 frames <-> RGB frames (yuv.hip; include/canonswap_yuv.h)
+int launch_yuv_to_rgb(const unsigned char* yuv, int F, int Ho, int Wo, int layout, int matrix, int full_range, unsigned char* rgb, hipStream_t st);
+int launch_rgb_to_yuv(const unsigned char* rgb, int F, int Ho, int Wo, int layout, int matrix, int full_range, int keep, unsigned char* yuv,
+                      hipStream_t st);
+
 // ---- motion extractor pieces (motion.hip)
 int launch_m_keypoints(const float* raw, float* x_t, float* x_can, float* rot, int N, hipStream_t st);
 int launch_m_keypoints_driven(const float* raw_driving, const float* raw_pose, const float* kp, float* x_t, int N, hipStream_t st);

@@ -3,6 +3,7 @@
 // and one launch each.
 #include "engine.h"
 #include "../../include/canonswap_landmarks.h"
+#include "../../include/canonswap_yuv.h"
 
 // ---- image-space steps around the generator
 static int soft_erosion_impl(cs_engine* e, int B, int H, int W, const void* mask, int mask_u8, const float* w, int ksize, float thr, int iters,
@@ -344,6 +345,40 @@ extern "C" int cs_lmk_decode(cs_engine* e, int B, const float* out_pts, int Np, 
     DevGuard guard(e->dev);
     hipStream_t st = (hipStream_t)stream;
     return e->run(1, st, [&] { return launch_lmk_decode(out_pts, Np, M, dsize, status, lmk, B, st); }, "lmk_decode");
+}
+
+// ---- 4:2:0 frames <-> RGB frames (include/canonswap_yuv.h): everything is refused before any launch; neither call uses engine scratch or
+// synchronises, F is not bound by max_batch
+static int yuv_check(const char* who, cs_engine* e, int F, const uint8_t* yuv, const uint8_t* rgb, int Ho, int Wo, int layout, int matrix, int full_range)
+{
+    if (!e || !yuv || !rgb) { cs_set_error("%s: NULL %s", who, !e ? "engine" : !yuv ? "yuv" : "rgb"); return -1; }
+    if (F < 1) { cs_set_error("%s: F = %d (at least 1)", who, F); return -1; }
+    if (Ho < 2 || Ho % 2 || Ho > 16384) { cs_set_error("%s: Ho = %d (an even number from 2 to 16384)", who, Ho); return -1; }
+    if (Wo < 2 || Wo % 2 || Wo > 16384) { cs_set_error("%s: Wo = %d (an even number from 2 to 16384)", who, Wo); return -1; }
+    if (layout != 0 && layout != 1) { cs_set_error("%s: layout %d (0: NV12, 1: I420)", who, layout); return -1; }
+    if (matrix != 0 && matrix != 1) { cs_set_error("%s: matrix %d (0: BT.601, 1: BT.709)", who, matrix); return -1; }
+    if (full_range != 0 && full_range != 1) { cs_set_error("%s: full_range %d (0 or 1)", who, full_range); return -1; }
+    const uintptr_t px = (uintptr_t)F * Ho * Wo, y0 = (uintptr_t)yuv, r0 = (uintptr_t)rgb;
+    if (y0 < r0 + px * 3 && r0 < y0 + px + px / 2) { cs_set_error("%s: rgb and yuv overlap", who); return -1; }
+    return 0;
+}
+
+extern "C" int cs_yuv_to_rgb(cs_engine* e, int F, const uint8_t* yuv, int Ho, int Wo, int layout, int matrix, int full_range, uint8_t* rgb, void* stream)
+{
+    if (yuv_check("cs_yuv_to_rgb", e, F, yuv, rgb, Ho, Wo, layout, matrix, full_range)) return -1;
+    DevGuard guard(e->dev);
+    hipStream_t st = (hipStream_t)stream;
+    return e->run(1, st, [&] { return launch_yuv_to_rgb(yuv, F, Ho, Wo, layout, matrix, full_range, rgb, st); }, "yuv_to_rgb");
+}
+
+extern "C" int cs_rgb_to_yuv(cs_engine* e, int F, const uint8_t* rgb, int Ho, int Wo, int layout, int matrix, int full_range, int keep, uint8_t* yuv,
+                             void* stream)
+{
+    if (yuv_check("cs_rgb_to_yuv", e, F, yuv, rgb, Ho, Wo, layout, matrix, full_range)) return -1;
+    if (keep != 0 && keep != 1) { cs_set_error("cs_rgb_to_yuv: keep %d (0 or 1)", keep); return -1; }
+    DevGuard guard(e->dev);
+    hipStream_t st = (hipStream_t)stream;
+    return e->run(1, st, [&] { return launch_rgb_to_yuv(rgb, F, Ho, Wo, layout, matrix, full_range, keep, yuv, st); }, "rgb_to_yuv");
 }
 
 // ---- getid on the engine (can_swap_e2e.py:102-107): nearest resize to 112 x 112, the ArcFace network, L2 normalisation.  Everything is refused

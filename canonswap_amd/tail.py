@@ -9,7 +9,9 @@ per-frame loop (src/can_swap_pipeline_e2e.py:223-283) no longer leaves the GPU b
                              (cv2.resize to one half, SegformerImageProcessor's PIL resize x 2, rescale, normalize, CHW) of B crops in one launch
 * ``concat_frames``          src/utils/video.py:84-109 (called at src/can_swap_pipeline_e2e.py:290, src/can_swap_pipeline_v2i.py:328): the side-by-side
                              video frame, up to four panels resized / packed to S x S uint8 and stacked left to right, B frames in one launch
-* ``SoftErosion``            src/utils/crop.py:21-47            (the reference runs it with .cuda() too: pure torch)
+* ``yuv_to_rgb``, ``rgb_to_yuv``   no counterpart: the reference lets swscale convert on the host (imageio-ffmpeg's rgb24, images2video).  NV12 / I420
+                             frames as the codec has them -> the chain's RGB frames and back, the blocks nothing wrote byte for byte (csrc/yuv.hip)
+* ``SoftErosion``            src/utils/crop.py:21-47           (the reference runs it with .cuda() too: pure torch)
 * ``prepare_paste_back``     src/utils/crop.py:515-521          (cv2.warpAffine of the float mask)
 * ``paste_back``             src/utils/crop.py:523-529          (cv2.warpAffine of the crop + blend)
 * ``paste_back_fused``       both of the above in one kernel launch per frame
@@ -234,6 +236,80 @@ def concat_frames(e: Engine, panels, kinds=None, shared=None, out=None):
     ptrs = (C.c_void_p * P)(*[t.data_ptr() for t in ts])
     e._call("cs_concat_frames", B, P, S, ptrs, (C.c_int * P)(*kinds), (C.c_int * P)(*shared), out)
     return out
+
+
+YUV_LAYOUTS = {"nv12": 0, "i420": 1}          # cs_yuv_to_rgb / cs_rgb_to_yuv: layout (i420 is ffmpeg's yuv420p)
+YUV_MATRICES = {"bt601": 0, "bt709": 1}       # matrix
+
+
+def yuv_format(who, layout, matrix, full_range):
+    """The three format arguments of the 4:2:0 calls -> the C ABI's integers; ValueError names the argument."""
+    if layout not in YUV_LAYOUTS:
+        raise ValueError(f"{who}: layout {layout!r} is none of {sorted(YUV_LAYOUTS)}")
+    if matrix not in YUV_MATRICES:
+        raise ValueError(f"{who}: matrix {matrix!r} is none of {sorted(YUV_MATRICES)}")
+    if not isinstance(full_range, (bool, np.bool_)) and full_range not in (0, 1):
+        raise ValueError(f"{who}: full_range {full_range!r} is neither True nor False")
+    return YUV_LAYOUTS[layout], YUV_MATRICES[matrix], int(bool(full_range))
+
+
+def yuv_frame_hw(who, shape, what="yuv"):
+    """(F, 3 Ho / 2, Wo) -> (Ho, Wo), both even and in 2 .. 16384; ValueError names `what`."""
+    if len(shape) != 3 or shape[0] < 1 or shape[1] < 3 or shape[1] % 3 or shape[2] < 2 or shape[2] % 2 or max(shape[1] // 3 * 2, shape[2]) > 16384:
+        raise ValueError(f"{who}: {what}: expected (F, 3 Ho / 2, Wo) uint8 4:2:0 frames with Ho and Wo even, 2 to 16384, got shape {tuple(shape)}")
+    return int(shape[1]) // 3 * 2, int(shape[2])
+
+
+def _disjoint(who, a, b):
+    a0, b0 = a.data_ptr(), b.data_ptr()
+    if a0 < b0 + b.numel() and b0 < a0 + a.numel():
+        raise ValueError(f"{who}: rgb and yuv overlap in memory")
+
+
+def yuv_to_rgb(e: Engine, yuv, layout="nv12", matrix="bt601", full_range=False, out=None):
+    """cs_yuv_to_rgb (include/canonswap_yuv.h): yuv (F, 3 Ho / 2, Wo) uint8, host or device - F frames of NV12 (the Y plane, then interleaved
+    U V rows) or I420 (Y, U plane, V plane), the memory of ffmpeg's rawvideo nv12 / yuv420p - -> (F, Ho, Wo, 3) uint8 RGB on the device, the
+    block's chroma replicated to its 2 x 2 pixels.  matrix "bt601" or "bt709"; full_range False: Y 16 - 235, chroma 16 - 240.  Integer
+    arithmetic, bit-equal to tests/yuv_ref.py.  No engine scratch, no allocation but the result, no host wait for device frames."""
+    who = "yuv_to_rgb"
+    fmt = yuv_format(who, layout, matrix, full_range)
+    t = torch.as_tensor(yuv)
+    if t.dtype != torch.uint8:
+        raise ValueError(f"{who}: yuv: expected uint8, got {t.dtype}")
+    Ho, Wo = yuv_frame_hw(who, t.shape)
+    t = t.to(e.device).contiguous()
+    try:
+        rgb = e._out(out, (t.shape[0], Ho, Wo, 3), torch.uint8)
+    except ValueError as err:
+        raise ValueError(f"{who}: out: {err}") from None
+    _disjoint(who, rgb, t)
+    e._call("cs_yuv_to_rgb", int(t.shape[0]), t, Ho, Wo, *fmt, rgb)
+    return rgb
+
+
+def rgb_to_yuv(e: Engine, rgb, layout="nv12", matrix="bt601", full_range=False, keep=None, out=None):
+    """cs_rgb_to_yuv: rgb (F, Ho, Wo, 3) uint8, host or device, Ho and Wo even -> (F, 3 Ho / 2, Wo) uint8 on the device in `layout`: Y per
+    pixel, U and V from the sums of R, G and B over the 2 x 2 block.  keep: the device YUV tensor the frames came from (contiguous, of the
+    result's shape); it is updated in place and returned: a block whose four RGB pixels still are what its six bytes decode to keeps those
+    bytes, every other block is re-encoded, so what nothing wrote since yuv_to_rgb comes back as it went in.  Pass keep or out, not both."""
+    who = "rgb_to_yuv"
+    fmt = yuv_format(who, layout, matrix, full_range)
+    t = torch.as_tensor(rgb)
+    if t.dtype != torch.uint8 or t.dim() != 4 or t.shape[3] != 3 or t.shape[0] < 1:
+        raise ValueError(f"{who}: rgb: expected (F, Ho, Wo, 3) uint8, got {tuple(t.shape)} {t.dtype}")
+    F, Ho, Wo = int(t.shape[0]), int(t.shape[1]), int(t.shape[2])
+    if Ho < 2 or Wo < 2 or Ho % 2 or Wo % 2 or max(Ho, Wo) > 16384:
+        raise ValueError(f"{who}: rgb: 4:2:0 needs an even Ho and Wo from 2 to 16384, got {Ho} x {Wo}")
+    if keep is not None and out is not None:
+        raise ValueError(f"{who}: keep / out: keep is the output as well; pass one of the two")
+    t = t.to(e.device).contiguous()
+    try:
+        yuv = e._out(keep if keep is not None else out, (F, Ho * 3 // 2, Wo), torch.uint8)
+    except ValueError as err:
+        raise ValueError(f"{who}: {'keep' if keep is not None else 'out'}: {err}") from None
+    _disjoint(who, t, yuv)
+    e._call("cs_rgb_to_yuv", F, t, Ho, Wo, *fmt, int(keep is not None), yuv)
+    return yuv
 
 
 class SoftErosion:

@@ -7,7 +7,9 @@ batch beside the generator of its neighbours instead of around its own:
     for f0, f1, view in drv.run(frames, lmk, source_id, masks=masks): ...     # view: pinned (f1 - f0, Ho, Wo, 3) u8, valid until the next next()
     out = drv.swap_video(frames, lmk, source_id, parse=True)                  # or drained into one (N, Ho, Wo, 3) array
 
-Host Python only: chain.FrameChain, tail, torch streams and events; no kernel and no C-ABI entry of its own.
+Host Python over chain.FrameChain, tail, torch streams and events.  In the default pixel_format "rgb24" the driver has no kernel
+of its own.  In "nv12" and "i420" it has two, cs_yuv_to_rgb and cs_rgb_to_yuv (include/canonswap_yuv.h, tail.yuv_to_rgb / rgb_to_yuv; DESIGN
+8.13): the frames cross the link as the codec has them, 1.5 bytes per pixel each way instead of 3, and are converted on the device.
 
 The schedule is one batch ahead.  Iteration k of the loop, all of it enqueued from the calling thread (the engine is not thread-safe):
     1. upload batch k + 1: host frames -> pinned slot -> device slot (k + 1) % 2, on the upload stream
@@ -29,6 +31,17 @@ The ordering rules.  Three streams beside the caller's: HostFrames.stream (uploa
        consumer has asked for the next item - the generator does not run between two next() calls.
     f. On close(), break, or an exception (the caller's logits_fn included), chain.drop_prefetches() runs and the caller's stream waits for
        the upload and the sink's stream (drop_prefetches joins the chain's side stream): the driver and its chain are usable again.
+The 4:2:0 formats (pixel_format="nv12" / "i420", with matrix= and full_range=).  frames, out= and the yielded views are (N, 3 Ho / 2, Wo)
+uint8, the memory of ffmpeg's rawvideo; the slots above hold YUV, and two further device slots (batch, Ho, Wo, 3) hold the RGB frames the
+chain works on.  Per slot: 1. the upload as above, into the device YUV slot; 2. on the caller's stream, behind the wait of rule b,
+cs_yuv_to_rgb writes the RGB slot; 3. crop, prefetch, chain and in-place paste-back as above, on the RGB slot; 4. cs_rgb_to_yuv(keep=1)
+converts the RGB slot back into the YUV slot it came from; 5. `pasted` is recorded behind it; 6. the YUV slot is downloaded.  The RGB slots
+are read and written on the caller's stream only, so stream order is all they need; rules a - f, their events and their waits are the same
+lines in both formats, and there is no further stream.  A batch without a face is not converted at all.  Because of keep, a frame without a
+face and every 2 x 2 block outside what the paste-back changed come back with the bytes they came in with; the blocks the paste changed are
+re-encoded (Y per pixel, U and V from the block's sums).  Per step the link carries B * Ho * Wo * 3 / 2 bytes each way (64 frames of 1080 x
+1920: 199 MB), the two launches move 597 MB and 796 MB of device memory.
+
 What the chain orders itself (stage A against the generator, the double buffer) stands in chain._StagedChain and is not restated here.
 On a latency-mode engine FrameChain.prefetch refuses; the driver runs stage A in-line there and keeps the rest of the schedule.  Stage A
 is prefetched only when the masks come finished (masks=): where it makes them of logits (logits_fn, parse=True) it runs in-line.
@@ -102,40 +115,56 @@ def _host_copy(dst, src):
         np.copyto(dst.numpy(), src)
 
 
-class _Source:
-    """The caller's frames, validated once and never written: `n` frames of `hw`; `pinned` is the (n, Ho, Wo, 3) pinned tensor they already
-    are, or None; fill(dst, f0, f1) copies frames [f0, f1) into the first rows of the pinned tensor dst."""
+PIXEL_FORMATS = ("rgb24", "nv12", "i420")
 
-    def __init__(self, frames, who="frames"):
+
+def _yuv_hw(shape, what):
+    """A 4:2:0 frame's (3 Ho / 2, Wo) -> (Ho, Wo); both must be even, which for Ho means a row count that is a multiple of 3."""
+    rows, Wo = int(shape[0]), int(shape[1])
+    if rows % 3 or Wo % 2:
+        raise ValueError(f"{what}: a 4:2:0 frame is (3 Ho / 2, Wo) uint8 with Ho and Wo even, got {rows} x {Wo} (Ho = {rows * 2 / 3:g})")
+    return rows // 3 * 2, Wo
+
+
+class _Source:
+    """The caller's frames, validated once and never written: `n` frames of `hw`, each of shape `frame` ((Ho, Wo, 3), or (3 Ho / 2, Wo) with
+    yuv=True); `pinned` is the (n, *frame) pinned tensor they already are, or None; fill(dst, f0, f1) copies frames [f0, f1) into the first
+    rows of the pinned tensor dst."""
+
+    def __init__(self, frames, who="frames", yuv=False):
         import torch
         self.pinned, self._arr, self._seq = None, None, None
+        self.yuv = bool(yuv)
+        one, ok = ("(3 Ho / 2, Wo)", lambda sh: len(sh) == 2) if yuv else ("(Ho, Wo, 3)", lambda sh: len(sh) == 3 and sh[2] == 3)
+        many = "(N, " + one[1:]
         if isinstance(frames, torch.Tensor):
             if frames.device.type != "cpu":
                 raise ValueError(f"{who}: expected host frames, got a tensor on {frames.device} (FrameChain takes device frames as they are)")
-            if frames.dtype != torch.uint8 or frames.dim() != 4 or frames.shape[3] != 3:
-                raise ValueError(f"{who}: expected (N, Ho, Wo, 3) uint8, got {tuple(frames.shape)} {frames.dtype}")
+            if frames.dtype != torch.uint8 or frames.dim() < 1 or not ok(frames.shape[1:]):
+                raise ValueError(f"{who}: expected {many} uint8, got {tuple(frames.shape)} {frames.dtype}")
             if frames.is_pinned() and frames.is_contiguous():
                 self.pinned = frames
             else:
                 self._arr = frames.detach().numpy()
-            self.n, self.hw = int(frames.shape[0]), (int(frames.shape[1]), int(frames.shape[2]))
+            self.n, self.frame = int(frames.shape[0]), tuple(int(v) for v in frames.shape[1:])
         elif isinstance(frames, np.ndarray):
-            if frames.dtype != np.uint8 or frames.ndim != 4 or frames.shape[3] != 3:
-                raise ValueError(f"{who}: expected (N, Ho, Wo, 3) uint8, got {tuple(frames.shape)} {frames.dtype}")
+            if frames.dtype != np.uint8 or frames.ndim < 1 or not ok(frames.shape[1:]):
+                raise ValueError(f"{who}: expected {many} uint8, got {tuple(frames.shape)} {frames.dtype}")
             self._arr = frames
-            self.n, self.hw = int(frames.shape[0]), (int(frames.shape[1]), int(frames.shape[2]))
+            self.n, self.frame = int(frames.shape[0]), tuple(int(v) for v in frames.shape[1:])
         else:
             try:
                 seq = [f.detach().numpy() if isinstance(f, torch.Tensor) else np.asarray(f) for f in frames]
             except TypeError:
-                raise ValueError(f"{who}: expected an (N, Ho, Wo, 3) uint8 array, a CPU tensor or a sequence of (Ho, Wo, 3) uint8 arrays") from None
+                raise ValueError(f"{who}: expected an {many} uint8 array, a CPU tensor or a sequence of {one} uint8 arrays") from None
             for j, f in enumerate(seq):
-                if f.dtype != np.uint8 or f.ndim != 3 or f.shape[2] != 3:
-                    raise ValueError(f"{who}: frame {j}: expected (Ho, Wo, 3) uint8, got {tuple(f.shape)} {f.dtype}")
+                if f.dtype != np.uint8 or not ok(f.shape):
+                    raise ValueError(f"{who}: frame {j}: expected {one} uint8, got {tuple(f.shape)} {f.dtype}")
                 if f.shape != seq[0].shape:
                     raise ValueError(f"{who}: frame {j} is {f.shape[0]} x {f.shape[1]}, frame 0 is {seq[0].shape[0]} x {seq[0].shape[1]}: one size per video")
             self._seq = seq
-            self.n, self.hw = len(seq), ((int(seq[0].shape[0]), int(seq[0].shape[1])) if seq else (0, 0))
+            self.n, self.frame = len(seq), (tuple(int(v) for v in seq[0].shape) if seq else ((0, 0) if yuv else (0, 0, 3)))
+        self.hw = _yuv_hw(self.frame, who) if yuv else self.frame[:2]
 
     def fill(self, dst, f0, f1):
         if self._arr is not None:
@@ -146,23 +175,25 @@ class _Source:
 
 
 class _Slots:
-    """What HostFrames and FrameSink share: a stream of their own and two pinned host buffers (batch, Ho, Wo, 3) u8, allocated at the first
-    reserve() of a size and kept."""
+    """What HostFrames and FrameSink share: a stream of their own and two pinned host buffers u8, (batch, Ho, Wo, 3) or for 4:2:0 frames
+    (batch, 3 Ho / 2, Wo), allocated at the first reserve() of a size and format and kept."""
 
     def __init__(self, device, batch):
         import torch
         self.device, self.batch = torch.device(device), int(batch)
         self.stream = torch.cuda.Stream(device=self.device)
-        self.hw, self.pinned = None, None
+        self.hw, self.yuv, self.pinned = None, False, None
 
-    def reserve(self, Ho, Wo):
+    def reserve(self, Ho, Wo, yuv=False):
         import torch
-        if self.hw != (Ho, Wo):
-            self.pinned = [torch.empty((self.batch, Ho, Wo, 3), dtype=torch.uint8, pin_memory=True) for _ in range(2)]
-            self._reserve_device(Ho, Wo)
-            self.hw = (Ho, Wo)
+        if (self.hw, self.yuv) != ((Ho, Wo), bool(yuv)):
+            frame = (Ho * 3 // 2, Wo) if yuv else (Ho, Wo, 3)
+            self.pinned = None
+            self.pinned = [torch.empty((self.batch,) + frame, dtype=torch.uint8, pin_memory=True) for _ in range(2)]
+            self._reserve_device(frame)
+            self.hw, self.yuv = (Ho, Wo), bool(yuv)
 
-    def _reserve_device(self, Ho, Wo):
+    def _reserve_device(self, frame):
         pass
 
 
@@ -178,10 +209,10 @@ class HostFrames(_Slots):
         self.copied = [torch.cuda.Event(), torch.cuda.Event()]
         self.consumed = [torch.cuda.Event(), torch.cuda.Event()]
 
-    def _reserve_device(self, Ho, Wo):
+    def _reserve_device(self, frame):
         import torch
         self.dev = None                                   # the old pair goes before the new one comes
-        self.dev = [torch.empty((self.batch, Ho, Wo, 3), dtype=torch.uint8, device=self.device) for _ in range(2)]
+        self.dev = [torch.empty((self.batch,) + frame, dtype=torch.uint8, device=self.device) for _ in range(2)]
 
     def upload(self, src: _Source, f0, f1, s, skip=(), mark=_no_mark):
         """Frames [f0, f1) of src into device slot s -> that slot's first f1 - f0 frames (a view).  Rules a and c.  mark: the driver's
@@ -258,6 +289,7 @@ class VideoSwapper:
             raise ValueError(f"_skip_waits: rule letters among {sorted(_RULES)}")
         self.upload = HostFrames(self.e.device, self.batch)
         self.sink = FrameSink(self.e.device, self.batch)
+        self._rgb, self._rgb_key = None, None      # the two RGB device slots of the 4:2:0 formats, made at the first such run of a size
         self.staging_ms = []              # host time of each batch's staging memcpy + H2D enqueue in the last run (tools/time_video.py reads it)
         self.trace = None                 # a list: the run appends (batch, name, timing event) at every stage boundary (tools/time_video.py)
 
@@ -266,9 +298,22 @@ class VideoSwapper:
         return [s for s in (self.upload.stream, self.sink.stream, self.chain._side) if s is not None]
 
     # ---- everything that can be refused, before anything is enqueued
-    def _check(self, frames, lmk, source_id, slots, frame_index, masks, parse, logits_fn):
+    @staticmethod
+    def _format(pixel_format, matrix, full_range):
+        """-> None for rgb24, else the (layout, matrix, full_range) names tail.yuv_to_rgb takes, checked."""
+        from . import tail
+        if pixel_format not in PIXEL_FORMATS:
+            raise ValueError(f"pixel_format: {pixel_format!r} is none of {PIXEL_FORMATS}")
+        if pixel_format == "rgb24":
+            return None
+        tail.yuv_format("swap_video", pixel_format, matrix, full_range)
+        return pixel_format, matrix, bool(full_range)
+
+    def _check(self, frames, lmk, source_id, slots, frame_index, masks, parse, logits_fn, fmt=None):
         import torch
-        src = frames if isinstance(frames, _Source) else _Source(frames)
+        src = frames if isinstance(frames, _Source) else _Source(frames, yuv=fmt is not None)
+        if src.n and fmt is not None and max(src.hw) > 16384:
+            raise ValueError(f"frames: 4:2:0 frames of {src.hw[0]} x {src.hw[1]} are above 16384 a side")
         if src.n and min(src.hw) < 1:
             raise ValueError(f"frames: empty frames ({src.hw[0]} x {src.hw[1]})")
         given = [k for k, v in (("masks", masks is not None), ("parse", bool(parse)), ("logits_fn", logits_fn is not None)) if v]
@@ -305,9 +350,13 @@ class VideoSwapper:
         plan = plan_batches(src.n, fi, self.batch, self.max_faces)
         return src, lmk, source_id, slots, fi, masks, plan
 
-    def run(self, frames, lmk, source_id=None, *, slots=None, frame_index=None, masks=None, parse=False, logits_fn=None, _into=None, **crop_cfg):
+    def run(self, frames, lmk, source_id=None, *, slots=None, frame_index=None, masks=None, parse=False, logits_fn=None, pixel_format="rgb24",
+            matrix="bt601", full_range=False, _into=None, **crop_cfg):
         """-> a generator of (f0, f1, view) in frame order: view the pinned (f1 - f0, Ho, Wo, 3) u8 array of the pasted-back frames [f0, f1),
         valid until the next next().
+        pixel_format "nv12" or "i420" (ffmpeg's yuv420p), with matrix "bt601" / "bt709" and full_range: frames and the views are 4:2:0,
+        (N, 3 Ho / 2, Wo) uint8 - an array, a CPU tensor or a sequence of (3 Ho / 2, Wo) arrays - converted on the device both ways; what the
+        paste-back did not change comes back byte for byte (the module's text).
         frames: (N, Ho, Wo, 3) uint8 ndarray, a sequence of N (Ho, Wo, 3) uint8 arrays, or a CPU tensor (a pinned one is uploaded from its own
         memory); never written.  lmk (B, n_points, 2): the landmarks of each face, host.  frame_index: the frame of each of the B faces
         (non-decreasing; a frame may hold several faces or none), None: one face per frame.  source_id (1, 512) for all faces or (B, 512), or
@@ -318,15 +367,16 @@ class VideoSwapper:
         for k in crop_cfg:
             if k not in ("dsize", "scale", "vy_ratio", "flag_do_rot"):
                 raise TypeError(f"run() got an unexpected keyword argument {k!r}")
-        checked = self._check(frames, lmk, source_id, slots, frame_index, masks, parse, logits_fn)
-        return self._run(*checked, bool(parse), logits_fn, _into, crop_cfg)
+        fmt = self._format(pixel_format, matrix, full_range)
+        checked = self._check(frames, lmk, source_id, slots, frame_index, masks, parse, logits_fn, fmt)
+        return self._run(*checked, bool(parse), logits_fn, _into, crop_cfg, fmt)
 
     def swap_video(self, frames, lmk, source_id=None, *, out=None, **kw):
-        """run() drained into out, an (N, Ho, Wo, 3) uint8 ndarray or CPU tensor (allocated when None) -> out.  A pinned contiguous tensor is
-        downloaded into directly."""
+        """run() drained into out, an (N, Ho, Wo, 3) uint8 ndarray or CPU tensor - (N, 3 Ho / 2, Wo) in a 4:2:0 pixel_format - (allocated when
+        None) -> out.  A pinned contiguous tensor is downloaded into directly."""
         import torch
-        src = _Source(frames)
-        shape = (src.n,) + src.hw + (3,)
+        src = _Source(frames, yuv=self._format(kw.get("pixel_format", "rgb24"), kw.get("matrix", "bt601"), kw.get("full_range", False)) is not None)
+        shape = (src.n,) + src.frame
         direct = None
         if out is None:
             out = np.empty(shape, np.uint8)
@@ -352,18 +402,23 @@ class VideoSwapper:
         return out
 
     # ---- the loop
-    def _run(self, src, lmk, source_id, slots, fi, masks, plan, parse, logits_fn, into, crop_cfg):
+    def _run(self, src, lmk, source_id, slots, fi, masks, plan, parse, logits_fn, into, crop_cfg, fmt=None):
         import time
         import torch
+        from . import tail
         if not plan:
             return
         e, chain, up, sink, skip = self.e, self.chain, self.upload, self.sink, self._skip
         main = torch.cuda.current_stream(e.device)
         self.staging_ms = []
         try:
-            up.reserve(*src.hw)
+            up.reserve(*src.hw, yuv=src.yuv)
             if into is None:
-                sink.reserve(*src.hw)
+                sink.reserve(*src.hw, yuv=src.yuv)
+            if fmt is not None and self._rgb_key != (src.hw, self.batch):                     # the RGB slots of the 4:2:0 formats: the caller's stream only
+                self._rgb = None
+                self._rgb = [torch.empty((self.batch,) + src.hw + (3,), dtype=torch.uint8, device=e.device) for _ in range(2)]
+                self._rgb_key = (src.hw, self.batch)
             if source_id is not None:
                 source_id = source_id.detach().to(e.device).float().reshape(-1, 512)
             if masks is not None and not isinstance(masks, torch.Tensor):
@@ -391,6 +446,10 @@ class VideoSwapper:
                     main.wait_event(up.copied[s])                                             # rule b
                 mark("crop_begin")
                 st = {"k": k, "span": (f0, f1), "slot": s, "dev": dev, "faces": b1 - b0}
+                if fmt is not None and b1 > b0:                                               # a batch without a face stays as it was uploaded
+                    st["yuv"], dev = dev, tail.yuv_to_rgb(e, dev, *fmt, out=self._rgb[s][: f1 - f0])
+                    st["dev"] = dev
+                    mark("rgb_ready")
                 if b1 > b0:
                     idx = np.arange(f1 - f0, dtype=np.int32) if fi is None else (fi[b0:b1] - f0).astype(np.int32)
                     c = chain.crop(dev, lmk[b0:b1], frame_index=idx, **crop_cfg)
@@ -414,6 +473,9 @@ class VideoSwapper:
                 if st["faces"]:
                     chain(st["crops"], st["masks"], st["M_c2o"], dev, st["source_id"], slots=st["slots"], out=dev, logits=st["logits"],
                           parse=parse, frame_index=st["index"])
+                    if fmt is not None:
+                        mark("paste_end")
+                        dev = tail.rgb_to_yuv(e, dev, *fmt, keep=st["yuv"])                   # back into the YUV slot the batch came in
                 sink.pasted[s].record(main)
                 mark("chain_end")
                 f0, f1 = st["span"]

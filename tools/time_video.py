@@ -1,6 +1,7 @@
 """Timing of the video driver (canonswap_amd/video.py) on one MI355X: host frames through FrameChain and back; prints one JSON line.
 
     python tools/time_video.py [--frames 640] [--batch 64] [--size 1080x1920] [--reps 10] [--out profiles/video_b64.json]
+    python tools/time_video.py --pixel-format nv12 --out profiles/video_yuv_b64.json
 
 One process, every shape warmed, profiler off.  Per repetition, in alternation on the same box, one pass over the same video each (a host
 clock around a pass that ends with its last frame on the host, or in a device synchronise):
@@ -11,7 +12,12 @@ clock around a pass that ends with its last frame on the host, or in a device sy
 The MEDIAN of the repetitions with min and max, the ratios a/c and a/b in frames per second, the bytes moved per step, the host-side staging
 time per batch, and - from one further traced pass per source kind, timing events at every stage boundary of the driver - where a step's time
 goes: the copies, the caller's stream waiting for an upload, the sink waiting for the paste-back.  Nothing is fixed in advance: the record
-holds what was measured.  Needs a GPU: the engine raises without one."""
+holds what was measured.  Needs a GPU: the engine raises without one.
+
+--pixel-format nv12 (or i420) adds, in the same alternation, the driver on 4:2:0 frames of the same size (random bytes, pageable to pageable
+and pinned to pinned; checked against the synchronous device loop yuv_to_rgb, crop, chain, rgb_to_yuv(keep=) per batch), its traced pass,
+the bytes over the link in either format, and the two conversion launches on one step's frames timed on their own (events around each,
+median of 20, with the bytes they move and the rate that makes)."""
 import argparse
 import json
 import os
@@ -41,7 +47,10 @@ def _stage_times(trace, nb):
                                                                       "chain_end", "d2h_begin", "d2h_end"))]
     span = lambda a, b: round(statistics.median(ev[(k, a)].elapsed_time(ev[(k, b)]) for k in ks), 3)
     step = round(statistics.median(ev[(k, "chain_end")].elapsed_time(ev[(k + 1, "chain_end")]) for k in ks[:-1]), 3)
-    return {"batches": len(ks), "step_chain_end_to_chain_end": step, "h2d_copy": span("h2d_begin", "h2d_end"), "d2h_copy": span("d2h_begin", "d2h_end"),
+    yuv = {}
+    if ks and all((k, n) in ev for k in ks for n in ("rgb_ready", "paste_end")):          # a 4:2:0 pass: the two conversions, inside `crop` and `generator...`
+        yuv = {"yuv_to_rgb_incl_in_crop": span("crop_begin", "rgb_ready"), "rgb_to_yuv_keep_incl_in_generator_and_paste": span("paste_end", "chain_end")}
+    return {**yuv, "batches": len(ks), "step_chain_end_to_chain_end": step, "h2d_copy": span("h2d_begin", "h2d_end"), "d2h_copy": span("d2h_begin", "d2h_end"),
             "caller_stream_waits_for_upload": span("crop_queued", "crop_begin"), "crop": span("crop_begin", "crop_end"),
             "generator_and_paste_incl_wait_for_stage_a": span("chain_begin", "chain_end"), "sink_waits_after_paste": span("chain_end", "d2h_begin"),
             "paste_end_to_frames_on_host": span("chain_end", "d2h_end")}
@@ -53,6 +62,7 @@ def main():
     ap.add_argument("--batch", type=int, default=64)
     ap.add_argument("--size", default="1080x1920")
     ap.add_argument("--reps", type=int, default=10, help="timed repetitions per candidate (>= 10), one pass over the video each")
+    ap.add_argument("--pixel-format", default="rgb24", choices=["rgb24", "nv12", "i420"], help="also time the driver on 4:2:0 frames of this format")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     N, B = a.frames, a.batch
@@ -109,6 +119,30 @@ def main():
 
     cands = {"a_pageable_to_pageable": a_pageable, "a_pinned_to_pageable": a_pinned, "a_pinned_to_pinned": a_pinned_to_pinned,
              "b_synchronous_loop": b_loop, "c_chain_device_resident_prefetched": c_resident}
+    fmt = a.pixel_format
+    if fmt != "rgb24":
+        from canonswap_amd import tail
+        ybase = r.integers(0, 256, size=(min(N, B), Ho * 3 // 2, Wo), dtype=np.uint8)
+        yuv = np.concatenate([ybase] * ((N + len(ybase) - 1) // len(ybase)))[:N]
+        del ybase
+        yuv_pin = torch.from_numpy(yuv).pin_memory()
+        yout_np, yout_pin, yloop = np.empty_like(yuv), torch.empty(yuv.shape, dtype=torch.uint8).pin_memory(), np.empty_like(yuv)
+
+        def y_pageable():
+            drv.swap_video(yuv, lmk, slots=slots, masks=masks, out=yout_np, pixel_format=fmt)
+
+        def y_pinned_to_pinned():
+            drv.swap_video(yuv_pin, lmk, slots=slots, masks=masks, out=yout_pin, pixel_format=fmt)
+
+        def y_loop():
+            for f0, f1, b0, b1 in plan:
+                y = torch.from_numpy(yuv[f0:f1]).to(dev)
+                fr = tail.yuv_to_rgb(e, y, fmt)
+                c = chain.crop(fr, lmk[b0:b1])
+                chain(c["crops"], masks[b0:b1], c["M_c2o"], fr, slots=slots[b0:b1], out=fr)
+                yloop[f0:f1] = tail.rgb_to_yuv(e, fr, fmt, keep=y).cpu().numpy()
+
+        cands.update({f"a_{fmt}_pageable_to_pageable": y_pageable, f"a_{fmt}_pinned_to_pinned": y_pinned_to_pinned, f"b_{fmt}_synchronous_loop": y_loop})
     t = {k: [] for k in cands}
     staging = {k: [] for k in cands if k.startswith("a_")}
     with torch.cuda.device(dev):
@@ -118,6 +152,11 @@ def main():
         b_loop()
         a_pinned_to_pinned()
         same = bool(np.array_equal(out_pin.numpy(), out_np))                     # the driver's bytes against the loop's, at the timed size
+        if fmt != "rgb24":
+            y_loop()
+            y_pinned_to_pinned()
+            same = same and bool(np.array_equal(yout_pin.numpy(), yloop))
+            kept_blocks = float(((yloop[:B] == yuv[:B])[:, :Ho].reshape(B, Ho // 2, 2, Wo // 2, 2).all(axis=(2, 4))).mean())
         for i in range(reps):
             print(f"repetition {i + 1} of {reps}", file=sys.stderr, flush=True)
             for k, f in cands.items():
@@ -128,12 +167,40 @@ def main():
                 if k in staging:
                     staging[k].append(statistics.median(drv.staging_ms))
         stages = {}
-        for k in ("a_pageable_to_pageable", "a_pinned_to_pinned"):
+        for k in [k for k in cands if k.startswith("a_") and k != "a_pinned_to_pageable"]:
             drv.trace = []
             cands[k]()
             torch.cuda.synchronize(dev)
             stages[k] = _stage_times(drv.trace, len(plan))
             drv.trace = None
+
+        launches = None
+        if fmt != "rgb24":                                                       # the two conversions of one step's frames, on their own
+            y64 = torch.from_numpy(yuv[:B]).to(dev)
+            rgb64 = tail.yuv_to_rgb(e, y64, fmt)
+            c = chain.crop(rgb64, lmk[:B])
+            chain(c["crops"], masks[:B], c["M_c2o"], rgb64, slots=slots[:B], out=rgb64)      # pasted: what the encode meets in the driver
+            back = y64.clone()
+            scratch_rgb = torch.empty_like(rgb64)
+
+            def timed(f):
+                ms = []
+                for _ in range(20):
+                    a0, a1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                    a0.record()
+                    f()
+                    a1.record()
+                    a1.synchronize()
+                    ms.append(a0.elapsed_time(a1))
+                return statistics.median(ms), min(ms), max(ms)
+
+            px = B * Ho * Wo
+            d_ms, k_ms = timed(lambda: tail.yuv_to_rgb(e, y64, fmt, out=scratch_rgb)), timed(lambda: tail.rgb_to_yuv(e, rgb64, fmt, keep=back))
+            launches = {"frames": B, "yuv_to_rgb": {"ms": round(d_ms[0], 4), "min_max_ms": [round(d_ms[1], 4), round(d_ms[2], 4)], "bytes": px * 9 // 2,
+                                                     "TBps": round(px * 4.5 / d_ms[0] / 1e9, 3)},
+                        "rgb_to_yuv_keep": {"ms": round(k_ms[0], 4), "min_max_ms": [round(k_ms[1], 4), round(k_ms[2], 4)], "bytes": px * 6,
+                                            "TBps": round(px * 6 / k_ms[0] / 1e9, 3)},
+                        "share_of_blocks_kept_in_the_first_step": round(kept_blocks, 4)}
 
     med = {k: statistics.median(v) for k, v in t.items()}
     fps = {k: N / med[k] * 1e3 for k in med}
@@ -147,10 +214,13 @@ def main():
         "ratio_a_over_c": {k: round(fps[k] / fps["c_chain_device_resident_prefetched"], 4) for k in staging},
         "ratio_a_over_b": {k: round(fps[k] / fps["b_synchronous_loop"], 4) for k in staging},
         "bytes_per_step": {"frames_up": step_bytes, "frames_down": step_bytes, "masks_up": 0, "total": 2 * step_bytes},
-        "link_GBps_at_the_measured_rate": {k: round(2 * step_bytes / (med[k] / len(plan)) / 1e6, 2) for k in staging},
+        "link_GBps_at_the_measured_rate": {k: round((1 if fmt in k else 2) * step_bytes / (med[k] / len(plan)) / 1e6, 2) for k in staging},
         "host_staging_ms_per_batch": {k: round(statistics.median(v), 3) for k, v in staging.items()},
         "stage_ms_per_step_traced_pass": stages,
         "driver_equals_loop_bytes": same,
+        **({} if fmt == "rgb24" else {"pixel_format": fmt, "bytes_per_step_" + fmt: {"frames_up": step_bytes // 2, "frames_down": step_bytes // 2,
+                                                                                      "total": step_bytes},
+                                      "conversion_launches_one_step": launches}),
         "torch_intra_op_threads": torch.get_num_threads(),
         "device": torch.cuda.get_device_name(dev),
     }
