@@ -8,6 +8,7 @@ from __future__ import annotations
 
 import ctypes as C
 import os
+from typing import NamedTuple
 
 import torch          # before the library is loaded, see load()
 
@@ -17,8 +18,6 @@ ABI_VERSION = 4          # CS_ABI_VERSION of include/canonswap_hip.h
 MAX_IDENTITY_SLOTS = 8      # CS_MAX_IDENTITY_SLOTS (include/canonswap_hip.h)
 DET_MAX_CAND = 1024         # CS_DET_MAX_CAND: candidates per frame cs_det_decode takes
 DET_MAX_FACES = 256         # CS_DET_MAX_FACES: the largest max_faces of cs_det_decode
-LMK_ABI_VERSION = 1         # CS_LMK_ABI_VERSION of include/canonswap_landmarks.h
-YUV_ABI_VERSION = 1         # CS_YUV_ABI_VERSION of include/canonswap_yuv.h
 
 
 class ConvDesc(C.Structure):
@@ -54,7 +53,7 @@ class LmkLayout(C.Structure):
 vp, ci, cf, cl, cd = C.c_void_p, C.c_int, C.c_float, C.c_long, C.c_double
 pi, pd, pvp = C.POINTER(ci), C.POINTER(cd), C.POINTER(vp)
 # The binding, stated once: entry point -> (restype, argtypes), in the order of include/canonswap_hip.h.  tests/test_abi_cpu.py compares it with the
-# header class by class (pointer / int / long / float / double), and the header with the recorded tests/golden/abi_v4.txt.
+# header class by class (pointer / int / long / float / double), and the header with the recorded tests/golden/abi_v4.txt (HEADERS below).
 ABI = {
     "cs_create": (ci, [ci, ci, pvp]),
     "cs_destroy": (None, [vp]),
@@ -147,73 +146,96 @@ ABI = {
     "cs_op_parser_upadd": (ci, [vp, vp, vp, vp, vp, ci, ci, ci, ci, vp]),
     "cs_op_parser_read": (ci, [vp, ci, ci, vp, vp]),
 }
-# The landmark runner's entry points: a table of their own beside ABI, as their header stands beside canonswap_hip.h (the reason is stated there);
-# tests/test_landmarks_cpu.py compares it with include/canonswap_landmarks.h class by class.  load() binds it, call() takes names from either table.
+# The landmark runner's entry points: a table of their own beside ABI, as their header stands beside canonswap_hip.h (the reason is stated there).
 ABI_LANDMARKS = {
-    "cs_lmk_abi_version": (ci, []),      # a value, not a status
+    "cs_lmk_abi_version": (ci, []),
     "cs_lmk_input": (ci, [vp, ci, ci, vp, ci, ci, pi, vp, ci, LmkLayout, ci, cf, cf, ci, ci, vp, vp, vp, vp, vp]),
     "cs_lmk_decode": (ci, [vp, ci, vp, ci, vp, ci, vp, vp, vp]),
 }
-TAKES_STREAM_LANDMARKS = frozenset({"cs_lmk_input", "cs_lmk_decode"})
-# The 4:2:0 conversions, the third table: include/canonswap_yuv.h, compared class by class by tests/test_yuv_cpu.py.
+# The 4:2:0 conversions, the third table: include/canonswap_yuv.h.
 ABI_YUV = {
-    "cs_yuv_abi_version": (ci, []),      # a value, not a status
+    "cs_yuv_abi_version": (ci, []),
     "cs_yuv_to_rgb": (ci, [vp, ci, vp, ci, ci, ci, ci, ci, vp, vp]),
     "cs_rgb_to_yuv": (ci, [vp, ci, vp, ci, ci, ci, ci, ci, ci, vp, vp]),
 }
-TAKES_STREAM_YUV = frozenset({"cs_yuv_to_rgb", "cs_rgb_to_yuv"})
-_TABLES = {**ABI, **ABI_LANDMARKS, **ABI_YUV}
-STATUS = frozenset(name for name, (restype, _) in _TABLES.items()
-                   if restype is ci and name not in ("cs_abi_version", "cs_lmk_abi_version", "cs_yuv_abi_version"))      # 0, or the text is in cs_last_error()
-# The header's stream parameters are all the last one, `void* stream`; every entry has one but these (tests/test_abi_cpu.py reads the names).
-TAKES_STREAM = frozenset(ABI) - {"cs_create", "cs_destroy", "cs_last_error", "cs_abi_version", "cs_upload", "cs_finalize_weights", "cs_set_latency_mode",
-                                 "cs_profile_begin", "cs_profile_end", "cs_profile_exec_flops", "cs_op_chan_stats_partial_floats", "cs_op_g_stop", "cs_op_v_stop"}
+
+
+class Header(NamedTuple):
+    """One header under include/ as the package binds it; tests/test_abi_cpu.py compares it with the header and the header's recorded text."""
+    file: str
+    table: dict             # entry point -> (restype, argtypes), in the header's order
+    version_define: str
+    version: int
+    version_call: str       # returns `version`: a value, not a status
+    structs: dict           # C name -> ctypes class
+    constants: dict         # the header's other #defines: C name -> value
+    ab_may_lack: bool       # an A/B library of an older tree (CANONSWAP_LIB, tools/cmp_libs.py) may lack the whole header
+
+
+def _header(file, table, version_define, version, structs, constants, ab_may_lack):
+    (version_call,) = (name for name, sig in table.items() if sig == (C.c_int, []))          # the table's one `int f(void)`
+    return Header(file, table, version_define, version, version_call, structs, constants, ab_may_lack)
+
+
+# A further header is a further record: everything below follows from these.
+HEADERS = (
+    _header("canonswap_hip.h", ABI, "CS_ABI_VERSION", ABI_VERSION, {"cs_conv_desc": ConvDesc},
+            {"CS_MAX_IDENTITY_SLOTS": MAX_IDENTITY_SLOTS, "CS_DET_MAX_CAND": DET_MAX_CAND, "CS_DET_MAX_FACES": DET_MAX_FACES}, False),
+    _header("canonswap_landmarks.h", ABI_LANDMARKS, "CS_LMK_ABI_VERSION", 1, {"cs_lmk_layout": LmkLayout}, {}, True),
+    _header("canonswap_yuv.h", ABI_YUV, "CS_YUV_ABI_VERSION", 1, {}, {}, True),
+)
+_TABLES = {name: sig for h in HEADERS for name, sig in h.table.items()}
+if len(_TABLES) != sum(len(h.table) for h in HEADERS):
+    raise ImportError("canonswap_amd/_lib.py: an entry point stands in two headers' tables")
+_VERSION_CALLS = frozenset(h.version_call for h in HEADERS)
+STATUS = frozenset(name for name, (restype, _) in _TABLES.items() if restype is ci) - _VERSION_CALLS      # 0, or the text is in cs_last_error()
+# The headers' stream parameters are all the last one, `void* stream`; every entry has one but the version calls and these (tests/test_abi_cpu.py).
+TAKES_STREAM = frozenset(_TABLES) - _VERSION_CALLS - {
+    "cs_create", "cs_destroy", "cs_last_error", "cs_upload", "cs_finalize_weights", "cs_set_latency_mode", "cs_profile_begin", "cs_profile_end",
+    "cs_profile_exec_flops", "cs_op_chan_stats_partial_floats", "cs_op_g_stop", "cs_op_v_stop"}
 _PTR_SLOTS = {name: tuple(t in (vp, C.c_char_p) or issubclass(t, C._Pointer) for t in argtypes) for name, (_, argtypes) in _TABLES.items()}      # or a number
 del vp, ci, cf, cl, cd, pi, pd, pvp
 ABI_SYMBOLS = list(ABI)
-# tests only; an A/B build of an older tree - CANONSWAP_LIB, tools/cmp_libs.py - has none of these: load() binds them where they exist
+# tests only; an A/B build of an older tree - CANONSWAP_LIB, tools/cmp_libs.py - has none of these: bind() binds them where they exist
 ABI_OPTIONAL = ("cs_op_g_read", "cs_op_g_fill", "cs_op_g_stop", "cs_op_v_read", "cs_op_v_fill", "cs_op_v_stop", "cs_op_conv_first", "cs_op_norm_act",
                 "cs_op_split16")
 _lib = None
 
 
+def bind(lib, ab=False):
+    """Give every entry point of HEADERS its restype and argtypes on `lib` (a CDLL, or anything with the entry points as attributes) and check
+    each header's version.  A missing entry point raises AttributeError, but for the ABI_OPTIONAL ones and, with `ab`, for a whole header that
+    an A/B library may lack: it is skipped where its version call is missing, and a call of one of its names raises AttributeError then."""
+    for h in HEADERS:
+        if ab and h.ab_may_lack and not hasattr(lib, h.version_call):
+            continue
+        speaks = getattr(lib, h.version_call)()          # (ctypes' default restype is the int it returns)
+        if speaks != h.version:
+            what, binds = ((f"C-ABI version {speaks}", f"{h.version} (include/{h.file}: {h.version_define})") if h is HEADERS[0] else
+                           (f"version {speaks} of include/{h.file}", h.version))
+            raise RuntimeError(f"{LIB_PATH} speaks {what}, this package binds version {binds}: rebuild with __graft_entry__.build()")
+        for name, (restype, argtypes) in h.table.items():
+            if name in ABI_OPTIONAL and not hasattr(lib, name):
+                continue
+            f = getattr(lib, name)
+            f.restype, f.argtypes = restype, argtypes
+    return lib
+
+
 def load():
     """Load the shared library; raises RuntimeError if it is missing (no fallback)."""
     global _lib
-    if _lib is not None:
-        return _lib
-    if not os.path.exists(LIB_PATH):
-        raise RuntimeError(
-            f"{LIB_PATH} is missing: the HIP engine has not been built. Run `python -c 'import __graft_entry__ as g; g.build()'` "
-            "(needs hipcc); canonswap_amd has no CPU fallback.")
-    # The process must hold ONE HIP runtime.  This package's callers pass torch tensors and torch's stream, and torch carries its own
-    # libamdhip64 / libhsa-runtime64: imported first, its copies satisfy this library's NEEDED entries too.  Loaded the other way round (this
-    # library first - `python __graft_entry__.py smoke`, whose build() checks the ABI before anything imports torch) the system runtime and
-    # torch's both initialise and cs_create sees 0 devices.  Hence the import of torch at the top of this module.
-    lib = C.CDLL(LIB_PATH)
-    if lib.cs_abi_version() != ABI_VERSION:
-        raise RuntimeError(f"{LIB_PATH} speaks C-ABI version {lib.cs_abi_version()}, this package binds version {ABI_VERSION} "
-                           "(include/canonswap_hip.h: CS_ABI_VERSION): rebuild with __graft_entry__.build()")
-    # An A/B library of an older tree (CANONSWAP_LIB, tools/cmp_libs.py) may have no landmark or no 4:2:0 entry points: there each further table
-    # is bound where it exists, and a call of a missing name raises AttributeError.  The in-tree library must carry all of them.
-    ab = bool(os.environ.get("CANONSWAP_LIB"))
-    beside = [(ABI_LANDMARKS, "cs_lmk_abi_version", LMK_ABI_VERSION, "include/canonswap_landmarks.h"),
-              (ABI_YUV, "cs_yuv_abi_version", YUV_ABI_VERSION, "include/canonswap_yuv.h")]
-    absent = set()
-    for table, version_call, _, _ in beside:
-        if ab and not hasattr(lib, version_call):
-            absent |= set(table)
-    for name, (restype, argtypes) in _TABLES.items():
-        if (name in ABI_OPTIONAL or name in absent) and not hasattr(lib, name):
-            continue
-        f = getattr(lib, name)          # (a missing symbol raises AttributeError here)
-        f.restype, f.argtypes = restype, argtypes
-    for table, version_call, version, header in beside:
-        if version_call not in absent and getattr(lib, version_call)() != version:
-            raise RuntimeError(f"{LIB_PATH} speaks version {getattr(lib, version_call)()} of {header}, this package binds version "
-                               f"{version}: rebuild with __graft_entry__.build()")
-    _lib = lib
-    return lib
+    if _lib is None:
+        if not os.path.exists(LIB_PATH):
+            raise RuntimeError(
+                f"{LIB_PATH} is missing: the HIP engine has not been built. Run `python -c 'import __graft_entry__ as g; g.build()'` "
+                "(needs hipcc); canonswap_amd has no CPU fallback.")
+        # The process must hold ONE HIP runtime.  This package's callers pass torch tensors and torch's stream, and torch carries its own
+        # libamdhip64 / libhsa-runtime64: imported first, its copies satisfy this library's NEEDED entries too.  Loaded the other way round (this
+        # library first - `python __graft_entry__.py smoke`, whose build() checks the ABI before anything imports torch) the system runtime and
+        # torch's both initialise and cs_create sees 0 devices.  Hence the import of torch at the top of this module.
+        _lib = bind(C.CDLL(LIB_PATH), ab=bool(os.environ.get("CANONSWAP_LIB")))          # the in-tree library must carry every header
+    return _lib
 
 
 _test_lib = None
@@ -237,7 +259,7 @@ def check(rc: int, what: str):
 
 
 def call(name, *args, what=None, device=None):
-    """The one way into the library: entry point `name` of ABI, ABI_LANDMARKS or ABI_YUV with exactly its arguments, checked before the library is touched.  A torch tensor
+    """The one way into the library: entry point `name` of any of HEADERS with exactly its arguments, checked before the library is touched.  A torch tensor
     stands for its address: in a pointer slot only, and only from a GPU (device=: from that one); None is NULL; the rest goes to ctypes as it is
     (contiguity and dtype are the caller's).  A nonzero status raises RuntimeError("<what or name> failed: <cs_last_error>"); values are returned."""
     argtypes = _TABLES[name][1]

@@ -70,7 +70,7 @@ class Engine:
     def _call(self, name, *args, what=None):
         """Entry point `name` on this engine: the handle first, torch's current stream of the engine's device last where the entry point takes
         one, tensors from that device only (_lib.call), under the package's one device guard (the C side keeps its own)."""
-        if name in _lib.TAKES_STREAM or name in _lib.TAKES_STREAM_LANDMARKS or name in _lib.TAKES_STREAM_YUV:
+        if name in _lib.TAKES_STREAM:
             args += (self._stream(),)
         with torch.cuda.device(self.device):
             return _lib.call(name, self.h, *args, what=what, device=self.device)

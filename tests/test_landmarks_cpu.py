@@ -1,5 +1,5 @@
-"""The landmark runner's two sides (cs_lmk_input, cs_lmk_decode; canonswap_amd/landmarks.py) without a GPU: the C ABI of
-include/canonswap_landmarks.h against its binding table, the geometry function of csrc/lmk_geometry.h compiled for the host and held to the
+"""The landmark runner's two sides (cs_lmk_input, cs_lmk_decode; canonswap_amd/landmarks.py) without a GPU: what the C ABI of
+include/canonswap_landmarks.h states beyond its types (those: test_abi_cpu.py), the geometry function of csrc/lmk_geometry.h compiled for the host and held to the
 reference's own matrices (tests/golden/crop_geometry.npz) and to its guard on landmarks that must be refused, and track_video's batch planning
 with a stub engine.
 
@@ -16,7 +16,6 @@ import numpy as np
 import pytest
 
 import landmarks_ref as LR
-from test_abi_cpu import _c_class, _ctypes_class, mismatches, stream_entries
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HEADER = os.path.join(ROOT, "include", "canonswap_landmarks.h")
@@ -32,65 +31,10 @@ def _cfg(c):
 
 
 # ------------------------------------------------------------------------------------------------ the C ABI
-def render_landmarks_header(text):
-    """include/canonswap_landmarks.h as lines, in test_abi_cpu's form: `name: ret(class, ...)` per prototype (a cs_lmk_layout by value is class
-    `layout`), `name class` per field of cs_lmk_layout (an array field is `int[n]`), `CS_LMK_ABI_VERSION value`."""
-    text = re.sub(r"/\*.*?\*/", " ", text, flags=re.S)
-    defines = dict(re.findall(r"^[ \t]*#[ \t]*define[ \t]+(\w+)[ \t]+(\w+)", text, flags=re.M))
-    text = re.sub(r"^[ \t]*#[^\n]*", " ", text, flags=re.M)
-    text = re.sub(r'extern\s+"C"\s*\{', " ", text)
-    struct = re.search(r"typedef\s+struct\s+cs_lmk_layout\s*\{(.*?)\}\s*cs_lmk_layout\s*;", text, flags=re.S)
-    assert struct, "cs_lmk_layout: no such struct in the header"
-    text = text[:struct.start()] + text[struct.end():]
-    *statements, rest = text.split(";")
-    assert rest.strip() == "}", rest
-    lines = []
-    for s in statements:
-        m = re.fullmatch(r"\s*([\w\s\*]+?)\s*\b(cs_\w+)\s*\((.*)\)\s*", s, flags=re.S)
-        assert m, s
-        ret, name, params = m.groups()
-        params = [] if params.strip() == "void" else params.split(",")
-        cls = ["layout" if re.fullmatch(r"\s*cs_lmk_layout\s+\w+\s*", p) else _c_class(p, name, True) for p in params]
-        lines.append(f"{name}: {_c_class(ret, name, False)}({', '.join(cls)})")
-    for s in struct.group(1).split(";"):
-        if not s.strip():
-            continue
-        first, *more = s.split(",")
-        base = first.split()[0]
-        for d in [first[len(first) - len(first.lstrip()) + len(base):]] + more:
-            name, dim = re.fullmatch(r"\s*(\w+)\s*(?:\[(\d+)\])?\s*", d).groups()
-            lines.append(f"{name} {base}[{dim}]" if dim else f"{name} {base}")
-    lines.append(f"CS_LMK_ABI_VERSION {defines['CS_LMK_ABI_VERSION']}")
-    return lines
-
-
-def render_landmarks_binding(_lib):
-    cls = lambda t, owner: "layout" if t is _lib.LmkLayout else _ctypes_class(t, owner)
-    lines = [f"{name}: {cls(ret, name)}({', '.join(cls(a, name) for a in args)})" for name, (ret, args) in _lib.ABI_LANDMARKS.items()]
-    for name, t in _lib.LmkLayout._fields_:
-        lines.append(f"{name} int[{t._length_}]" if issubclass(t, C.Array) else f"{name} {_ctypes_class(t, name)}")
-    return lines + [f"CS_LMK_ABI_VERSION {_lib.LMK_ABI_VERSION}"]
-
-
-def test_header_equals_binding():
-    from canonswap_amd import _lib
-    header = open(HEADER).read()
-    assert mismatches(render_landmarks_header(header), render_landmarks_binding(_lib), "canonswap_amd/_lib.py ABI_LANDMARKS") == []
-    assert render_landmarks_header(header) == render_landmarks_binding(_lib)
-    assert stream_entries(header) == set(_lib.TAKES_STREAM_LANDMARKS)
-    assert not set(_lib.ABI_LANDMARKS) & set(_lib.ABI)
-    bad = header.replace("const float* lmk, int N", "const float* lmk, long N")          # the check can fail
-    assert any(m.startswith("cs_lmk_input:") for m in mismatches(render_landmarks_header(bad), render_landmarks_binding(_lib), "the table"))
-
-
 def test_symbols_are_exported_and_bound():
+    """(The entry points' types, arity and export, the header against its record and its recorded text: test_abi_cpu.py.)"""
     from canonswap_amd import _lib
-    lib = _lib.load()
-    for name, (ret, args) in _lib.ABI_LANDMARKS.items():
-        assert hasattr(lib, name), f"{name}: not exported"
-        f = getattr(lib, name)
-        assert list(f.argtypes) == list(args) and f.restype is ret, name
-    assert lib.cs_lmk_abi_version() == _lib.LMK_ABI_VERSION == 1
+    assert _lib.load().cs_lmk_abi_version() == 1
     assert "cs_lmk_abi_version" not in _lib.STATUS and {"cs_lmk_input", "cs_lmk_decode"} <= _lib.STATUS
     with pytest.raises(TypeError, match="cs_lmk_decode takes 9 arguments"):             # the same checks as any other entry point (_lib.call)
         _lib.call("cs_lmk_decode", None)

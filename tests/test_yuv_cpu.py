@@ -1,6 +1,6 @@
 """The 4:2:0 conversions (cs_yuv_to_rgb, cs_rgb_to_yuv; include/canonswap_yuv.h) without a GPU: the numpy restatement tests/yuv_ref.py, which
 defines their integer arithmetic, against the standards' float64 formula; csrc/yuv_math.h compiled for the host against the restatement, bit for
-bit; the keep rule; the C ABI against its binding table; and what the Python wrappers and the video driver refuse before they touch a GPU.
+bit; the keep rule; the C ABI beyond its types (those: test_abi_cpu.py); and what the Python wrappers and the video driver refuse before they touch a GPU.
 
 Bounds.  Decode: the coefficients carry 14 fractional bits, so each of at most three products is off by at most 2^-15 of its factor, which is
 below 255: |integer result before the shift - float64 formula| < 3 x 2^-15 x 255 < 0.03.  Rounding two numbers 0.03 apart gives integers at
@@ -8,14 +8,12 @@ most 1 apart: every channel within 1 LSB of the rounded (and clamped) float64 va
 give < 3 x 2^-17 x 255 per pixel, far below 0.03: the same 1 LSB, for luma and for chroma."""
 import ctypes as C
 import os
-import re
 import subprocess
 
 import numpy as np
 import pytest
 
 import yuv_ref as YR
-from test_abi_cpu import _c_class, _ctypes_class, mismatches, stream_entries
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HEADER = os.path.join(ROOT, "include", "canonswap_yuv.h")
@@ -149,48 +147,10 @@ def test_the_kernels_arithmetic_equals_the_restatement(host, matrix, full_range)
 
 
 # ------------------------------------------------------------------------------------------------ the C ABI
-def render_yuv_header(text):
-    """include/canonswap_yuv.h as lines, in test_abi_cpu's form: `name: ret(class, ...)` per prototype, then `CS_YUV_ABI_VERSION value`."""
-    text = re.sub(r"/\*.*?\*/", " ", text, flags=re.S)
-    defines = dict(re.findall(r"^[ \t]*#[ \t]*define[ \t]+(\w+)[ \t]+(\w+)", text, flags=re.M))
-    text = re.sub(r"^[ \t]*#[^\n]*", " ", text, flags=re.M)
-    text = re.sub(r'extern\s+"C"\s*\{', " ", text)
-    *statements, rest = text.split(";")
-    assert rest.strip() == "}", rest
-    lines = []
-    for s in statements:
-        m = re.fullmatch(r"\s*([\w\s\*]+?)\s*\b(cs_\w+)\s*\((.*)\)\s*", s, flags=re.S)
-        assert m, s
-        ret, name, params = m.groups()
-        params = [] if params.strip() == "void" else params.split(",")
-        lines.append(f"{name}: {_c_class(ret, name, False)}({', '.join(_c_class(p, name, True) for p in params)})")
-    return lines + [f"CS_YUV_ABI_VERSION {defines['CS_YUV_ABI_VERSION']}"]
-
-
-def render_yuv_binding(_lib):
-    lines = [f"{name}: {_ctypes_class(ret, name)}({', '.join(_ctypes_class(a, name) for a in args)})" for name, (ret, args) in _lib.ABI_YUV.items()]
-    return lines + [f"CS_YUV_ABI_VERSION {_lib.YUV_ABI_VERSION}"]
-
-
-def test_header_equals_binding():
-    from canonswap_amd import _lib
-    header = open(HEADER).read()
-    assert mismatches(render_yuv_header(header), render_yuv_binding(_lib), "canonswap_amd/_lib.py ABI_YUV") == []
-    assert render_yuv_header(header) == render_yuv_binding(_lib)
-    assert stream_entries(header) == set(_lib.TAKES_STREAM_YUV) == {"cs_yuv_to_rgb", "cs_rgb_to_yuv"}
-    assert not set(_lib.ABI_YUV) & (set(_lib.ABI) | set(_lib.ABI_LANDMARKS))
-    bad = header.replace("int full_range, int keep", "int full_range, long keep")          # the check can fail
-    assert any(m.startswith("cs_rgb_to_yuv:") for m in mismatches(render_yuv_header(bad), render_yuv_binding(_lib), "the table"))
-
-
 def test_symbols_are_exported_and_bound():
+    """(The entry points' types, arity and export, the header against its record and its recorded text: test_abi_cpu.py.)"""
     from canonswap_amd import _build, _lib
-    lib = _lib.load()
-    for name, (ret, args) in _lib.ABI_YUV.items():
-        assert hasattr(lib, name), f"{name}: not exported"
-        f = getattr(lib, name)
-        assert list(f.argtypes) == list(args) and f.restype is ret, name
-    assert lib.cs_yuv_abi_version() == _lib.YUV_ABI_VERSION == 1
+    assert _lib.load().cs_yuv_abi_version() == 1
     assert "cs_yuv_abi_version" not in _lib.STATUS and {"cs_yuv_to_rgb", "cs_rgb_to_yuv"} <= _lib.STATUS
     with pytest.raises(TypeError, match="cs_rgb_to_yuv takes 11 arguments"):
         _lib.call("cs_rgb_to_yuv", None)
