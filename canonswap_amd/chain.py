@@ -132,17 +132,18 @@ class _StagedChain:
         self._side.wait_stream(main)                      # the crops (and AnimateChain's source state) were produced on the caller's stream
         self._side.wait_event(self._free[slot])           # the generator that read this half of the double buffer is done
         with torch.cuda.stream(self._side):
+            e.wait_prefetch()                             # another chain's stage A on this engine: the one M and SoftErosion scratch
             res = self._stage_a(crops_u8, *args, slot)
             ready = torch.cuda.Event()
             ready.record(self._side)
+        e._prefetch_ready = ready                         # every later user of that scratch, on any stream, waits for it (Engine.wait_prefetch)
         self._pending.append((crops_u8, slot, res, ready))
 
     def drop_prefetches(self):
         """Forget staged batches that will not be run (their buffers are reused by the next prefetch).  Their stage A may still be running
         on the side stream: the caller's stream waits for it, as an in-line stage A must (both use the engine's M and SoftErosion scratch)."""
         self._pending = []
-        if self._side is not None:
-            torch.cuda.current_stream(self.e.device).wait_stream(self._side)
+        self.e.wait_prefetch()
 
     def _resolve(self, crops_u8, *args):
         """Head of __call__ -> (slot, stage A's result): the staged batch whose crops tensor is this one (slot = its half of the double
@@ -153,8 +154,7 @@ class _StagedChain:
             _, slot, res, ready = self._pending.pop(hit[0])
             main.wait_event(ready)
             return slot, res
-        if self._side is not None:
-            main.wait_stream(self._side)      # a prefetch in flight uses the same M and SoftErosion scratch in the engine
+        self.e.wait_prefetch()                # a prefetch in flight, this chain's or another's, uses the same M and SoftErosion scratch in the engine
         return None, self._stage_a(crops_u8, *args, "inline")
 
     def _release(self, slot):
@@ -187,20 +187,24 @@ class FrameChain(_StagedChain):
             logits = self.e.parser(pv, out=self._get(("logits", slot), (B, self.e.parser_cfg["L"], 128, 128), torch.float32))
         I = tail.prepare_crops(self.e, t, out=self._get(("I", slot), (B, 3, 256, 256), torch.float32))      # cropper.py:209 + can_swap_e2e.py:147-163
         x_t, x_can = self.keypoints(I, slot)                                                              # can_swap_pipeline_e2e.py:111-125, 243
+        made = None
         if logits is not None:
-            m = tail.face_masks(self.e, logits, self.valid, out=self._get(("mask", slot), (B, 512, 512), torch.uint8))
+            m = made = tail.face_masks(self.e, logits, self.valid, out=self._get(("mask", slot), (B, 512, 512), torch.uint8))
         else:
             m = torch.as_tensor(masks)
         soft = tail.soft_erosion_frames(self.e, m, self.se.weight, self.se.kernel_size, self.se.threshold, self.se.iterations,
                                         out=self._get(("soft", slot), (B,) + tuple(m.shape[-2:]), torch.float32))      # :274
-        return I, x_t, x_can, soft
+        return I, x_t, x_can, soft, made                      # made: the u8 mask stage A made (logits=, parse=True), None for the caller's masks
 
     def prefetch(self, crops_u8, masks=None, logits=None, parse=False):
         """Stage A of the NEXT batch on a side stream (masks, logits= or parse=True as in __call__; the engine's parser then runs there too, beside the generator: its workspace is its own), so that it runs beside the generator of the current one
         (M and the staging are bandwidth / latency bound, the generator is matrix-pipe bound): call it before __call__ of the current batch; the next __call__ with
         the same crops tensor picks the result up (the soft masks of that batch included: they depend on the parser's labels only).  M's workspace is its own, the batch's inputs land in the other half of a double buffer.
         Staged batches may be run in any order.  Not on a latency-mode engine: there every small plain conv (M's and the generator's
-        alike) runs split-K on the engine's one partial-sum buffer, which M on the side stream and the generator would share."""
+        alike) runs split-K on the engine's one partial-sum buffer, which M on the side stream and the generator would share.
+        NOT YET SAFE with logits= or parse=True beside the generator: the mask stage A makes then came out with a few isolated bytes flipped
+        (and the soft mask and frame pixels with them) in about half of the batches staged while the host ran ahead of the device; the cause
+        is not found.  With masks= the bytes are the in-line chain's.  video.VideoSwapper stages such batches in-line."""
         self._mask_or_logits(masks, logits, "FrameChain.prefetch", parse)
         self._stage_ahead(crops_u8, masks, logits, parse)
 
@@ -213,8 +217,10 @@ class FrameChain(_StagedChain):
         concat=True: also the frames of the pipeline's side-by-side video (:290, video.py:84-109), "concat" (B,512,2048,3) u8 (into concat_out):
         driving crop | rec_can (:248-250) | I_can (:257-259) | I_p.  The generator then runs its two debug decodes, into chain-owned buffers; without
         concat it runs neither.
-        -> {"frames": (B,Ho,Wo,3) u8[, "concat"][, "crops_out", "x_t", "x_can", "soft_mask" with keep=True, and "rec_can", "swap_can"
-        (B,3,512,512) fp32 with keep and concat]}
+        -> {"frames": (B,Ho,Wo,3) u8[, "concat"][, "crops_out", "x_t", "x_can", "I", "soft_mask", "mask" with keep=True, and "rec_can", "swap_can"
+        (B,3,512,512) fp32 with keep and concat]}.  "mask": the (B,512,512) u8 0/1 mask stage A made of the logits (logits=, parse=True), None where
+        the caller passed masks.  The kept stages are the chain's own buffers, not copies (no launch is added): "mask", "soft_mask", "I", "x_t" and
+        "x_can" of a prefetched batch are rewritten by the prefetch after the next one, "crops_out" by the next call.
         frame_index (B host ints, non-decreasing, in [0, F)): B faces in F frames.  Everything above stays per face (B up to the engine's
         max_batch; crops, masks / logits, M_c2o, source_id / slots, "concat", the kept stages); frames_ori, out and "frames" are (F,Ho,Wo,3): face b
         is pasted into frame frame_index[b], the faces of a frame in their order (tail.paste_back_faces), a frame without a face comes back as
@@ -225,7 +231,7 @@ class FrameChain(_StagedChain):
         self._mask_or_logits(masks, logits, "FrameChain", parse)
         if frame_index is not None:                                   # before anything is enqueued: the error names the argument
             frame_index = tail.frame_index_of(frame_index, len(crops_u8), len(frames_ori))
-        slot, (I, x_t, x_can, soft) = self._resolve(crops_u8, masks, logits, parse)
+        slot, (I, x_t, x_can, soft, made) = self._resolve(crops_u8, masks, logits, parse)
         B = I.shape[0]
         rec = self._get("rec_can", (B, 3, 512, 512), torch.float32) if concat else None
         swp = self._get("swap_can", (B, 3, 512, 512), torch.float32) if concat else None
@@ -240,7 +246,7 @@ class FrameChain(_StagedChain):
         if concat:
             res["concat"] = self._concat(crops_u8, [(rec, 3, 0), (swp, 3, 0)], gen, concat_out)  # :290
         if keep:
-            res.update(crops_out=gen, x_t=x_t, x_can=x_can, soft_mask=soft, I=I)
+            res.update(crops_out=gen, x_t=x_t, x_can=x_can, soft_mask=soft, I=I, mask=made)
             if concat:
                 res.update(rec_can=rec, swap_can=swp)
         return res

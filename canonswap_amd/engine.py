@@ -35,6 +35,14 @@ class Engine:
         self._ids = []            # resident identities: [slot, device copy (512,), last tensor seen, its _version, use tick]
         self._tick = 0
         self.parser_cfg = None    # geometry of the face parser the loaded blobs hold ("P.cfg"), or None
+        self._prefetch_ready = None      # the event behind the latest stage A a chain staged on its side stream (chain._StagedChain), or None
+
+    def wait_prefetch(self):
+        """The current stream waits for the latest stage A that a chain of this engine prefetched on its side stream: it uses the engine's one M
+        workspace and SoftErosion scratch, and so does whoever calls this.  One wait_event; nothing where no prefetch was ever made.
+        Every prefetch waits for the one before it, so the latest event stands for all of them."""
+        if self._prefetch_ready is not None:
+            torch.cuda.current_stream(self.device).wait_event(self._prefetch_ready)
 
     def close(self):
         if getattr(self, "h", None):
@@ -253,6 +261,7 @@ class Engine:
         """cs_motion_extract without the per-head split: (B, 328) fp32."""
         img = self._in(img, (3, 256, 256))
         out = self._out(out, (img.shape[0], 328), torch.float32)
+        self.wait_prefetch()                                  # M's workspace is the one a prefetched stage A uses
         self._call("cs_motion_extract", img.shape[0], img, out)
         return out
 

@@ -333,6 +333,7 @@ class SoftErosion:
         N, _, H, W = m.shape
         soft = torch.empty_like(m)
         hard = torch.empty((N, 1, H, W), dtype=torch.uint8, device=e.device)
+        e.wait_prefetch()                                     # the engine's SoftErosion scratch is the one a prefetched stage A uses
         e._call("cs_soft_erosion", N, H, W, m, self.weight, self.kernel_size, float(self.threshold), self.iterations, soft, hard)
         return soft, hard.bool()
 
@@ -354,6 +355,7 @@ def soft_erosion_frames(e: Engine, masks, weight, kernel_size=21, threshold=0.9,
     out = e._out(out, (B, H, W), torch.float32)
     if weight.dtype != torch.float32 or weight.numel() != kernel_size * kernel_size or not weight.is_contiguous() or weight.device != e.device:
         raise ValueError("weight must be the contiguous kernel_size x kernel_size fp32 kernel on the engine's device")
+    e.wait_prefetch()                                         # the engine's SoftErosion scratch is the one a prefetched stage A uses
     e._call("cs_soft_erosion_frames", B, H, W, m, int(m.dtype == torch.uint8), weight, kernel_size, float(threshold), iterations, out, None)
     return out
 

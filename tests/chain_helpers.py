@@ -52,6 +52,15 @@ def _masks(n, seed=5):
     return np.stack(out)
 
 
+def _logits(n, seed):
+    """Fixed stand-in logits (n, 19, 128, 128): noise, with the skin class (1, a valid one) raised in a block about the middle.  Noise is rich
+    in near-ties of the arg-max: one changed logit flips a label."""
+    g = torch.Generator().manual_seed(seed)
+    lg = torch.randn((n, 19, 128, 128), generator=g)
+    lg[:, 1, 30:100, 36:92] += 8.0
+    return lg.cuda()
+
+
 def _timed():
     return torch.cuda.Event(enable_timing=True)
 

@@ -8,7 +8,7 @@ import pytest
 import torch
 
 import chain_helpers
-from chain_helpers import _masks, _occupy
+from chain_helpers import _logits, _masks, _occupy
 
 pytestmark = pytest.mark.gpu
 
@@ -278,14 +278,6 @@ def test_a_consumer_may_scribble_on_a_view_until_the_next_item(swapper_m, chain,
 
 
 # ---------------------------------------------------------------------------------------------------------------- 6, 7: early exit, logits_fn
-def _logits(n, seed):
-    """Fixed stand-in logits (n, 19, 128, 128): noise, with the skin class (1, a valid one) raised in a block about the middle."""
-    g = torch.Generator().manual_seed(seed)
-    lg = torch.randn((n, 19, 128, 128), generator=g)
-    lg[:, 1, 30:100, 36:92] += 8.0
-    return lg.cuda()
-
-
 def test_early_exit_leaves_the_driver_usable(swapper_m, chain, scene):
     """Rule f: `break` after the first batch, and a logits_fn that raises on its second call; each time the same driver then runs the whole
     video and matches the loop, and nothing stays staged in the chain."""
