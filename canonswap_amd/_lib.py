@@ -193,6 +193,20 @@ STATUS = frozenset(name for name, (restype, _) in _TABLES.items() if restype is 
 TAKES_STREAM = frozenset(_TABLES) - _VERSION_CALLS - {
     "cs_create", "cs_destroy", "cs_last_error", "cs_upload", "cs_finalize_weights", "cs_set_latency_mode", "cs_profile_begin", "cs_profile_end",
     "cs_profile_exec_flops", "cs_op_chan_stats_partial_floats", "cs_op_g_stop", "cs_op_v_stop"}
+# The engine's device memory that more than one stream can reach, by group, and the entry points that read or write it.  Engine._call orders two
+# calls of one group that come on different streams; the C side orders nothing.  An entry point without a row writes only what the caller passes
+# and may run beside anything.  One case stays outside: on a latency-mode engine M's small convs go split-K on sk_buf, which is G's; the chains'
+# prefetch refuses such an engine (chain._StagedChain._stage_ahead), so M never runs beside the generator there.
+_SCRATCH_GROUPS = {
+    "M": ("cs_motion_extract",),                                                       # m_x, m_y, m_h, m_h32, m_sumsq, m_scale
+    "SE": ("cs_soft_erosion", "cs_soft_erosion_frames"),                               # se_a, se_b, se_part
+    "P": ("cs_parser", "cs_op_parser_read"),                                           # psr
+    "A": ("cs_identity", "cs_identity_u8", "cs_op_identity_read"),                     # idn
+    "G": ("cs_set_identity", "cs_extract_feature_3d", "cs_warp", "cs_warp_out", "cs_swap", "cs_swap_ids", "cs_refine", "cs_warp_forward",
+          "cs_spade_decode", "cs_swap_frames", "cs_swap_frames_ids", "cs_animate_frames", "cs_op_t_layer", "cs_op_t_read", "cs_op_m_pointwise",
+          "cs_op_dm_read", "cs_op_g_read", "cs_op_g_fill", "cs_op_v_read", "cs_op_v_fill"),      # vs, va, vsp, dm_*, g_*, seg16, w_t3, tmask, style,
+}                                                                                      # the statistics pool, sk_buf, slot_dev, img_a/b
+SCRATCH = {name: group for group, names in _SCRATCH_GROUPS.items() for name in names}      # entry point -> its group
 _PTR_SLOTS = {name: tuple(t in (vp, C.c_char_p) or issubclass(t, C._Pointer) for t in argtypes) for name, (_, argtypes) in _TABLES.items()}      # or a number
 del vp, ci, cf, cl, cd, pi, pd, pvp
 ABI_SYMBOLS = list(ABI)

@@ -51,7 +51,8 @@ from .engine import Engine
 class _StagedChain:
     """What the two chains share: engine, SoftErosion module, named buffers and the staging pipeline.  Stage A of a batch (`_stage_a`, the
     subclass's own: everything the generator needs from the crops) runs in-line on the caller's stream, or ahead of time on a side stream
-    into one half of a double buffer.  Every stream-ordering rule of FrameChain and AnimateChain stands here, once."""
+    into one half of a double buffer.  Every stream-ordering rule for the memory FrameChain and AnimateChain own stands here, once; the
+    engine's scratch (M, SoftErosion, parser) is ordered between streams by the call path itself, Engine._call."""
 
     def __init__(self, swapper, kernel_size, threshold, iterations, valid):
         self.sw = swapper
@@ -132,18 +133,17 @@ class _StagedChain:
         self._side.wait_stream(main)                      # the crops (and AnimateChain's source state) were produced on the caller's stream
         self._side.wait_event(self._free[slot])           # the generator that read this half of the double buffer is done
         with torch.cuda.stream(self._side):
-            e.wait_prefetch()                             # another chain's stage A on this engine: the one M and SoftErosion scratch
             res = self._stage_a(crops_u8, *args, slot)
             ready = torch.cuda.Event()
             ready.record(self._side)
-        e._prefetch_ready = ready                         # every later user of that scratch, on any stream, waits for it (Engine.wait_prefetch)
         self._pending.append((crops_u8, slot, res, ready))
 
     def drop_prefetches(self):
         """Forget staged batches that will not be run (their buffers are reused by the next prefetch).  Their stage A may still be running
-        on the side stream: the caller's stream waits for it, as an in-line stage A must (both use the engine's M and SoftErosion scratch)."""
+        on the side stream, reading the caller's crops and writing the chain's double buffer: the caller's stream waits for it."""
         self._pending = []
-        self.e.wait_prefetch()
+        if self._side is not None:
+            torch.cuda.current_stream(self.e.device).wait_stream(self._side)
 
     def _resolve(self, crops_u8, *args):
         """Head of __call__ -> (slot, stage A's result): the staged batch whose crops tensor is this one (slot = its half of the double
@@ -154,7 +154,6 @@ class _StagedChain:
             _, slot, res, ready = self._pending.pop(hit[0])
             main.wait_event(ready)
             return slot, res
-        self.e.wait_prefetch()                # a prefetch in flight, this chain's or another's, uses the same M and SoftErosion scratch in the engine
         return None, self._stage_a(crops_u8, *args, "inline")
 
     def _release(self, slot):

@@ -75,13 +75,7 @@ def det_lut(mean=DET_MEAN, std=DET_STD) -> np.ndarray:
 def _det_lut_on(e: Engine, mean, std):
     """The table on the engine's device, uploaded once per engine and set of constants."""
     key = (tuple([float(mean)] * 3 if np.ndim(mean) == 0 else [float(v) for v in mean]), float(std))
-    cache = e.__dict__.setdefault("_det_luts", {})
-    t = cache.get(key)
-    if t is None:
-        t = torch.from_numpy(det_lut(*key)).to(e.device)
-        torch.cuda.current_stream(e.device).synchronize()      # once: later calls may come from any stream
-        cache[key] = t
-    return t
+    return e.device_table(("det_lut",) + key, lambda: det_lut(*key))
 
 
 def _frames(frames, who):

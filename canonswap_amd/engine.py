@@ -35,14 +35,8 @@ class Engine:
         self._ids = []            # resident identities: [slot, device copy (512,), last tensor seen, its _version, use tick]
         self._tick = 0
         self.parser_cfg = None    # geometry of the face parser the loaded blobs hold ("P.cfg"), or None
-        self._prefetch_ready = None      # the event behind the latest stage A a chain staged on its side stream (chain._StagedChain), or None
-
-    def wait_prefetch(self):
-        """The current stream waits for the latest stage A that a chain of this engine prefetched on its side stream: it uses the engine's one M
-        workspace and SoftErosion scratch, and so does whoever calls this.  One wait_event; nothing where no prefetch was ever made.
-        Every prefetch waits for the one before it, so the latest event stands for all of them."""
-        if self._prefetch_ready is not None:
-            torch.cuda.current_stream(self.device).wait_event(self._prefetch_ready)
+        self._scratch_last = {}   # scratch group (_lib.SCRATCH) -> the torch stream that used it last (_call)
+        self._tables = {}         # device_table()
 
     def close(self):
         if getattr(self, "h", None):
@@ -73,13 +67,22 @@ class Engine:
             self.parser_cfg = {"depths": c[0:4], "widths": c[4:8], "heads": c[8:12], "sr": c[12:16], "mlp": c[16], "D": c[17], "L": c[18]}
 
     def _stream(self):
-        return C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+        return torch.cuda.current_stream(self.device)
 
     def _call(self, name, *args, what=None):
         """Entry point `name` on this engine: the handle first, torch's current stream of the engine's device last where the entry point takes
-        one, tensors from that device only (_lib.call), under the package's one device guard (the C side keeps its own)."""
+        one, tensors from that device only (_lib.call), under the package's one device guard (the C side keeps its own).  An entry point that
+        uses a scratch group of the engine (_lib.SCRATCH) first makes its stream wait for the stream that used the group last, where that is
+        another one: every cross-stream ordering of engine-owned memory is made here, and no call site places a wait."""
         if name in _lib.TAKES_STREAM:
-            args += (self._stream(),)
+            cur = self._stream()
+            group = _lib.SCRATCH.get(name)
+            if group is not None:
+                last = self._scratch_last.get(group)
+                if last is not None and last != cur:
+                    cur.wait_stream(last)
+                self._scratch_last[group] = cur
+            args += (cur.cuda_stream,)
         with torch.cuda.device(self.device):
             return _lib.call(name, self.h, *args, what=what, device=self.device)
 
@@ -111,6 +114,14 @@ class Engine:
         if not isinstance(t, torch.Tensor) or t.device != self.device or t.dtype != dtype or tuple(t.shape) != tuple(shape) \
                 or not t.is_contiguous():
             raise ValueError(f"output buffer must be a contiguous {dtype} tensor of shape {tuple(shape)} on {self.device}")
+        return t
+
+    def device_table(self, key, build):
+        """The small constant table `key` on the engine's device: build() -> a numpy array, made and uploaded once per engine."""
+        t = self._tables.get(key)
+        if t is None:
+            t = self._tables[key] = torch.from_numpy(build()).to(self.device)
+            torch.cuda.current_stream(self.device).synchronize()      # once: later calls may come from any stream
         return t
 
     def set_identity(self, source_id: torch.Tensor, slot: int = 0):
@@ -261,7 +272,6 @@ class Engine:
         """cs_motion_extract without the per-head split: (B, 328) fp32."""
         img = self._in(img, (3, 256, 256))
         out = self._out(out, (img.shape[0], 328), torch.float32)
-        self.wait_prefetch()                                  # M's workspace is the one a prefetched stage A uses
         self._call("cs_motion_extract", img.shape[0], img, out)
         return out
 
@@ -406,8 +416,7 @@ class Engine:
     def parser(self, pixel_values, out=None):
         """The SegFormer face parser on the engine (can_swap_pipeline_e2e.py:178-182: model(pixel_values).logits): pixel_values (B,3,H,W) fp32, H and W
         multiples of 32 up to 512 x 512 (what parser_input makes of the crops) -> logits (B,L,H/4,W/4) fp32 on the device, the tensor face_masks
-        takes.  Needs the "parser" state-dict among the loaded weights.  A workspace of its own: it may be enqueued beside the generator, but two
-        parser calls on one engine must be ordered with each other."""
+        takes.  Needs the "parser" state-dict among the loaded weights.  A workspace of its own: it may be enqueued beside the generator."""
         if not self.has_parser:
             raise RuntimeError("parser: the engine holds no face parser (pass the 'parser' state-dict with the weights)")
         if not isinstance(pixel_values, torch.Tensor) or pixel_values.dim() != 4 or pixel_values.shape[1] != 3 or min(pixel_values.shape) < 1:

@@ -117,13 +117,7 @@ def parser_lut(mean=PARSER_MEAN, std=PARSER_STD, rescale=PARSER_RESCALE) -> np.n
 def _parser_lut_on(e: Engine, mean, std, rescale):
     """The table on the engine's device, uploaded once per engine and set of constants."""
     key = (tuple(float(m) for m in mean), tuple(float(s) for s in std), float(rescale))
-    cache = e.__dict__.setdefault("_parser_luts", {})
-    t = cache.get(key)
-    if t is None:
-        t = torch.from_numpy(parser_lut(*key)).to(e.device)
-        torch.cuda.current_stream(e.device).synchronize()      # once: later calls may come from any stream
-        cache[key] = t
-    return t
+    return e.device_table(("parser_lut",) + key, lambda: parser_lut(*key))
 
 
 ID_MEAN, ID_STD = (0.485, 0.456, 0.406), (0.229, 0.224, 0.225)      # ID_transform's Normalize (can_swap_pipeline_e2e.py:43-46, can_swap_pipeline_v2i.py:44-47)
@@ -144,13 +138,7 @@ def id_lut(mean=ID_MEAN, std=ID_STD) -> np.ndarray:
 def id_lut_on(e: Engine, mean=ID_MEAN, std=ID_STD):
     """The table on the engine's device, uploaded once per engine and set of constants."""
     key = (tuple(float(m) for m in mean), tuple(float(s) for s in std))
-    cache = e.__dict__.setdefault("_id_luts", {})
-    t = cache.get(key)
-    if t is None:
-        t = torch.from_numpy(id_lut(*key)).to(e.device)
-        torch.cuda.current_stream(e.device).synchronize()      # once: later calls may come from any stream
-        cache[key] = t
-    return t
+    return e.device_table(("id_lut",) + key, lambda: id_lut(*key))
 
 
 def parser_input(e: Engine, crops_u8, halve=None, mean=PARSER_MEAN, std=PARSER_STD, rescale=PARSER_RESCALE, out=None, want_u8=False, out_u8=None):
@@ -333,7 +321,6 @@ class SoftErosion:
         N, _, H, W = m.shape
         soft = torch.empty_like(m)
         hard = torch.empty((N, 1, H, W), dtype=torch.uint8, device=e.device)
-        e.wait_prefetch()                                     # the engine's SoftErosion scratch is the one a prefetched stage A uses
         e._call("cs_soft_erosion", N, H, W, m, self.weight, self.kernel_size, float(self.threshold), self.iterations, soft, hard)
         return soft, hard.bool()
 
@@ -355,7 +342,6 @@ def soft_erosion_frames(e: Engine, masks, weight, kernel_size=21, threshold=0.9,
     out = e._out(out, (B, H, W), torch.float32)
     if weight.dtype != torch.float32 or weight.numel() != kernel_size * kernel_size or not weight.is_contiguous() or weight.device != e.device:
         raise ValueError("weight must be the contiguous kernel_size x kernel_size fp32 kernel on the engine's device")
-    e.wait_prefetch()                                         # the engine's SoftErosion scratch is the one a prefetched stage A uses
     e._call("cs_soft_erosion_frames", B, H, W, m, int(m.dtype == torch.uint8), weight, kernel_size, float(threshold), iterations, out, None)
     return out
 

@@ -38,6 +38,118 @@ def fake(monkeypatch):
     return put
 
 
+class StubStream:
+    """Stands for a torch stream: a name, the pointer the library gets, and a record of every wait_stream in `log`, the list the fake library
+    records its calls in, so that the order of the two can be read off."""
+
+    def __init__(self, name, cuda_stream, log=None):
+        self.name, self.cuda_stream, self.log = name, cuda_stream, log
+
+    def wait_stream(self, other):
+        self.log.append(("wait_stream", (self.name, other.name)))
+
+    def __eq__(self, other):                              # torch hands out a new object per current_stream() call: equal by the stream, as there
+        return isinstance(other, StubStream) and other.cuda_stream == self.cuda_stream
+
+    __hash__ = None
+
+
+class Guard:
+    def __init__(self, device):
+        pass
+
+    def __enter__(self):
+        pass
+
+    def __exit__(self, *exc):
+        pass
+
+
+@pytest.fixture
+def ordered(fake, monkeypatch):
+    """-> (run, lib): run(name, stream name) drives Engine._call for entry point `name` with that stream current, on a stub engine that has
+    seen nothing yet; lib.calls holds the waits and the library's calls in the order they were made."""
+    names = ("cs_motion_extract", "cs_soft_erosion", "cs_soft_erosion_frames", "cs_parser", "cs_pack_u8", "cs_swap_frames_ids")
+    lib = fake(**{n: 0 for n in names})
+    monkeypatch.setattr(torch.cuda, "device", Guard)
+
+    class Stub:
+        h, device, _scratch_last, current = C.c_void_p(0x1000), torch.device("cuda:0"), {}, None
+
+        def _stream(self):
+            return StubStream(self.current, {"X": 0x10, "Y": 0x20, "Z": 0x30}[self.current], lib.calls)
+    e = Stub()
+
+    def run(name, stream):
+        e.current = stream
+        Engine._call(e, name, *[None] * (len(_lib._TABLES[name][1]) - 2))      # all but the handle and the stream
+        assert lib.calls[-1][0] == name and lib.calls[-1][1][-1] == e._stream().cuda_stream      # the call is the last thing made, on that stream
+    return run, lib, e
+
+
+def _waits(lib):
+    return [args for name, args in lib.calls if name == "wait_stream"]
+
+
+def test_a_group_is_ordered_between_streams_and_only_there(ordered):
+    run, lib, e = ordered
+    run("cs_motion_extract", "X")
+    assert _waits(lib) == []
+    run("cs_motion_extract", "Y")                         # the same group on another stream: one wait, enqueued before the library is called
+    assert [n for n, _ in lib.calls] == ["cs_motion_extract", "wait_stream", "cs_motion_extract"] and _waits(lib) == [("Y", "X")]
+    run("cs_motion_extract", "Y")                         # again on Y: nothing further
+    assert _waits(lib) == [("Y", "X")]
+    run("cs_motion_extract", "X")                         # back on X
+    assert _waits(lib) == [("Y", "X"), ("X", "Y")] and lib.calls[-2][0] == "wait_stream"
+    run("cs_soft_erosion", "Z")                           # SE's two entry points are one group
+    run("cs_soft_erosion_frames", "X")
+    assert _waits(lib) == [("Y", "X"), ("X", "Y"), ("X", "Z")]
+
+
+def test_two_groups_do_not_order_each_other(ordered):
+    run, lib, e = ordered
+    run("cs_motion_extract", "X")
+    run("cs_parser", "Y")
+    run("cs_swap_frames_ids", "Z")
+    run("cs_soft_erosion_frames", "Y")
+    assert _waits(lib) == []
+    assert {g: s.name for g, s in e._scratch_last.items()} == {"M": "X", "P": "Y", "G": "Z", "SE": "Y"}
+
+
+def test_an_entry_point_without_a_row_never_waits(ordered):
+    run, lib, e = ordered
+    assert "cs_pack_u8" not in _lib.SCRATCH
+    run("cs_motion_extract", "X")
+    before = dict(e._scratch_last)
+    for stream in ("Y", "X", "Z"):
+        run("cs_pack_u8", stream)
+    assert _waits(lib) == [] and e._scratch_last == before and list(before) == ["M"]
+    run("cs_motion_extract", "X")                         # and M's last stream is still X
+    assert _waits(lib) == []
+
+
+def test_one_stream_waits_nowhere(ordered):
+    run, lib, e = ordered
+    for name in ("cs_motion_extract", "cs_parser", "cs_soft_erosion", "cs_pack_u8", "cs_swap_frames_ids", "cs_soft_erosion_frames") * 2:
+        run(name, "X")
+    assert _waits(lib) == [] and len(lib.calls) == 12
+
+
+def test_the_scratch_table():
+    assert set(_lib.SCRATCH) <= _lib.TAKES_STREAM
+    assert set(_lib.SCRATCH.values()) == {"M", "SE", "P", "A", "G"}
+    stage_a = {"cs_motion_extract": "M", "cs_soft_erosion": "SE", "cs_soft_erosion_frames": "SE", "cs_parser": "P"}      # what stage A reaches
+    assert {n: _lib.SCRATCH.get(n) for n in stage_a} == stage_a
+    assert all(_lib._TABLES[n][1][0] is C.c_void_p for n in _lib.SCRATCH)      # scratch belongs to an engine: each takes the handle
+
+
+def test_no_placed_wait_remains():
+    files = [f for ext in ("py", "hip", "h", "txt") for f in glob.glob(os.path.join(ROOT, "canonswap_amd", "**", "*." + ext), recursive=True)]
+    assert len(files) > 30
+    left = [(os.path.relpath(f, ROOT), n + 1) for f in files for n, line in enumerate(open(f)) if re.search(r"wait_prefetch|_prefetch_ready", line)]
+    assert left == []
+
+
 def test_an_unknown_name_raises(fake):
     lib = fake()
     with pytest.raises(KeyError, match="cs_no_such_entry"):
@@ -126,10 +238,10 @@ def test_engine_call_puts_the_handle_first_and_the_stream_last(fake, monkeypatch
     monkeypatch.setattr(torch.cuda, "device", Guard)
 
     class Stub:
-        h, device, stream = C.c_void_p(0x1000), torch.device("cuda:0"), C.c_void_p(0x2000)
+        h, device, stream, _scratch_last = C.c_void_p(0x1000), torch.device("cuda:0"), 0x2000, {}
 
         def _stream(self):
-            return self.stream
+            return StubStream("main", self.stream)
     e, img, out = Stub(), C.c_void_p(0x3000), C.c_void_p(0x4000)
     assert "cs_pack_u8" in _lib.TAKES_STREAM and "cs_set_latency_mode" not in _lib.TAKES_STREAM
     Engine._call(e, "cs_pack_u8", 1, img, out, 4, 4)

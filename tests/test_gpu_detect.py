@@ -108,7 +108,7 @@ def test_det_input_refuses_bad_arguments_before_any_launch(engine):
     for kw, word in (({"F": 0}, "F = 0"), ({"frames": None}, "frames"), ({"lut": None}, "lut"), ({"blob": None}, "blob"), ({"Ho": 0}, "Ho = 0"),
                      ({"Hd": 16385}, "16384"), ({"Wd": 0}, "16384"), ({"Ho": 1, "Wo": 8000}, "empty")):
         a = dict(good, **kw)
-        rc = lib.cs_det_input(e.h, a["F"], p(a["frames"]), a["Ho"], a["Wo"], a["Hd"], a["Wd"], 1, p(a["lut"]), p(a["blob"]), e._stream())
+        rc = lib.cs_det_input(e.h, a["F"], p(a["frames"]), a["Ho"], a["Wo"], a["Hd"], a["Wd"], 1, p(a["lut"]), p(a["blob"]), e._stream().cuda_stream)
         err = lib.cs_last_error().decode()
         assert rc != 0 and "cs_det_input" in err and word in err, (kw, err)
     torch.cuda.synchronize()
@@ -289,7 +289,7 @@ def test_det_decode_refuses_bad_arguments_before_any_launch(engine):
         a = dict(good, **kw)
         ptrs = (C.c_void_p * len(a["ptrs"]))(*a["ptrs"])
         return lib.cs_det_decode(e.h, a["F"], a["n"], (C.c_int * len(a["strides"]))(*a["strides"]), a["na"], ptrs, a["Hd"], a["Wd"], a["scale"], a["thr"],
-                                 a["nms"], a["max_num"], 0, a["Ho"], a["Wo"], a["max_faces"], p(a["det"]), p(a["kps"]), p(a["count"]), e._stream())
+                                 a["nms"], a["max_num"], 0, a["Ho"], a["Wo"], a["max_faces"], p(a["det"]), p(a["kps"]), p(a["count"]), e._stream().cuda_stream)
     no_kps = good["ptrs"][:6] + [None] * 3
     part = good["ptrs"][:8] + [None]
     for kw, word in (({"F": 0}, "F = 0"), ({"na": 1}, "layout"), ({"strides": (8, 16, 64)}, "layout"), ({"n": 4, "strides": (8, 16, 32, 64)}, "layout"),

@@ -202,7 +202,7 @@ def test_refused_arguments_launch_nothing(engine, scene):
     good = ip(scene["fi"].tolist())
 
     def paste(B=B, F=F, crops=crops, masks=masks, index=good, mp=mp, ori=ori, out=out):
-        return lib.cs_paste_back_faces(e.h, B, F, _ptr(crops), _ptr(masks), 16, 16, index, mp, _ptr(ori), _ptr(out), Ho, Wo, e._stream())
+        return lib.cs_paste_back_faces(e.h, B, F, _ptr(crops), _ptr(masks), 16, 16, index, mp, _ptr(ori), _ptr(out), Ho, Wo, e._stream().cuda_stream)
 
     cases = [dict(crops=None), dict(masks=None), dict(index=None), dict(mp=None), dict(ori=None), dict(F=0), dict(B=-1),
              dict(index=ip([0, 0, 2, 2, 2, 4])), dict(index=ip([0, 0, 2, 2, 2, -1])), dict(index=ip([0, 0, 2, 1, 2, 3])), dict(F=3)]
@@ -218,7 +218,7 @@ def test_refused_arguments_launch_nothing(engine, scene):
     Io = torch.full((B, 3, 256, 256), -3.0, device=ori.device)
 
     def crop(B=B, F=F, frames=frames, index=good, mp=mp, dsize=8, out=co, I=None):
-        return lib.cs_crop_faces(e.h, B, F, _ptr(frames), Ho, Wo, index, mp, dsize, _ptr(out), _ptr(I), e._stream())
+        return lib.cs_crop_faces(e.h, B, F, _ptr(frames), Ho, Wo, index, mp, dsize, _ptr(out), _ptr(I), e._stream().cuda_stream)
 
     for kw in [dict(frames=None), dict(index=None), dict(mp=None), dict(out=None), dict(F=0), dict(B=0), dict(B=-2), dict(F=3),
                dict(index=ip([0, 0, 2, 2, 2, 4])), dict(index=ip([1, 0, 2, 2, 2, 3])), dict(dsize=6), dict(dsize=0), dict(dsize=16388), dict(I=Io)]:

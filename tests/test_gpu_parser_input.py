@@ -150,11 +150,11 @@ def test_custom_constants_change_only_the_table(eng):
     assert torch.equal(got["resized_u8"].cpu(), _t(ref["resized_u8"]))
     again = tail.parser_input(eng, crops)                                         # the defaults' table is still the defaults'
     assert _same_bits(again, ref["pixel_values"])
-    n = len(eng._parser_luts)
+    n = len(eng._tables)
     assert n >= 2
     tail.parser_input(eng, crops, mean=mean, std=std, rescale=rescale)
     tail.parser_input(eng, crops, mean=list(mean), std=np.array(std), rescale=rescale)
-    assert len(eng._parser_luts) == n                                             # cached per engine and constants
+    assert len(eng._tables) == n                                             # cached per engine and constants
 
 
 def test_default_halving_and_the_staged_intermediate(eng):

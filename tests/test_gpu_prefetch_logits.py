@@ -181,18 +181,21 @@ def _same(a, b):
     return torch.equal(a, b) if isinstance(a, torch.Tensor) else np.array_equal(a, b)
 
 
-@pytest.mark.parametrize("user", ["second-chain", "set-source", "soft-erosion", "soft-erosion-module", "motion-extract"])
+@pytest.mark.parametrize("user", ["second-chain", "set-source", "soft-erosion", "soft-erosion-module", "motion-extract", "parser"])
 def test_second_user_of_the_scratch_waits_for_the_prefetch(swapper, pool, user):
     """The engine has one M workspace and one SoftErosion scratch.  While a prefetch is pending behind a held side stream (the pattern of
     test_inline_stage_a_waits_for_a_prefetch_in_flight), another user of that scratch is called on the caller's stream: a second FrameChain
     in-line, AnimateChain.set_source, tail.soft_erosion_frames, the SoftErosion module, Engine.motion_extract_raw.  It must run behind the staged stage A - its
-    end on the caller's stream comes after the prefetch's - and both it and the prefetched batch come out as when run alone."""
+    end on the caller's stream comes after the prefetch's - and both it and the prefetched batch come out as when run alone.
+    "parser": the same for the engine's one parser workspace: the held prefetch is staged with parse=True, the second user is Engine.parser on
+    the caller's stream.  Nothing but that parser call runs beside the stage A, no generator (DESIGN 8.11's condition is absent)."""
     from canonswap_amd import tail
     from canonswap_amd.chain import AnimateChain, FrameChain
     e = swapper.engine
     b0, b1 = _batches(pool, (2, 2), first=3)
     chain = FrameChain(swapper)
-    want1 = _run(chain, b1, "masks")
+    src = "parse" if user == "parser" else "masks"          # what the held prefetch is staged with
+    want1 = _run(chain, b1, src)
     I0 = tail.prepare_crops(e, b0["crops"])
     other_chain, anim = FrameChain(swapper), AnimateChain(swapper)
 
@@ -206,31 +209,58 @@ def test_second_user_of_the_scratch_waits_for_the_prefetch(swapper, pool, user):
             return tail.soft_erosion_frames(e, b0["masks"], chain.se.weight, 21, 0.9, 3)
         if user == "soft-erosion-module":
             return chain.se(b0["masks"][:, None].float())[0]
+        if user == "parser":
+            return e.parser(chain.parser_input(b0["crops"]))
         return e.motion_extract_raw(I0)
 
     alone = other()
     torch.cuda.synchronize()
-    _prefetch(chain, b1, "masks")                        # a first prefetch / hit pair creates the side stream
-    assert _same(_run(chain, b1, "masks"), want1)
+    _prefetch(chain, b1, src)                        # a first prefetch / hit pair creates the side stream
+    assert _same(_run(chain, b1, src), want1)
     a, z = _timed(), _timed()
     a.record()
     other()
     z.record()
     z.synchronize()
     _occupy(chain._side, max(40.0, 8 * a.elapsed_time(z)))
-    _prefetch(chain, b1, "masks")
+    _prefetch(chain, b1, src)
     staged = _timed()
     staged.record(chain._side)                            # right behind the prefetch's `ready` event on the side stream
     beside = other()
     end = _timed()
     end.record()
-    got1 = _run(chain, b1, "masks")
+    got1 = _run(chain, b1, src)
     torch.cuda.synchronize()
     print(f"{user}: alone {a.elapsed_time(z):.2f} ms; its end {staged.elapsed_time(end):.2f} ms after the prefetch's")
     assert staged.elapsed_time(end) > 0, f"{user} on the caller's stream did not wait for the stage A staged on the side stream"
     assert _same(beside, alone), f"{user} beside a prefetch differs from {user} alone"
     assert _same(got1, want1), f"the batch prefetched beside {user} differs from the in-line run"
     assert not chain._pending
+
+
+def test_two_caller_streams_on_the_m_workspace_are_ordered(swapper, pool):
+    """No chain at all: Engine.motion_extract_raw on stream s1, held busy so that the call is certainly pending, then the same call with other
+    images on stream s2.  Both use the engine's one M workspace, so s2's call runs behind s1's - its end comes after s1's - and both results
+    are those of the same calls on a single stream."""
+    from canonswap_amd import tail
+    e = swapper.engine
+    Ia, Ib = tail.prepare_crops(e, pool["crops"][3:5]), tail.prepare_crops(e, pool["crops"][5:7])
+    want_a, want_b = e.motion_extract_raw(Ia), e.motion_extract_raw(Ib)
+    torch.cuda.synchronize()
+    assert not torch.equal(want_a, want_b)
+    s1, s2 = torch.cuda.Stream(), torch.cuda.Stream()
+    _occupy(s1, 40.0)
+    end1, end2 = _timed(), _timed()
+    with torch.cuda.stream(s1):
+        got_a = e.motion_extract_raw(Ia)
+        end1.record()
+    with torch.cuda.stream(s2):
+        got_b = e.motion_extract_raw(Ib)
+        end2.record()
+    torch.cuda.synchronize()
+    print(f"two streams: s2's motion_extract_raw ends {end1.elapsed_time(end2):.2f} ms after s1's")
+    assert end1.elapsed_time(end2) > 0, "motion_extract_raw on s2 did not wait for the one pending on s1"
+    assert torch.equal(got_a, want_a) and torch.equal(got_b, want_b)
 
 
 # ---------------------------------------------------------------------------------------------------------------- d. guard bands

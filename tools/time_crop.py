@@ -72,7 +72,7 @@ def main():
     rows = [(C.c_void_p(frames[b].data_ptr()), C.cast(m6[b].ctypes.data, d6), C.c_void_p(crops_p[b].data_ptr())) for b in range(B)]
 
     def parent(with_I):
-        st = e._stream()
+        st = e._stream().cuda_stream
         for f, m, c in rows:
             if e.lib.cs_warp_affine_u8(e.h, f, Ho, Wo, m, c, dsize, dsize, st):
                 raise RuntimeError("cs_warp_affine_u8")

@@ -81,7 +81,7 @@ def main():
     masks = torch.from_numpy(soft).to(dev)[None].expand(B, -1, -1).contiguous()
     d6, ip = C.POINTER(C.c_double), C.POINTER(C.c_int)
     m6 = lambda M: np.ascontiguousarray(np.asarray(M, np.float64).reshape(len(M), 9)[:, :6])
-    st = lambda: e._stream()
+    st = lambda: e._stream().cuda_stream
 
     def ok(rc, what):
         if rc:
