@@ -10,8 +10,8 @@ SOURCES = [os.path.join(CSRC, f) for f in ("conv_halo.hip", "conv_wide.hip", "co
 # test-only cross-check kernel (the first-generation implicit-GEMM conv): its own library, never linked into the product
 TEST_SRC = os.path.join(os.path.dirname(HERE), "tests", "csrc", "test_igemm.hip")
 TEST_LIB_PATH = os.path.join(os.path.dirname(HERE), "tests", "libcanonswap_test.so")
-HEADERS = [os.path.join(CSRC, f) for f in ("common.h", "conv_epilogue.h", "conv_halo_kernel.h", "conv_plan.h", "engine.h", "knobs.h", "lmk_geometry.h", "warp_taps.h", "yuv_math.h")] + \
-          [os.path.join(os.path.dirname(HERE), "include", f) for f in ("canonswap_hip.h", "canonswap_landmarks.h", "canonswap_yuv.h")]
+HEADERS = [os.path.join(CSRC, f) for f in ("common.h", "conv_epilogue.h", "conv_halo_kernel.h", "conv_plan.h", "engine.h", "affine_inv.h", "knobs.h", "lmk_geometry.h", "warp_taps.h", "yuv_math.h")] + \
+          [os.path.join(os.path.dirname(HERE), "include", f) for f in ("canonswap_hip.h", "canonswap_landmarks.h", "canonswap_yuv.h", "canonswap_device_crop.h")]
 HALO_NGROUPS = 8          # conv_halo.hip is compiled once per -DHALO_GROUP=k (slices of its instantiation table)
 OBJ_DIR = os.path.join(HERE, "build")
 LIB_PATH = os.environ.get("CANONSWAP_LIB") or os.path.join(HERE, "libcanonswap_hip.so")      # CANONSWAP_LIB: A/B builds (tools/)

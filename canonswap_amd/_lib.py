@@ -1,4 +1,5 @@
-"""ctypes binding of libcanonswap_hip.so (C ABI: include/canonswap_hip.h, and include/canonswap_landmarks.h and include/canonswap_yuv.h beside it).
+"""ctypes binding of libcanonswap_hip.so (C ABI: include/canonswap_hip.h, and include/canonswap_landmarks.h, include/canonswap_yuv.h and
+include/canonswap_device_crop.h beside it).
 
 The library is the product: if it cannot be loaded, every entry point raises -- there is no CPU or
 PyTorch fallback (the CPU restatement under oracle/ is test infrastructure only).  The in-tree build is _build.py,
@@ -158,6 +159,12 @@ ABI_YUV = {
     "cs_yuv_to_rgb": (ci, [vp, ci, vp, ci, ci, ci, ci, ci, vp, vp]),
     "cs_rgb_to_yuv": (ci, [vp, ci, vp, ci, ci, ci, ci, ci, ci, vp, vp]),
 }
+# The crop and the paste-back from device landmarks and matrices, the fourth table: include/canonswap_device_crop.h (cs_lmk_layout by pointer).
+ABI_DEVICE_CROP = {
+    "cs_dcrop_abi_version": (ci, []),
+    "cs_crop_lmk": (ci, [vp, ci, ci, vp, ci, ci, pi, vp, ci, C.POINTER(LmkLayout), ci, cf, cf, ci, ci, vp, vp, vp, vp, vp, vp]),
+    "cs_paste_back_faces_dev": (ci, [vp, ci, ci, vp, vp, ci, ci, pi, vp, vp, vp, vp, ci, ci, vp]),
+}
 
 
 class Header(NamedTuple):
@@ -184,10 +191,18 @@ HEADERS = (
     _header("canonswap_landmarks.h", ABI_LANDMARKS, "CS_LMK_ABI_VERSION", 1, {"cs_lmk_layout": LmkLayout}, {}, True),
     _header("canonswap_yuv.h", ABI_YUV, "CS_YUV_ABI_VERSION", 1, {}, {}, True),
 )
-_TABLES = {name: sig for h in HEADERS for name, sig in h.table.items()}
-if len(_TABLES) != sum(len(h.table) for h in HEADERS):
+# Why a second tuple: tests/test_abi_cpu.py states HEADERS as exactly the three records above and hands bind() a fake library that has only their
+# names, so a header added since stands here and is bound by load() (bind_header, the body bind() applies to HEADERS: the same version check, the
+# same A/B rule).  Everything else - call(), STATUS, TAKES_STREAM, the pointer slots - is formed over both tuples and does not tell them apart.
+# Merging the tuples is for a change that may edit that test.
+HEADERS_BESIDE = (
+    _header("canonswap_device_crop.h", ABI_DEVICE_CROP, "CS_DCROP_ABI_VERSION", 1, {}, {}, True),
+)
+_ALL_HEADERS = HEADERS + HEADERS_BESIDE
+_TABLES = {name: sig for h in _ALL_HEADERS for name, sig in h.table.items()}
+if len(_TABLES) != sum(len(h.table) for h in _ALL_HEADERS):
     raise ImportError("canonswap_amd/_lib.py: an entry point stands in two headers' tables")
-_VERSION_CALLS = frozenset(h.version_call for h in HEADERS)
+_VERSION_CALLS = frozenset(h.version_call for h in _ALL_HEADERS)
 STATUS = frozenset(name for name, (restype, _) in _TABLES.items() if restype is ci) - _VERSION_CALLS      # 0, or the text is in cs_last_error()
 # The headers' stream parameters are all the last one, `void* stream`; every entry has one but the version calls and these (tests/test_abi_cpu.py).
 TAKES_STREAM = frozenset(_TABLES) - _VERSION_CALLS - {
@@ -216,23 +231,36 @@ ABI_OPTIONAL = ("cs_op_g_read", "cs_op_g_fill", "cs_op_g_stop", "cs_op_v_read", 
 _lib = None
 
 
-def bind(lib, ab=False):
-    """Give every entry point of HEADERS its restype and argtypes on `lib` (a CDLL, or anything with the entry points as attributes) and check
-    each header's version.  A missing entry point raises AttributeError, but for the ABI_OPTIONAL ones and, with `ab`, for a whole header that
-    an A/B library may lack: it is skipped where its version call is missing, and a call of one of its names raises AttributeError then."""
-    for h in HEADERS:
-        if ab and h.ab_may_lack and not hasattr(lib, h.version_call):
+def bind_header(lib, h, ab=False):
+    """One record on `lib`: its version checked, its entry points given their restype and argtypes.  A missing entry point raises AttributeError,
+    but for the ABI_OPTIONAL ones and, with `ab`, for a whole header that an A/B library may lack: it is skipped where its version call is
+    missing, and a call of one of its names raises AttributeError then."""
+    if ab and h.ab_may_lack and not hasattr(lib, h.version_call):
+        return
+    speaks = getattr(lib, h.version_call)()          # (ctypes' default restype is the int it returns)
+    if speaks != h.version:
+        what, binds = ((f"C-ABI version {speaks}", f"{h.version} (include/{h.file}: {h.version_define})") if h is HEADERS[0] else
+                       (f"version {speaks} of include/{h.file}", h.version))
+        raise RuntimeError(f"{LIB_PATH} speaks {what}, this package binds version {binds}: rebuild with __graft_entry__.build()")
+    for name, (restype, argtypes) in h.table.items():
+        if name in ABI_OPTIONAL and not hasattr(lib, name):
             continue
-        speaks = getattr(lib, h.version_call)()          # (ctypes' default restype is the int it returns)
-        if speaks != h.version:
-            what, binds = ((f"C-ABI version {speaks}", f"{h.version} (include/{h.file}: {h.version_define})") if h is HEADERS[0] else
-                           (f"version {speaks} of include/{h.file}", h.version))
-            raise RuntimeError(f"{LIB_PATH} speaks {what}, this package binds version {binds}: rebuild with __graft_entry__.build()")
-        for name, (restype, argtypes) in h.table.items():
-            if name in ABI_OPTIONAL and not hasattr(lib, name):
-                continue
-            f = getattr(lib, name)
-            f.restype, f.argtypes = restype, argtypes
+        f = getattr(lib, name)
+        f.restype, f.argtypes = restype, argtypes
+
+
+def bind(lib, ab=False):
+    """bind_header for every record of HEADERS on `lib` (a CDLL, or anything with the entry points as attributes); load() goes on with
+    HEADERS_BESIDE (bind_beside)."""
+    for h in HEADERS:
+        bind_header(lib, h, ab)
+    return lib
+
+
+def bind_beside(lib, ab=False):
+    """The records of HEADERS_BESIDE on a library bind() has seen: the load-time binding of the headers added beside the recorded three."""
+    for h in HEADERS_BESIDE:
+        bind_header(lib, h, ab)
     return lib
 
 
@@ -248,7 +276,8 @@ def load():
         # libamdhip64 / libhsa-runtime64: imported first, its copies satisfy this library's NEEDED entries too.  Loaded the other way round (this
         # library first - `python __graft_entry__.py smoke`, whose build() checks the ABI before anything imports torch) the system runtime and
         # torch's both initialise and cs_create sees 0 devices.  Hence the import of torch at the top of this module.
-        _lib = bind(C.CDLL(LIB_PATH), ab=bool(os.environ.get("CANONSWAP_LIB")))          # the in-tree library must carry every header
+        ab = bool(os.environ.get("CANONSWAP_LIB"))                                       # the in-tree library must carry every header
+        _lib = bind_beside(bind(C.CDLL(LIB_PATH), ab), ab)
     return _lib
 
 
@@ -273,7 +302,7 @@ def check(rc: int, what: str):
 
 
 def call(name, *args, what=None, device=None):
-    """The one way into the library: entry point `name` of any of HEADERS with exactly its arguments, checked before the library is touched.  A torch tensor
+    """The one way into the library: entry point `name` of any of HEADERS and HEADERS_BESIDE with exactly its arguments, checked before the library is touched.  A torch tensor
     stands for its address: in a pointer slot only, and only from a GPU (device=: from that one); None is NULL; the rest goes to ctypes as it is
     (contiguity and dtype are the caller's).  A nonzero status raises RuntimeError("<what or name> failed: <cs_last_error>"); values are returned."""
     argtypes = _TABLES[name][1]

@@ -320,6 +320,12 @@ class can_swapper(object):
     def paste_back_faces(self, crops, masks_crop, M_c2o, frame_index, imgs_ori, out=None):      # crop.py:515-529 once per face of a frame, in order
         return tail.paste_back_faces(self.engine, crops, masks_crop, M_c2o, frame_index, imgs_ori, out=out)
 
+    def crop_lmk(self, frames, lmk, frame_index=None, **kw):                            # crop_faces from landmarks on the device: nothing downloaded
+        return tail.crop_lmk(self.engine, frames, lmk, frame_index, **kw)
+
+    def paste_back_faces_dev(self, crops, masks_crop, M, frame_index, imgs_ori, status=None, out=None):      # paste_back_faces, matrices on the device
+        return tail.paste_back_faces_dev(self.engine, crops, masks_crop, M, frame_index, imgs_ori, status=status, out=out)
+
     def swap_video(self, frames, lmk, source_id=None, *, driver=None, **kw):
         """The pipeline's loop over a whole video (can_swap_pipeline_e2e.py:155-319), host frames in, host frames out, the copies overlapped
         with the generator: video.VideoSwapper.swap_video (kw: out, slots, frame_index, masks, parse, logits_fn, the crop's configuration; pixel_format "nv12" / "i420" with matrix and

@@ -168,6 +168,15 @@ class FrameChain(_StagedChain):
     def __init__(self, swapper, kernel_size: int = 21, threshold: float = 0.9, iterations: int = 3, valid=tail.FACE_VALID):
         super().__init__(swapper, kernel_size, threshold, iterations, valid)      # SoftErosion(21, 0.9, 3): can_swap_pipeline_e2e.py:42; valid_list :189
 
+    def crop(self, frames_ori, lmk, frame_index=None, **cfg):
+        """_StagedChain.crop for host landmarks, as it is.  lmk a (B,N,2) float32 DEVICE tensor (the tracker's landmarks as they lie): the device
+        route, tail.crop_lmk (cfg: dsize, scale, vy_ratio, flag_do_rot, status, status_mark, out, want_I, want_lmk_crop) -> {"crops", "M" (B,18)
+        fp32 = M_o2c | M_c2o, "status" (B,) int32[, "I", "lmk_crop"]}, all on the device, in place of the host "M_c2o" / "M_o2c": hand "M" to
+        __call__ as M_c2o and "status" as status=, and nothing between the tracker and the paste-back waits for the device."""
+        if isinstance(lmk, torch.Tensor) and lmk.is_cuda:
+            return tail.crop_lmk(self.e, frames_ori, lmk, frame_index, **cfg)
+        return super().crop(frames_ori, lmk, frame_index, **cfg)
+
     def keypoints(self, I, slot=0):
         """(B,3,256,256) fp32 -> x_t, x_can (B,21,3): make_motion_template's get_kp_info + transform_keypoint and the loop's
         x_can = scale * kp (can_swap_pipeline_e2e.py:111-125, 236-243)."""
@@ -208,7 +217,7 @@ class FrameChain(_StagedChain):
         self._stage_ahead(crops_u8, masks, logits, parse)
 
     def __call__(self, crops_u8, masks, M_c2o, frames_ori, source_id=None, slots=None, out=None, keep=False, logits=None, concat=False,
-                 concat_out=None, parse=False, frame_index=None):
+                 concat_out=None, parse=False, frame_index=None, status=None):
         """parse=True (masks None, no logits=): the engine's own face parser makes the logits of the crops in stage A (parser_input -> parser).
         crops_u8 (B,512,512,3) or (B,256,256,3) u8; masks (B,512,512) u8 0/1 or fp32 (the parser's `torch.isin(labels, valid)`), or None
         with logits= (B,C,128,128), (B,C,256,256) or (B,C,512,512) fp32: the parser's logits, masked here (tail.face_masks with the chain's valid);
@@ -223,11 +232,19 @@ class FrameChain(_StagedChain):
         frame_index (B host ints, non-decreasing, in [0, F)): B faces in F frames.  Everything above stays per face (B up to the engine's
         max_batch; crops, masks / logits, M_c2o, source_id / slots, "concat", the kept stages); frames_ori, out and "frames" are (F,Ho,Wo,3): face b
         is pasted into frame frame_index[b], the faces of a frame in their order (tail.paste_back_faces), a frame without a face comes back as
-        it is.  B = 0 (crops (0,512,512,3), F >= 1): no generator runs, "frames" is frames_ori (copied into out, if given)."""
+        it is.  B = 0 (crops (0,512,512,3), F >= 1): no generator runs, "frames" is frames_ori (copied into out, if given).
+        M_c2o a (B,18) float32 DEVICE tensor (chain.crop's "M" of device landmarks, M_c2o = M[:, 9:]): the paste-back reads the matrices where
+        they lie (tail.paste_back_faces_dev; frame_index None: arange(B)), status= (B,) int32 on the device, optional: crop's "status", a face
+        with a non-zero entry is not pasted.  Host matrices go the way they went."""
         e = self.e
         if frame_index is not None and torch.as_tensor(crops_u8).shape[0] == 0:
             return self._no_faces(frames_ori, frame_index, out)
         self._mask_or_logits(masks, logits, "FrameChain", parse)
+        on_device = isinstance(M_c2o, torch.Tensor) and M_c2o.is_cuda      # the (B,18) matrices of chain.crop's device route
+        if status is not None and not on_device:
+            raise ValueError("FrameChain: status= goes with a (B,18) device M_c2o (chain.crop of device landmarks)")
+        if on_device and frame_index is None:
+            frame_index = range(len(crops_u8))
         if frame_index is not None:                                   # before anything is enqueued: the error names the argument
             frame_index = tail.frame_index_of(frame_index, len(crops_u8), len(frames_ori))
         slot, (I, x_t, x_can, soft, made) = self._resolve(crops_u8, masks, logits, parse)
@@ -236,7 +253,9 @@ class FrameChain(_StagedChain):
         swp = self._get("swap_can", (B, 3, 512, 512), torch.float32) if concat else None
         gen = e.swap_frames(I, x_t, x_can, source_id, want_f32=False, want_u8=True, slots=slots,
                             out_u8=self._get("gen", (B, 512, 512, 3), torch.uint8), out_rec=rec, out_swap=swp)["out_u8"]   # :242-267
-        if frame_index is None:
+        if on_device:                                                                           # :279-282, the matrices read where they lie
+            frames = tail.paste_back_faces_dev(e, gen, soft, M_c2o, frame_index, frames_ori, status=status, out=out)
+        elif frame_index is None:
             frames = tail.paste_back_batch(e, gen, soft, M_c2o, frames_ori, out=out)            # :279-282
         else:
             frames = tail.paste_back_faces(e, gen, soft, M_c2o, frame_index, frames_ori, out=out)      # :279-282 once per face of a frame

@@ -271,6 +271,13 @@ int launch_lmk_input(const unsigned char* frames, int Ho, int Wo, const int* fra
                      hipStream_t st);
 int launch_lmk_decode(const float* out_pts, int Np, const float* M, int dsize, const int* status, float* lmk, int B, hipStream_t st);
 
+// ---- the crop and the paste-back from device landmarks and matrices (landmarks.hip, imgops.hip; include/canonswap_device_crop.h)
+int launch_crop_lmk(const unsigned char* frames, int Ho, int Wo, const int* frame_index, const float* lmk, int N, const cs_lmk_layout& L, int dsize,
+                    float scale, float vy_ratio, int flag_do_rot, int status_mark, float* M, unsigned char* crops, float* I, float* lmk_crop,
+                    int* status, int B, hipStream_t st);
+int launch_paste_faces_dev(const unsigned char* crops, const float* masks, int Hc, int Wc, const float* M, const int* status, const int* frame_index,
+                           const unsigned char* oris, unsigned char* outs, int B, int F, int Ho, int Wo, hipStream_t st);
+
 // ---- 4:2:0 frames <-> RGB frames (yuv.hip; include/canonswap_yuv.h)
 int launch_yuv_to_rgb(const unsigned char* yuv, int F, int Ho, int Wo, int layout, int matrix, int full_range, unsigned char* rgb, hipStream_t st);
 int launch_rgb_to_yuv(const unsigned char* rgb, int F, int Ho, int Wo, int layout, int matrix, int full_range, int keep, unsigned char* yuv,

@@ -4,6 +4,7 @@
 #include "engine.h"
 #include "../../include/canonswap_landmarks.h"
 #include "../../include/canonswap_yuv.h"
+#include "../../include/canonswap_device_crop.h"
 
 // ---- image-space steps around the generator
 static int soft_erosion_impl(cs_engine* e, int B, int H, int W, const void* mask, int mask_u8, const float* w, int ksize, float thr, int iters,
@@ -295,6 +296,35 @@ extern "C" int cs_det_decode(cs_engine* e, int F, int n_levels, const int* strid
     }, "det_decode");
 }
 
+// What cs_lmk_input and cs_crop_lmk check alike, behind their NULL checks: sizes, the layout's indices, the crop's parameters, frame_index (B host
+// ints in [0, F), any order).  Sets the error and returns nonzero; nothing has been launched then.
+static int check_lmk_args(const char* who, int B, int F, int Ho, int Wo, const int* frame_index, int N, const cs_lmk_layout& layout, int dsize,
+                          float scale, float vy_ratio, int status_mark)
+{
+    if (B < 1 || F < 1 || Ho < 1 || Wo < 1) { cs_set_error("%s: B = %d, F = %d, Ho = %d, Wo = %d (each at least 1)", who, B, F, Ho, Wo); return -1; }
+    if (dsize < 4 || dsize % 4 || dsize > 16384) { cs_set_error("%s: dsize %d (a multiple of 4 from 4 to 16384)", who, dsize); return -1; }
+    if (N < 1 || N > (1 << 20)) { cs_set_error("%s: N = %d landmarks outside [1, 2^20]", who, N); return -1; }
+    if (layout.n_eye < 1 || layout.n_eye > 4) { cs_set_error("%s: layout.n_eye %d outside [1, 4]", who, layout.n_eye); return -1; }
+    for (int i = 0; i < layout.n_eye; ++i)
+        if (layout.left[i] < 0 || layout.left[i] >= N || layout.right[i] < 0 || layout.right[i] >= N) {
+            cs_set_error("%s: layout eye index %d (%d, %d) outside [0, N = %d)", who, i, layout.left[i], layout.right[i], N);
+            return -1;
+        }
+    if (layout.lip[0] < 0 || layout.lip[0] >= N || layout.lip[1] < 0 || layout.lip[1] >= N) {
+        cs_set_error("%s: layout lip indices (%d, %d) outside [0, N = %d)", who, layout.lip[0], layout.lip[1], N);
+        return -1;
+    }
+    if (!(scale > 0.f) || scale > 3.0e38f) { cs_set_error("%s: scale %g is not a positive finite number", who, (double)scale); return -1; }
+    if (!(fabsf(vy_ratio) <= 3.0e38f)) { cs_set_error("%s: vy_ratio %g is not finite", who, (double)vy_ratio); return -1; }
+    if (status_mark == 0) { cs_set_error("%s: status_mark 0 (a refused face is marked with a non-zero value)", who); return -1; }
+    for (int b = 0; b < B; ++b)
+        if (frame_index[b] < 0 || frame_index[b] >= F) {
+            cs_set_error("%s: frame_index[%d] = %d outside [0, %d)", who, b, frame_index[b], F);
+            return -1;
+        }
+    return 0;
+}
+
 // ---- the landmark runner's input (human_landmark_runner.py:62, :76) and decode (:82-83): everything is refused before any launch; neither call
 // uses engine scratch or synchronises, B and F are not bound by max_batch
 extern "C" int cs_lmk_input(cs_engine* e, int B, int F, const uint8_t* frames, int Ho, int Wo, const int* frame_index, const float* lmk, int N,
@@ -305,27 +335,7 @@ extern "C" int cs_lmk_input(cs_engine* e, int B, int F, const uint8_t* frames, i
         cs_set_error("cs_lmk_input: NULL %s", !e ? "engine" : !frames ? "frames" : !frame_index ? "frame_index" : !lmk ? "lmk" : !M ? "M" : !inp ? "inp" : "status");
         return -1;
     }
-    if (B < 1 || F < 1 || Ho < 1 || Wo < 1) { cs_set_error("cs_lmk_input: B = %d, F = %d, Ho = %d, Wo = %d (each at least 1)", B, F, Ho, Wo); return -1; }
-    if (dsize < 4 || dsize % 4 || dsize > 16384) { cs_set_error("cs_lmk_input: dsize %d (a multiple of 4 from 4 to 16384)", dsize); return -1; }
-    if (N < 1 || N > (1 << 20)) { cs_set_error("cs_lmk_input: N = %d landmarks outside [1, 2^20]", N); return -1; }
-    if (layout.n_eye < 1 || layout.n_eye > 4) { cs_set_error("cs_lmk_input: layout.n_eye %d outside [1, 4]", layout.n_eye); return -1; }
-    for (int i = 0; i < layout.n_eye; ++i)
-        if (layout.left[i] < 0 || layout.left[i] >= N || layout.right[i] < 0 || layout.right[i] >= N) {
-            cs_set_error("cs_lmk_input: layout eye index %d (%d, %d) outside [0, N = %d)", i, layout.left[i], layout.right[i], N);
-            return -1;
-        }
-    if (layout.lip[0] < 0 || layout.lip[0] >= N || layout.lip[1] < 0 || layout.lip[1] >= N) {
-        cs_set_error("cs_lmk_input: layout lip indices (%d, %d) outside [0, N = %d)", layout.lip[0], layout.lip[1], N);
-        return -1;
-    }
-    if (!(scale > 0.f) || scale > 3.0e38f) { cs_set_error("cs_lmk_input: scale %g is not a positive finite number", (double)scale); return -1; }
-    if (!(fabsf(vy_ratio) <= 3.0e38f)) { cs_set_error("cs_lmk_input: vy_ratio %g is not finite", (double)vy_ratio); return -1; }
-    if (status_mark == 0) { cs_set_error("cs_lmk_input: status_mark 0 (a refused face is marked with a non-zero value)"); return -1; }
-    for (int b = 0; b < B; ++b)
-        if (frame_index[b] < 0 || frame_index[b] >= F) {
-            cs_set_error("cs_lmk_input: frame_index[%d] = %d outside [0, %d)", b, frame_index[b], F);
-            return -1;
-        }
+    if (check_lmk_args("cs_lmk_input", B, F, Ho, Wo, frame_index, N, layout, dsize, scale, vy_ratio, status_mark)) return -1;
     DevGuard guard(e->dev);
     hipStream_t st = (hipStream_t)stream;
     return e->run(1, st, [&] {
@@ -438,4 +448,47 @@ extern "C" int cs_parser(cs_engine* e, int B, const float* pixel_values, int H, 
         TRY(e->run(1, st, [&] { return parser_forward(P, nb, H, W, logits_out + (size_t)b0 * P.L * (H / 4) * (W / 4), st); }, "parser"));
     }
     return 0;
+}
+
+// ---- the crop and the paste-back from landmarks and matrices on the device (include/canonswap_device_crop.h): everything is refused before any
+// launch; neither call uses engine scratch or synchronises
+extern "C" int cs_dcrop_abi_version(void) { return CS_DCROP_ABI_VERSION; }
+
+extern "C" int cs_crop_lmk(cs_engine* e, int B, int F, const uint8_t* frames, int Ho, int Wo, const int* frame_index, const float* lmk, int N,
+                           const cs_lmk_layout* layout, int dsize, float scale, float vy_ratio, int flag_do_rot, int status_mark, float* M,
+                           uint8_t* crops, float* I_out, float* lmk_crop, int* status, void* stream)
+{
+    if (!e || !frames || !frame_index || !lmk || !layout || !M || !crops || !status) {
+        cs_set_error("cs_crop_lmk: NULL %s", !e ? "engine" : !frames ? "frames" : !frame_index ? "frame_index" : !lmk ? "lmk" : !layout ? "layout" :
+                     !M ? "M" : !crops ? "crops" : "status");
+        return -1;
+    }
+    if (check_lmk_args("cs_crop_lmk", B, F, Ho, Wo, frame_index, N, *layout, dsize, scale, vy_ratio, status_mark)) return -1;
+    if (I_out && dsize != 256 && dsize != 512) { cs_set_error("cs_crop_lmk: I_out goes with dsize 256 or 512 (got %d)", dsize); return -1; }
+    DevGuard guard(e->dev);
+    hipStream_t st = (hipStream_t)stream;
+    return e->run(1, st, [&] {
+        return launch_crop_lmk(frames, Ho, Wo, frame_index, lmk, N, *layout, dsize, scale, vy_ratio, flag_do_rot != 0, status_mark, M, crops, I_out,
+                               lmk_crop, status, B, st);
+    }, "crop_lmk");
+}
+
+extern "C" int cs_paste_back_faces_dev(cs_engine* e, int B, int F, const uint8_t* crops, const float* masks_crop, int Hc, int Wc, const int* frame_index,
+                                       const float* M, const int* status, const uint8_t* imgs_ori, uint8_t* out, int Ho, int Wo, void* stream)
+{
+    // B == 0: no face at all, the frames are copied; crops, masks, index, matrices and status are then not read and may be NULL
+    if (!e || !imgs_ori || !out) { cs_set_error("cs_paste_back_faces_dev: NULL %s", !e ? "engine" : !imgs_ori ? "imgs_ori" : "out"); return -1; }
+    if (B > 0 && (!crops || !masks_crop || !frame_index || !M)) {
+        cs_set_error("cs_paste_back_faces_dev: NULL %s", !crops ? "crops" : !masks_crop ? "masks_crop" : !frame_index ? "frame_index" : "M");
+        return -1;
+    }
+    if (B < 0 || F < 1 || Ho < 1 || Wo < 1 || (B > 0 && (Hc < 1 || Wc < 1))) {
+        cs_set_error("cs_paste_back_faces_dev: B = %d faces, F = %d frames, Hc = %d, Wc = %d, Ho = %d, Wo = %d", B, F, Hc, Wc, Ho, Wo);
+        return -1;
+    }
+    if (check_frame_index("cs_paste_back_faces_dev", frame_index, B, F)) return -1;
+    DevGuard guard(e->dev);
+    hipStream_t st = (hipStream_t)stream;
+    return e->run(1, st, [&] { return launch_paste_faces_dev(crops, masks_crop, Hc, Wc, M, status, frame_index, imgs_ori, out, B, F, Ho, Wo, st); },
+                  "paste_back_faces_dev");
 }

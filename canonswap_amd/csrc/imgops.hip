@@ -16,7 +16,7 @@
 // once inlined their multiply and add fuse again.  The fp32 convolution of SoftErosion asks for fmaf explicitly.
 #pragma clang fp contract(off)
 
-#include "warp_taps.h"      // staged_value, AffineInv, affine_coords, Tap, tap_at, tap_u8x3 (shared with landmarks.hip)
+#include "warp_taps.h"      // staged_value, affine_coords, Tap, tap_at, tap_u8x3 (shared with landmarks.hip); AffineInv, invert_affine, face_box (affine_inv.h)
 
 #define LAUNCH_CHECK(name)                                                                       \
     do {                                                                                         \
@@ -268,12 +268,13 @@ __global__ void __launch_bounds__(256) paste_kernel(const unsigned char* __restr
 // paste_kernel with mask_crop (tests/test_gpu_chain.py holds the two bit-equal).
 struct AffineBatch { AffineInv a[64]; };      // 3 KB of kernel arguments: no device-side staging buffer, nothing to race with
 
-// one face into a thread's four pixels (xb .. xb + 3, y), px their 12 bytes: the pixel is truncated to 8 bits, as paste_back's astype(np.uint8)
-__device__ __forceinline__ void paste_px4(const unsigned char* __restrict__ crop, const float* __restrict__ mask_crop, int Hc, int Wc,
-                                          const AffineInv& A, int xb, int y, unsigned char* px)
+// one face into a thread's PX pixels (xb .. xb + PX - 1, y), px their 3 PX bytes: the pixel is truncated to 8 bits, as paste_back's astype(np.uint8)
+template <int PX>
+__device__ __forceinline__ void paste_px(const unsigned char* __restrict__ crop, const float* __restrict__ mask_crop, int Hc, int Wc,
+                                         const AffineInv& A, int xb, int y, unsigned char* px)
 {
 #pragma unroll
-    for (int k = 0; k < 4; ++k) {
+    for (int k = 0; k < PX; ++k) {
         const Tap t = tap_at(A, xb + k, y, Hc, Wc);
         if (t.outside) continue;                                           // the original pixel
         const float m = tap_f32(mask_crop, Wc, t);
@@ -300,20 +301,20 @@ __global__ void __launch_bounds__(256) paste_batch_kernel(const unsigned char* _
     unsigned wv[3] = {ori[0], ori[1], ori[2]};
     unsigned char* px = (unsigned char*)wv;
     const int y = (int)((q * 4) / Wo), xb = (int)((q * 4) % Wo);
-    paste_px4(crop, mask_crop, Hc, Wc, A, xb, y, px);
+    paste_px<4>(crop, mask_crop, Hc, Wc, A, xb, y, px);
     out[0] = wv[0]; out[1] = wv[1]; out[2] = wv[2];
 }
 
 // ---- several faces per frame: prepare_paste_back + paste_back (crop.py:515-529) applied once per face of a frame, in the faces' order, each on
 // the result of the one before, in ONE pass over the frame.  blockIdx.y = frame of the launch; a thread owns the four pixels of
-// paste_batch_kernel, loads their three dwords once, walks its frame's faces (paste_px4 per face: paste_batch_kernel's arithmetic, the pixel
+// paste_batch_kernel, loads their three dwords once, walks its frame's faces (paste_px<4> per face: paste_batch_kernel's arithmetic, the pixel
 // truncated to 8 bits after every face, as sequential paste_back calls leave it) and stores the three dwords once: the frames between two faces
 // never exist in memory.  A frame without a face is copied (in place: left alone).  Matrices, boxes and face ranges are kernel arguments:
 // FACES_PER_LAUNCH = 48 faces and at most as many frames per launch, 48 x (48 B matrix + 16 B box) + 49 x 4 B ranges = 3272 B beside ~70 B of
 // scalars, under HIP's 4 KB argument block with the room AffineBatch leaves (64 matrices alone are 3 KB; with box and range 64 faces would be 4356 B).
 // box: a conservative integer rectangle (x0, y0, x1, y1, inclusive, clipped to the frame; x0 > x1: empty) that holds every pixel of the frame
 // for which !tap_at(...).outside, so a group of four pixels outside it skips the face before any double-precision coordinate is formed - most of
-// a 1080p frame, for every face.  It prunes only: inside it every pixel still decides by tap_at (face_box below for why it cannot cut a pixel).
+// a 1080p frame, for every face.  It prunes only: inside it every pixel still decides by tap_at (face_box, affine_inv.h, for why it cannot cut a pixel).
 // oris / outs may be ONE buffer, and a launch may continue a frame that an earlier launch began (resume: frame 0 of this launch is read from
 // outs): a thread reads and writes its own twelve bytes only, so neither is a race.  crops and masks must not overlap outs.
 constexpr int FACES_PER_LAUNCH = 48;
@@ -339,7 +340,7 @@ __global__ void __launch_bounds__(256) paste_faces_kernel(const unsigned char* _
     const int y = (int)((q * 4) / Wo), xb = (int)((q * 4) % Wo);
     for (int i = i0; i < i1; ++i) {
         if (y < FB.box[i][1] || y > FB.box[i][3] || xb + 3 < FB.box[i][0] || xb > FB.box[i][2]) continue;
-        paste_px4(crops + (long)i * Hc * Wc * 3, masks + (long)i * Hc * Wc, Hc, Wc, FB.a[i], xb, y, (unsigned char*)wv);
+        paste_px<4>(crops + (long)i * Hc * Wc * 3, masks + (long)i * Hc * Wc, Hc, Wc, FB.a[i], xb, y, (unsigned char*)wv);
     }
     out[0] = wv[0]; out[1] = wv[1]; out[2] = wv[2];
 }
@@ -481,20 +482,6 @@ __global__ void __launch_bounds__(256) warp_f32_kernel(const float* __restrict__
     dst[i] = tap_f32(src, Ws, tap_at(A, x, y, Hs, Ws));
 }
 
-static AffineInv invert_affine(const double M[6])      // imgwarp.cpp warpAffine, !WARP_INVERSE_MAP
-{
-    AffineInv A;
-    for (int i = 0; i < 6; ++i) A.m[i] = M[i];
-    double D = A.m[0] * A.m[4] - A.m[1] * A.m[3];
-    D = D != 0 ? 1. / D : 0;
-    const double A11 = A.m[4] * D, A22 = A.m[0] * D;
-    A.m[0] = A11; A.m[1] *= -D; A.m[3] *= -D; A.m[4] = A22;
-    const double b1 = -A.m[0] * A.m[2] - A.m[1] * A.m[5];
-    const double b2 = -A.m[3] * A.m[2] - A.m[4] * A.m[5];
-    A.m[2] = b1; A.m[5] = b2;
-    return A;
-}
-
 // B matrices, inverted, in chunks of the 64 that one launch takes as kernel arguments: launch(first frame, frames, matrices) per chunk
 template <typename F>
 static int for_affine_batches(const double* M, int B, F launch)
@@ -583,38 +570,6 @@ int launch_paste_batch(const unsigned char* crops, const float* masks, int Hc, i
     });
 }
 
-// The box of paste_faces_kernel for one face, A its frame -> crop map.  A pixel (x, y) reads the crop (!outside) only if -1 <= sx <= Wc - 1 and
-// -1 <= sy <= Hc - 1, where sx = floor(u + 1/64 + e), u = A0 x + A1 y + A2 and |e| <= 1/1024 + the doubles' rounding (affine_coords: two rint at
-// 10 bits, + 16, >> 10), so u lies in [-1.017, Wc - 0.014], v likewise: inside R = [-1.0625, Wc + 0.0625] x [-1.0625, Hc + 0.0625] with 0.045 to
-// spare.  The pixels with (u, v) in R are the parallelogram A^-1 R; an affine map takes R's hull to the hull of its four corners, so the box
-// of the four corners A^-1 c, widened by one pixel on every side, holds them all, given that A^-1 c is off by less than that pixel: with the
-// guards below (entries up to 1e6, linear part at least 1e-3 and of condition (max |a|)^2 / |det| up to 1e4) the doubles' error in a corner that
-// lies within 1e5 pixels of the frame is below 1e-2 pixel.  Any other matrix (singular, not finite, a crop above the 32767 at which
-// affine_coords saturates) gets the whole frame: the box then prunes nothing, and the result is the same.
-static void face_box(const AffineInv& A, int Hc, int Wc, int Ho, int Wo, int (&box)[4])
-{
-    box[0] = 0; box[1] = 0; box[2] = Wo - 1; box[3] = Ho - 1;
-    const double* m = A.m;
-    double big = 0, lin = 0;
-    for (int i = 0; i < 6; ++i) big = fmax(big, fabs(m[i]));
-    for (int i : {0, 1, 3, 4}) lin = fmax(lin, fabs(m[i]));
-    const double D = m[0] * m[4] - m[1] * m[3];
-    if (!(big <= 1e6) || !(lin >= 1e-3) || !(fabs(D) * 1e4 >= lin * lin) || Hc > 32767 || Wc > 32767) return;
-    const double us[2] = {-1.0625, (double)Wc + 0.0625}, vs[2] = {-1.0625, (double)Hc + 0.0625};
-    double lo[2] = {HUGE_VAL, HUGE_VAL}, hi[2] = {-HUGE_VAL, -HUGE_VAL};
-    for (int c = 0; c < 4; ++c) {
-        const double du = us[c & 1] - m[2], dv = vs[c >> 1] - m[5];
-        const double p[2] = {(m[4] * du - m[1] * dv) / D, (m[0] * dv - m[3] * du) / D};
-        for (int k = 0; k < 2; ++k) { lo[k] = fmin(lo[k], p[k]); hi[k] = fmax(hi[k], p[k]); }
-    }
-    const double top[2] = {(double)Wo - 1, (double)Ho - 1};
-    for (int k = 0; k < 2; ++k) {
-        const double a = fmax(floor(lo[k]) - 1, 0.), b = fmin(ceil(hi[k]) + 1, top[k]);
-        if (!(a <= b)) { box[0] = box[1] = 1; box[2] = box[3] = 0; return; }      // the face does not reach the frame
-        box[k] = (int)a; box[k + 2] = (int)b;
-    }
-}
-
 // B faces into F frames, face b into frame frame_index[b] (non-decreasing, in [0, F): the caller checks), in the faces' order.  A launch takes up
 // to FACES_PER_LAUNCH faces and as many frames; a frame whose faces do not fit is finished by the next launch, which reads what this one wrote
 // (stream order).  outs == oris pastes in place.  Odd widths / unaligned buffers: the single-frame kernel per face, in order, the first face of a
@@ -666,6 +621,96 @@ int launch_paste_faces(const unsigned char* crops, const float* masks, int Hc, i
     return 0;
 }
 
+// ---- the same with the matrices in device memory (cs_paste_back_faces_dev, include/canonswap_device_crop.h): M is B x 18 fp32 as cs_crop_lmk and
+// cs_lmk_input write it, M_c2o = M + 18 b + 9.  What paste_faces_kernel gets as kernel arguments - a face's inverted matrix and its box - a
+// workgroup forms itself: the faces of its frame in chunks of DEV_FACE_CHUNK, thread i of the chunk widens face i's six floats to double and runs
+// invert_affine and face_box (affine_inv.h: the text launch_paste_faces runs on the host, so the AffineInv has the host form's bits) into LDS,
+// once per workgroup; after the barrier every thread walks the chunk as paste_faces_kernel walks its range.  Nothing is staged in device
+// memory, so two calls on two streams share nothing.  A face with status != 0 gets the empty box and is skipped like a face that does not
+// reach the frame.  The faces come from device memory, so a frame's faces never have to be split over launches: only the frames' ranges are
+// kernel arguments, DEV_FRAMES_PER_LAUNCH of them (absolute face numbers).  PX = 4: a thread's four pixels as three dwords, as above; PX = 1: one
+// pixel, byte by byte - odd widths and buffers off a 4-byte boundary, where the host form launches paste_kernel per face: the same values, since
+// for a pixel outside the crop paste_kernel's blend is 0 * 0 + 1 * ori = ori exactly.
+constexpr int DEV_FRAMES_PER_LAUNCH = 48, DEV_FACE_CHUNK = 16;
+struct FrameFaces { int first[DEV_FRAMES_PER_LAUNCH + 1]; };      // frame j of the launch owns faces first[j] .. first[j + 1] - 1
+
+template <int PX>
+__global__ void __launch_bounds__(256) paste_faces_dev_kernel(const unsigned char* __restrict__ crops, const float* __restrict__ masks, int Hc, int Wc,
+                                                              const float* __restrict__ M, const int* __restrict__ status, FrameFaces FF,
+                                                              const unsigned char* oris, unsigned char* outs, int Ho, int Wo)
+{
+    __shared__ AffineInv s_a[DEV_FACE_CHUNK];
+    __shared__ int s_box[DEV_FACE_CHUNK][4];
+    const int j = blockIdx.y, tid = threadIdx.x;
+    const int i0 = FF.first[j], i1 = FF.first[j + 1];
+    if (i0 == i1 && oris == outs) return;                          // in place, no face: nothing to do (the whole workgroup leaves)
+    const long q = (long)blockIdx.x * 256 + tid;                   // group of PX pixels
+    const long P = (long)Ho * Wo;
+    const bool live = q * PX < P;                                  // the others only help to form the matrices and keep the barriers
+    const unsigned char* in = oris + ((long)j * P + q * PX) * 3;
+    unsigned char* out = outs + ((long)j * P + q * PX) * 3;
+    unsigned wv[3] = {0u, 0u, 0u};
+    unsigned char* px = (unsigned char*)wv;
+    if (live) {
+        if constexpr (PX == 4) { wv[0] = ((const unsigned*)in)[0]; wv[1] = ((const unsigned*)in)[1]; wv[2] = ((const unsigned*)in)[2]; }
+        else { px[0] = in[0]; px[1] = in[1]; px[2] = in[2]; }
+    }
+    const int y = (int)((q * PX) / Wo), xb = (int)((q * PX) % Wo);
+    for (int c0 = i0; c0 < i1; c0 += DEV_FACE_CHUNK) {
+        const int nc = min(DEV_FACE_CHUNK, i1 - c0);
+        __syncthreads();                                           // the chunk before has been read by everyone
+        if (tid < nc) {
+            const int b = c0 + tid;
+            AffineInv A = {};
+            int box[4] = {1, 1, 0, 0};                             // empty: a face that is not pasted
+            if (!status || status[b] == 0) {
+                const float* m = M + (long)b * 18 + 9;
+                const double Md[6] = {(double)m[0], (double)m[1], (double)m[2], (double)m[3], (double)m[4], (double)m[5]};
+                A = invert_affine(Md);
+                face_box(A, Hc, Wc, Ho, Wo, box);
+            }
+            s_a[tid] = A;
+#pragma unroll
+            for (int k = 0; k < 4; ++k) s_box[tid][k] = box[k];
+        }
+        __syncthreads();
+        if (!live) continue;
+        for (int i = 0; i < nc; ++i) {
+            if (y < s_box[i][1] || y > s_box[i][3] || xb + PX - 1 < s_box[i][0] || xb > s_box[i][2]) continue;
+            paste_px<PX>(crops + (long)(c0 + i) * Hc * Wc * 3, masks + (long)(c0 + i) * Hc * Wc, Hc, Wc, s_a[i], xb, y, px);
+        }
+    }
+    if (!live) return;
+    if constexpr (PX == 4) { ((unsigned*)out)[0] = wv[0]; ((unsigned*)out)[1] = wv[1]; ((unsigned*)out)[2] = wv[2]; }
+    else { out[0] = px[0]; out[1] = px[1]; out[2] = px[2]; }
+}
+
+// frame_index is checked by the caller (non-decreasing, in [0, F)); B = 0: it is not read.  outs == oris pastes in place.
+int launch_paste_faces_dev(const unsigned char* crops, const float* masks, int Hc, int Wc, const float* M, const int* status, const int* frame_index,
+                           const unsigned char* oris, unsigned char* outs, int B, int F, int Ho, int Wo, hipStream_t st)
+{
+    const long P = (long)Ho * Wo;
+    const bool wide = Wo % 4 == 0 && ((uintptr_t)oris & 3) == 0 && ((uintptr_t)outs & 3) == 0;
+    const unsigned blocks = (unsigned)(((wide ? P / 4 : P) + 255) / 256);
+    int b = 0;
+    for (int f0 = 0; f0 < F; f0 += DEV_FRAMES_PER_LAUNCH) {
+        const int nf = F - f0 < DEV_FRAMES_PER_LAUNCH ? F - f0 : DEV_FRAMES_PER_LAUNCH, b0 = b;
+        FrameFaces FF = {};
+        FF.first[0] = b;
+        for (int j = 0; j < nf; ++j) {
+            while (b < B && frame_index[b] == f0 + j) ++b;
+            FF.first[j + 1] = b;
+        }
+        if (b == b0 && oris == outs) continue;                        // in place, no face in these frames
+        const unsigned char* from = oris + (long)f0 * P * 3;
+        unsigned char* to = outs + (long)f0 * P * 3;
+        if (wide) hipLaunchKernelGGL(paste_faces_dev_kernel<4>, dim3(blocks, nf), dim3(256), 0, st, crops, masks, Hc, Wc, M, status, FF, from, to, Ho, Wo);
+        else hipLaunchKernelGGL(paste_faces_dev_kernel<1>, dim3(blocks, nf), dim3(256), 0, st, crops, masks, Hc, Wc, M, status, FF, from, to, Ho, Wo);
+        LAUNCH_CHECK("paste_faces_dev");
+    }
+    return 0;
+}
+
 // ---------------------------------------------------------------------------------------------- the crop itself
 // crop_image's image step (src/utils/crop.py:429-455 as src/utils/cropper.py:196-209 calls it per frame): cv2.warpAffine(frame, M_o2c[:2],
 // (dsize, dsize), INTER_LINEAR), BORDER_CONSTANT 0, for B frames in one launch; blockIdx.y = frame, the matrices are kernel arguments as in
@@ -701,30 +746,7 @@ __global__ void __launch_bounds__(256) crop_batch_kernel(const unsigned char* __
     for (int r = 0; r < ROWS; ++r)
 #pragma unroll
         for (int k = 0; k < 4; ++k) crop_pixel(frame, Ho, Wo, A, xb + k, yb + r, v[r][k]);
-#pragma unroll
-    for (int r = 0; r < ROWS; ++r) {
-        unsigned w[3] = {0u, 0u, 0u};
-#pragma unroll
-        for (int j = 0; j < 12; ++j) w[j >> 2] |= (unsigned)v[r][j / 3][j % 3] << ((j & 3) * 8);
-        unsigned* out = (unsigned*)(crops + (((long)n * dsize + yb + r) * dsize + xb) * 3);
-        out[0] = w[0]; out[1] = w[1]; out[2] = w[2];
-    }
-    if constexpr (STAGE == 2) {
-        const int Wd = dsize >> 1;
-#pragma unroll
-        for (int c = 0; c < 3; ++c) {
-            const int a = (v[0][0][c] + v[0][1][c] + v[1][0][c] + v[1][1][c] + 2) >> 2;
-            const int b = (v[0][2][c] + v[0][3][c] + v[1][2][c] + v[1][3][c] + 2) >> 2;
-            *(float2*)(I + (((long)n * 3 + c) * Wd + (yb >> 1)) * Wd + (xb >> 1)) = make_float2(staged_value(a), staged_value(b));
-        }
-    } else if constexpr (STAGE == 1) {
-#pragma unroll
-        for (int c = 0; c < 3; ++c)
-#pragma unroll
-            for (int r = 0; r < 2; ++r)
-                *(float4*)(I + (((long)n * 3 + c) * dsize + yb + r) * dsize + xb) =
-                    make_float4(staged_value(v[r][0][c]), staged_value(v[r][1][c]), staged_value(v[r][2][c]), staged_value(v[r][3][c]));
-    }
+    crop_store<STAGE, true>(v, n, yb, xb, dsize, crops, I);          // warp_taps.h: the crop's dwords and, with STAGE, the staged input
 }
 
 // dsize: a multiple of 4 (the caller checks); I != nullptr: dsize 256 or 512.  B is chunked by the 64 matrices of a launch, so it is not bound

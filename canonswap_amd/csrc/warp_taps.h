@@ -2,13 +2,12 @@
 // crop kernels of imgops.hip and the landmark runner's crop of landmarks.hip: one text, so that a crop cut by either file has the same bits.
 // Device code only.  The including file turns fp contraction off (#pragma clang fp contract(off)) BEFORE it includes this header.
 #pragma once
+#include "affine_inv.h"      // AffineInv, and invert_affine / face_box for the host and the device
 
 // a byte as the networks' fp32 input: / 255, clipped (can_swap_e2e.py:126-163, human_landmark_runner.py:76)
 __device__ __forceinline__ float staged_value(int v) { return fminf(fmaxf((float)v / 255.f, 0.f), 1.f); }
 
 // ---------------------------------------------------------------------------------------------- cv2.warpAffine, INTER_LINEAR
-struct AffineInv { double m[6]; };      // destination -> source map (what warpAffine derives from M)
-
 // OpenCV's fixed-point source coordinate of destination pixel (x, y): AB_BITS = 10, INTER_BITS = 5 (imgwarp.cpp warpAffine)
 __device__ __forceinline__ void affine_coords(const AffineInv& A, int x, int y, int& sx, int& sy, int& fx, int& fy)
 {
@@ -58,5 +57,52 @@ __device__ __forceinline__ void tap_u8x3(const unsigned char* __restrict__ src, 
         const int t10 = (t.y1 && t.x0) ? p[(long)Ws * 3 + c] : 0;
         const int t11 = (t.y1 && t.x1) ? p[(long)Ws * 3 + 3 + c] : 0;
         res[c] = (t00 * w00 + t01 * w01 + t10 * w10 + t11 * w11 + (1 << 14)) >> 15;
+    }
+}
+
+// A thread's block of crop n - four pixels of a row, of two rows with STAGE != 0 - from its registers (v[row][pixel][channel], 8-bit values): the
+// crop's bytes (12 per row = three dwords) and, with STAGE != 0, what prepare_crops_kernel would make of them, so that the crop is not read back:
+// STAGE 2 (dsize 512): the two 2 x 2 means (a + b + c + d + 2) >> 2, / 255, one float2 per channel of the NCHW fp32 input; STAGE 1 (dsize 256):
+// / 255 only, one float4 per row and channel.  WIDE = false: the same values byte by byte and float by float, for buffers off their boundaries
+// (crops: 4 bytes, I: 16).  crop_batch_kernel (imgops.hip) and crop_lmk_kernel (landmarks.hip) both store through here.
+template <int STAGE, bool WIDE>
+__device__ __forceinline__ void crop_store(const int (&v)[STAGE ? 2 : 1][4][3], long n, int yb, int xb, int dsize, unsigned char* __restrict__ crops,
+                                           float* __restrict__ I)
+{
+    constexpr int ROWS = STAGE ? 2 : 1;
+#pragma unroll
+    for (int r = 0; r < ROWS; ++r) {
+        unsigned char* d = crops + ((n * dsize + yb + r) * dsize + xb) * 3;
+        if constexpr (WIDE) {
+            unsigned w[3] = {0u, 0u, 0u};
+#pragma unroll
+            for (int j = 0; j < 12; ++j) w[j >> 2] |= (unsigned)v[r][j / 3][j % 3] << ((j & 3) * 8);
+            unsigned* out = (unsigned*)d;
+            out[0] = w[0]; out[1] = w[1]; out[2] = w[2];
+        } else {
+#pragma unroll
+            for (int j = 0; j < 12; ++j) d[j] = (unsigned char)v[r][j / 3][j % 3];
+        }
+    }
+    if constexpr (STAGE == 2) {
+        const int Wd = dsize >> 1;
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+            const int a = (v[0][0][c] + v[0][1][c] + v[1][0][c] + v[1][1][c] + 2) >> 2;
+            const int b = (v[0][2][c] + v[0][3][c] + v[1][2][c] + v[1][3][c] + 2) >> 2;
+            float* d = I + ((n * 3 + c) * Wd + (yb >> 1)) * Wd + (xb >> 1);
+            if constexpr (WIDE) *(float2*)d = make_float2(staged_value(a), staged_value(b));
+            else { d[0] = staged_value(a); d[1] = staged_value(b); }
+        }
+    } else if constexpr (STAGE == 1) {
+#pragma unroll
+        for (int c = 0; c < 3; ++c)
+#pragma unroll
+            for (int r = 0; r < 2; ++r) {
+                float* d = I + ((n * 3 + c) * dsize + yb + r) * dsize + xb;
+                const float4 q = make_float4(staged_value(v[r][0][c]), staged_value(v[r][1][c]), staged_value(v[r][2][c]), staged_value(v[r][3][c]));
+                if constexpr (WIDE) *(float4*)d = q;
+                else { d[0] = q.x; d[1] = q.y; d[2] = q.z; d[3] = q.w; }
+            }
     }
 }

@@ -20,10 +20,13 @@ per-frame loop (src/can_swap_pipeline_e2e.py:223-283) no longer leaves the GPU b
                              package), cv2.warpAffine of B frames in one launch; ``crop_frames_M``: the same with the caller's matrices
 * ``crop_faces``, ``paste_back_faces``   several faces per frame: face b is cut from, and pasted into, frame frame_index[b]; the paste is
                              paste_back once per face of a frame, in order, in one pass over the frame (``crop_faces_M``: the caller's matrices)
+* ``crop_lmk``, ``paste_back_faces_dev``   the same two from landmarks and matrices that never leave the device (cs_crop_lmk,
+                             cs_paste_back_faces_dev): the geometry of csrc/lmk_geometry.h in front of the crop, the matrices inverted
+                             by the paste kernel itself - nothing is downloaded between the tracker and the paste-back
 * ``prepare_crops``          src/utils/cropper.py:209 + src/can_swap_e2e.py:126-163 (INTER_AREA 512 -> 256, /255, HWC -> CHW)
 * ``FrameStreamer``          streamed upload of the uint8 crops instead of the whole-video residency of prepare_videos
 
-Every operation is a HIP kernel of libcanonswap_hip.so (csrc/imgops.hip); there is no torch / CPU fallback.
+Every operation is a HIP kernel of libcanonswap_hip.so (csrc/imgops.hip; crop_lmk: csrc/landmarks.hip); there is no torch / CPU fallback.
 """
 from __future__ import annotations
 
@@ -557,6 +560,107 @@ def paste_back_faces(e: Engine, crops, masks_crop, M_c2o, frame_index, imgs_ori,
     out = e._out(out, ori.shape, torch.uint8)
     e._call("cs_paste_back_faces", B, F, crops if B else None, mc if B else None, crops.shape[1], crops.shape[2],
             _index_ptr(idx) if B else None, mp, ori, out, ori.shape[1], ori.shape[2])
+    return out
+
+
+def _device_tensor(e: Engine, t, shape, dtype, name, who):
+    """A caller's tensor exactly as a kernel reads or writes it - dtype, shape, on the engine's device, contiguous - or ValueError naming the
+    argument; checked in that order, so the message says what is wrong first.  shape: None where any is wanted (-1: any size of that axis)."""
+    if not isinstance(t, torch.Tensor) or t.dtype != dtype:
+        raise ValueError(f"{who}: {name} must be a {dtype} tensor, got {getattr(t, 'dtype', type(t).__name__)}")
+    if len(shape) != t.dim() or any(want not in (-1, have) for want, have in zip(shape, t.shape)):
+        raise ValueError(f"{who}: {name} must have shape {tuple(shape)} (-1: any), got {tuple(t.shape)}")
+    if t.device != e.device:
+        raise ValueError(f"{who}: {name} must be on {e.device}, it is on {t.device}: it is read where it is, not uploaded")
+    if not t.is_contiguous():
+        raise ValueError(f"{who}: {name} must be contiguous")
+    return t
+
+
+def _u8_frames(frames, name, who):
+    fr = torch.as_tensor(frames)
+    if fr.dtype != torch.uint8 or fr.dim() != 4 or fr.shape[3] != 3 or fr.shape[0] < 1:
+        raise ValueError(f"{who}: {name} must be (F,Ho,Wo,3) uint8 frames, F >= 1")
+    return fr
+
+
+def crop_lmk(e: Engine, frames, lmk, frame_index=None, dsize=512, scale=2.3, vy_ratio=-0.125, flag_do_rot=True, status=None, status_mark=1, out=None,
+             want_I=False, want_lmk_crop=False):
+    """crop_faces from landmarks that never leave the device (cs_crop_lmk, one launch per 64 faces): frames (F,Ho,Wo,3) u8; lmk (B,N,2) float32 ON
+    THE DEVICE, the landmarks of the B faces in their frames (landmarks.layout_of(N) says which span the eye-lip axis); frame_index as in crop_faces
+    (None: face b in frame b) -> {"crops": (B,dsize,dsize,3) u8, "M": (B,18) fp32 = M_o2c 3x3 | M_c2o 3x3 with the bits lmk_input writes,
+    "status": (B,) int32[, "I": (B,3,256,256) fp32 = prepare_crops(crops) with want_I (dsize 256 or 512)][, "lmk_crop": (B,N,2) fp32, the
+    landmarks in the crop's frame, with want_lmk_crop]}, all on the device; nothing is downloaded and nothing waits for the device.  crops equals
+    crop_faces_M on M[:, :9] downloaded and widened.  A face the guard refuses (a landmark not finite, an empty box, a matrix entry above 1e6) gets
+    status_mark in status and zeros everywhere else; status is sticky (a non-zero entry on entry: refused, kept): pass the tracker's, or None to
+    start at zero.  out: a dict with any of "crops", "M", "I", "lmk_crop" as the caller's buffers.
+    LandmarkTracker.track's (N,S,Np,2) output reshaped to (N S,Np,2) with frame_index = repeat(arange(N), S) is a valid lmk: the tracker, this
+    crop, the generator and paste_back_faces_dev are then enqueued one behind the other without a host wait."""
+    from .landmarks import layout_of      # (landmarks imports this module)
+    who = "crop_lmk"
+    fr = _u8_frames(frames, "frames", who)
+    F = int(fr.shape[0])
+    pts = _device_tensor(e, lmk, (-1, -1, 2), torch.float32, "lmk", who)
+    B, N = int(pts.shape[0]), int(pts.shape[1])
+    if B < 1 or N < 1:
+        raise ValueError(f"{who}: lmk must hold at least one face and one landmark, got {tuple(pts.shape)}")
+    if frame_index is None and B != F:
+        raise ValueError(f"{who}: frame_index: {B} landmark sets for {F} frames and no frame_index")
+    idx = frame_index_of(np.arange(B) if frame_index is None else frame_index, B, F, f"{who}: frame_index")
+    layout = layout_of(N)
+    dsize = int(dsize)
+    if not 4 <= dsize <= 16384 or dsize % 4:
+        raise ValueError(f"{who}: dsize {dsize} (a multiple of 4 from 4 to 16384)")
+    if int(status_mark) == 0:
+        raise ValueError(f"{who}: status_mark must not be 0")
+    out = dict(out or {})
+    unknown = set(out) - {"crops", "M", "I", "lmk_crop"}
+    if unknown:
+        raise ValueError(f"{who}: out has no buffer named {sorted(unknown)}")
+    want = {"crops": True, "M": True, "I": want_I or out.get("I") is not None, "lmk_crop": want_lmk_crop or out.get("lmk_crop") is not None}
+    if want["I"] and dsize not in (256, 512):
+        raise ValueError(f"{who}: want_I goes with dsize 256 or 512 (got {dsize})")
+    shapes = {"crops": ((B, dsize, dsize, 3), torch.uint8), "M": ((B, 18), torch.float32), "I": ((B, 3, 256, 256), torch.float32),
+              "lmk_crop": ((B, N, 2), torch.float32)}
+    for k, t in out.items():
+        if t is not None:
+            _device_tensor(e, t, *shapes[k], f"out[{k!r}]", who)
+    if status is not None:
+        _device_tensor(e, status, (B,), torch.int32, "status", who)
+    buf = {k: (out[k] if out.get(k) is not None else torch.empty(shapes[k][0], dtype=shapes[k][1], device=e.device)) if want[k] else None for k in shapes}
+    status = status if status is not None else torch.zeros((B,), dtype=torch.int32, device=e.device)
+    fr = fr.to(e.device).contiguous()
+    e._call("cs_crop_lmk", B, F, fr, fr.shape[1], fr.shape[2], _index_ptr(idx), pts, N, C.byref(layout), dsize, float(scale), float(vy_ratio),
+            int(bool(flag_do_rot)), int(status_mark), buf["M"], buf["crops"], buf["I"], buf["lmk_crop"], status)
+    res = {"crops": buf["crops"], "M": buf["M"], "status": status}
+    res.update({k: buf[k] for k in ("I", "lmk_crop") if want[k]})
+    return res
+
+
+def paste_back_faces_dev(e: Engine, crops, masks_crop, M, frame_index, imgs_ori, status=None, out=None):
+    """paste_back_faces with the matrices read from device memory (cs_paste_back_faces_dev): M (B,18) float32 ON THE DEVICE, crop_lmk's or
+    lmk_input's (M_c2o = M[:, 9:]); status (B,) int32 on the device or None: a face with a non-zero entry is skipped as if it were not listed;
+    everything else as paste_back_faces takes it -> (F,Ho,Wo,3) u8, the bytes of paste_back_faces on M[:, 9:] downloaded and widened.  out may be
+    imgs_ori itself (in place); B = 0 copies the frames (M is not read and may be None).  Nothing is downloaded and nothing waits for the device."""
+    who = "paste_back_faces_dev"
+    crops, ori = torch.as_tensor(crops), _u8_frames(imgs_ori, "imgs_ori", who)
+    if crops.dtype != torch.uint8 or crops.dim() != 4 or crops.shape[3] != 3:
+        raise ValueError(f"{who}: crops must be (B,Hc,Wc,3) uint8")
+    B, F = int(crops.shape[0]), int(ori.shape[0])
+    mc = torch.as_tensor(masks_crop)
+    if tuple(mc.shape) != tuple(crops.shape[:3]):
+        raise ValueError(f"{who}: masks_crop must be (B, Hc, Wc), one mask per face")
+    idx = frame_index_of(frame_index, B, F, f"{who}: frame_index")
+    if B:
+        _device_tensor(e, M, (B, 18), torch.float32, "M", who)
+    if B and status is not None:
+        _device_tensor(e, status, (B,), torch.int32, "status", who)
+    if out is not None:
+        _device_tensor(e, out, tuple(ori.shape), torch.uint8, "out", who)
+    crops, ori, mc = crops.to(e.device).contiguous(), ori.to(e.device).contiguous(), mc.to(e.device).float().contiguous()
+    out = out if out is not None else torch.empty_like(ori)
+    e._call("cs_paste_back_faces_dev", B, F, crops if B else None, mc if B else None, crops.shape[1], crops.shape[2], _index_ptr(idx) if B else None,
+            M if B else None, status if B else None, ori, out, ori.shape[1], ori.shape[2])
     return out
 
 
