@@ -26,8 +26,8 @@ def isa_check(obj_dir: str | None = None) -> dict:
     Those kernels stream weight fragments with inline-asm `global_load_dwordx4` the compiler does not track and wait for them with
     an explicit `s_waitcnt vmcnt(WCH * (PFD - 1))`.  A compiler change that moves, duplicates or drops one of these would read stale
     registers without any diagnostic.  This disassembles every conv_halo object and checks, per
-    ST = 0 kernel: exactly PFD = 4 counted waits `s_waitcnt vmcnt(3 * WCH)`; after each of them an MFMA that reads the ring slot's
-    registers and then that slot's reload (WCH `global_load_dwordx4` into the same registers the prologue primed it with); and the
+    ST = 0 kernel: exactly PFD = 4 counted waits `s_waitcnt vmcnt(3 * WCH)`; the 4 x WCH fragments of the ring in 16 WCH distinct registers;
+    after each wait, for every fragment of the slot, an MFMA whose weight operand is that fragment's registers, and then that slot's reload (WCH `global_load_dwordx4` into the same registers the prologue primed it with); and the
     final `s_waitcnt vmcnt(0)` drain before the epilogue.  Raises RuntimeError on any mismatch; returns {kernel: waits found}."""
     import re
     obj_dir = obj_dir or OBJ_DIR
@@ -52,6 +52,8 @@ def isa_check(obj_dir: str | None = None) -> dict:
             prime = [r for i, r in loads if i < waits[0]][-4 * wch:]          # the ring as the prologue primed it: 4 slots x WCH fragments
             if len(prime) != 4 * wch:
                 raise RuntimeError(f"isa_check: {name}: the prologue primes {len(prime)} ring registers, expected {4 * wch}")
+            if len({r + j for r in prime for j in range(4)}) != 16 * wch:      # (what a spilled slot looks like: two fragments in v[52:55] and v[50:53])
+                raise RuntimeError(f"isa_check: {name}: the ring's fragments overlap in registers: v{sorted(prime)}")
             for k, w in enumerate(waits):
                 slot = prime[k * wch:(k + 1) * wch]
                 end = waits[k + 1] if k + 1 < 4 else len(body)
@@ -63,6 +65,10 @@ def isa_check(obj_dir: str | None = None) -> dict:
                 uses = [j for j, l in enumerate(seg[:first_reload]) if "v_mfma" in l and any(f"v[{r}:{r + 3}]" in l for r in slot)]
                 if not uses:
                     raise RuntimeError(f"isa_check: {name}: no MFMA reads ring slot {k} (v{slot}) between its wait and its reload")
+                # every fragment of the slot, not a copy of it: a copy or a spill made before the untracked load landed holds stale data
+                for r in slot:
+                    if not any("v_mfma" in l and re.search(rf"v_mfma\S+ [av]\[\d+:\d+\], v\[{r}:{r + 3}\],", l) for l in seg[:first_reload]):
+                        raise RuntimeError(f"isa_check: {name}: no MFMA takes v[{r}:{r + 3}] of ring slot {k} as its weight operand (a copy or a spill of the ring?)")
             tail = "\n".join(body[waits[-1]:])
             if "s_waitcnt vmcnt(0)" not in tail:
                 raise RuntimeError(f"isa_check: {name}: the ring is not drained (s_waitcnt vmcnt(0)) before the epilogue")

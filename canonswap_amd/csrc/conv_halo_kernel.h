@@ -162,7 +162,8 @@ template <int ST, int PAD> constexpr int halo_pool_shift(int bit)
     return 0;
 }
 
-// kernels that can run a grouped launch (ConvParams::nphase)
+// kernels that can run a grouped launch (ConvParams::nphase): all but the dynamic-shape ones with four fragments or more per wave - today the
+// 160-wide tiles (WCH == 5); the 128 x 256 tiles (WCH == 4) are built for the static shapes only
 template <int WCH, int ST> constexpr bool halo_phase_group() { return !(ST == 0 && WCH >= 4); }
 
 // kernels that carry the 2-D pooling epilogue (conv_epilogue.h, EP_POOL_HB)
@@ -225,8 +226,8 @@ __global__ void __launch_bounds__(256, (WCH == 4 ? 2 : ((WCH == 2 && WPX == 8 &&
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     // grouped launch (ConvParams::nphase): blockIdx.z picks the phase's weights, leading padding and output offset
-    // (not in the dynamic-shape 128 x 256 kernels: with anything added hipcc re-allocates their hand-counted weight ring - _lib.isa_check - and no
-    // grouped layer runs on them)
+    // (not in the dynamic-shape kernels of the 160-wide tiles: with anything added hipcc re-allocates their hand-counted weight ring - _isa.isa_check -
+    // and no grouped layer runs on them.  The 128 x 256 tiles have no dynamic-shape kernel at all: conv_halo.hip, launch_halo_cfg)
     constexpr bool PHK = halo_phase_group<WCH, ST>();
     const int phz = (PHK && p.nphase) ? (int)blockIdx.z : 0;
     const int PHv = (PHK && p.nphase) ? p.ph_PH[phz] : p.PH, PWv = (PHK && p.nphase) ? p.ph_PW[phz] : p.PW;
@@ -335,7 +336,7 @@ __global__ void __launch_bounds__(256, (WCH == 4 ? 2 : ((WCH == 2 && WPX == 8 &&
         int climit = p.Cin - c0;                 // channels of this chunk that exist
         // (64-channel chunks: the 1x1 kernels and the dynamic-shape ones they fall back to on small maps, with an even cg - the two
         // 32-channel halves of a chunk are then neighbours in memory; the launcher checks.  Compiled into nothing else: the 128 x 256
-        // kernels with hand-counted rings tolerate no addition, DESIGN 5.6 rule 9)
+        // kernels tolerate no addition, DESIGN 5.6 rule 9 - their dynamic-shape form, which the WCH != 4 below names, is no longer built)
         if ((CK == 32 || ST == 15 || (ST == 0 && WCH != 4)) && p.cg > 0) {
             const int j = c0 >> 5;
             coff = (long)(j / p.cg) * p.in_sG + (j % p.cg) * 32;

@@ -34,6 +34,12 @@ extern "C" int cs_op_conv(const cs_conv_desc* d, void* stream)
     if (d->cfg == CFG_LAT) return launch_conv_lat(p, c.mode, (hipStream_t)stream);
     if (d->cfg >= 10 || d->cfg == -2) {      // conv_halo: the given tile configuration, or the engine's
         const HaloPlan plan = halo_plan(p, c.mode, d->cfg >= 10 ? d->cfg : -1, d->tile_w, d->tile_h, c.cg_ck64);
+        // set_tile() takes nT = extent / tile and the kernel stores whole tiles: the remainder of an extent that is no multiple of its tile would
+        // stay unwritten (the engine's layers are powers of two; here the caller chooses)
+        if ((p.nTW << p.lgTW) != p.W || (p.nTH << p.lgTH) != p.H || (p.nTD << p.lgTD) != p.D) {
+            cs_set_error("cs_op_conv: output extent %d x %d x %d is not a whole number of %d x %d x %d tiles", p.D, p.H, p.W, 1 << p.lgTD, 1 << p.lgTH, 1 << p.lgTW);
+            return -1;
+        }
         if (d->xcd_map > 0) p.xcd_map = d->xcd_map - 1;
         p.ragged = d->ragged; p.ep_general = d->ep_general;
         return launch_conv_halo(p, plan.hcfg, d->ck ? d->ck : plan.ck, c.mode, (hipStream_t)stream);

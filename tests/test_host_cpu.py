@@ -299,3 +299,35 @@ def test_t_blobs_restated_in_fp32_match_the_oracles_modulated_weight(state_dicts
     err = np.abs(wm.astype(np.float16).astype(np.float64) - ref) / ulp
     print(f"\n{layer}: max error {err.max():.3f} fp16 ulp, style {np.abs(style - ref_s).max():.2e}")
     assert err.max() <= 1.0
+
+
+def test_isa_check_rejects_a_spilled_dynamic_ring(monkeypatch):
+    """The ring of a dynamic-shape conv_halo kernel (ST = 0) on made-up disassembly, two fragments per slot: accepted as the kernels have it;
+    refused when two fragments share registers, and when a fragment of a slot is no MFMA's weight operand (the MFMA reads a copy instead)."""
+    from canonswap_amd import _isa
+    name = "_Z16conv_halo_kernelILi32ELi8ELi2ELi1ELi4ELi0ELb0ELb0ELi0EEv10ConvParams"
+
+    def text(regs, operand=lambda r: r):
+        lines = ["\tglobal_load_dwordx4 v[%d:%d], v[60:61], off" % (r, r + 3) for r in regs]
+        for k in range(4):
+            slot = regs[2 * k:2 * k + 2]
+            lines.append("\ts_waitcnt vmcnt(6)")
+            lines += ["\tv_mfma_f32_16x16x32_f16 v[100:103], v[%d:%d], v[50:53], v[100:103]" % (operand(r), operand(r) + 3) for r in slot]
+            lines += ["\tglobal_load_dwordx4 v[%d:%d], v[60:61], off" % (r, r + 3) for r in slot]
+        lines += ["\tv_mfma_f32_16x16x32_f16 v[100:103], v[0:3], v[50:53], v[100:103]", "\ts_waitcnt vmcnt(0)", "\ts_endpgm"]
+        return "0000000000001000 <%s>:\n%s\n" % (name, "\n".join(lines))
+
+    monkeypatch.setattr(_isa, "_isa_check_wide", lambda *a: {})
+    monkeypatch.setattr(_isa, "_isa_check_lat", lambda *a: {})
+    monkeypatch.setattr(_isa.os.path, "exists", lambda p: True)
+    good = list(range(0, 32, 4))
+
+    def run(txt):
+        monkeypatch.setattr(_isa, "_disassemble", lambda d, o, oname: txt if oname == "conv_halo_g0.o" else "")
+        return _isa.isa_check("nowhere")
+
+    assert run(text(good)) == {name: 4}
+    with pytest.raises(RuntimeError, match="overlap"):
+        run(text([0, 4, 8, 12, 16, 20, 26, 24]))
+    with pytest.raises(RuntimeError, match="no MFMA takes v\\[28:31\\]"):
+        run(text(good, operand=lambda r: 24 if r == 28 else r))
