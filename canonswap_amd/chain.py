@@ -45,7 +45,7 @@ from __future__ import annotations
 import torch
 
 from . import tail
-from .engine import Engine
+from .engine import Engine, u8_images
 
 
 class _StagedChain:
@@ -273,9 +273,7 @@ class FrameChain(_StagedChain):
     def _no_faces(self, frames_ori, frame_index, out):
         """A batch of frames in which nobody was found: nothing to generate.  The frames come back as they are, copied into `out` if given
         (cs_paste_back_faces with B = 0)."""
-        fr = torch.as_tensor(frames_ori)
-        if fr.dtype != torch.uint8 or fr.dim() != 4 or fr.shape[3] != 3 or fr.shape[0] < 1:
-            raise ValueError("expected FxHoxWox3 uint8 original frames, F >= 1")
+        fr = u8_images(frames_ori, True, 1, "frames_ori", "FrameChain")
         tail.frame_index_of(frame_index, 0, fr.shape[0])
         if out is None:
             return {"frames": fr.to(self.e.device)}
@@ -325,10 +323,7 @@ class AnimateChain(_StagedChain):
         Everything on the device, on the caller's stream.  -> {"I_can" (512,512,3) u8, "swap_can" (1,3,512,512), "x_swap", "x_s" (1,21,3)}"""
         e = self.e
         self.drop_prefetches()                                                       # staged key-points were formed with the old kp_swap / pose
-        ori = torch.as_tensor(img_ori)
-        if ori.dtype != torch.uint8 or ori.dim() != 3 or ori.shape[2] != 3:
-            raise ValueError("img_ori: expected ONE HoxWox3 uint8 image")
-        ori = ori.to(e.device).contiguous()
+        ori = u8_images(img_ori, False, 1, "img_ori", "AnimateChain.set_source").to(e.device).contiguous()
         self._mask_or_logits(mask, logits, "AnimateChain.set_source", parse)
         if parse:
             c1 = torch.as_tensor(crop_u8)
@@ -384,9 +379,7 @@ class AnimateChain(_StagedChain):
             if not isinstance(t, torch.Tensor) or t.dtype != dt or tuple(t.shape) != shape:
                 raise ValueError(f"load_source_state: {k} must be a {dt} tensor of shape {shape}")
             src[k] = t.to(e.device).contiguous()
-        ori, mo = d["img_ori"], d["mask_ori"]
-        if not isinstance(ori, torch.Tensor) or ori.dtype != torch.uint8 or ori.dim() != 3 or ori.shape[2] != 3:
-            raise ValueError("load_source_state: img_ori must be an HoxWox3 uint8 tensor")
+        ori, mo = u8_images(d["img_ori"], False, 1, "img_ori", "load_source_state"), d["mask_ori"]
         if not isinstance(mo, torch.Tensor) or mo.dtype != torch.float32 or tuple(mo.shape) != tuple(ori.shape[:2]):
             raise ValueError("load_source_state: mask_ori must be an fp32 tensor of the size of img_ori")
         src["img_ori"], src["mask_ori"] = ori.to(e.device).contiguous(), mo.to(e.device).contiguous()

@@ -131,13 +131,21 @@ extern "C" int cs_paste_back_shared(cs_engine* e, int B, const uint8_t* crops, i
     return e->run(1, st, [&] { return launch_paste_shared(crops, Hc, Wc, mask_ori, M_c2o, img_ori, out, B, Ho, Wo, st); }, "paste_back_shared");
 }
 
+// The crop size of every crop entry point: a multiple of 4 (a thread owns four pixels of a row); the fp32 staging I_out exists for 256 and 512.
+// Sets the error and returns nonzero otherwise.
+static int check_dsize(const char* who, int dsize, const void* I_out)
+{
+    if (dsize < 4 || dsize % 4 || dsize > 16384) { cs_set_error("%s: dsize %d (a multiple of 4 from 4 to 16384)", who, dsize); return -1; }
+    if (I_out && dsize != 256 && dsize != 512) { cs_set_error("%s: I_out goes with dsize 256 or 512 (got %d)", who, dsize); return -1; }
+    return 0;
+}
+
 // ---- the crop in front of both chains (crop.py:429-455 per frame, cropper.py:196-209)
 extern "C" int cs_crop_frames(cs_engine* e, int B, const uint8_t* frames, int Ho, int Wo, const double* M_o2c, int dsize, uint8_t* crops, float* I_out,
                               void* stream)
 {
     if (!e || !frames || !M_o2c || !crops || B < 1 || Ho < 1 || Wo < 1) { cs_set_error("cs_crop_frames: bad arguments"); return -1; }
-    if (dsize < 4 || dsize % 4 || dsize > 16384) { cs_set_error("cs_crop_frames: dsize %d (a multiple of 4 from 4 to 16384)", dsize); return -1; }
-    if (I_out && dsize != 256 && dsize != 512) { cs_set_error("cs_crop_frames: I_out goes with dsize 256 or 512 (got %d)", dsize); return -1; }
+    if (check_dsize("cs_crop_frames", dsize, I_out)) return -1;
     DevGuard guard(e->dev);
     hipStream_t st = (hipStream_t)stream;
     return e->run(1, st, [&] { return launch_crop_batch(frames, Ho, Wo, M_o2c, nullptr, dsize, crops, I_out, B, st); }, "crop_frames");
@@ -168,8 +176,7 @@ extern "C" int cs_crop_faces(cs_engine* e, int B, int F, const uint8_t* frames, 
         cs_set_error("cs_crop_faces: bad arguments (B = %d faces, F = %d frames)", B, F);
         return -1;
     }
-    if (dsize < 4 || dsize % 4 || dsize > 16384) { cs_set_error("cs_crop_faces: dsize %d (a multiple of 4 from 4 to 16384)", dsize); return -1; }
-    if (I_out && dsize != 256 && dsize != 512) { cs_set_error("cs_crop_faces: I_out goes with dsize 256 or 512 (got %d)", dsize); return -1; }
+    if (check_dsize("cs_crop_faces", dsize, I_out)) return -1;
     if (check_frame_index("cs_crop_faces", frame_index, B, F)) return -1;
     DevGuard guard(e->dev);
     hipStream_t st = (hipStream_t)stream;
@@ -302,7 +309,7 @@ static int check_lmk_args(const char* who, int B, int F, int Ho, int Wo, const i
                           float scale, float vy_ratio, int status_mark)
 {
     if (B < 1 || F < 1 || Ho < 1 || Wo < 1) { cs_set_error("%s: B = %d, F = %d, Ho = %d, Wo = %d (each at least 1)", who, B, F, Ho, Wo); return -1; }
-    if (dsize < 4 || dsize % 4 || dsize > 16384) { cs_set_error("%s: dsize %d (a multiple of 4 from 4 to 16384)", who, dsize); return -1; }
+    if (check_dsize(who, dsize, nullptr)) return -1;
     if (N < 1 || N > (1 << 20)) { cs_set_error("%s: N = %d landmarks outside [1, 2^20]", who, N); return -1; }
     if (layout.n_eye < 1 || layout.n_eye > 4) { cs_set_error("%s: layout.n_eye %d outside [1, 4]", who, layout.n_eye); return -1; }
     for (int i = 0; i < layout.n_eye; ++i)
@@ -351,7 +358,7 @@ extern "C" int cs_lmk_decode(cs_engine* e, int B, const float* out_pts, int Np, 
         return -1;
     }
     if (B < 1 || Np < 1 || Np > (1 << 20)) { cs_set_error("cs_lmk_decode: B = %d, Np = %d (B at least 1, Np in [1, 2^20])", B, Np); return -1; }
-    if (dsize < 4 || dsize % 4 || dsize > 16384) { cs_set_error("cs_lmk_decode: dsize %d (a multiple of 4 from 4 to 16384)", dsize); return -1; }
+    if (check_dsize("cs_lmk_decode", dsize, nullptr)) return -1;
     DevGuard guard(e->dev);
     hipStream_t st = (hipStream_t)stream;
     return e->run(1, st, [&] { return launch_lmk_decode(out_pts, Np, M, dsize, status, lmk, B, st); }, "lmk_decode");
@@ -464,7 +471,7 @@ extern "C" int cs_crop_lmk(cs_engine* e, int B, int F, const uint8_t* frames, in
         return -1;
     }
     if (check_lmk_args("cs_crop_lmk", B, F, Ho, Wo, frame_index, N, *layout, dsize, scale, vy_ratio, status_mark)) return -1;
-    if (I_out && dsize != 256 && dsize != 512) { cs_set_error("cs_crop_lmk: I_out goes with dsize 256 or 512 (got %d)", dsize); return -1; }
+    if (check_dsize("cs_crop_lmk", dsize, I_out)) return -1;      // behind the other checks, as before: dsize itself has passed
     DevGuard guard(e->dev);
     hipStream_t st = (hipStream_t)stream;
     return e->run(1, st, [&] {

@@ -244,7 +244,7 @@ __global__ void __launch_bounds__(256) paste_kernel(const unsigned char* __restr
                                                     const float* __restrict__ mask_ori, int Hc, int Wc, AffineInv A,
                                                     const unsigned char* ori, unsigned char* out, int Ho, int Wo)
 {
-    // ori and out may be ONE buffer (launch_paste_faces' fallback pastes face after face into the frame): a thread reads and writes its own pixel only
+    // ori and out may be ONE buffer: a thread reads and writes its own pixel only
     const long i = (long)blockIdx.x * 256 + threadIdx.x;
     if (i >= (long)Ho * Wo) return;
     const int y = (int)(i / Wo), x = (int)(i % Wo);
@@ -262,11 +262,50 @@ __global__ void __launch_bounds__(256) paste_kernel(const unsigned char* __restr
 }
 
 // ---- the paste-back step of B frames in one launch (can_swap_pipeline_e2e.py:273-283 per frame: SoftErosion mask -> prepare_paste_back ->
-// paste_back).  blockIdx.y = frame; a thread owns four consecutive pixels of a row = 12 bytes = three dwords of the original and of the
-// result (the single-frame kernel above moves them byte by byte).  A pixel whose source position lies outside the crop has mask 0 and
-// warped value 0: v = 0 * 0 + (1 - 0) * ori = ori exactly, so it is copied - most of a 1080p frame.  Same arithmetic per pixel as
-// paste_kernel with mask_crop (tests/test_gpu_chain.py holds the two bit-equal).
+// paste_back).  blockIdx.y = frame; a thread owns PX consecutive pixels of a row, loads them once and stores them once.  PX = 4: 12 bytes = three
+// dwords of the original and of the result (the single-frame kernel above moves them byte by byte); PX = 1: one pixel, byte by byte - widths that are
+// no multiple of 4 and buffers off a 4-byte boundary.  A pixel whose source position lies outside the crop has mask 0 and warped value 0:
+// v = 0 * 0 + (1 - 0) * ori = ori exactly, so it is copied - most of a 1080p frame - and paste_kernel, which blends it, leaves the same byte.
+// Same arithmetic per pixel as paste_kernel with mask_crop (tests/test_gpu_chain.py holds the two bit-equal).
 struct AffineBatch { AffineInv a[64]; };      // 3 KB of kernel arguments: no device-side staging buffer, nothing to race with
+
+// A thread's group q of PX pixels of a frame as dwords, loaded and stored once: PX = 8: 24 bytes, 8-byte aligned (three 8-byte accesses); PX = 4:
+// three dwords; PX = 1: three single bytes, in the low bytes of w[0].  The launchers choose PX by the row width and the buffers' alignment.
+template <int PX> constexpr int PX_WORDS = (PX * 3 + 3) / 4;
+
+template <int PX>
+__device__ __forceinline__ void load_px(const unsigned char* frame, long q, unsigned (&w)[PX_WORDS<PX>])
+{
+    if constexpr (PX == 8) {
+#pragma unroll
+        for (int j = 0; j < 3; ++j) {
+            const uint2 v = ((const uint2*)frame)[q * 3 + j];
+            w[2 * j] = v.x; w[2 * j + 1] = v.y;
+        }
+    } else if constexpr (PX == 1) {
+        const unsigned char* in = frame + q * 3;
+        w[0] = in[0] | in[1] << 8 | in[2] << 16;
+    } else {
+#pragma unroll
+        for (int j = 0; j < PX_WORDS<PX>; ++j) w[j] = ((const unsigned*)frame)[q * PX_WORDS<PX> + j];
+    }
+}
+
+template <int PX>
+__device__ __forceinline__ void store_px(unsigned char* frame, long q, const unsigned (&w)[PX_WORDS<PX>])
+{
+    if constexpr (PX == 8) {
+        uint2* out = (uint2*)frame + q * 3;
+        out[0] = make_uint2(w[0], w[1]); out[1] = make_uint2(w[2], w[3]); out[2] = make_uint2(w[4], w[5]);
+    } else if constexpr (PX == 1) {
+        unsigned char* out = frame + q * 3;
+        out[0] = (unsigned char)w[0]; out[1] = (unsigned char)(w[0] >> 8); out[2] = (unsigned char)(w[0] >> 16);
+    } else {
+        unsigned* out = (unsigned*)frame + q * PX_WORDS<PX>;
+#pragma unroll
+        for (int j = 0; j < PX_WORDS<PX>; ++j) out[j] = w[j];
+    }
+}
 
 // one face into a thread's PX pixels (xb .. xb + PX - 1, y), px their 3 PX bytes: the pixel is truncated to 8 bits, as paste_back's astype(np.uint8)
 template <int PX>
@@ -285,38 +324,37 @@ __device__ __forceinline__ void paste_px(const unsigned char* __restrict__ crop,
     }
 }
 
+template <int PX>
 __global__ void __launch_bounds__(256) paste_batch_kernel(const unsigned char* __restrict__ crops, const float* __restrict__ masks, int Hc, int Wc,
                                                           AffineBatch AB, const unsigned char* __restrict__ oris,
                                                           unsigned char* __restrict__ outs, int Ho, int Wo)
 {
     const int n = blockIdx.y;
-    const long q = (long)blockIdx.x * 256 + threadIdx.x;          // group of four pixels
+    const long q = (long)blockIdx.x * 256 + threadIdx.x;          // group of PX pixels
     const long P = (long)Ho * Wo;
-    if (q * 4 >= P) return;
+    if (q * PX >= P) return;
     const AffineInv& A = AB.a[n];
     const unsigned char* crop = crops + (long)n * Hc * Wc * 3;
     const float* mask_crop = masks + (long)n * Hc * Wc;
-    const unsigned* ori = (const unsigned*)(oris + (long)n * P * 3) + q * 3;
-    unsigned* out = (unsigned*)(outs + (long)n * P * 3) + q * 3;
-    unsigned wv[3] = {ori[0], ori[1], ori[2]};
-    unsigned char* px = (unsigned char*)wv;
-    const int y = (int)((q * 4) / Wo), xb = (int)((q * 4) % Wo);
-    paste_px<4>(crop, mask_crop, Hc, Wc, A, xb, y, px);
-    out[0] = wv[0]; out[1] = wv[1]; out[2] = wv[2];
+    unsigned wv[PX_WORDS<PX>];
+    load_px<PX>(oris + (long)n * P * 3, q, wv);
+    const int y = (int)((q * PX) / Wo), xb = (int)((q * PX) % Wo);
+    paste_px<PX>(crop, mask_crop, Hc, Wc, A, xb, y, (unsigned char*)wv);
+    store_px<PX>(outs + (long)n * P * 3, q, wv);
 }
 
 // ---- several faces per frame: prepare_paste_back + paste_back (crop.py:515-529) applied once per face of a frame, in the faces' order, each on
-// the result of the one before, in ONE pass over the frame.  blockIdx.y = frame of the launch; a thread owns the four pixels of
-// paste_batch_kernel, loads their three dwords once, walks its frame's faces (paste_px<4> per face: paste_batch_kernel's arithmetic, the pixel
-// truncated to 8 bits after every face, as sequential paste_back calls leave it) and stores the three dwords once: the frames between two faces
+// the result of the one before, in ONE pass over the frame.  blockIdx.y = frame of the launch; a thread owns the PX pixels of
+// paste_batch_kernel, loads them once, walks its frame's faces (paste_faces_px: paste_batch_kernel's arithmetic per face, the pixel
+// truncated to 8 bits after every face, as sequential paste_back calls leave it) and stores them once: the frames between two faces
 // never exist in memory.  A frame without a face is copied (in place: left alone).  Matrices, boxes and face ranges are kernel arguments:
 // FACES_PER_LAUNCH = 48 faces and at most as many frames per launch, 48 x (48 B matrix + 16 B box) + 49 x 4 B ranges = 3272 B beside ~70 B of
 // scalars, under HIP's 4 KB argument block with the room AffineBatch leaves (64 matrices alone are 3 KB; with box and range 64 faces would be 4356 B).
 // box: a conservative integer rectangle (x0, y0, x1, y1, inclusive, clipped to the frame; x0 > x1: empty) that holds every pixel of the frame
-// for which !tap_at(...).outside, so a group of four pixels outside it skips the face before any double-precision coordinate is formed - most of
+// for which !tap_at(...).outside, so a group of pixels outside it skips the face before any double-precision coordinate is formed - most of
 // a 1080p frame, for every face.  It prunes only: inside it every pixel still decides by tap_at (face_box, affine_inv.h, for why it cannot cut a pixel).
 // oris / outs may be ONE buffer, and a launch may continue a frame that an earlier launch began (resume: frame 0 of this launch is read from
-// outs): a thread reads and writes its own twelve bytes only, so neither is a race.  crops and masks must not overlap outs.
+// outs): a thread reads and writes its own bytes only, so neither is a race.  crops and masks must not overlap outs.
 constexpr int FACES_PER_LAUNCH = 48;
 struct FaceBatch {
     AffineInv a[FACES_PER_LAUNCH];
@@ -325,24 +363,35 @@ struct FaceBatch {
 };
 static_assert(sizeof(FaceBatch) <= 3328, "FaceBatch and the scalars beside it must fit HIP's 4 KB of kernel arguments");
 
+// The walk over n faces of a frame, in order, into a thread's PX pixels: the box test, then paste_px.  crops / masks / a / box: face 0 of the
+// walk; a and box are read where they lie, paste_faces_kernel's kernel arguments (scalar loads).
+template <int PX>
+__device__ __forceinline__ void paste_faces_px(const unsigned char* __restrict__ crops, const float* __restrict__ masks, int Hc, int Wc,
+                                               const AffineInv* a, const int (*box)[4], int n, int xb, int y, unsigned char* px)
+{
+    for (int i = 0; i < n; ++i) {
+        if (y < box[i][1] || y > box[i][3] || xb + PX - 1 < box[i][0] || xb > box[i][2]) continue;
+        paste_px<PX>(crops + (long)i * Hc * Wc * 3, masks + (long)i * Hc * Wc, Hc, Wc, a[i], xb, y, px);
+    }
+}
+
+template <int PX>
 __global__ void __launch_bounds__(256) paste_faces_kernel(const unsigned char* __restrict__ crops, const float* __restrict__ masks, int Hc, int Wc,
                                                           FaceBatch FB, const unsigned char* oris, unsigned char* outs, int Ho, int Wo, int resume)
 {
     const int j = blockIdx.y;
-    const long q = (long)blockIdx.x * 256 + threadIdx.x;          // group of four pixels
+    const long q = (long)blockIdx.x * 256 + threadIdx.x;          // group of PX pixels
     const long P = (long)Ho * Wo;
-    if (q * 4 >= P) return;
+    if (q * PX >= P) return;
     const int i0 = FB.first[j], i1 = FB.first[j + 1];
-    const unsigned* in = (const unsigned*)((j == 0 && resume ? outs : oris) + (long)j * P * 3) + q * 3;
-    unsigned* out = (unsigned*)(outs + (long)j * P * 3) + q * 3;
+    const unsigned char* in = (j == 0 && resume ? outs : oris) + (long)j * P * 3;
+    unsigned char* out = outs + (long)j * P * 3;
     if (i0 == i1 && in == out) return;                             // in place, no face: nothing to do
-    unsigned wv[3] = {in[0], in[1], in[2]};
-    const int y = (int)((q * 4) / Wo), xb = (int)((q * 4) % Wo);
-    for (int i = i0; i < i1; ++i) {
-        if (y < FB.box[i][1] || y > FB.box[i][3] || xb + 3 < FB.box[i][0] || xb > FB.box[i][2]) continue;
-        paste_px<4>(crops + (long)i * Hc * Wc * 3, masks + (long)i * Hc * Wc, Hc, Wc, FB.a[i], xb, y, (unsigned char*)wv);
-    }
-    out[0] = wv[0]; out[1] = wv[1]; out[2] = wv[2];
+    unsigned wv[PX_WORDS<PX>];
+    load_px<PX>(in, q, wv);
+    const int y = (int)((q * PX) / Wo), xb = (int)((q * PX) % Wo);
+    paste_faces_px<PX>(crops + (long)i0 * Hc * Wc * 3, masks + (long)i0 * Hc * Wc, Hc, Wc, FB.a + i0, FB.box + i0, i1 - i0, xb, y, (unsigned char*)wv);
+    store_px<PX>(out, q, wv);
 }
 
 // ---- paste-back of B generated frames into ONE image under ONE mask and ONE matrix (can_swap_pipeline_v2i.py:317-321: every frame is
@@ -351,20 +400,8 @@ __global__ void __launch_bounds__(256) paste_faces_kernel(const unsigned char* _
 // as fx, fy), the mask value, the image's pixels - and the thread then walks its group of frames (blockIdx.y), reading that frame's four crop
 // taps only.  A pixel with mask 0 (v = 0 * res + 1 * ori = ori) or with all four taps outside the crop (res = 0: v = m * 0 + (1 - m) * ori,
 // the same for every frame) never touches the crop; most of a 1080p frame is such pixels and is stored from registers, frame after frame.
-// PX pixels of a row per thread: 8 (24 bytes, 8-byte aligned: one 16-byte and one 8-byte store) or 4 (12 bytes, as paste_batch_kernel).
-template <int PX>
-__device__ __forceinline__ void store_px(unsigned char* frame, long q, const unsigned (&w)[PX * 3 / 4])
-{
-    if constexpr (PX == 8) {
-        uint2* out = (uint2*)frame + q * 3;
-        out[0] = make_uint2(w[0], w[1]); out[1] = make_uint2(w[2], w[3]); out[2] = make_uint2(w[4], w[5]);
-    } else {
-        unsigned* out = (unsigned*)frame + q * (PX * 3 / 4);
-#pragma unroll
-        for (int j = 0; j < PX * 3 / 4; ++j) out[j] = w[j];
-    }
-}
-
+// PX pixels of a row per thread: 8 (24 bytes, 8-byte aligned: one 16-byte and one 8-byte store) or 4 (12 bytes, as paste_batch_kernel); it
+// loads the image beside the mask itself and stores through store_px.
 template <int PX>
 __global__ void __launch_bounds__(256) paste_shared_kernel(const unsigned char* __restrict__ crops, int Hc, int Wc, AffineInv A,
                                                            const float* __restrict__ mask_ori, const unsigned char* __restrict__ ori,
@@ -527,8 +564,9 @@ int launch_resize_half(const float* in, float* out, long planes, int H, int W, h
     return 0;
 }
 
-// B frames into one image: eight pixels per thread where rows and buffers allow 8-byte accesses, four pixels (dwords) otherwise; odd widths /
-// unaligned buffers: the single-frame kernel per frame (same arithmetic).  The frame groups are grid rows, so B is not bound by a chunk size.
+// B frames into one image: eight pixels per thread where rows and buffers allow 8-byte accesses, four pixels (dwords) otherwise; widths that are
+// no multiple of 4 / buffers off a 4-byte boundary: the single-frame kernel per frame (same arithmetic; the kernel's packed-dword bookkeeping has
+// no byte form).  The frame groups are grid rows, so B is not bound by a chunk size.
 int launch_paste_shared(const unsigned char* crops, int Hc, int Wc, const float* mask_ori, const double M[6], const unsigned char* ori,
                         unsigned char* outs, int B, int Ho, int Wo, hipStream_t st)
 {
@@ -551,20 +589,25 @@ int launch_paste_shared(const unsigned char* crops, int Hc, int Wc, const float*
     return 0;
 }
 
+// Whether the batched paste kernels may move a thread's four pixels as three dwords (PX = 4): rows of a multiple of four pixels in buffers on a
+// 4-byte boundary.  Otherwise PX = 1: one pixel per thread, byte by byte, the same values.
+static bool wide_px(const unsigned char* oris, const unsigned char* outs, int Wo)
+{
+    return Wo % 4 == 0 && ((uintptr_t)oris & 3) == 0 && ((uintptr_t)outs & 3) == 0;
+}
+
 int launch_paste_batch(const unsigned char* crops, const float* masks, int Hc, int Wc, const double* M, const unsigned char* oris,
                        unsigned char* outs, int B, int Ho, int Wo, hipStream_t st)
 {
     const long P = (long)Ho * Wo;
-    if (Wo % 4 != 0 || ((uintptr_t)oris & 3) != 0 || ((uintptr_t)outs & 3) != 0) {
-        // odd widths / unaligned buffers: the single-frame kernel per frame (same arithmetic)
-        for (int i = 0; i < B; ++i)
-            if (launch_paste(crops + (long)i * Hc * Wc * 3, masks + (long)i * Hc * Wc, nullptr, Hc, Wc, M + (long)i * 6, oris + (long)i * P * 3,
-                             outs + (long)i * P * 3, Ho, Wo, st)) return -1;
-        return 0;
-    }
+    const bool wide = wide_px(oris, outs, Wo);
+    const dim3 grid((unsigned)(((wide ? P / 4 : P) + 255) / 256));
     return for_affine_batches(M, B, [&](int b0, int nb, const AffineBatch& AB) {
-        hipLaunchKernelGGL(paste_batch_kernel, dim3((unsigned)((P / 4 + 255) / 256), nb), dim3(256), 0, st, crops + (long)b0 * Hc * Wc * 3,
-                           masks + (long)b0 * Hc * Wc, Hc, Wc, AB, oris + (long)b0 * P * 3, outs + (long)b0 * P * 3, Ho, Wo);
+        const unsigned char *c = crops + (long)b0 * Hc * Wc * 3, *from = oris + (long)b0 * P * 3;
+        const float* m = masks + (long)b0 * Hc * Wc;
+        unsigned char* to = outs + (long)b0 * P * 3;
+        if (wide) hipLaunchKernelGGL(paste_batch_kernel<4>, dim3(grid.x, nb), dim3(256), 0, st, c, m, Hc, Wc, AB, from, to, Ho, Wo);
+        else hipLaunchKernelGGL(paste_batch_kernel<1>, dim3(grid.x, nb), dim3(256), 0, st, c, m, Hc, Wc, AB, from, to, Ho, Wo);
         LAUNCH_CHECK("paste_batch");
         return 0;
     });
@@ -572,26 +615,13 @@ int launch_paste_batch(const unsigned char* crops, const float* masks, int Hc, i
 
 // B faces into F frames, face b into frame frame_index[b] (non-decreasing, in [0, F): the caller checks), in the faces' order.  A launch takes up
 // to FACES_PER_LAUNCH faces and as many frames; a frame whose faces do not fit is finished by the next launch, which reads what this one wrote
-// (stream order).  outs == oris pastes in place.  Odd widths / unaligned buffers: the single-frame kernel per face, in order, the first face of a
-// frame from oris into outs, the others in place (the same arithmetic); there a frame without a face is copied by the runtime.
+// (stream order).  outs == oris pastes in place.  The same launches at PX = 1 where wide_px refuses the dwords.
 int launch_paste_faces(const unsigned char* crops, const float* masks, int Hc, int Wc, const double* M, const int* frame_index,
                        const unsigned char* oris, unsigned char* outs, int B, int F, int Ho, int Wo, hipStream_t st)
 {
     const long P = (long)Ho * Wo, C = (long)Hc * Wc;
-    if (Wo % 4 != 0 || ((uintptr_t)oris & 3) != 0 || ((uintptr_t)outs & 3) != 0) {
-        int b = 0;
-        for (int f = 0; f < F; ++f) {
-            const unsigned char* from = oris + (long)f * P * 3;
-            unsigned char* to = outs + (long)f * P * 3;
-            if ((b == B || frame_index[b] != f) && from != to) {
-                hipError_t r = hipMemcpyAsync(to, from, (size_t)P * 3, hipMemcpyDeviceToDevice, st);
-                if (r != hipSuccess) { cs_set_error("paste_faces copy: %s", hipGetErrorString(r)); return -1; }
-            }
-            for (; b < B && frame_index[b] == f; ++b, from = to)
-                if (launch_paste(crops + b * C * 3, masks + b * C, nullptr, Hc, Wc, M + (long)b * 6, from, to, Ho, Wo, st)) return -1;
-        }
-        return 0;
-    }
+    const bool wide = wide_px(oris, outs, Wo);
+    const unsigned blocks = (unsigned)(((wide ? P / 4 : P) + 255) / 256);
     constexpr int N = FACES_PER_LAUNCH;
     int b = 0, f = 0, resume = 0;
     while (f < F) {
@@ -611,8 +641,10 @@ int launch_paste_faces(const unsigned char* crops, const float* masks, int Hc, i
             split = take < cnt;
         }
         if (nb || oris != outs) {
-            hipLaunchKernelGGL(paste_faces_kernel, dim3((unsigned)((P / 4 + 255) / 256), nf), dim3(256), 0, st, crops + b0 * C * 3, masks + b0 * C, Hc,
-                               Wc, FB, oris + (long)f0 * P * 3, outs + (long)f0 * P * 3, Ho, Wo, resume);
+            const unsigned char* from = oris + (long)f0 * P * 3;
+            unsigned char* to = outs + (long)f0 * P * 3;
+            if (wide) hipLaunchKernelGGL(paste_faces_kernel<4>, dim3(blocks, nf), dim3(256), 0, st, crops + b0 * C * 3, masks + b0 * C, Hc, Wc, FB, from, to, Ho, Wo, resume);
+            else hipLaunchKernelGGL(paste_faces_kernel<1>, dim3(blocks, nf), dim3(256), 0, st, crops + b0 * C * 3, masks + b0 * C, Hc, Wc, FB, from, to, Ho, Wo, resume);
             LAUNCH_CHECK("paste_faces");
         }
         f = f0 + nf - split;                                          // a split frame is frame 0 of the next launch, read from outs
@@ -628,9 +660,9 @@ int launch_paste_faces(const unsigned char* crops, const float* masks, int Hc, i
 // once per workgroup; after the barrier every thread walks the chunk as paste_faces_kernel walks its range.  Nothing is staged in device
 // memory, so two calls on two streams share nothing.  A face with status != 0 gets the empty box and is skipped like a face that does not
 // reach the frame.  The faces come from device memory, so a frame's faces never have to be split over launches: only the frames' ranges are
-// kernel arguments, DEV_FRAMES_PER_LAUNCH of them (absolute face numbers).  PX = 4: a thread's four pixels as three dwords, as above; PX = 1: one
-// pixel, byte by byte - odd widths and buffers off a 4-byte boundary, where the host form launches paste_kernel per face: the same values, since
-// for a pixel outside the crop paste_kernel's blend is 0 * 0 + 1 * ori = ori exactly.
+// kernel arguments, DEV_FRAMES_PER_LAUNCH of them (absolute face numbers).  PX as in the host form: 4, or 1 where wide_px refuses the dwords.
+// The pixel group and the face walk are written out here, not taken from load_px / store_px / paste_faces_px: through them this kernel measured
+// 1.3 % (PX = 4) to 10 % (PX = 1) slower than this text on the same inputs.
 constexpr int DEV_FRAMES_PER_LAUNCH = 48, DEV_FACE_CHUNK = 16;
 struct FrameFaces { int first[DEV_FRAMES_PER_LAUNCH + 1]; };      // frame j of the launch owns faces first[j] .. first[j + 1] - 1
 
@@ -690,7 +722,7 @@ int launch_paste_faces_dev(const unsigned char* crops, const float* masks, int H
                            const unsigned char* oris, unsigned char* outs, int B, int F, int Ho, int Wo, hipStream_t st)
 {
     const long P = (long)Ho * Wo;
-    const bool wide = Wo % 4 == 0 && ((uintptr_t)oris & 3) == 0 && ((uintptr_t)outs & 3) == 0;
+    const bool wide = wide_px(oris, outs, Wo);
     const unsigned blocks = (unsigned)(((wide ? P / 4 : P) + 255) / 256);
     int b = 0;
     for (int f0 = 0; f0 < F; f0 += DEV_FRAMES_PER_LAUNCH) {
@@ -719,17 +751,12 @@ int launch_paste_faces_dev(const unsigned char* crops, const float* masks, int H
 // made wide is the store: a thread owns four consecutive crop pixels of a row = 12 bytes = three dwords, a wave's stores of one row are contiguous.
 // STAGE != 0: the thread owns a 4 x 2 block and also writes what prepare_crops_kernel would make of it, from its registers - the crop is not
 // read back: STAGE 2 (dsize 512): the two 2 x 2 means (a + b + c + d + 2) >> 2, / 255, as one float2 per channel of the NCHW fp32 input;
-// STAGE 1 (dsize 256): / 255 only, one float4 per row and channel.
-__device__ __forceinline__ void crop_pixel(const unsigned char* __restrict__ frame, int Ho, int Wo, const AffineInv& A, int x, int y, int (&res)[3])
-{
-    const Tap t = tap_at(A, x, y, Ho, Wo);
-    res[0] = res[1] = res[2] = 0;                                    // all four taps outside the frame: the border value
-    if (!t.outside) tap_u8x3(frame, Wo, t, res);
-}
-
+// STAGE 1 (dsize 256): / 255 only, one float4 per row and channel.  WIDE: crops on a 4-byte and I on a 16-byte boundary; otherwise the same
+// values byte by byte and float by float (crop_store<STAGE, false>).  A template parameter, not crop_lmk_kernel's launch-uniform flag: with both
+// stores in one body STAGE 1 takes 72 VGPRs, seven waves per SIMD, where the wide store alone takes 48 and runs eight.
 struct CropSource { int frame[64]; };         // crop n of a launch is cut from frame[n] of `frames` (several faces of one frame: the same entry)
 
-template <int STAGE>
+template <int STAGE, bool WIDE>
 __global__ void __launch_bounds__(256) crop_batch_kernel(const unsigned char* __restrict__ frames, int Ho, int Wo, AffineBatch AB, CropSource CS,
                                                          int dsize, unsigned char* __restrict__ crops, float* __restrict__ I)
 {
@@ -740,39 +767,30 @@ __global__ void __launch_bounds__(256) crop_batch_kernel(const unsigned char* __
     if (g >= gw * (dsize / ROWS)) return;
     const int yb = (g / gw) * ROWS, xb = (g % gw) * 4;
     const AffineInv& A = AB.a[n];
-    const unsigned char* frame = frames + (long)CS.frame[n] * Ho * Wo * 3;
     int v[ROWS][4][3];
-#pragma unroll
-    for (int r = 0; r < ROWS; ++r)
-#pragma unroll
-        for (int k = 0; k < 4; ++k) crop_pixel(frame, Ho, Wo, A, xb + k, yb + r, v[r][k]);
-    crop_store<STAGE, true>(v, n, yb, xb, dsize, crops, I);          // warp_taps.h: the crop's dwords and, with STAGE, the staged input
+    crop_read<ROWS>(frames + (long)CS.frame[n] * Ho * Wo * 3, Ho, Wo, A, xb, yb, v);      // warp_taps.h, as crop_store
+    crop_store<STAGE, WIDE>(v, n, yb, xb, dsize, crops, I);          // the crop's bytes and, with STAGE, the staged input
 }
 
 // dsize: a multiple of 4 (the caller checks); I != nullptr: dsize 256 or 512.  B is chunked by the 64 matrices of a launch, so it is not bound
 // by anything.  frame_index: crop b is cut from frame frame_index[b] (cs_crop_faces); nullptr: from frame b (cs_crop_frames).  Buffers that do
-// not allow the wide stores (a crop buffer off a 4-byte, an I off a 16-byte boundary): the single-frame kernel per
-// crop and prepare_crops_kernel behind it - the same arithmetic.
+// not allow the wide stores (a crop buffer off a 4-byte, an I off a 16-byte boundary): the same launches, storing narrow.
 int launch_crop_batch(const unsigned char* frames, int Ho, int Wo, const double* M, const int* frame_index, int dsize, unsigned char* crops, float* I,
                       int B, hipStream_t st)
 {
-    const long P = (long)Ho * Wo * 3, C = (long)dsize * dsize * 3;
-    if (((uintptr_t)crops & 3) != 0 || ((uintptr_t)I & 15) != 0) {
-        for (int i = 0; i < B; ++i)
-            if (launch_paste(frames + (frame_index ? frame_index[i] : i) * P, nullptr, nullptr, Ho, Wo, M + (long)i * 6, nullptr, crops + i * C, dsize,
-                             dsize, st)) return -1;
-        return I ? launch_prepare_crops(crops, I, B, dsize, dsize, dsize / 256, st) : 0;
-    }
+    const long C = (long)dsize * dsize * 3;
+    const bool wide = ((uintptr_t)crops & 3) == 0 && ((uintptr_t)I & 15) == 0;      // rows are multiples of four pixels: aligned with the base
     const int stage = I ? dsize / 256 : 0, rows = stage ? 2 : 1;
     const dim3 grid((unsigned)(((long)(dsize / 4) * (dsize / rows) + 255) / 256));
+    const auto kernel = stage == 2 ? (wide ? crop_batch_kernel<2, true> : crop_batch_kernel<2, false>)
+                      : stage == 1 ? (wide ? crop_batch_kernel<1, true> : crop_batch_kernel<1, false>)
+                                   : (wide ? crop_batch_kernel<0, true> : crop_batch_kernel<0, false>);
     return for_affine_batches(M, B, [&](int b0, int nb, const AffineBatch& AB) {
         CropSource CS;
         for (int i = 0; i < 64; ++i) CS.frame[i] = i < nb ? (frame_index ? frame_index[b0 + i] : b0 + i) : 0;
         unsigned char* c = crops + b0 * C;
         float* Ib = I ? I + (long)b0 * 3 * 256 * 256 : nullptr;
-        if (stage == 2) hipLaunchKernelGGL(crop_batch_kernel<2>, dim3(grid.x, nb), dim3(256), 0, st, frames, Ho, Wo, AB, CS, dsize, c, Ib);
-        else if (stage == 1) hipLaunchKernelGGL(crop_batch_kernel<1>, dim3(grid.x, nb), dim3(256), 0, st, frames, Ho, Wo, AB, CS, dsize, c, Ib);
-        else hipLaunchKernelGGL(crop_batch_kernel<0>, dim3(grid.x, nb), dim3(256), 0, st, frames, Ho, Wo, AB, CS, dsize, c, Ib);
+        hipLaunchKernelGGL(kernel, dim3(grid.x, nb), dim3(256), 0, st, frames, Ho, Wo, AB, CS, dsize, c, Ib);
         LAUNCH_CHECK("crop_batch");
         return 0;
     });

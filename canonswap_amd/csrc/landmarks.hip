@@ -206,23 +206,12 @@ __global__ void __launch_bounds__(256) crop_lmk_kernel(const unsigned char* __re
     const int g = blockIdx.x * 256 + tid;
     if (g >= gw * (dsize / ROWS)) return;
     const int yb = (g / gw) * ROWS, xb = (g % gw) * 4;
-    int v[ROWS][4][3];
-#pragma unroll
-    for (int r = 0; r < ROWS; ++r)
-#pragma unroll
-        for (int k = 0; k < 4; ++k) v[r][k][0] = v[r][k][1] = v[r][k][2] = 0;
+    int v[ROWS][4][3] = {};                                          // a refused face: zeros
     if (ok) {
         AffineInv A;
 #pragma unroll
         for (int i = 0; i < 6; ++i) A.m[i] = s.A[i];
-        const unsigned char* frame = frames + (long)p.frame[n] * p.Ho * p.Wo * 3;
-#pragma unroll
-        for (int r = 0; r < ROWS; ++r)
-#pragma unroll
-            for (int k = 0; k < 4; ++k) {
-                const Tap t = tap_at(A, xb + k, yb + r, p.Ho, p.Wo);
-                if (!t.outside) tap_u8x3(frame, p.Wo, t, v[r][k]);      // all four taps outside the frame: the border value 0
-            }
+        crop_read<ROWS>(frames + (long)p.frame[n] * p.Ho * p.Wo * 3, p.Ho, p.Wo, A, xb, yb, v);
     }
     if (p.wide_crops) crop_store<STAGE, true>(v, n, yb, xb, dsize, crops, I);
     else crop_store<STAGE, false>(v, n, yb, xb, dsize, crops, I);

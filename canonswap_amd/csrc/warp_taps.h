@@ -60,6 +60,24 @@ __device__ __forceinline__ void tap_u8x3(const unsigned char* __restrict__ src, 
     }
 }
 
+// A thread's block of a crop, read from its frame: v[row][pixel][channel] = the pixels (xb .. xb + 3, yb .. yb + ROWS - 1) of the crop under A, a
+// pixel whose four taps all lie outside the frame the border value 0.  crop_batch_kernel (imgops.hip) and crop_lmk_kernel (landmarks.hip) both
+// read through here and store through crop_store.
+template <int ROWS>
+__device__ __forceinline__ void crop_read(const unsigned char* __restrict__ frame, int Ho, int Wo, const AffineInv& A, int xb, int yb,
+                                          int (&v)[ROWS][4][3])
+{
+#pragma unroll
+    for (int r = 0; r < ROWS; ++r)
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            const Tap t = tap_at(A, xb + k, yb + r, Ho, Wo);
+            int res[3] = {0, 0, 0};      // a pixel of its own, copied into v: written into v[r][k] in place, two rows take 220 and more VGPRs
+            if (!t.outside) tap_u8x3(frame, Wo, t, res);
+            v[r][k][0] = res[0]; v[r][k][1] = res[1]; v[r][k][2] = res[2];
+        }
+}
+
 // A thread's block of crop n - four pixels of a row, of two rows with STAGE != 0 - from its registers (v[row][pixel][channel], 8-bit values): the
 // crop's bytes (12 per row = three dwords) and, with STAGE != 0, what prepare_crops_kernel would make of them, so that the crop is not read back:
 // STAGE 2 (dsize 512): the two 2 x 2 means (a + b + c + d + 2) >> 2, / 255, one float2 per channel of the NCHW fp32 input; STAGE 1 (dsize 256):

@@ -22,7 +22,7 @@ import numpy as np
 import torch
 
 from . import _lib, align
-from .engine import Engine
+from .engine import Engine, u8_images
 
 DET_MEAN, DET_STD = 127.5, 128.0                    # SCRFD.input_mean / input_std (scrfd.py:107-108)
 LAYOUTS = {3: ((8, 16, 32), 2), 5: ((8, 16, 32, 64, 128), 1)}      # levels -> (strides, anchors per cell) (scrfd.py:114-131)
@@ -80,11 +80,7 @@ def _det_lut_on(e: Engine, mean, std):
 
 def _frames(frames, who):
     t = torch.as_tensor(frames)
-    if t.dim() == 3:
-        t = t[None]
-    if t.dtype != torch.uint8 or t.dim() != 4 or t.shape[3] != 3 or min(t.shape) < 1:
-        raise ValueError(f"{who} expects (F, Ho, Wo, 3) uint8 frames")
-    return t
+    return u8_images(t[None] if t.dim() == 3 else t, True, 1, "frames", who)
 
 
 def det_input(e: Engine, frames, det_size=(640, 640), swap_rb=SWAP_RB, mean=DET_MEAN, std=DET_STD, out=None):

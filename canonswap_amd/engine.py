@@ -17,6 +17,17 @@ def _ptr(t):
     return C.c_void_p(0 if t is None else t.data_ptr())
 
 
+def u8_images(x, batch, least, name, who):
+    """Argument `name` of `who` as 8-bit RGB images, tensor or array, host or device: with batch (B,H,W,3) uint8, B >= least, without ONE
+    (H,W,3) uint8 image, H and W at least 1 -> the tensor where it lies (the caller uploads), or ValueError.  The one text of this check
+    for every wrapper of the package."""
+    t = torch.as_tensor(x)
+    if t.dtype != torch.uint8 or t.dim() != (4 if batch else 3) or t.shape[-1] != 3 or min(t.shape[-3:]) < 1 or (batch and t.shape[0] < least):
+        want = f"(B,H,W,3) uint8 frames or crops, B >= {least}" if batch else "ONE (H,W,3) uint8 image"
+        raise ValueError(f"{who}: {name} must be {want}, got {tuple(t.shape)} {t.dtype}")
+    return t
+
+
 class Engine:
     """One engine per device; not thread-safe (same contract as the C ABI)."""
 
@@ -284,10 +295,7 @@ class Engine:
 
     def unpack_u8(self, img_u8):
         """BxHxWx3 uint8 (host or device) -> Bx3xHxW fp32 in [0,1] on the device (prepare_source / prepare_videos arithmetic)."""
-        t = torch.as_tensor(img_u8)
-        if t.dtype != torch.uint8 or t.ndim != 4 or t.shape[3] != 3:
-            raise ValueError("expected a BxHxWx3 uint8 array")
-        t = t.to(self.device).contiguous()
+        t = u8_images(img_u8, True, 0, "img_u8", "unpack_u8").to(self.device).contiguous()
         B, H, W, _ = t.shape
         out = self._new(B, 3, H, W)
         self._call("cs_unpack_u8", B, t, out, H, W)
@@ -375,10 +383,7 @@ class Engine:
         can_swap_pipeline_e2e.py:43-46) as a (3,256) table, then getid; lut: another table (tail.id_lut builds them)."""
         from . import tail
         t = torch.as_tensor(crops_u8)
-        if t.dim() == 3:
-            t = t[None]
-        if t.dtype != torch.uint8 or t.dim() != 4 or t.shape[3] != 3 or min(t.shape) < 1:
-            raise ValueError("identity_u8 expects (B, H, W, 3) uint8 crops")
+        t = u8_images(t[None] if t.dim() == 3 else t, True, 1, "crops_u8", "identity_u8")
         if t.shape[0] > self.max_batch:
             raise ValueError(f"batch {t.shape[0]} outside [1, {self.max_batch}]")
         t = t.to(self.device).contiguous()

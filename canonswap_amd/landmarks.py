@@ -22,7 +22,7 @@ import numpy as np
 import torch
 
 from . import _lib, crop as crop_geometry, tail, video
-from .engine import Engine
+from .engine import Engine, u8_images
 
 RUNNER_DSIZE, RUNNER_SCALE, RUNNER_VY_RATIO = 224, 1.5, -0.1      # crop_image's defaults, which human_landmark_runner.py:62 leaves as they are
 
@@ -53,11 +53,7 @@ def _engine_of(swapper) -> Engine:
 
 def _frames(e, frames, who):
     t = torch.as_tensor(frames)
-    if t.dim() == 3:
-        t = t[None]
-    if t.dtype != torch.uint8 or t.dim() != 4 or t.shape[3] != 3 or min(t.shape) < 1:
-        raise ValueError(f"{who} expects (F, Ho, Wo, 3) uint8 frames")
-    return t.to(e.device).contiguous()
+    return u8_images(t[None] if t.dim() == 3 else t, True, 1, "frames", who).to(e.device).contiguous()
 
 
 def _dsize(dsize, who):

@@ -36,7 +36,7 @@ import numpy as np
 import torch
 
 from . import crop as crop_geometry
-from .engine import Engine
+from .engine import Engine, u8_images
 
 
 def _m6(M, B=None):
@@ -44,6 +44,21 @@ def _m6(M, B=None):
     a = np.asarray(M, dtype=np.float64)
     m = np.ascontiguousarray(a.reshape(-1)[:6] if B is None else a.reshape(B, -1)[:, :6])
     return m, m.ctypes.data_as(C.POINTER(C.c_double))
+
+
+def _m6_of(M, B, name, who):
+    """B host matrices, (B,2,3) or (B,3,3), B >= 1 -> _m6's pair; ValueError names the argument."""
+    if B < 1 or tuple(np.shape(M)) not in ((B, 2, 3), (B, 3, 3)):
+        raise ValueError(f"{who}: {name} must be (B,2,3) or (B,3,3) host matrices, B = {B if B >= 0 else '?'} >= 1, got shape {tuple(np.shape(M))}")
+    return _m6(M, B)
+
+
+def _masks_of(masks_crop, crops, who):
+    """The soft masks of B crops (B,Hc,Wc,3), host or device -> the (B,Hc,Wc) tensor where it lies (the caller converts and uploads)."""
+    mc = torch.as_tensor(masks_crop)
+    if tuple(mc.shape) != tuple(crops.shape[:3]):
+        raise ValueError(f"{who}: masks_crop must be (B, Hc, Wc), one mask per crop, got {tuple(mc.shape)} for crops {tuple(crops.shape)}")
+    return mc
 
 
 def _mask_hw(e: Engine, mask):
@@ -152,10 +167,7 @@ def parser_input(e: Engine, crops_u8, halve=None, mean=PARSER_MEAN, std=PARSER_S
     either crop size).  Bit-equal to PIL's two-pass fixed-point bilinear resize and the processor's numpy lines (parser_lut).  With want_u8 (or
     out_u8) {"pixel_values", "resized_u8"}, resized_u8 (B,Ho,Wo,3) uint8: the resized image before rescale / normalize."""
     t = torch.as_tensor(crops_u8)
-    if t.dim() == 3:
-        t = t[None]
-    if t.dtype != torch.uint8 or t.dim() != 4 or t.shape[3] != 3 or min(t.shape) < 1:
-        raise ValueError("parser_input expects (B, H, W, 3) uint8 crops")
+    t = u8_images(t[None] if t.dim() == 3 else t, True, 1, "crops_u8", "parser_input")
     B, H, W, _ = t.shape
     if halve is None:
         halve = (H, W) == (512, 512)
@@ -285,9 +297,7 @@ def rgb_to_yuv(e: Engine, rgb, layout="nv12", matrix="bt601", full_range=False, 
     bytes, every other block is re-encoded, so what nothing wrote since yuv_to_rgb comes back as it went in.  Pass keep or out, not both."""
     who = "rgb_to_yuv"
     fmt = yuv_format(who, layout, matrix, full_range)
-    t = torch.as_tensor(rgb)
-    if t.dtype != torch.uint8 or t.dim() != 4 or t.shape[3] != 3 or t.shape[0] < 1:
-        raise ValueError(f"{who}: rgb: expected (F, Ho, Wo, 3) uint8, got {tuple(t.shape)} {t.dtype}")
+    t = u8_images(rgb, True, 1, "rgb", who)
     F, Ho, Wo = int(t.shape[0]), int(t.shape[1]), int(t.shape[2])
     if Ho < 2 or Wo < 2 or Ho % 2 or Wo % 2 or max(Ho, Wo) > 16384:
         raise ValueError(f"{who}: rgb: 4:2:0 needs an even Ho and Wo from 2 to 16384, got {Ho} x {Wo}")
@@ -352,15 +362,14 @@ def soft_erosion_frames(e: Engine, masks, weight, kernel_size=21, threshold=0.9,
 def paste_back_batch(e: Engine, crops, masks_crop, M_c2o, imgs_ori, out=None):
     """prepare_paste_back + paste_back (crop.py:515-529) of B frames in one launch: crops (B,Hc,Wc,3) u8, masks_crop (B,Hc,Wc) fp32 soft masks
     in the crop frame, M_c2o (B,2,3) or (B,3,3) host matrices crop -> original, imgs_ori (B,Ho,Wo,3) u8 -> (B,Ho,Wo,3) u8."""
-    crops, ori = torch.as_tensor(crops), torch.as_tensor(imgs_ori)
-    if crops.dtype != torch.uint8 or crops.dim() != 4 or crops.shape[3] != 3 or ori.dtype != torch.uint8 or ori.dim() != 4 or ori.shape[3] != 3:
-        raise ValueError("expected BxHxWx3 uint8 crops and original frames")
+    who = "paste_back_batch"
+    crops, ori = u8_images(crops, True, 1, "crops", who), u8_images(imgs_ori, True, 1, "imgs_ori", who)
     crops, ori = crops.to(e.device).contiguous(), ori.to(e.device).contiguous()
     B = crops.shape[0]
-    mc = torch.as_tensor(masks_crop).to(e.device).float().contiguous()
-    if tuple(mc.shape) != tuple(crops.shape[:3]) or ori.shape[0] != B:
-        raise ValueError("masks_crop must be (B, Hc, Wc) and imgs_ori must hold B frames")
-    mm, mp = _m6(M_c2o, B)
+    mc = _masks_of(masks_crop, crops, who).to(e.device).float().contiguous()
+    if ori.shape[0] != B:
+        raise ValueError(f"{who}: imgs_ori must hold the {B} frames of the crops, got {ori.shape[0]}")
+    mm, mp = _m6_of(M_c2o, B, "M_c2o", who)
     out = e._out(out, ori.shape, torch.uint8)
     e._call("cs_paste_back_batch", B, crops, mc, crops.shape[1], crops.shape[2], mp, ori, out, ori.shape[1], ori.shape[2])
     return out
@@ -370,11 +379,7 @@ def paste_back_shared(e: Engine, crops, M_c2o, img_ori, mask_ori, out=None):
     """paste_back (crop.py:523-529) of B generated frames into ONE image, as the loop of can_swap_pipeline_v2i.py:317-321 does on a fresh copy
     of the source image per frame: crops (B,Hc,Wc,3) u8, M_c2o 2x3 / 3x3 host, img_ori (Ho,Wo,3) u8, mask_ori (Ho,Wo) fp32 (prepare_paste_back's
     result, :255-258) -> (B,Ho,Wo,3) u8, frame b bit-equal to paste_back(crops[b], M_c2o, img_ori, mask_ori)."""
-    crops, ori = torch.as_tensor(crops), torch.as_tensor(img_ori)
-    if crops.dtype != torch.uint8 or crops.dim() != 4 or crops.shape[3] != 3 or crops.shape[0] < 1:
-        raise ValueError("expected BxHcxWcx3 uint8 crops")
-    if ori.dtype != torch.uint8 or ori.dim() != 3 or ori.shape[2] != 3:
-        raise ValueError("expected ONE HoxWox3 uint8 image")
+    crops, ori = u8_images(crops, True, 1, "crops", "paste_back_shared"), u8_images(img_ori, False, 1, "img_ori", "paste_back_shared")
     crops, ori = crops.to(e.device).contiguous(), ori.to(e.device).contiguous()
     mo = _mask_hw(e, mask_ori)
     if tuple(mo.shape) != tuple(ori.shape[:2]):
@@ -386,16 +391,13 @@ def paste_back_shared(e: Engine, crops, M_c2o, img_ori, mask_ori, out=None):
     return out
 
 
-def _u8_hwc(e: Engine, img):
-    t = torch.as_tensor(img)
-    if t.dtype != torch.uint8 or t.dim() != 3 or t.shape[2] != 3:
-        raise ValueError("expected an HxWx3 uint8 image")
-    return t.to(e.device).contiguous()
+def _u8_hwc(e: Engine, img, name, who):
+    return u8_images(img, False, 1, name, who).to(e.device).contiguous()
 
 
 def warp_affine_u8(e: Engine, img, M, dsize):
     """cv2.warpAffine(img, M[:2], dsize=(W, H), flags=cv2.INTER_LINEAR) for HxWx3 uint8 (crop.py:49-63 _transform_img)."""
-    src = _u8_hwc(e, img)
+    src = _u8_hwc(e, img, "img", "warp_affine_u8")
     Wd, Hd = int(dsize[0]), int(dsize[1])
     dst = torch.empty((Hd, Wd, 3), dtype=torch.uint8, device=e.device)
     m, mp = _m6(M)
@@ -416,7 +418,7 @@ def prepare_paste_back(e: Engine, mask_crop, crop_M_c2o, dsize):
 
 def paste_back(e: Engine, img_crop, M_c2o, img_ori, mask_ori):
     """crop.py:523-529: result = warp(img_crop); clip(mask_ori * result + (1 - mask_ori) * img_ori, 0, 255) as uint8."""
-    crop, ori = _u8_hwc(e, img_crop), _u8_hwc(e, img_ori)
+    crop, ori = _u8_hwc(e, img_crop, "img_crop", "paste_back"), _u8_hwc(e, img_ori, "img_ori", "paste_back")
     mo = _mask_hw(e, mask_ori)
     if tuple(mo.shape) != tuple(ori.shape[:2]):
         raise ValueError("mask_ori must have the size of img_ori")
@@ -428,7 +430,7 @@ def paste_back(e: Engine, img_crop, M_c2o, img_ori, mask_ori):
 
 def paste_back_fused(e: Engine, img_crop, mask_crop, M_c2o, img_ori):
     """prepare_paste_back + paste_back in one launch: the soft mask stays in the crop frame (HcxWc float32)."""
-    crop, ori = _u8_hwc(e, img_crop), _u8_hwc(e, img_ori)
+    crop, ori = _u8_hwc(e, img_crop, "img_crop", "paste_back_fused"), _u8_hwc(e, img_ori, "img_ori", "paste_back_fused")
     mc = _mask_hw(e, mask_crop)
     if tuple(mc.shape) != tuple(crop.shape[:2]):
         raise ValueError("mask_crop must have the size of img_crop")
@@ -442,34 +444,36 @@ def prepare_crops(e: Engine, crops_u8, out=None) -> torch.Tensor:
     """uint8 crops (B,512,512,3) or (B,256,256,3), host or device -> (B,3,256,256) fp32 in [0,1] on the device: the cropper's
     cv2.resize(..., (256, 256), INTER_AREA) (cropper.py:209) fused with prepare_source / prepare_videos (can_swap_e2e.py:126-163)."""
     t = torch.as_tensor(crops_u8)
-    if t.dim() == 3:
-        t = t[None]
-    if t.dtype != torch.uint8 or t.dim() != 4 or t.shape[3] != 3:
-        raise ValueError("expected BxHxWx3 uint8 crops")
-    t = t.to(e.device).contiguous()
+    t = u8_images(t[None] if t.dim() == 3 else t, True, 0, "crops_u8", "prepare_crops").to(e.device).contiguous()
     B, H, W, _ = t.shape
     out = e._out(out, (B, 3, 256, 256), torch.float32)
     e._call("cs_prepare_crops", B, t, H, W, out)
     return out
 
 
+def _crop_M(e: Engine, who, frames, M_o2c, frame_index, dsize, out, want_I, out_I):
+    """crop_frames_M (frame_index None: crop b from frame b, cs_crop_frames) and crop_faces_M (B matrices, crop b from frame frame_index[b],
+    cs_crop_faces)."""
+    fr = u8_images(frames, True, 1, "frames", who).to(e.device).contiguous()
+    F, dsize = fr.shape[0], int(dsize)
+    B = F if frame_index is None else int(np.shape(M_o2c)[0]) if np.ndim(M_o2c) == 3 else -1
+    mm, mp = _m6_of(M_o2c, B, "M_o2c", who)
+    idx = None if frame_index is None else frame_index_of(frame_index, B, F)
+    want_I = want_I or out_I is not None
+    crops = e._out(out, (B, dsize, dsize, 3), torch.uint8)
+    I = e._out(out_I, (B, 3, 256, 256), torch.float32) if want_I else None
+    if idx is None:
+        e._call("cs_crop_frames", B, fr, fr.shape[1], fr.shape[2], mp, dsize, crops, I)
+    else:
+        e._call("cs_crop_faces", B, F, fr, fr.shape[1], fr.shape[2], _index_ptr(idx), mp, dsize, crops, I)
+    return {"crops": crops, "I": I} if want_I else {"crops": crops}
+
+
 def crop_frames_M(e: Engine, frames, M_o2c, dsize, out=None, want_I=False, out_I=None):
     """crop_image_mo2c's image step (crop.py:457-461) of B frames in one launch: frames (B,Ho,Wo,3) u8, M_o2c (B,2,3) or (B,3,3) host matrices original ->
     crop, dsize a multiple of 4 -> {"crops": (B,dsize,dsize,3) u8 on the device, crops[b] = cv2.warpAffine(frames[b], M_o2c[b][:2], (dsize, dsize),
     INTER_LINEAR)[, "I": (B,3,256,256) fp32 = prepare_crops(crops), from the same launch; dsize 256 or 512 only]}."""
-    fr = torch.as_tensor(frames)
-    if fr.dtype != torch.uint8 or fr.dim() != 4 or fr.shape[3] != 3 or fr.shape[0] < 1:
-        raise ValueError("expected BxHoxWox3 uint8 frames")
-    fr = fr.to(e.device).contiguous()
-    B, dsize = fr.shape[0], int(dsize)
-    if tuple(np.shape(M_o2c)) not in ((B, 2, 3), (B, 3, 3)):
-        raise ValueError(f"M_o2c must be (B,2,3) or (B,3,3) for the {B} frames, got {tuple(np.shape(M_o2c))}")
-    mm, mp = _m6(M_o2c, B)
-    want_I = want_I or out_I is not None
-    crops = e._out(out, (B, dsize, dsize, 3), torch.uint8)
-    I = e._out(out_I, (B, 3, 256, 256), torch.float32) if want_I else None
-    e._call("cs_crop_frames", B, fr, fr.shape[1], fr.shape[2], mp, dsize, crops, I)
-    return {"crops": crops, "I": I} if want_I else {"crops": crops}
+    return _crop_M(e, "crop_frames_M", frames, M_o2c, None, dsize, out, want_I, out_I)
 
 
 def crop_frames(e: Engine, frames, lmk, dsize=512, scale=2.3, vy_ratio=-0.125, flag_do_rot=True, out=None, want_I=False, out_I=None):
@@ -510,21 +514,7 @@ def crop_faces_M(e: Engine, frames, M_o2c, frame_index, dsize, out=None, want_I=
     in [0, F); a frame may own several faces or none) -> {"crops": (B,dsize,dsize,3) u8, crops[b] = cv2.warpAffine(frames[frame_index[b]], M_o2c[b][:2],
     (dsize, dsize), INTER_LINEAR)[, "I": (B,3,256,256) fp32 = prepare_crops(crops)]}: the bits of crop_frames_M on frames[frame_index], no frame
     gathered.  B >= 1."""
-    fr = torch.as_tensor(frames)
-    if fr.dtype != torch.uint8 or fr.dim() != 4 or fr.shape[3] != 3 or fr.shape[0] < 1:
-        raise ValueError("expected FxHoxWox3 uint8 frames")
-    fr = fr.to(e.device).contiguous()
-    F, dsize = fr.shape[0], int(dsize)
-    B = int(np.shape(M_o2c)[0]) if np.ndim(M_o2c) == 3 else -1
-    if B < 1 or tuple(np.shape(M_o2c)) not in ((B, 2, 3), (B, 3, 3)):
-        raise ValueError(f"M_o2c must be (B,2,3) or (B,3,3), B >= 1 faces, got {tuple(np.shape(M_o2c))}")
-    idx = frame_index_of(frame_index, B, F)
-    mm, mp = _m6(M_o2c, B)
-    want_I = want_I or out_I is not None
-    crops = e._out(out, (B, dsize, dsize, 3), torch.uint8)
-    I = e._out(out_I, (B, 3, 256, 256), torch.float32) if want_I else None
-    e._call("cs_crop_faces", B, F, fr, fr.shape[1], fr.shape[2], _index_ptr(idx), mp, dsize, crops, I)
-    return {"crops": crops, "I": I} if want_I else {"crops": crops}
+    return _crop_M(e, "crop_faces_M", frames, M_o2c, frame_index, dsize, out, want_I, out_I)
 
 
 def crop_faces(e: Engine, frames, lmk, frame_index, dsize=512, scale=2.3, vy_ratio=-0.125, flag_do_rot=True, out=None, want_I=False, out_I=None):
@@ -543,20 +533,13 @@ def paste_back_faces(e: Engine, crops, masks_crop, M_c2o, frame_index, imgs_ori,
     crop frame, M_c2o (B,2,3) or (B,3,3) host, frame_index B host ints (non-decreasing, in [0, F)), imgs_ori (F,Ho,Wo,3) u8 -> (F,Ho,Wo,3) u8; a frame
     without a face is copied.  out may be the imgs_ori tensor itself (in place).  B = 0 (crops (0,Hc,Wc,3)) copies the frames.  Bit-equal to
     paste_back_fused face by face, and with frame_index = arange(B) to paste_back_batch."""
-    crops, ori = torch.as_tensor(crops), torch.as_tensor(imgs_ori)
-    if crops.dtype != torch.uint8 or crops.dim() != 4 or crops.shape[3] != 3 or ori.dtype != torch.uint8 or ori.dim() != 4 or ori.shape[3] != 3:
-        raise ValueError("expected BxHcxWcx3 uint8 crops and FxHoxWox3 uint8 original frames")
-    if ori.shape[0] < 1:
-        raise ValueError("imgs_ori must hold at least one frame")
+    who = "paste_back_faces"
+    crops, ori = u8_images(crops, True, 0, "crops", who), u8_images(imgs_ori, True, 1, "imgs_ori", who)
     crops, ori = crops.to(e.device).contiguous(), ori.to(e.device).contiguous()
     B, F = crops.shape[0], ori.shape[0]
-    mc = torch.as_tensor(masks_crop).to(e.device).float().contiguous()
-    if tuple(mc.shape) != tuple(crops.shape[:3]):
-        raise ValueError("masks_crop must be (B, Hc, Wc), one mask per face")
+    mc = _masks_of(masks_crop, crops, who).to(e.device).float().contiguous()
     idx = frame_index_of(frame_index, B, F)
-    if B and tuple(np.shape(M_c2o)) not in ((B, 2, 3), (B, 3, 3)):
-        raise ValueError(f"M_c2o must be (B,2,3) or (B,3,3) for the {B} faces, got {tuple(np.shape(M_c2o))}")
-    mm, mp = _m6(M_c2o, B) if B else (None, None)
+    mm, mp = _m6_of(M_c2o, B, "M_c2o", who) if B else (None, None)
     out = e._out(out, ori.shape, torch.uint8)
     e._call("cs_paste_back_faces", B, F, crops if B else None, mc if B else None, crops.shape[1], crops.shape[2],
             _index_ptr(idx) if B else None, mp, ori, out, ori.shape[1], ori.shape[2])
@@ -577,13 +560,6 @@ def _device_tensor(e: Engine, t, shape, dtype, name, who):
     return t
 
 
-def _u8_frames(frames, name, who):
-    fr = torch.as_tensor(frames)
-    if fr.dtype != torch.uint8 or fr.dim() != 4 or fr.shape[3] != 3 or fr.shape[0] < 1:
-        raise ValueError(f"{who}: {name} must be (F,Ho,Wo,3) uint8 frames, F >= 1")
-    return fr
-
-
 def crop_lmk(e: Engine, frames, lmk, frame_index=None, dsize=512, scale=2.3, vy_ratio=-0.125, flag_do_rot=True, status=None, status_mark=1, out=None,
              want_I=False, want_lmk_crop=False):
     """crop_faces from landmarks that never leave the device (cs_crop_lmk, one launch per 64 faces): frames (F,Ho,Wo,3) u8; lmk (B,N,2) float32 ON
@@ -598,7 +574,7 @@ def crop_lmk(e: Engine, frames, lmk, frame_index=None, dsize=512, scale=2.3, vy_
     crop, the generator and paste_back_faces_dev are then enqueued one behind the other without a host wait."""
     from .landmarks import layout_of      # (landmarks imports this module)
     who = "crop_lmk"
-    fr = _u8_frames(frames, "frames", who)
+    fr = u8_images(frames, True, 1, "frames", who)
     F = int(fr.shape[0])
     pts = _device_tensor(e, lmk, (-1, -1, 2), torch.float32, "lmk", who)
     B, N = int(pts.shape[0]), int(pts.shape[1])
@@ -643,13 +619,9 @@ def paste_back_faces_dev(e: Engine, crops, masks_crop, M, frame_index, imgs_ori,
     everything else as paste_back_faces takes it -> (F,Ho,Wo,3) u8, the bytes of paste_back_faces on M[:, 9:] downloaded and widened.  out may be
     imgs_ori itself (in place); B = 0 copies the frames (M is not read and may be None).  Nothing is downloaded and nothing waits for the device."""
     who = "paste_back_faces_dev"
-    crops, ori = torch.as_tensor(crops), _u8_frames(imgs_ori, "imgs_ori", who)
-    if crops.dtype != torch.uint8 or crops.dim() != 4 or crops.shape[3] != 3:
-        raise ValueError(f"{who}: crops must be (B,Hc,Wc,3) uint8")
+    crops, ori = u8_images(crops, True, 0, "crops", who), u8_images(imgs_ori, True, 1, "imgs_ori", who)
     B, F = int(crops.shape[0]), int(ori.shape[0])
-    mc = torch.as_tensor(masks_crop)
-    if tuple(mc.shape) != tuple(crops.shape[:3]):
-        raise ValueError(f"{who}: masks_crop must be (B, Hc, Wc), one mask per face")
+    mc = _masks_of(masks_crop, crops, who)
     idx = frame_index_of(frame_index, B, F, f"{who}: frame_index")
     if B:
         _device_tensor(e, M, (B, 18), torch.float32, "M", who)

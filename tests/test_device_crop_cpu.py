@@ -224,6 +224,79 @@ def test_paste_back_faces_dev_refuses_before_the_library_is_touched(stub):
         tail.paste_back_faces_dev(stub, crops, masks, M, fi, ori[0])
 
 
+def test_paste_back_batch_names_a_wrong_matrix_count_before_the_library_is_touched(stub):
+    from canonswap_amd import tail
+    crops, masks = torch.zeros((3, 8, 8, 3), dtype=torch.uint8), torch.zeros((3, 8, 8))
+    ori = torch.zeros((3, 12, 16, 3), dtype=torch.uint8)
+    for bad in (np.zeros((2, 3, 3)), np.zeros((3, 9)), np.zeros((3, 3, 2))):
+        with pytest.raises(ValueError, match="paste_back_batch: M_c2o"):
+            tail.paste_back_batch(stub, crops, masks, bad, ori)
+    for bad in (np.zeros((2, 3, 3)), np.zeros((3, 6))):
+        with pytest.raises(ValueError, match="crop_frames_M: M_o2c"):
+            tail.crop_frames_M(stub, ori, bad, 8)
+        with pytest.raises(ValueError, match="paste_back_faces: M_c2o"):
+            tail.paste_back_faces(stub, crops, masks, bad, [0, 0, 1], ori)
+    for bad in (np.zeros((3, 6)), np.zeros((3, 3, 2)), np.zeros((0, 3, 3))):
+        with pytest.raises(ValueError, match="crop_faces_M: M_o2c"):
+            tail.crop_faces_M(stub, ori[:2], bad, [0, 1, 1][:len(bad)], 8)
+
+
+def _u8(*shape):
+    return torch.zeros(shape, dtype=torch.uint8)
+
+
+# every public wrapper that takes 8-bit RGB images: (its name in the message, the argument, a call with that argument as `x`, and what it takes:
+# "batch", "one" image, or "either" - a batch, or one image that it makes a batch of)
+def _image_wrappers():
+    from canonswap_amd import chain, detect, landmarks, tail
+    from canonswap_amd.engine import Engine
+    M, M3 = np.eye(3), np.stack([np.eye(3)] * 3)
+    crops, masks, frames = _u8(3, 8, 8, 3), torch.zeros((3, 8, 8)), _u8(3, 12, 16, 3)
+    return [
+        ("parser_input", "crops_u8", lambda e, x: tail.parser_input(e, x), "either"),
+        ("prepare_crops", "crops_u8", lambda e, x: tail.prepare_crops(e, x), "either"),
+        ("rgb_to_yuv", "rgb", lambda e, x: tail.rgb_to_yuv(e, x), "batch"),
+        ("paste_back_batch", "crops", lambda e, x: tail.paste_back_batch(e, x, masks, M3, frames), "batch"),
+        ("paste_back_batch", "imgs_ori", lambda e, x: tail.paste_back_batch(e, crops, masks, M3, x), "batch"),
+        ("paste_back_shared", "crops", lambda e, x: tail.paste_back_shared(e, x, M, frames[0], torch.zeros((12, 16))), "batch"),
+        ("paste_back_shared", "img_ori", lambda e, x: tail.paste_back_shared(e, crops, M, x, torch.zeros((12, 16))), "one"),
+        ("warp_affine_u8", "img", lambda e, x: tail.warp_affine_u8(e, x, M, (8, 8)), "one"),
+        ("paste_back", "img_crop", lambda e, x: tail.paste_back(e, x, M, frames[0], torch.zeros((12, 16))), "one"),
+        ("paste_back", "img_ori", lambda e, x: tail.paste_back(e, crops[0], M, x, torch.zeros((12, 16))), "one"),
+        ("paste_back_fused", "img_crop", lambda e, x: tail.paste_back_fused(e, x, masks[0], M, frames[0]), "one"),
+        ("paste_back_fused", "img_ori", lambda e, x: tail.paste_back_fused(e, crops[0], masks[0], M, x), "one"),
+        ("crop_frames_M", "frames", lambda e, x: tail.crop_frames_M(e, x, M3, 8), "batch"),
+        ("crop_faces_M", "frames", lambda e, x: tail.crop_faces_M(e, x, M3, [0, 0, 0], 8), "batch"),
+        ("paste_back_faces", "imgs_ori", lambda e, x: tail.paste_back_faces(e, crops, masks, M3, [0, 0, 0], x), "batch"),
+        ("crop_lmk", "frames", lambda e, x: tail.crop_lmk(e, x, _meta((3, 203, 2), torch.float32), dsize=8), "batch"),
+        ("paste_back_faces_dev", "imgs_ori", lambda e, x: tail.paste_back_faces_dev(e, crops, masks, _meta((3, 18), torch.float32), [0, 0, 0], x), "batch"),
+        ("unpack_u8", "img_u8", lambda e, x: Engine.unpack_u8(e, x), "batch"),
+        ("identity_u8", "crops_u8", lambda e, x: Engine.identity_u8(e, x), "either"),
+        ("det_input", "frames", lambda e, x: detect.det_input(e, x), "either"),
+        ("lmk_input", "frames", lambda e, x: landmarks.lmk_input(e, x, np.zeros((3, 203, 2), np.float32)), "either"),
+        ("FrameChain", "frames_ori", lambda e, x: chain.FrameChain._no_faces(types.SimpleNamespace(e=e), x, [], None), "batch"),
+        ("load_source_state", "img_ori", lambda e, x: chain.AnimateChain.load_source_state(
+            types.SimpleNamespace(e=e), {"f_swap_can_2": torch.zeros((1, 32, 16, 64, 64)), "x_swap": torch.zeros((1, 21, 3)), "kp_swap": torch.zeros((21, 3)),
+                                         "raw_pose": torch.zeros((1, 328)), "img_ori": x}), "one"),
+    ]
+
+
+def test_every_wrapper_refuses_what_is_not_8_bit_rgb_under_its_own_name(stub):
+    """The shared check (engine.u8_images): a float tensor, a channel-first tensor and an empty batch are refused with a ValueError that names the
+    wrapper and the argument, before the library is touched.  unpack_u8 and prepare_crops alone take an empty batch as far as the library."""
+    from canonswap_amd.engine import u8_images
+    for who, name, call, takes in _image_wrappers():
+        good = _u8(12, 16, 3) if takes == "one" else _u8(3, 12, 16, 3)
+        bads = [good.float(), good.movedim(-1, -3).contiguous(), good[..., :0, :], good[0, 0] if takes == "either" else good[0] if takes == "batch" else good[None]]
+        if takes != "one" and who not in ("unpack_u8", "prepare_crops"):
+            bads.append(good[:0])
+        for bad in bads:
+            with pytest.raises(ValueError, match=f"{who}: {name} must be"):
+                call(stub, bad)
+    assert u8_images(np.zeros((2, 4, 4, 3), np.uint8), True, 1, "a", "f").shape == (2, 4, 4, 3)      # an array comes back as a tensor
+    assert u8_images(_u8(0, 4, 4, 3), True, 0, "a", "f").shape[0] == 0 and u8_images(_u8(4, 4, 3), False, 1, "a", "f").dim() == 3
+
+
 def test_the_chain_and_the_swapper_reach_the_wrappers():
     import inspect
     from canonswap_amd import can_swap_e2e, chain

@@ -90,7 +90,7 @@ def test_soft_erosion_frames_vs_oracle(swapper_m):
 @pytest.mark.parametrize("size", [(720, 1280), (301, 403)])
 def test_paste_back_batch_equals_single_frames(swapper_m, size):
     """One launch for B frames (four pixels per thread, copies outside the crop) == the single-frame kernel, which is bit-exact against
-    oracle/cv_ref.py (test_gpu_tail.py); the odd width takes the per-frame fallback."""
+    oracle/cv_ref.py (test_gpu_tail.py); the odd width takes the same launch at one pixel per thread (paste_batch_kernel<1>)."""
     from canonswap_amd import tail
     from oracle import cv_ref as R
     Ho, Wo = size

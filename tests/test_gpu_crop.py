@@ -145,7 +145,8 @@ def test_fused_staging_is_prepare_crops(engine, dsize):
 
 def test_crop_frames_M_and_caller_buffers(engine):
     """A caller's own matrices (crop_image_mo2c): (B,3,3) and (B,2,3), float32 or float64, give crop_frames' crops; `out` is written in place;
-    a crop buffer off a 4-byte boundary / an I buffer off a 16-byte one take the per-frame kernels: the same bytes."""
+    a crop buffer off a 4-byte boundary / an I buffer off a 16-byte one are stored byte by byte and float by float from the same launch, at
+    dsize 512 (two rows per thread, the 2 x 2 means) and 256: the same bytes."""
     from canonswap_amd import tail
     B, Ho, Wo = 3, 1080, 1920
     frames = torch.from_numpy(_frames(B, Ho, Wo, 59)).cuda()
@@ -157,16 +158,17 @@ def test_crop_frames_M_and_caller_buffers(engine):
         assert set(got) == {"crops"} and torch.equal(got["crops"], want["crops"])
     out = torch.zeros((B, 512, 512, 3), dtype=torch.uint8, device=engine.device)
     assert tail.crop_frames_M(engine, frames, M, 512, out=out)["crops"] is out and torch.equal(out, want["crops"])
-    raw = torch.zeros(B * 512 * 512 * 3 + 1, dtype=torch.uint8, device=engine.device)
-    odd = raw[1:].view(B, 512, 512, 3)
-    assert odd.data_ptr() % 4 == 1 and odd.is_contiguous()
-    got = tail.crop_frames_M(engine, frames, M, 512, out=odd, want_I=True)
-    assert torch.equal(odd, want["crops"]) and torch.equal(got["I"], want["I"])
-    rawI = torch.zeros(B * 3 * 256 * 256 + 1, dtype=torch.float32, device=engine.device)
-    oddI = rawI[1:].view(B, 3, 256, 256)
-    assert oddI.data_ptr() % 16 == 4
-    got = tail.crop_frames_M(engine, frames, M, 512, out_I=oddI)
-    assert torch.equal(got["crops"], want["crops"]) and torch.equal(oddI, want["I"])
+    for dsize, w in ((512, want), (256, tail.crop_frames(engine, frames, lmk, dsize=256, want_I=True))):
+        raw = torch.zeros(B * dsize * dsize * 3 + 1, dtype=torch.uint8, device=engine.device)
+        odd = raw[1:].view(B, dsize, dsize, 3)
+        assert odd.data_ptr() % 4 == 1 and odd.is_contiguous()
+        got = tail.crop_frames_M(engine, frames, w["M_o2c"], dsize, out=odd, want_I=True)
+        assert torch.equal(odd, w["crops"]) and torch.equal(got["I"], w["I"])
+        rawI = torch.zeros(B * 3 * 256 * 256 + 1, dtype=torch.float32, device=engine.device)
+        oddI = rawI[1:].view(B, 3, 256, 256)
+        assert oddI.data_ptr() % 16 == 4
+        got = tail.crop_frames_M(engine, frames, w["M_o2c"], dsize, out_I=oddI)
+        assert torch.equal(got["crops"], w["crops"]) and torch.equal(oddI, w["I"])
     host = tail.crop_frames_M(engine, frames.cpu().numpy(), M, 512)                     # host frames are uploaded, as paste_back_batch's are
     assert torch.equal(host["crops"], want["crops"])
 

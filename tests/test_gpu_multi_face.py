@@ -126,7 +126,7 @@ def test_one_face_per_frame_is_paste_back_batch(engine, scene):
 
 
 def test_odd_width_and_buffers_off_the_dword_grid_give_the_same_bits(engine, scene):
-    """Wo % 4 != 0, or imgs_ori / out one byte off a 4-byte boundary: the single-frame kernel per face, in order."""
+    """Wo % 4 != 0, or imgs_ori / out one byte off a 4-byte boundary: the same launches, one pixel per thread (paste_faces_kernel<1>)."""
     from canonswap_amd import tail
     r = np.random.Generator(np.random.PCG64(9))
     ori_np = r.integers(0, 256, size=(4, 23, 37, 3), dtype=np.uint8)
@@ -141,6 +141,31 @@ def test_odd_width_and_buffers_off_the_dword_grid_give_the_same_bits(engine, sce
         out = src if dst == "same" else dst
         got = tail.paste_back_faces(engine, crops, masks, scene["M"], scene["fi"], src, out=out)
         assert (out is None or got is out) and np.array_equal(got.cpu().numpy(), scene["want"])
+
+
+def test_a_frame_in_two_launches_off_the_dword_grid(engine, chunks):
+    """paste_faces_kernel<1> across a launch boundary with resume: the 70 faces of `chunks`, imgs_ori and out one byte off the dword grid, out of
+    place and in place."""
+    from canonswap_amd import tail
+    crops, masks, ori = _dev(chunks["crops"], chunks["masks"], chunks["ori"])
+    src, out = _off_by_one(ori), _off_by_one(torch.zeros_like(ori))
+    assert tail.paste_back_faces(engine, crops, masks, chunks["M"], chunks["fi"], src, out=out) is out
+    assert np.array_equal(out.cpu().numpy(), chunks["want"]) and torch.equal(src, ori)
+    assert tail.paste_back_faces(engine, crops, masks, chunks["M"], chunks["fi"], src, out=src) is src
+    assert np.array_equal(src.cpu().numpy(), chunks["want"])
+
+
+def test_paste_back_batch_of_an_odd_width_over_two_chunks_of_matrices(engine):
+    """paste_batch_kernel<1> across the 64 matrices of a launch: 66 frames of 10 x 13 (Wo % 4 = 1), 8 x 8 crops, one face per frame."""
+    from canonswap_amd import tail
+    r = np.random.Generator(np.random.PCG64(17))
+    B, Ho, Wo, Hc, Wc = 66, 10, 13, 8, 8
+    M = np.stack([MF.similarity(r.uniform(0.6, 1.6), r.uniform(-0.8, 0.8), r.uniform(-3, 6), r.uniform(-3, 4)) for _ in range(B)])
+    crops, masks, ori = MF._bytes(r, (B, Hc, Wc, 3)), MF._masks(r, B, Hc, Wc), MF._bytes(r, (B, Ho, Wo, 3))
+    want = MF.paste_faces(crops, masks, M, np.arange(B), ori)
+    got = tail.paste_back_batch(engine, *_dev(crops, masks), M, _dev(ori)[0]).cpu().numpy()
+    assert np.array_equal(got, want), [b for b in range(B) if not np.array_equal(got[b], want[b])]
+    assert (want[0] != ori[0]).any() and (want[65] != ori[65]).any()
 
 
 # ------------------------------------------------------------------------------------------------ crop
@@ -165,8 +190,21 @@ def test_crops_equal_the_reference_and_crop_frames_on_the_gathered_frames(engine
     assert np.array_equal(got["crops"].cpu().numpy(), want)
     assert torch.equal(got["crops"], tail.crop_frames_M(engine, fr[torch.from_numpy(fi).long().cuda()], M, dsize)["crops"])
     assert not np.array_equal(want[1], want[2]) and (want[4] == 0).any() and want[4].any()
-    odd = _off_by_one(torch.zeros_like(got["crops"]))                                   # a crop buffer off the dword grid: the per-crop kernel
+    odd = _off_by_one(torch.zeros_like(got["crops"]))                                   # a crop buffer off the dword grid: the same launch, narrow stores
     assert tail.crop_faces_M(engine, fr, M, fi, dsize, out=odd)["crops"] is odd and torch.equal(odd, got["crops"])
+
+
+def test_narrow_stores_over_two_chunks_of_matrices(engine):
+    """66 faces at dsize 8 into a crop buffer one byte off the dword grid: crop_store<0, false> across the 64 matrices of a launch."""
+    from canonswap_amd import tail
+    frames, M, fi = _crop_case(sorted(list(range(5)) * 13 + [4]))
+    assert len(fi) == 66
+    fr = torch.from_numpy(frames).cuda()
+    want = tail.crop_faces_M(engine, fr, M, fi, 8)["crops"]
+    odd = _off_by_one(torch.zeros_like(want))
+    assert tail.crop_faces_M(engine, fr, M, fi, 8, out=odd)["crops"] is odd and torch.equal(odd, want)
+    assert np.array_equal(odd.cpu().numpy(), MF.crop_faces(frames, M, fi, 8))
+    assert not torch.equal(odd[63], odd[64]) and odd[65].any()
 
 
 @pytest.mark.parametrize("dsize", [256, 512])

@@ -207,8 +207,8 @@ def _tap_classes(M, Hd, Wd):
 
 @pytest.mark.parametrize("dest", ["24x32", "24x28", "23x29", "crop24"])
 def test_shared_tap_every_class_vs_oracle(swapper, dest):
-    """Destinations: 24x32 (paste_shared's 8-pixel path, paste_batch's dword path), 24x28 (the 4-pixel path), 23x29 (the single-frame fallback
-    of both), and cs_crop_frames at dsize 24.  Bit for bit against the cv_ref composition; the inputs are checked to hold every tap class."""
+    """Destinations: 24x32 (paste_shared's 8-pixel path, paste_batch's dword path), 24x28 (the 4-pixel path), 23x29 (paste_shared's single-frame
+    fallback, paste_batch's one-pixel path), and cs_crop_frames at dsize 24.  Bit for bit against the cv_ref composition; the inputs are checked to hold every tap class."""
     from canonswap_amd import tail
     from oracle import cv_ref as R
     e = swapper.engine
